@@ -40,6 +40,9 @@ At ``--gpus 1`` the line also carries ``config4_one_device`` (BASELINE.json conf
 288 GB device: 102 GB of u + 102 GB of resident probabilities -- NOT the 8-GPU metric) and ``scaling_model``: the pieces of
 one iteration measured on ONE GPU at the shard sizes of 1, 2, 4 and 8 ranks, and what they predict for the strong-scaling
 curve -- a model, labelled as such, since no multi-GPU run can be made from here.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the timed solver call returned after its last step (f_k, the
+per-state sums at f_k, the stopping statistics and iteration counts) as ``DIR/<name>.npy`` in float64.
 """
 import argparse
 import json
@@ -500,6 +503,18 @@ def scaling_model_object(dev, K, N_total, seed, steps, warmup):
     }
 
 
+def dump_outputs(out_dir, f_end, res):
+    """What the timed solver call hands its caller after its last step, as ``out_dir/<name>.npy`` (float64, ~2 kB at K = 128):
+    the free energies, the per-state sums at them, the step's stopping statistics and its iteration counts."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"f_k": f_end, "psum": res["psum"], "gnorm": res["gnorm"], "max_delta": res["max_delta"],
+              "iterations_nr_sci": [res["iterations"], res["nr_iter"], res["sci_iter"]]}
+    for name, a in arrays.items():
+        if a is None:
+            raise RuntimeError(f"--dump-outputs: the solver returned no {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def spawn_ranks(n):
     """``python bench.py --gpus N`` without a launcher: start N ranks of this script (one per GPU, RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* set as a launcher would) and wait.  Returns the exit code: 3 if the box has fewer than N GPUs, the
@@ -578,7 +593,12 @@ def main():
     ap.add_argument("--config4", type=int, default=-1,
                     help="also measure config 4 (K=128, N=1e8 in total, sharded) after the headline run: -1 = only with 8 or more "
                          "GPUs (default), 0 = never, 1 = always (needs 205 GB on a single GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed solver call returned in its last step as DIR/<name>.npy "
+                         "(float64; the inputs depend on the arguments only, so two builds can be compared output for output)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -670,6 +690,8 @@ def main():
         group.allreduce(t, "max")
         elapsed = float(t[0])
     assert res["iterations"] == args.steps, res
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, f_end, res)
 
     # ---- wall-clock to converge from f = 0 (reported, not the headline value): whole solves, build sweep included ----
     def timed_solve(min_sc_iter, warm=False):

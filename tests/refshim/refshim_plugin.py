@@ -1,4 +1,4 @@
-"""pytest plugin used by tests/test_reference_suite.py and tools/reference_on_gpu_box.sh: runs the REFERENCE'S OWN test
+"""pytest plugin used by tools/reference_on_gpu_box.sh: runs the REFERENCE'S OWN test
 files (read in place from the reference tree on PYTHONPATH) with ``pymbar.MBAR`` and ``pymbar.mbar_solvers`` replaced by this
 repository's host-side mirror.
 

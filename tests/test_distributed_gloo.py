@@ -51,13 +51,26 @@ def _worker(rank, world, port, out_dir):
 
 
 def test_two_rank_sharded_solve_matches_unsharded(tmp_path):
-    import torch.multiprocessing as mp
+    import multiprocessing
 
     from oracle import mbar_oracle as oracle
     from pymbar_amd import testsystems as ts
 
     port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    # Plain spawned processes: torch is imported by the ranks only.  In this process it would load PyTorch's own HIP runtime
+    # next to the one libmbar_hip.so links, and the GPU tests that follow in the same session (RCCL) would run on both.
+    ctx = multiprocessing.get_context("spawn")
+    ranks = [ctx.Process(target=_worker, args=(rank, 2, port, str(tmp_path))) for rank in range(2)]
+    for p in ranks:
+        p.start()
+    try:
+        for p in ranks:
+            p.join(timeout=300)
+        assert [p.exitcode for p in ranks] == [0, 0], [p.exitcode for p in ranks]
+    finally:
+        for p in ranks:
+            if p.is_alive():
+                p.kill()
     r0 = np.load(tmp_path / "rank0.npz")
     r1 = np.load(tmp_path / "rank1.npz")
     assert int(r0["n1"]) == int(r1["n0"]) and int(r0["n0"]) == 0 and int(r1["n1"]) == 1000
