@@ -365,6 +365,35 @@ int mbar_ctx_timing_reset(mbar_ctx* ctx);
 /* Peak-rate micro-benchmark of v_mfma_f64_16x16x4_f64 on this device (TFLOP/s). */
 int mbar_mfma_f64_peak(mbar_ctx* ctx, double* tflops);
 
+/* ---- weighted kernel-density sums (pymbar_amd.kde.KernelDensity, fes_type="kde" of pymbar_amd.FES) ----------------------
+ * A handle holds N samples of dimension d (1 <= d <= 8) resident on one device, one kernel and one bandwidth h, and C columns
+ * of non-negative sample weights V (N x C).  mbar_kde_eval returns for M query points
+ *     L[m, c] = log sum_n V[n, c] k_h(|q_m - x_n|) - log sum_n V[n, c] + log-normaliser(kernel, d, h)
+ * (euclidean distance), which is what sklearn.neighbors.KernelDensity(kernel, bandwidth=h).fit(X, sample_weight=V[:, c])
+ * .score_samples(Q) computes -- exactly: the sum runs over every pair, in log space with a running per-query shift, so the log
+ * density stays finite and exact where every term underflows (gaussian / exponential far from the data).  Compact kernels
+ * give -inf where no sample of positive weight lies strictly inside the support (|q - x| < h, sklearn's convention), a column of
+ * zero total weight gives NaN.  Two identical calls return identical bits (partial sums merged in a fixed order).  Columns are
+ * processed in passes of up to 32: device memory is (d + min(C, 32)) N doubles plus O(M) per pass; with C <= 32 the weights stay
+ * resident between calls.  Buffers come from the block cache of mbar_cache_trim.  Errors: mbar_last_error(NULL).
+ * Not thread-safe (one handle per caller thread). */
+typedef struct mbar_kde mbar_kde;
+#define MBAR_KDE_GAUSSIAN 0
+#define MBAR_KDE_TOPHAT 1
+#define MBAR_KDE_EPANECHNIKOV 2
+#define MBAR_KDE_EXPONENTIAL 3
+#define MBAR_KDE_LINEAR 4
+#define MBAR_KDE_COSINE 5
+/* x: N x d row-major host array (finite), bandwidth > 0.  The weights start as one column of ones. */
+int mbar_kde_create(mbar_kde** out, int device, int kernel, int d, int64_t N, const double* x, double bandwidth);
+void mbar_kde_destroy(mbar_kde* kde);
+/* v: N x C row-major host array, finite and >= 0 (zero weights are legal and contribute nothing). */
+int mbar_kde_set_weights(mbar_kde* kde, int64_t C, const double* v);
+/* q: M x d row-major host array (finite); out: M x C row-major host array of log densities. */
+int mbar_kde_eval(mbar_kde* kde, int64_t M, const double* q, double* out);
+/* The log-normaliser log(1 / integral of k_h over R^d) the library adds (host only; tests / documentation). */
+int mbar_kde_log_norm(int kernel, int d, double bandwidth, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,9 +7,10 @@ does not load the library or touch a GPU; the first computation does, and fails 
 """
 from . import mbar_solvers, testsystems, utils
 from ._lib import BackendUnavailable, MbarHipError, trim_device_cache
+from .fes import FES
 from .mbar import MBAR
 from .utils import ParameterError
 
-__all__ = ["MBAR", "mbar_solvers", "testsystems", "utils", "ParameterError", "BackendUnavailable", "MbarHipError",
+__all__ = ["MBAR", "FES", "mbar_solvers", "testsystems", "utils", "ParameterError", "BackendUnavailable", "MbarHipError",
            "trim_device_cache"]
 __version__ = "0.1.0"

@@ -110,6 +110,11 @@ SIGNATURES = {
     "mbar_ctx_timing": (C.c_int, [_ctx, C.c_int, _dp, _ip]),
     "mbar_ctx_timing_reset": (C.c_int, [_ctx]),
     "mbar_mfma_f64_peak": (C.c_int, [_ctx, _dp]),
+    "mbar_kde_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int64, _dp, C.c_double]),
+    "mbar_kde_destroy": (None, [C.c_void_p]),
+    "mbar_kde_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "mbar_kde_eval": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
+    "mbar_kde_log_norm": (C.c_int, [C.c_int, C.c_int, C.c_double, _dp]),
 }
 
 _lib = None

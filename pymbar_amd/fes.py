@@ -15,9 +15,10 @@ one vector and one label array (``mbar_ctx_fill_masked_rows``), the bin free ene
 reduction the solver already has (``mbar_lognum``: ``f_i = -log sum_{n in bin i} exp(-u_n - logden_n)``), and the
 covariance input ``W^T W`` of the augmented weights is one MFMA Gram sweep (``mbar_gram_w``).
 
-Only the histogram estimator's weight extraction is mirrored (binning conventions, reference points and the
-uncertainty formula of ``FES._get_fes_histogram``); kernel density / spline surfaces and the Monte Carlo sampler of the
-reference consume the same ``log_w_n`` vector and are not part of the K x N path.
+The histogram estimator's weight extraction is mirrored here (binning conventions, reference points and the uncertainty
+formula of ``FES._get_fes_histogram``).  :class:`FES` puts it behind the reference's class interface together with kernel-density
+surfaces, whose sums run in ``pymbar_amd.kde`` (its own device path, not the K x N matrix); spline surfaces and the Monte Carlo
+sampler of the reference are not provided.
 """
 import logging
 
@@ -147,3 +148,264 @@ def histogram_fes(mbar, u_n, sample_label, reference="from-lowest", reference_la
     finally:
         dm.close()
     return out
+
+
+_NOT_HERE = "not supported on this backend"
+
+
+class FES:
+    """``pymbar.FES`` on the MI355X path (pymbar/fes.py:74-1609): the MBAR solve on the device, histogram surfaces through
+    :func:`label_samples` / :func:`histogram_fes`, kernel-density surfaces through :class:`pymbar_amd.kde.KernelDensity`.
+
+    Supported: ``fes_type="histogram"`` (``get_fes`` from-lowest / from-specified, uncertainties None or "analytical") and
+    ``fes_type="kde"`` (from-lowest / from-specified / from-normalization, uncertainties None or "bootstrap").  Spline surfaces,
+    histogram bootstraps and the histogram from-normalization / all-differences modes raise ``ParameterError``.  The deliberate
+    differences from the reference are listed in INTEGRATION.md ("FES")."""
+
+    def __init__(self, u_kn, N_k, verbose=False, mbar_options=None, timings=True, **kwargs):
+        from .mbar import MBAR
+        from .utils import kln_to_kn
+
+        for key, val in kwargs.items():
+            logger.warning(f"Warning: parameter {key}={val} is unrecognized and unused.")
+        self.N_k = np.array(N_k, dtype=np.int64)
+        if np.ndim(u_kn) == 3:
+            u_kn = kln_to_kn(u_kn, N_k=self.N_k)
+        self.u_kn = np.array(u_kn, dtype=np.float64)
+        K, N = self.u_kn.shape
+        if np.sum(self.N_k) != N:
+            raise ParameterError(
+                "The sum of all N_k must equal the total number of samples (length of second dimension of u_kn.")
+        self.K, self.N = K, N
+        self.verbose = verbose
+        self.timings = bool(timings)
+        if mbar_options is None:
+            self.mbar = MBAR(self.u_kn, self.N_k)
+        else:  # the reference's defaults for the options it does not find (fes.py:160-200)
+            opts = dict(mbar_options)
+            for o in ("maximum_iterations", "relative_tolerance", "verbose", "initial_f_k", "solver_protocol", "initialize",
+                      "x_kindices"):
+                opts.setdefault(o, None)
+            if opts["maximum_iterations"] is None:
+                opts["maximum_iterations"] = 10000
+            if opts["relative_tolerance"] is None:
+                opts["relative_tolerance"] = 1.0e-7
+            if opts["initialize"] is None:
+                opts["initialize"] = "zeros"
+            self.mbar = MBAR(self.u_kn, self.N_k, maximum_iterations=opts["maximum_iterations"],
+                             relative_tolerance=opts["relative_tolerance"], verbose=bool(opts["verbose"]),
+                             initial_f_k=opts["initial_f_k"], solver_protocol=opts["solver_protocol"],
+                             initialize=opts["initialize"], x_kindices=opts["x_kindices"])
+        self.fes_type = None
+        self.kde = None
+        self.kdes = None
+        self.histogram_data = None
+        self.histogram_datas = None
+        self.n_bootstraps = 0
+        self.bootstrap_weights = None
+        if self.verbose:
+            logger.info("FES initialized")
+
+    # ---- generate ---------------------------------------------------------------------------------------------------------
+    def generate_fes(self, u_n, x_n, fes_type="histogram", histogram_parameters=None, kde_parameters=None,
+                     spline_parameters=None, n_bootstraps=0, seed=-1):
+        """Build the surface (pymbar/fes.py:221-438).  kde: the replicates of ``n_bootstraps > 0`` draw from the global NumPy
+        stream exactly as the reference does and become weight columns over the ORIGINAL positions (see ``_generate_kde``)."""
+        from timeit import default_timer as timer
+
+        from .utils import kn_to_n
+
+        result_vals = dict()
+        self.fes_type = fes_type
+        if np.ndim(u_n) == 2:
+            u_n = kn_to_n(u_n, N_k=self.N_k)
+        self.u_n = np.asarray(u_n, dtype=np.float64)
+        if seed >= 0:
+            np.random.seed(seed)
+        if not np.issubdtype(type(n_bootstraps), np.integer) or n_bootstraps == 1:
+            raise ValueError(f"n_bootstraps must be an integer of 0 or >=2, it was set to {n_bootstraps}")
+        self.n_bootstraps = n_bootstraps
+        start = timer()
+        x_n = np.asarray(x_n, dtype=np.float64)
+        if x_n.ndim == 1:
+            x_n = x_n.reshape(-1, 1)
+        if fes_type == "histogram":
+            if n_bootstraps > 0:
+                raise ParameterError(f"histogram surfaces with n_bootstraps > 0 are {_NOT_HERE}")
+            self._generate_histogram(x_n, histogram_parameters)
+        elif fes_type == "kde":
+            self._generate_kde(x_n, kde_parameters, n_bootstraps)
+        elif fes_type == "spline":
+            raise ParameterError(f"fes_type 'spline' is {_NOT_HERE}")
+        else:
+            raise ParameterError(f"fes_type {fes_type} is not defined!")
+        if self.timings:
+            result_vals["timing"] = timer() - start
+        return result_vals
+
+    def _normalized_weights(self):
+        log_w_n = self.mbar._computeUnnormalizedLogWeights(self.u_n)  # (fes.py:403-410)
+        w_n = np.exp(log_w_n - np.max(log_w_n))
+        return w_n / np.sum(w_n)
+
+    def _generate_kde(self, x_n, kde_parameters, n_bootstraps):
+        from .kde import SKLEARN_PARAMS, KernelDensity
+
+        kde_parameters = {} if kde_parameters is None else kde_parameters
+        for k in kde_parameters:
+            if k not in SKLEARN_PARAMS:
+                raise ParameterError(f"Warning: {k} is not a parameter in KernelDensity")
+        kde = KernelDensity()
+        kde.set_params(**{k: v for k, v in kde_parameters.items()})
+        self.kde_parameters = kde_parameters
+        if len(x_n) != self.N:
+            raise DataError("x_n must have one row per sample")
+        self.w_n = self._normalized_weights()
+        self._w_kn = None
+        kde.fit(x_n, sample_weight=self.w_n)
+        self.kde = kde
+        self._kde_dim = x_n.shape[1]
+        # Replicate b of the reference (fes.py:385-400, 696) refits on x_n[bootstrap_indices] with the b = 0 weights self.w_n:
+        # a KDE over the original positions with weights v_b[n] = sum of w_n[j] over the draws j with bootstrap_indices[j] = n.
+        # Its per-replicate MBAR solves (fes.py:403, one per state) change nothing a KDE surface reads and are skipped; the draws
+        # are the reference's, from the global stream, state by state, in the same order, and each skipped MBAR construction
+        # still takes the one number it draws for its own seed (mbar.py:273-274).
+        N_k = self.mbar.N_k
+        cols = np.empty((self.N, n_bootstraps + 1), dtype=np.float64)
+        cols[:, 0] = self.w_n
+        idx = np.arange(0, self.N)
+        for b in range(1, n_bootstraps + 1):
+            index = 0
+            for k in range(self.mbar.K):
+                idx[index:index + N_k[k]] = index + np.random.randint(0, N_k[k], size=N_k[k])
+                index += N_k[k]
+                np.random.randint(np.iinfo(np.int32).max)  # (the rseed draw of the skipped MBAR construction)
+            cols[:, b] = np.bincount(idx, weights=self.w_n, minlength=self.N)
+        self.bootstrap_weights = cols
+        self.kdes = None  # (the replicates are the columns 1..B of bootstrap_weights, evaluated in one device pass)
+
+    @property
+    def w_kn(self):
+        """``exp(mbar.Log_W_nk)`` (fes.py:413): built on first access only."""
+        if getattr(self, "_w_kn", None) is None:
+            self._w_kn = np.exp(self.mbar.Log_W_nk)
+        return self._w_kn
+
+    def _generate_histogram(self, x_n, histogram_parameters):
+        if histogram_parameters is None or "bin_edges" not in histogram_parameters:
+            raise ParameterError("histogram_parameters['bin_edges'] cannot be undefined with fes_type = histogram")
+        bins = histogram_parameters["bin_edges"]
+        if np.ndim(bins[0]) == 0:
+            bins = [bins]
+        bins = [np.asarray(b, dtype=np.float64) for b in bins]
+        self.histogram_parameters = dict(histogram_parameters, bin_edges=bins)
+        if x_n.shape != (self.N, len(bins)):
+            raise DataError("x_n and bin_edges have inconsistent dimension")
+        self.w_n = self._normalized_weights()
+        self._w_kn = None
+        labels, grid = label_samples(x_n, bins)
+        raw = histogram_fes(self.mbar, self.u_n, labels, uncertainty_method=None)
+        # bins are numbered in order of first appearance like the reference's bin_order (fes.py:552-560); grid_of_label[i] is
+        # the tuple of grid indices of bin i (None: the bin of the samples left of the grid)
+        self.histogram_data = dict(bins=bins, dims=len(bins), f=raw["f_raw"], sample_label=labels, grid_of_label=grid,
+                                   label_of_grid={g: i for i, g in enumerate(grid) if g is not None})
+
+    # ---- evaluate ---------------------------------------------------------------------------------------------------------
+    def get_fes(self, x, reference_point="from-lowest", fes_reference=None, uncertainty_method=None):
+        """Free energies (and uncertainties) at the points x (pymbar/fes.py:1167-1231)."""
+        x = np.array(x, dtype=np.float64)
+        if x.ndim <= 1:
+            x = x.reshape(-1, 1)
+        if self.fes_type == "histogram":
+            return self._get_fes_histogram(x, reference_point, fes_reference, uncertainty_method)
+        if self.fes_type == "kde":
+            return self._get_fes_kde(x, reference_point, fes_reference, uncertainty_method)
+        raise ParameterError(f"fes_type {self.fes_type} is not supported")
+
+    def _get_fes_kde(self, x, reference_point, fes_reference, uncertainty_method):
+        if x.shape[1] != self._kde_dim:
+            raise DataError("query coordinates have inconsistent dimension with the data the FES is fit to.")
+        if reference_point not in ("from-lowest", "from-specified", "from-normalization"):
+            raise ParameterError(f"reference point choice {reference_point} for kde is unavailable")
+        if uncertainty_method not in (None, "bootstrap"):
+            raise ParameterError(f"Uncertainty method {uncertainty_method} for kde is not implemented")
+        if uncertainty_method == "bootstrap" and self.n_bootstraps == 0:
+            raise ParameterError("Cannot calculate bootstrap error of bootstrap KDE's not determined")
+        M = len(x)
+        q = x
+        if reference_point == "from-specified":
+            ref = np.array(fes_reference, dtype=np.float64).reshape(1, -1)
+            if ref.shape[1] != self._kde_dim:
+                raise DataError("fes_reference has inconsistent dimension with the data the FES is fit to.")
+            q = np.vstack([x, ref])
+        if uncertainty_method == "bootstrap":
+            L = self.kde.score_samples_columns(q, self.bootstrap_weights)  # all replicates in one pass
+        else:
+            L = self.kde.score_samples(q)[:, None]
+        f_all = -L[:, 0]
+        f_i = f_all[:M]
+        fmin = 0.0
+        if reference_point == "from-lowest":
+            fmin = np.min(f_i)
+        elif reference_point == "from-specified":
+            fmin = f_all[M]
+        f_i = f_i - fmin
+        df_i = None
+        if uncertainty_method == "bootstrap":
+            df_i = np.std(-L[:M, 1:] - fmin, axis=1)  # (from-normalization: no shift, the spread is the same)
+        return {"f_i": f_i, "df_i": df_i}
+
+    def _get_fes_histogram(self, x, reference_point, fes_reference, uncertainty_method):
+        hd = self.histogram_data
+        bins, dims = hd["bins"], hd["dims"]
+        if x.shape[1] != dims:
+            raise DataError("query coordinates have inconsistent dimension with the data the FES is fit to.")
+        if uncertainty_method == "bootstrap":
+            raise ParameterError(f"bootstrap uncertainties of histogram surfaces are {_NOT_HERE}")
+        if uncertainty_method not in (None, "analytical"):
+            raise ParameterError(f"Uncertainty_method {uncertainty_method} is not a valid option")
+        if reference_point in ("from-normalization", "all-differences"):
+            raise ParameterError(f"reference point {reference_point!r} for histogram surfaces is {_NOT_HERE}")
+        ref_label = None
+        if reference_point == "from-specified":
+            if fes_reference is None:
+                raise ParameterError("Specified reference point for FES not given")
+            ref = np.atleast_1d(np.asarray(fes_reference, dtype=np.float64))
+            g = tuple(int(np.digitize(ref[d], bins[d]) - 1) for d in range(dims))
+            if any(gd < 0 or gd >= len(bins[d]) - 1 for d, gd in enumerate(g)) or g not in hd["label_of_grid"]:
+                raise ParameterError(f"Specified reference point {ref} is not in a populated bin of the FES region")
+            ref_label = hd["label_of_grid"][g]
+        elif reference_point != "from-lowest":
+            raise ParameterError(f"reference point {reference_point!r} is not a valid option")
+        res = histogram_fes(self.mbar, self.u_n, hd["sample_label"], reference=reference_point, reference_label=ref_label,
+                            uncertainty_method=uncertainty_method)
+        # each query point to its bin (fes.py:1419-1440): NaN outside the grid and in bins without samples
+        loc = np.stack([np.digitize(x[:, d], bins[d]) - 1 for d in range(dims)], axis=1)
+        f_x = np.full(len(x), np.nan)
+        df_x = np.full(len(x), np.nan)
+        for i, l in enumerate(loc):
+            if np.any(l < 0) or any(l[d] >= len(bins[d]) - 1 for d in range(dims)):
+                continue
+            j = hd["label_of_grid"].get(tuple(int(v) for v in l))
+            if j is None:
+                continue
+            f_x[i] = res["f_i"][j]
+            if uncertainty_method is not None:
+                df_x[i] = res["df_i"][j]
+        out = {"f_i": f_x}
+        if uncertainty_method is not None:
+            out["df_i"] = df_x
+        return out
+
+    # ---- accessors --------------------------------------------------------------------------------------------------------
+    def get_mbar(self):
+        if self.mbar is not None:
+            return self.mbar
+        raise DataError("MBAR in the FES object is not initialized, cannot return it.")
+
+    def get_kde(self):
+        if self.fes_type == "kde":
+            if self.kde is not None:
+                return self.kde
+            raise ParameterError("Can't return the KernelDensity object because kde not yet defined")
+        raise ParameterError("Can't return the KernelDensity object because fes_type != kde")
