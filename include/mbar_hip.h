@@ -394,6 +394,42 @@ int mbar_kde_eval(mbar_kde* kde, int64_t M, const double* q, double* out);
 /* The log-normaliser log(1 / integral of k_h over R^d) the library adds (host only; tests / documentation). */
 int mbar_kde_log_norm(int kernel, int d, double bandwidth, double* out);
 
+/* ---- lagged fluctuation sums of a timeseries (pymbar_amd.timeseries) ---------------------------------------------------------
+ * A handle holds T values of a series A (and of B for a cross-correlation; NULL: the autocorrelation) resident on one device,
+ * split into K segments of lengths seg[0..K) (sum T; K = 1 for one series).  The device holds A' = A - shift_a, B' = B - shift_b;
+ * products A'_n B'_(n+t) never cross a segment boundary.  Every sum is double-double with a fixed reduction order: two identical
+ * calls return identical bits.  Device memory: about 40 bytes per value, plus 48 bytes per origin of a rule.  Errors:
+ * mbar_last_error(NULL).  Not thread-safe (one handle per caller thread).
+ *
+ * For an origin s of one series (N = T - s values, suffix means mu_A, mu_B of A[s:], B[s:]) and lag t < N:
+ *     X_AB(s, t) = sum_{n = s}^{T-1-t} (A_n - mu_A)(B_(n+t) - mu_B),   X_BA likewise with A and B exchanged.
+ * The stopping rule of pymbar.timeseries.statistical_inefficiency runs on the device, one thread per origin:
+ *     sigma2 = X_AB(s, 0) / N;  then for t = 1, 2, 3, ... (fast: 1, 2, 4, 7, 11, ... with increment 1, 2, 3, ...) while t < N - 1
+ *     (fft: t < N): C = (X_AB + X_BA) / (2 (N - t) sigma2); stop when C <= 0 and t > mintime; g += 2 C (1 - t / N) increment;
+ *     finally g = max(g, 1).
+ * status: 1 = stopped by the C test at lag stop[o] (the last lag evaluated), 3 = ran to the end (stop[o]: the first lag not
+ * evaluated), 2 = zero variance (the suffix is constant, or sigma2 == 0): g = 1, the caller decides. */
+typedef struct mbar_acf mbar_acf;
+int mbar_acf_create(mbar_acf** out, int device, int64_t T, const double* a, const double* b, int64_t K, const int64_t* seg,
+                    double shift_a, double shift_b);
+void mbar_acf_destroy(mbar_acf* acf);
+/* The rule at every origin s = o nskip < T - 1 (o < (T - 2) / nskip + 1; K must be 1); g, stop, status: one entry per origin
+ * (stop, status may be NULL).  With fft the rule runs with fast off and through t = N - 1. */
+int mbar_acf_suffix_g(mbar_acf* acf, int64_t nskip, int fast, int64_t mintime, int fft, double* g, int64_t* stop, int32_t* status);
+/* The rule of statistical_inefficiency_multiple over the K segments (autocorrelation; shift_a must be the mean of all values):
+ * sigma2 = sum A'^2 / T, C = (sum of the valid products / their count) / sigma2, loop while t < max N_k - 1, weight
+ * (1 - t / (T / K)).  ct (or NULL): C by schedule entry (entry 0 is lag 0, not written), ct_cap >= mbar_acf_schedule_length(fast,
+ * max N_k); entries up to the stop are written. */
+int mbar_acf_multiple_g(mbar_acf* acf, int fast, int64_t mintime, double* g, int64_t* stop, int32_t* status, int64_t ct_cap,
+                        double* ct);
+/* Entries of the lag schedule with a lag below tmax, lag 0 included (host only). */
+int mbar_acf_schedule_length(int fast, int64_t tmax, int64_t* out);
+/* Raw lag sums for nlags lags and norig increasing origins; xab, xba: [nlags][norig] (xba may be NULL).  segments == 0 (K = 1):
+ * X_AB(s, t), X_BA(s, t) about the suffix means, 0 for t >= N.  segments != 0: sum over n in [o_i, o_(i+1)) (o_norig = T) of
+ * A'_n B'_(n+t) (B'_n A'_(n+t)) over the valid pairs, about the shifts. */
+int mbar_acf_lag_sums(mbar_acf* acf, int64_t nlags, const int64_t* lags, int64_t norig, const int64_t* origins, int segments,
+                      double* xab, double* xba);
+
 #ifdef __cplusplus
 }
 #endif

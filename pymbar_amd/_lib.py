@@ -115,6 +115,12 @@ SIGNATURES = {
     "mbar_kde_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "mbar_kde_eval": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
     "mbar_kde_log_norm": (C.c_int, [C.c_int, C.c_int, C.c_double, _dp]),
+    "mbar_acf_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, _dp, _dp, C.c_int64, _ip, C.c_double, C.c_double]),
+    "mbar_acf_destroy": (None, [C.c_void_p]),
+    "mbar_acf_suffix_g": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _dp, _ip, C.POINTER(C.c_int32)]),
+    "mbar_acf_multiple_g": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _dp, _ip, C.POINTER(C.c_int32), C.c_int64, _dp]),
+    "mbar_acf_schedule_length": (C.c_int, [C.c_int, C.c_int64, _ip]),
+    "mbar_acf_lag_sums": (C.c_int, [C.c_void_p, C.c_int64, _ip, C.c_int64, _ip, C.c_int, _dp, _dp]),
 }
 
 _lib = None

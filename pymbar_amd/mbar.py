@@ -9,7 +9,8 @@ fp64 matrix cores and only K x K linear algebra (eigh / pinv) runs on the host.
 
 The ``Log_W_nk`` consumers (``compute_expectations*``, ``compute_perturbed_free_energies``,
 ``compute_entropy_and_enthalpy``) live in :mod:`pymbar_amd.expectations` and are bound as
-methods below.  Not mirrored (not on the K x N solver path): FES, timeseries, the other estimators.
+methods below.  Not mirrored here (not on the K x N solver path): FES (:mod:`pymbar_amd.fes`), timeseries (:mod:`pymbar_amd.timeseries`), the
+other estimators.
 """
 import copy
 import contextlib

@@ -21,6 +21,7 @@ __all__ = [
     "config3_params",
     "config5",
     "ladder_params",
+    "correlated_timeseries_example",
 ]
 
 
@@ -117,3 +118,23 @@ def config5(seed=0, K=40, n_per_state=2500, unsampled=(7, 23)):
     for k in unsampled:
         N_k[k] = 0
     return harmonic_u_kn(O_k, K_k, N_k, seed=seed) + (O_k, K_k)
+
+
+def correlated_timeseries_example(N=10000, tau=5.0, seed=None):
+    """A Gaussian AR(1) series of length N with correlation time tau (Janke, Eq. 41), as float32.
+
+    Bit-identical to ``pymbar.testsystems.correlated_timeseries_example`` for the same seed: ``N`` standard normal draws from
+    ``np.random.RandomState(seed)``, then ``A_0 = e_0`` and ``A_n = rho A_(n-1) + sigma e_n`` evaluated in fp64 and stored as float32
+    after every step, with ``rho = exp(-1 / tau)`` and ``sigma = sqrt(1 - rho^2)``."""
+    e = np.random.RandomState(seed).randn(N)
+    rho = float(np.exp(-1.0 / tau))
+    sigma = float(np.sqrt(1.0 - rho * rho))
+    out = np.zeros([N], np.float32)
+    if N == 0:
+        return out
+    prev = float(np.float32(e[0]))
+    out[0] = prev
+    for n in range(1, N):
+        prev = float(np.float32(rho * prev + sigma * float(e[n])))
+        out[n] = prev
+    return out
