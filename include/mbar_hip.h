@@ -430,6 +430,48 @@ int mbar_acf_schedule_length(int fast, int64_t tmax, int64_t* out);
 int mbar_acf_lag_sums(mbar_acf* acf, int64_t nlags, const int64_t* lags, int64_t norig, const int64_t* origins, int segments,
                       double* xab, double* xba);
 
+/* ---- BAR and EXP estimators (pymbar_amd.other_estimators) -----------------------------------------------------------------
+ * A handle holds P independent problems resident on one device: problem p has n_f[p] forward work values and n_r[p] reverse
+ * ones (w_f, w_r: the problems' values concatenated in order).  Each side is cut into chunks of MBAR_BAR_CHUNK values, fixed
+ * whatever P and the other problems are; chunk partials merge in a fixed order, so two identical calls return identical bits and
+ * a problem's answer does not depend on the batch it is in.  Values may be +inf (a Fermi factor / exp(-w) of 0); NaN and -inf are
+ * rejected.  A side may be empty only for the one-sided moments (mbar_bar_moments); the BAR calls need both sides.
+ *
+ * With M = log(n_f / n_r), x_F = M + w_F - DeltaF and x_R = w_R + DeltaF - M:
+ *     log_numer = log sum_F 1 / (1 + exp(x_F)),   log_denom = log sum_R 1 / (1 + exp(x_R)),   F(DeltaF) = log_numer - log_denom,
+ * each sum in log space with a per-chunk shift fixed by the chunk's minimum w (the largest term), so no term is lost to
+ * overflow or underflow.  log_numer2 / log_denom2 are the same sums of the squared factors.  Errors: mbar_last_error(NULL). */
+#define MBAR_BAR_CHUNK 4096
+/* state of the reference's BAR root find for one problem (bar(), other_estimators.py), advanced by mbar_bar_step_host on the
+ * host and by the same function on the device.  Callers fill method (0 false-position, 1 bisection, 2 self-consistent
+ * iteration), iterated, maximum_iterations, relative_tolerance, DeltaF (the start) and, for methods 0 / 1, UpperB / LowerB (the
+ * bracket: exp(w_F) and -exp(w_R)); everything else zero.  want_moments: after a normal end, one more pass stores
+ * moments = (log_numer, log_denom, log_numer2, log_denom2) at DeltaF (iterated) or DeltaF_initial. */
+typedef struct mbar_bar_state {
+    double DeltaF, DeltaF_old, DeltaF_initial, UpperB, LowerB, FUpperB, FLowerB, FNew, relative_change, relative_tolerance;
+    double req[2];          /* the DeltaF values the next pass evaluates (nreq of them) */
+    double moments[4];
+    int64_t method, iterated, maximum_iterations, iteration, phase, status, nreq, nzero, want_moments, moments_pending;
+} mbar_bar_state;
+/* status: 0 running, 1 ended normally, 2 NaN at a bracket end (Delta_f = 0), 3 no bound on the root (BoundsError),
+ * 4 iteration limit (ConvergenceError).  nzero: evaluations of F so far. */
+typedef struct mbar_bar mbar_bar;
+int mbar_bar_create(mbar_bar** out, int device, int64_t P, const int64_t* n_f, const double* w_f, const int64_t* n_r,
+                    const double* w_r);
+void mbar_bar_destroy(mbar_bar* bar);
+/* out[p][5] = (F, log_numer, log_denom, log_numer2, log_denom2) at DeltaF = deltaf[p], every problem in one pass. */
+int mbar_bar_zero(mbar_bar* bar, const double* deltaf, double* out);
+/* Runs the root find of every problem to its end on the device: states[P] in (initial), out (final); passes: evaluation passes
+ * enqueued (or NULL).  The host reads only the status block between groups of passes. */
+int mbar_bar_solve(mbar_bar* bar, mbar_bar_state* states, int64_t* passes);
+/* One-sided moments of every side s = 2 p + (0 forward, 1 reverse), out[s][5]:
+ *     (logsumexp(-w), sum x, sum (x - mean x)^2, sum w, sum (w - mean w)^2),  x = exp(-w - max(-w)), means over the side.
+ * An empty side gives (-inf, 0, 0, 0, 0). */
+int mbar_bar_moments(mbar_bar* bar, double* out);
+/* Advances one state on the host with the same function the device runs: F[0..nreq) are F at req[0..nreq) (ignored in the
+ * first call, which issues the first requests).  Returns the status.  Needs no GPU. */
+int mbar_bar_step_host(mbar_bar_state* state, const double* F);
+
 #ifdef __cplusplus
 }
 #endif

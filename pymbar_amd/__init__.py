@@ -5,12 +5,13 @@ the solver-facing part of ``pymbar.MBAR``.  All K x N sweeps run in ``csrc/libmb
 (hand-written HIP, C ABI in ``include/mbar_hip.h``), reached through ctypes.  Importing the package
 does not load the library or touch a GPU; the first computation does, and fails loudly if it cannot.
 """
-from . import mbar_solvers, testsystems, utils
+from . import mbar_solvers, other_estimators, testsystems, utils
 from ._lib import BackendUnavailable, MbarHipError, trim_device_cache
 from .fes import FES
 from .mbar import MBAR
+from .other_estimators import bar, bar_overlap, bar_zero, exp, exp_gauss
 from .utils import ParameterError
 
-__all__ = ["MBAR", "FES", "mbar_solvers", "testsystems", "utils", "ParameterError", "BackendUnavailable", "MbarHipError",
-           "trim_device_cache"]
+__all__ = ["MBAR", "FES", "mbar_solvers", "other_estimators", "testsystems", "utils", "ParameterError", "BackendUnavailable",
+           "MbarHipError", "trim_device_cache", "bar", "bar_overlap", "bar_zero", "exp", "exp_gauss"]
 __version__ = "0.1.0"

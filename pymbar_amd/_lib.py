@@ -28,6 +28,15 @@ class MbarHipError(RuntimeError):
         self.code = code
 
 
+class BarState(C.Structure):
+    """``mbar_bar_state`` of include/mbar_hip.h: one problem's BAR root find."""
+    _fields_ = [(n, C.c_double) for n in ("DeltaF", "DeltaF_old", "DeltaF_initial", "UpperB", "LowerB", "FUpperB", "FLowerB", "FNew",
+                                          "relative_change", "relative_tolerance")] + [
+        ("req", C.c_double * 2), ("moments", C.c_double * 4)] + [
+        (n, C.c_int64) for n in ("method", "iterated", "maximum_iterations", "iteration", "phase", "status", "nreq", "nzero",
+                                 "want_moments", "moments_pending")]
+
+
 class SolveResult(C.Structure):
     _fields_ = [
         ("iterations", C.c_int64),
@@ -121,6 +130,12 @@ SIGNATURES = {
     "mbar_acf_multiple_g": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _dp, _ip, C.POINTER(C.c_int32), C.c_int64, _dp]),
     "mbar_acf_schedule_length": (C.c_int, [C.c_int, C.c_int64, _ip]),
     "mbar_acf_lag_sums": (C.c_int, [C.c_void_p, C.c_int64, _ip, C.c_int64, _ip, C.c_int, _dp, _dp]),
+    "mbar_bar_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, _ip, _dp, _ip, _dp]),
+    "mbar_bar_destroy": (None, [C.c_void_p]),
+    "mbar_bar_zero": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "mbar_bar_solve": (C.c_int, [C.c_void_p, C.POINTER(BarState), _ip]),
+    "mbar_bar_moments": (C.c_int, [C.c_void_p, _dp]),
+    "mbar_bar_step_host": (C.c_int, [C.POINTER(BarState), _dp]),
 }
 
 _lib = None

@@ -138,3 +138,26 @@ def correlated_timeseries_example(N=10000, tau=5.0, seed=None):
         prev = float(np.float32(rho * prev + sigma * float(e[n])))
         out[n] = prev
     return out
+
+
+def gaussian_work_example(N_F=200, N_R=200, mu_F=2.0, DeltaF=None, sigma_F=1.0, seed=None):
+    """Forward and reverse Gaussian work samples related by the Crooks fluctuation theorem, as [w_F, w_R].
+
+    Bit-identical to ``pymbar.testsystems.gaussian_work_example`` for the same arguments: exactly one of ``mu_F`` and ``DeltaF``
+    is given and fixes the other through DeltaF = mu_F - sigma_F^2 / 2 (Zwanzig); the reverse distribution has mean
+    -mu_F + sigma_F^2 and width sigma_F exp(mu_F - sigma_F^2 / 2 - DeltaF); ``N_F`` then ``N_R`` standard normal draws from
+    ``np.random.RandomState(seed)`` are scaled and shifted (w = z sigma + mu)."""
+    if (mu_F is not None) and (DeltaF is not None):
+        raise ValueError("mu_F and DeltaF are not independent, and cannot both be specified; one must be set to None.")
+    if (mu_F is None) and (DeltaF is None):
+        raise ValueError("Either mu_F or DeltaF must be specified.")
+    if mu_F is None:
+        mu_F = DeltaF + sigma_F**2 / 2.0
+    if DeltaF is None:
+        DeltaF = mu_F - sigma_F**2 / 2.0
+    rng = np.random.RandomState(seed)
+    mu_R = -mu_F + sigma_F**2
+    sigma_R = sigma_F * np.exp(mu_F - sigma_F**2 / 2.0 - DeltaF)
+    w_F = rng.randn(N_F) * sigma_F + mu_F
+    w_R = rng.randn(N_R) * sigma_R + mu_R
+    return [w_F, w_R]
