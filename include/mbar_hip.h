@@ -472,6 +472,28 @@ int mbar_bar_moments(mbar_bar* bar, double* out);
  * first call, which issues the first requests).  Returns the status.  Needs no GPU. */
 int mbar_bar_step_host(mbar_bar_state* state, const double* F);
 
+/* ---- weighted B-spline moments (fes_type="spline" of pymbar_amd.FES) ---------------------------------------------------------
+ * A handle holds N samples x (finite) resident on one device, optional group labels g (N values in [0, G), G <= 1024; default
+ * one group) and C columns of finite sample weights V (N x C).  mbar_bspline_moments returns, for a knot vector t of nbasis + k + 1
+ * non-decreasing finite values (0 <= k <= 7, k + 1 <= nbasis <= 1024),
+ *     M[g, c, i] = sum over the samples n with g_n = g of V[n, c] B_{i,k,t}(x_n),   i = 0 .. nbasis - 1,
+ * with B_{i,k,t} the basis element scipy.interpolate.BSpline(t, e_i, k) evaluates with extrapolate=True: samples below t[k] use
+ * the first polynomial piece, samples at or above t[nbasis] the last one.  The partial sums are merged in a fixed order without
+ * floating-point atomics: two identical calls return identical bits.  Columns are processed in passes of up to 32; with C <= 32
+ * the weights stay resident between calls.  Errors: mbar_last_error(NULL).  Not thread-safe (one handle per caller thread). */
+typedef struct mbar_bspline mbar_bspline;
+/* x: N host values (finite).  The handle starts with one group and one column of ones. */
+int mbar_bspline_create(mbar_bspline** out, int device, int64_t N, const double* x);
+void mbar_bspline_destroy(mbar_bspline* bs);
+/* g: N host labels in [0, G) (NULL: every sample in group 0 and G = 1). */
+int mbar_bspline_set_groups(mbar_bspline* bs, int G, const int* g);
+/* v: N x C row-major host array of finite weights. */
+int mbar_bspline_set_weights(mbar_bspline* bs, int64_t C, const double* v);
+/* t: nbasis + k + 1 host knots; out: G x C x nbasis row-major host array. */
+int mbar_bspline_moments(mbar_bspline* bs, int k, int nbasis, const double* t, double* out);
+/* Device time of the last mbar_bspline_moments call's kernels (all passes, HIP events), in ms. */
+int mbar_bspline_kernel_ms(mbar_bspline* bs, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,12 @@ SIGNATURES = {
     "mbar_bar_solve": (C.c_int, [C.c_void_p, C.POINTER(BarState), _ip]),
     "mbar_bar_moments": (C.c_int, [C.c_void_p, _dp]),
     "mbar_bar_step_host": (C.c_int, [C.POINTER(BarState), _dp]),
+    "mbar_bspline_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, _dp]),
+    "mbar_bspline_destroy": (None, [C.c_void_p]),
+    "mbar_bspline_set_groups": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
+    "mbar_bspline_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "mbar_bspline_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
+    "mbar_bspline_kernel_ms": (C.c_int, [C.c_void_p, _dp]),
 }
 
 _lib = None

@@ -345,6 +345,28 @@ hipError_t launch_kde_combine(hipStream_t s, const KdeLaunch& a, int cv, const d
 hipError_t launch_kde_exact(hipStream_t s, const KdeLaunch& a, int64_t N, int64_t npairs, const int64_t* pq, const double* logW,
                             double lognorm, double* out);
 
+// ---- weighted B-spline moments (mbar_k_bspline.hip; C ABI in mbar_bspline.cpp) ---------------------------------------------
+constexpr int BSP_MAX_K = 7;             // spline degree
+constexpr int BSP_MAX_BASIS = 1024;      // basis functions
+constexpr int BSP_MAX_GROUPS = 1024;     // sample groups
+constexpr int BSP_MAX_CB = 32;           // weight columns per pass; a pass runs with the smallest of {1, 2, 4, 8, 16, 32} that holds them
+constexpr int BSP_SLAB_ENTRIES = 768;    // (cell, column) entries of one wave's LDS slab: 4 slabs + knots stay below 64 KB
+struct BsplineLaunch {
+    int k, nbasis, cb;
+    const double* X;   // [N] samples
+    const int* G;      // [N] group labels (NULL: one group)
+    const double* V;   // [N][cb] weights of the pass
+    int64_t N;
+    const double* t;   // [nbasis + k + 1] knots
+    int64_t nchunks, chunk;  // grid x: `chunk` samples (a multiple of 256) per workgroup
+    int cells, tile_cells, ntiles;  // grid y: tiles of `tile_cells` of the cells = G nbasis output rows
+    double* part;      // [nchunks][cells][cb]
+};
+size_t bspline_lds_bytes(int k, int nbasis, int tile_cells, int cb);
+hipError_t launch_bspline(hipStream_t s, const BsplineLaunch& a);
+// out[cell * cb + c] = the chunk partials summed in chunk order
+hipError_t launch_bspline_combine(hipStream_t s, const BsplineLaunch& a, double* out);
+
 // ---- lagged fluctuation sums of a timeseries (mbar_k_acf.hip; C ABI in mbar_acf.cpp) ----------------------------------------
 constexpr int ACF_WG = 256;                  // threads per workgroup
 constexpr int ACF_R = 8;                     // consecutive positions per thread

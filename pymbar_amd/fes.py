@@ -17,14 +17,15 @@ covariance input ``W^T W`` of the augmented weights is one MFMA Gram sweep (``mb
 
 The histogram estimator's weight extraction is mirrored here (binning conventions, reference points and the uncertainty
 formula of ``FES._get_fes_histogram``).  :class:`FES` puts it behind the reference's class interface together with kernel-density
-surfaces, whose sums run in ``pymbar_amd.kde`` (its own device path, not the K x N matrix); spline surfaces and the Monte Carlo
-sampler of the reference are not provided.
+surfaces, whose sums run in ``pymbar_amd.kde`` (its own device path, not the K x N matrix), and spline surfaces with the
+reference's Monte Carlo sampler of the spline coefficients, whose sums over the samples are B-spline moments computed once per
+fit in ``pymbar_amd.bspline``.
 """
 import logging
 
 import numpy as np
 
-from .utils import DataError, ParameterError
+from .utils import ConvergenceError, DataError, ParameterError
 
 logger = logging.getLogger(__name__)
 
@@ -151,15 +152,21 @@ def histogram_fes(mbar, u_n, sample_label, reference="from-lowest", reference_la
 
 
 _NOT_HERE = "not supported on this backend"
+SPLINE_WEIGHTS = ("unbiasedstate", "biasedstates", "simplesum")
+SPLINE_SCIPY_METHODS = ("Newton-CG", "CG", "BFGS", "L-BFGS-B", "TNC", "SLSQP")
+_SPLINE_REQUIRED = ("spline_weights", "nspline", "kdegree", "xrange", "optimization_algorithm", "spline_initialize")
+CUSTOM_NR_MAXITER = 500  # Newton steps of optimization_algorithm="Custom-NR" before ConvergenceError
 
 
 class FES:
     """``pymbar.FES`` on the MI355X path (pymbar/fes.py:74-1609): the MBAR solve on the device, histogram surfaces through
     :func:`label_samples` / :func:`histogram_fes`, kernel-density surfaces through :class:`pymbar_amd.kde.KernelDensity`.
 
-    Supported: ``fes_type="histogram"`` (``get_fes`` from-lowest / from-specified, uncertainties None or "analytical") and
-    ``fes_type="kde"`` (from-lowest / from-specified / from-normalization, uncertainties None or "bootstrap").  Spline surfaces,
-    histogram bootstraps and the histogram from-normalization / all-differences modes raise ``ParameterError``.  The deliberate
+    Supported: ``fes_type="histogram"`` (``get_fes`` from-lowest / from-specified, uncertainties None or "analytical"),
+    ``fes_type="kde"`` (from-lowest / from-specified / from-normalization, uncertainties None or "bootstrap") and
+    ``fes_type="spline"`` (from-lowest / from-specified, uncertainties None or "bootstrap", information criteria, and the Monte
+    Carlo sampler of the coefficients: ``sample_parameter_distribution``, ``get_confidence_intervals``, ``get_mc_data``).
+    Histogram bootstraps and the histogram from-normalization / all-differences modes raise ``ParameterError``.  The deliberate
     differences from the reference are listed in INTEGRATION.md ("FES")."""
 
     def __init__(self, u_kn, N_k, verbose=False, mbar_options=None, timings=True, **kwargs):
@@ -203,6 +210,11 @@ class FES:
         self.histogram_datas = None
         self.n_bootstraps = 0
         self.bootstrap_weights = None
+        self.spline_parameters = None
+        self.spline_data = None
+        self.fes_function = None
+        self.fes_functions = None
+        self.mc_data = None
         if self.verbose:
             logger.info("FES initialized")
 
@@ -236,7 +248,7 @@ class FES:
         elif fes_type == "kde":
             self._generate_kde(x_n, kde_parameters, n_bootstraps)
         elif fes_type == "spline":
-            raise ParameterError(f"fes_type 'spline' is {_NOT_HERE}")
+            self._generate_spline(x_n, spline_parameters, n_bootstraps)
         else:
             raise ParameterError(f"fes_type {fes_type} is not defined!")
         if self.timings:
@@ -320,6 +332,8 @@ class FES:
             return self._get_fes_histogram(x, reference_point, fes_reference, uncertainty_method)
         if self.fes_type == "kde":
             return self._get_fes_kde(x, reference_point, fes_reference, uncertainty_method)
+        if self.fes_type == "spline":
+            return self._get_fes_spline(x, reference_point, fes_reference, uncertainty_method)
         raise ParameterError(f"fes_type {self.fes_type} is not supported")
 
     def _get_fes_kde(self, x, reference_point, fes_reference, uncertainty_method):
@@ -396,6 +410,553 @@ class FES:
         if uncertainty_method is not None:
             out["df_i"] = df_x
         return out
+
+    # ---- spline surfaces (pymbar/fes.py:701-1166, 1611-2477) --------------------------------------------------------------
+    def _setup_spline(self, spline_parameters):
+        """Check and complete the parameters (the reference's ``_setup_fes_spline``) on a copy of the caller's dict."""
+        sp = {} if spline_parameters is None else dict(spline_parameters)
+        for key in _SPLINE_REQUIRED:
+            if key not in sp:
+                raise ParameterError(f"spline_parameters without '{key}' are {_NOT_HERE}")
+        if sp["spline_weights"] not in SPLINE_WEIGHTS:
+            raise ParameterError(f"spline_weights {sp['spline_weights']!r} is not one of {SPLINE_WEIGHTS}")
+        if sp["spline_weights"] != "unbiasedstate" and "fkbias" not in sp:
+            raise ParameterError(f"spline_parameters without 'fkbias' are {_NOT_HERE} for spline_weights {sp['spline_weights']!r}")
+        sp.setdefault("objective", "ml")
+        if sp["objective"] not in ("ml", "map"):
+            raise ParameterError(f"objective may only be 'ml' or 'map': you have selected {sp['objective']}")
+        if sp["objective"] == "ml":
+            if sp.get("map_data") is not None:
+                raise ParameterError("if 'objective' is 'ml' then 'map_data' structure containing priors should not be included")
+            sp["map_data"] = dict(logprior=None, dlogprior=None, ddlogprior=None)
+        else:
+            if "map_data" not in sp:
+                raise ParameterError("if 'objective' is 'map' you must include 'map_data' structure")
+            if sp["map_data"] is None:
+                raise ParameterError("MAP data must be defined if objective is MAP")
+            for key, what in (("logprior", "log prior"), ("dlogprior", "d(log prior)"), ("ddlogprior", "d^2(log prior)")):
+                if sp["map_data"].get(key) is None:
+                    raise ParameterError(f"{what} must be included if objective is MAP")
+        algorithm = sp["optimization_algorithm"]
+        if algorithm != "Custom-NR":
+            if algorithm not in SPLINE_SCIPY_METHODS:
+                raise ParameterError(f"Optimization method {algorithm} is not supported")
+            opts = dict(sp.get("optimize_options", {"disp": True, "ftol": 1e-7, "xtol": 1e-7}))
+            sp["scipy_tol"] = opts.pop("tol", None)  # (scipy takes tol as an argument, not an option)
+        else:
+            opts = dict(sp.get("optimize_options", {}))
+            if "gtol" not in opts:
+                opts.setdefault("tol", 1e-7)
+        sp["optimize_options"] = opts
+        t = np.zeros(int(sp["nspline"]) + int(sp["kdegree"]) + 1)
+        from .bspline import check_spline_shape
+
+        check_spline_shape(t, int(sp["kdegree"]))
+        self.spline_parameters = sp
+
+    def _initial_spline_points(self):
+        """``(xinit, yinit)`` of the three initialisations (the reference's ``_get_initial_spline_points``)."""
+        from scipy.interpolate import make_lsq_spline
+
+        sp = self.spline_parameters
+        nspline, kdegree, xrange = int(sp["nspline"]), int(sp["kdegree"]), sp["xrange"]
+        init = sp["spline_initialize"]
+        if init == "bias_free_energies":
+            f_k = self.mbar.f_k
+            if "bias_centers" not in sp:  # equally spaced centres assumed
+                return np.linspace(xrange[0], xrange[1], self.mbar.K + 1)[1:-1], f_k
+            centers = np.asarray(sp["bias_centers"])
+            order = np.argsort(centers)
+            K = self.mbar.K
+            if K >= 2 * nspline:
+                return centers[order], f_k[order]
+            # fewer states than twice the spline points: a coarser least-squares spline through the centres, sampled densely
+            nfit = int(np.round(K / 2))
+            tfit = self._knots(nfit, kdegree, xrange)
+            coarse = make_lsq_spline(centers[order], f_k[order], tfit, k=kdegree)
+            xinit = np.linspace(xrange[0], xrange[1], num=2 * nspline)
+            return xinit, coarse(xinit)
+        if init == "explicit":
+            for key in ("xinit", "yinit"):
+                if key not in sp:
+                    raise ParameterError(f"spline_initialize set as explicit, but no {key} array specified")
+            return np.asarray(sp["xinit"]), np.asarray(sp["yinit"])
+        if init == "zeros":
+            xinit = np.linspace(xrange[0], xrange[1], nspline + kdegree)
+            return xinit, np.zeros(len(xinit))
+        raise ParameterError(f"Initialization type {init} not recognized")
+
+    @staticmethod
+    def _knots(nspline, kdegree, xrange):
+        """``nspline + kdegree + 1`` knots: kdegree + 1 at each end of xrange, equally spaced in between."""
+        t = np.zeros(nspline + kdegree + 1)
+        t[0:kdegree] = xrange[0]
+        t[kdegree:nspline + 1] = np.linspace(xrange[0], xrange[1], num=nspline + 1 - kdegree, endpoint=True)
+        t[nspline + 1:nspline + kdegree + 1] = xrange[1]
+        return t
+
+    def _initial_spline(self, xinit, yinit):
+        """The starting spline, the basis elements and their integration ranges (the reference's ``_get_initial_spline``)."""
+        from scipy.interpolate import BSpline, make_lsq_spline
+
+        sp = self.spline_parameters
+        nspline, kdegree = int(sp["nspline"]), int(sp["kdegree"])
+        t = self._knots(nspline, kdegree, sp["xrange"])
+        order = np.argsort(xinit)
+        b = make_lsq_spline(xinit[order], yinit[order], t, k=kdegree)
+        b.c = b.c - b.c[0]  # the surface is defined up to a constant: the first coefficient is held at zero
+        basis = [BSpline(b.t, np.eye(nspline)[i], b.k) for i in range(nspline)]
+        lo, hi = t[:nspline], t[kdegree + 1:kdegree + 1 + nspline]  # support of basis element i
+        xrangei = np.stack([lo, hi], axis=1)
+        xrangeij = np.stack([np.maximum(lo[:, None], lo[None, :]), np.minimum(hi[:, None], hi[None, :])], axis=2)
+        return dict(initial_coefficients=b.c[1:], bspline_derivatives=basis, bspline=b, xrangei=xrangei, xrangeij=xrangeij)
+
+    def _spline_columns(self, n_bootstraps):
+        """Weight columns of the moments: b = 0 and one per bootstrap replicate, drawn from the global stream as the reference
+        draws them (per state the resampled indices, then the one number each skipped per-state MBAR construction draws for its
+        seed).  unbiasedstate: the replicate's normalised weights over the ORIGINAL positions -- draw counts times the weights
+        of MBAR re-solved with the counts as sample multiplicities (the reference's MBAR on the resampled matrix, fes.py:382-395);
+        biasedstates / simplesum: the draw counts (a column of ones for b = 0)."""
+        from .mbar_solvers import solve_mbar_for_all_states
+
+        mbar, N = self.mbar, self.N
+        unbiased = self.spline_parameters["spline_weights"] == "unbiasedstate"
+        cols = np.empty((N, n_bootstraps + 1), dtype=np.float64)
+        cols[:, 0] = self.w_n if unbiased else 1.0
+        self._spline_f_boots = []
+        idx = np.arange(0, N)
+        N_k = mbar.N_k
+        for b in range(1, n_bootstraps + 1):
+            index = 0
+            for k in range(mbar.K):
+                idx[index:index + N_k[k]] = index + np.random.randint(0, N_k[k], size=N_k[k])
+                index += N_k[k]
+                np.random.randint(np.iinfo(np.int32).max)  # (the rseed draw of the skipped MBAR construction)
+            counts = np.bincount(idx, minlength=N).astype(np.float64)
+            if not unbiased:
+                cols[:, b] = counts
+                continue
+            dm = mbar._dm
+            dm.set_sample_weights(counts)
+            try:
+                f_b = solve_mbar_for_all_states(dm, N_k, mbar.f_k, mbar.states_with_samples, None)
+            finally:
+                dm.set_sample_weights(None)
+            dm.set_Nk(N_k)
+            log_w = -(self.u_n + dm.logden(f_b))
+            drawn = counts > 0
+            w = np.zeros(N)
+            w[drawn] = counts[drawn] * np.exp(log_w[drawn] - np.max(log_w[drawn]))
+            cols[:, b] = w / np.sum(w)
+            self._spline_f_boots.append(f_b)
+        return cols
+
+    def _generate_spline(self, x_n, spline_parameters, n_bootstraps):
+        from scipy.optimize import minimize
+
+        from .bspline import DeviceBSplineMoments
+
+        self._setup_spline(spline_parameters)
+        sp = self.spline_parameters
+        if x_n.shape != (self.N, 1):
+            raise DataError("spline surfaces need one 1-D coordinate per sample (x_n of shape (N,) or (N, 1))")
+        self.fes_function = None
+        self.fes_functions = [] if n_bootstraps > 0 else None
+        self.mc_data = None
+        self._spline_cache = {}
+        self.w_n = self._normalized_weights()
+        self._w_kn = None
+        self.spline_data = self._initial_spline(*self._initial_spline_points())
+        cols = self._spline_columns(n_bootstraps)
+        biased = sp["spline_weights"] != "unbiasedstate"
+        K = self.mbar.K
+        groups = np.asarray(self.mbar.x_kindices) if biased else None
+        self._n_kind = np.bincount(np.asarray(self.mbar.x_kindices), minlength=K)
+        with DeviceBSplineMoments(x_n[:, 0], groups=groups, n_groups=K if biased else None) as dev:
+            dev.set_weights(cols)
+            self._spline_M = dev.moments(self.spline_data["bspline"].t, int(sp["kdegree"]))  # (G, 1 + B, nspline)
+        func, grad, hess = self._bspline_calculate_f, self._bspline_calculate_g, self._bspline_calculate_h
+        for b in range(n_bootstraps + 1):
+            x0 = (self.spline_data["initial_coefficients"] if b == 0 else self.spline_data["first_coefficients"]).copy()
+            if sp["optimization_algorithm"] == "Custom-NR":
+                xi = self._custom_newton_raphson(x0, b)
+            else:
+                res = minimize(func, x0, args=(b,), method=sp["optimization_algorithm"], jac=grad,
+                               hess=hess if sp["optimization_algorithm"] == "Newton-CG" else None, tol=sp["scipy_tol"],
+                               options=sp["optimize_options"])
+                xi = res["x"]
+            spline = self._val_to_spline(xi)
+            if b == 0:
+                self.spline_data["first_coefficients"] = xi
+                mll = func(xi, 0)
+                npar = len(xi)
+                self.spline_data["aic"] = float(2 * npar + 2 * mll)
+                self.spline_data["bic"] = float(2 * np.log(self.N) * npar + 2 * mll)
+                self.fes_function = spline
+            else:
+                self.fes_functions.append(spline)
+
+    def _custom_newton_raphson(self, xi, b):
+        """optimization_algorithm="Custom-NR": Newton steps ``dx = lstsq(H, g)``; a step that raises the objective by more than
+        10 % (or makes it infinite) is shortened to 0.9 of itself, up to 5 times (infinite: until finite); stop when the
+        gradient norm is at most gtol (or tol)."""
+        opts = self.spline_parameters["optimize_options"]
+        tol = opts["gtol"] if "gtol" in opts else opts["tol"]
+        func, grad, hess = self._bspline_calculate_f, self._bspline_calculate_g, self._bspline_calculate_h
+        f = func(xi, b)
+        for _ in range(CUSTOM_NR_MAXITER):
+            g = grad(xi, b)
+            gnorm = float(np.sqrt(np.dot(g, g)))
+            if opts.get("disp"):
+                logger.info(f"f = {f:.10f}. gradient norm = {gnorm:.10f}")
+            if gnorm <= tol:
+                return xi
+            dx = np.linalg.lstsq(hess(xi, b), g, rcond=None)[0]
+            xold, fold = xi, f
+            xi = xold - dx
+            f = func(xi, b)
+            count = 0
+            while (f >= fold * 1.1 and count < 5) or (not np.isfinite(f) and count < 200):
+                dx = 0.9 * dx
+                xi = xold - dx
+                f = func(xi, b)
+                count += 1
+        raise ConvergenceError(f"Custom-NR did not reach gradient norm {tol} in {CUSTOM_NR_MAXITER} steps")
+
+    def _val_to_spline(self, xi):
+        """The BSpline with coefficients (c_0, xi) on the fitted knots (c_0 = 0)."""
+        from scipy.interpolate import BSpline
+
+        template = self.spline_data["bspline"]
+        c = np.zeros(len(xi) + 1)
+        c[0] = template.c[0]
+        c[1:] = xi
+        return BSpline(template.t, c, template.k)
+
+    def _spline_scaling(self):
+        K = self.mbar.K
+        if self.spline_parameters["spline_weights"] == "simplesum":
+            return (self.N / K) * np.ones(K)
+        return self.mbar.N_k
+
+    def _spline_integrals(self, xi, need_pE):
+        """The reference's quadratures at xi, cached per xi (so that the Hessian needs no preceding gradient call):
+        pF (unbiasedstate: the partition function of the surface; biased: one per state with its bias) and, with need_pE,
+        the normalised Boltzmann averages of the basis elements 1 .. nspline-1 (pE, or gkquad[i, k] per state)."""
+        from scipy.integrate import quad
+
+        key = np.asarray(xi, dtype=np.float64).tobytes()
+        ent = self._spline_cache.get(key)
+        if ent is None:
+            if len(self._spline_cache) > 8:
+                self._spline_cache.clear()
+            ent = self._spline_cache[key] = {}
+        if "pF" in ent and (not need_pE or "pE" in ent):
+            return ent
+        sp = self.spline_parameters
+        bloc = self._val_to_spline(xi)
+        xr = sp["xrange"]
+        basis = self.spline_data["bspline_derivatives"]
+        xrangei = self.spline_data["xrangei"]
+        nspline = int(sp["nspline"])
+        if sp["spline_weights"] == "unbiasedstate":
+            def boltz(x):
+                return np.exp(-bloc(x))
+
+            if "pF" not in ent:
+                ent["pF"] = quad(boltz, xr[0], xr[1])[0]
+            if need_pE:
+                pE = np.zeros(nspline - 1)
+                for i in range(nspline - 1):
+                    pE[i] = quad(lambda x, i=i: basis[i + 1](x) * boltz(x), xrangei[i + 1, 0], xrangei[i + 1, 1])[0]
+                    pE[i] /= ent["pF"]
+                ent["pE"] = pE
+        else:
+            fkbias = sp["fkbias"]
+            K = self.mbar.K
+
+            def boltz(x, k):
+                return np.exp(-bloc(x) - fkbias[k](x))
+
+            if "pF" not in ent:
+                ent["pF"] = np.array([quad(boltz, xr[0], xr[1], args=(k,))[0] for k in range(K)])
+            if need_pE:
+                gk = np.zeros([nspline - 1, K])
+                for k in range(K):
+                    for i in range(nspline - 1):
+                        pE = quad(lambda x, k, i=i: basis[i + 1](x) * boltz(x, k), xrangei[i + 1, 0], xrangei[i + 1, 1],
+                                  args=(k,))[0]
+                        gk[i, k] = pE / ent["pF"][k]
+                ent["pE"] = gk
+        ent["bloc"] = bloc
+        return ent
+
+    def _spline_data_dot(self, c, b):
+        """The data term sum over the samples of (weight) x s(x_n) for coefficients c, from the moments of column b."""
+        M = self._spline_M
+        w = self.spline_parameters["spline_weights"]
+        if w == "unbiasedstate":
+            return self.N * float(np.dot(c, M[0, b]))
+        f = 0.0
+        for k in range(self.mbar.K):
+            if w == "biasedstates":
+                f += float(np.dot(c, M[k, b]))
+            else:
+                f += (self.N / self.mbar.K) * (float(np.dot(c, M[k, b])) / self._n_kind[k])
+        return f
+
+    def _bspline_calculate_f(self, xi, b=0):
+        """Minus the log likelihood (ml) or posterior (map) of the surface with coefficients (0, xi), replicate b
+        (pymbar/fes.py:2102-2183): the data term from the moments, the partition functions by the reference's quadrature."""
+        ent = self._spline_integrals(xi, need_pE=False)
+        f = self._spline_data_dot(ent["bloc"].c, b)
+        if self.spline_parameters["spline_weights"] == "unbiasedstate":
+            f += self.N * np.log(ent["pF"])
+        else:
+            f += float(np.dot(self._spline_scaling(), np.log(ent["pF"])))
+        logprior = self.spline_parameters["map_data"]["logprior"]
+        if logprior is not None:
+            f -= logprior(np.concatenate([[0], xi], axis=None))
+        return float(f)
+
+    def _bspline_calculate_g(self, xi, b=0):
+        """Gradient of :meth:`_bspline_calculate_f` with respect to xi (pymbar/fes.py:2185-2298)."""
+        ent = self._spline_integrals(xi, need_pE=True)
+        M = self._spline_M
+        w = self.spline_parameters["spline_weights"]
+        if w == "unbiasedstate":
+            g = self.N * M[0, b, 1:]
+            g = g - self.N * ent["pE"]
+        else:
+            if w == "biasedstates":
+                g = np.sum(M[:, b, 1:], axis=0)
+            else:
+                g = np.zeros(M.shape[2] - 1)
+                for k in range(self.mbar.K):
+                    g += (self.N / self.mbar.K) * (M[k, b, 1:] / self._n_kind[k])
+            g = g - np.dot(ent["pE"], self._spline_scaling())
+        dlogprior = self.spline_parameters["map_data"]["dlogprior"]
+        if dlogprior is not None:
+            g = g - dlogprior(np.concatenate([[0], xi], axis=None))
+        return g
+
+    def _bspline_calculate_h(self, xi, b=0):
+        """Hessian of :meth:`_bspline_calculate_f` (pymbar/fes.py:2300-2414); it has no data term.  Self-contained: the
+        averages it needs come from the cache of xi or are computed here."""
+        from scipy.integrate import quad
+
+        ent = self._spline_integrals(xi, need_pE=True)
+        sp = self.spline_parameters
+        nspline, kdegree = int(sp["nspline"]), int(sp["kdegree"])
+        basis = self.spline_data["bspline_derivatives"]
+        xrangeij = self.spline_data["xrangeij"]
+        bloc, pF, pE = ent["bloc"], ent["pF"], ent["pE"]
+        N = self.N
+        if sp["spline_weights"] == "unbiasedstate":
+            h = -N * np.outer(pE, pE)
+            for i in range(nspline - 1):
+                for j in range(0, i + 1):
+                    if abs(i - j) <= kdegree:
+                        q = quad(lambda x: basis[i + 1](x) * basis[j + 1](x) * np.exp(-bloc(x)), xrangeij[i + 1, j + 1, 0],
+                                 xrangeij[i + 1, j + 1, 1])[0]
+                        h[i, j] += N * q / pF
+        else:
+            fkbias = sp["fkbias"]
+            scaling = self._spline_scaling()
+            K = self.mbar.K
+            h = np.zeros([nspline - 1, nspline - 1])
+            for k in range(K):
+                h += -scaling[k] * np.outer(pE[:, k], pE[:, k])
+            for i in range(nspline - 1):
+                for j in range(0, i + 1):
+                    if abs(i - j) <= kdegree:
+                        for k in range(K):
+                            q = scaling[k] * quad(lambda x, k: basis[i + 1](x) * basis[j + 1](x) * np.exp(-bloc(x) - fkbias[k](x)),
+                                                  xrangeij[i + 1, j + 1, 0], xrangeij[i + 1, j + 1, 1], args=(k,))[0]
+                            h[i, j] += q / pF[k]
+        for i in range(nspline - 1):
+            for j in range(i + 1, nspline - 1):
+                h[i, j] = h[j, i]
+        ddlogprior = sp["map_data"]["ddlogprior"]
+        if ddlogprior is not None:
+            h = h - ddlogprior(np.concatenate([[0], xi], axis=None))
+        return h
+
+    def get_information_criteria(self, type="akaike"):
+        """The Akaike or Bayesian information criterion of the fitted spline (pymbar/fes.py:1125-1166)."""
+        if self.fes_type != "spline":
+            raise ParameterError(f"Information criteria currently only defined for spline approaches, you are currently using {type}")
+        if type in ("akaike", "Akaike", "AIC", "aic"):
+            return self.spline_data["aic"]
+        if type in ("bayesian", "Bayesian", "BIC", "bic"):
+            return self.spline_data["bic"]
+        raise ParameterError(f"Information criteria of type '{type}' not defined")
+
+    def _get_fes_spline(self, x, reference_point, fes_reference, uncertainty_method):
+        if x.shape[1] != 1:
+            raise DataError("splines FES only supported in 1D")
+        x = x[:, 0]
+        f_i = self.fes_function(x)
+        if reference_point == "from-lowest":
+            fmin = np.min(f_i)
+        elif reference_point == "from-specified":
+            if fes_reference is None:
+                raise ParameterError("Specified reference point for FES not given")
+            fmin = float(self.fes_function(np.asarray(fes_reference, dtype=np.float64).reshape(-1)[0]))
+        else:
+            raise ParameterError(f"reference point {reference_point} not implemented for spline fes")
+        f_i = f_i - fmin
+        if uncertainty_method is None:
+            df_i = None
+        elif uncertainty_method == "bootstrap":
+            if self.fes_functions is None:
+                raise ParameterError("Cannot calculate via uncertainties error if bootstrapping was not performed running get_fes")
+            fall = np.stack([fb(x) - fmin for fb in self.fes_functions], axis=-1)
+            df_i = np.std(fall, axis=-1)
+        else:
+            raise ParameterError(f"Uncertainty method {uncertainty_method} for spline is not implemented")
+        return {"f_i": f_i, "df_i": df_i}
+
+    # ---- Monte Carlo over the spline coefficients (pymbar/fes.py:1690-2100) ------------------------------------------------
+    def sample_parameter_distribution(self, x_n, mc_parameters=None, decorrelate=True, verbose=True):
+        """Metropolis sampling of the normalised spline coefficients under the posterior of the fitted weighting
+        (pymbar/fes.py:1690-1833): the same proposals, the same draws from the global stream in the same order, the same
+        quadrature normalisation.  The likelihood's sums over x_n are moments computed once per call; the surface of
+        ``get_fes`` is left as fitted (the chain's current spline is ``mc_data["bspline"]``)."""
+        from scipy.integrate import quad
+        from scipy.interpolate import BSpline
+
+        from . import timeseries
+        from .bspline import DeviceBSplineMoments
+
+        if self.fes_type != "spline":
+            raise ParameterError("Sampling of posterior is only supported for spline type")
+        if self.spline_parameters is None:
+            raise ParameterError("Must specify spline_parameters to sample the distributions")
+        if self.fes_function is None:
+            raise ParameterError("Need to generate an initial splined FES using generate_fes before performing MCMC sampling")
+        sp = self.spline_parameters
+        weights, xr = sp["spline_weights"], sp["xrange"]
+        x_n = np.asarray(x_n, dtype=np.float64)
+        if x_n.reshape(-1).shape != (self.N,):
+            raise DataError("x_n must hold one 1-D coordinate per sample")
+        mc = {} if mc_parameters is None else dict(mc_parameters)
+        if mc_parameters is None:
+            logger.info("Using default MC parameters")
+        mc.setdefault("niterations", 5000)
+        mc.setdefault("fraction_change", 0.01)
+        mc.setdefault("sample_every", 50)
+        mc.setdefault("print_every", 1000)
+        mc.setdefault("logprior", lambda x: 0)
+        niterations, sample_every = int(mc["niterations"]), int(mc["sample_every"])
+        print_every, logprior = int(mc["print_every"]), mc["logprior"]
+
+        base = self.fes_function
+        t, kdeg = base.t, base.k
+        norm = quad(lambda x: np.exp(-base(x)), xr[0], xr[1])[0]
+        c = base.c + np.log(norm)
+        self.mc_data = dict(original_spline=BSpline(t, c.copy(), kdeg), naccept=0)
+
+        # the likelihood: the sums over x_n are c . moments (+ the bias sums of the biased weightings, fixed per call)
+        K, N = self.mbar.K, self.N
+        xk = np.asarray(self.mbar.x_kindices)
+        if weights == "unbiasedstate":
+            with DeviceBSplineMoments(x_n.reshape(-1)) as dev:
+                dev.set_weights(self.w_n)
+                m = dev.moments(t, kdeg)[0, 0]
+        else:
+            with DeviceBSplineMoments(x_n.reshape(-1), groups=xk, n_groups=K) as dev:
+                Mk = dev.moments(t, kdeg)[:, 0]
+            bias_sum = np.array([float(np.sum(sp["fkbias"][k](x_n[xk == k]))) for k in range(K)])
+            n_k = np.bincount(xk, minlength=K)
+
+        def loglikelihood(cc):
+            spline = BSpline(t, cc, kdeg)
+            if weights == "unbiasedstate":
+                return N * float(np.dot(cc, m))
+            ll = 0.0
+            for k in range(K):
+                lnZ = np.log(quad(lambda x, k: np.exp(-(spline(x) + sp["fkbias"][k](x))), xr[0], xr[1], args=(k,))[0])
+                if weights == "simplesum":
+                    ll += (N / K) * ((float(np.dot(cc, Mk[k])) + bias_sum[k]) / n_k[k])
+                    ll += (N / K) * lnZ
+                else:
+                    ll += float(np.dot(cc, Mk[k])) + bias_sum[k]
+                    ll += self.N_k[k] * lnZ
+            return ll
+
+        crange = np.max(c) - np.min(c)
+        dc = mc["fraction_change"] * crange
+        nsamples = (niterations + sample_every - 1) // sample_every
+        csamples = np.zeros([len(c), nsamples])
+        logposteriors = np.zeros(nsamples)
+        current = loglikelihood(c) - logprior(c)
+        for n in range(niterations):
+            rchange = dc * np.random.normal()
+            ci = np.random.randint(len(c))
+            cnew = c.copy()
+            cnew[ci] += rchange
+            trial = BSpline(t, cnew, kdeg)
+            cnew = cnew + np.log(quad(lambda x: np.exp(-trial(x)), xr[0], xr[1])[0])
+            proposed = loglikelihood(cnew) - logprior(cnew)
+            d = proposed - current
+            if d <= 0 or np.random.random() < np.exp(-d):
+                c, current = cnew, proposed
+                self.mc_data["naccept"] += 1
+            if n % sample_every == 0:
+                csamples[:, n // sample_every] = c
+                logposteriors[n // sample_every] = current
+            if n % print_every == 0 and verbose:
+                logger.info(f"MC Step {n} of {niterations}: log posterior {current}, coefficients {c}")
+        if verbose:
+            logger.info("Done MC sampling")
+        t_mc, g_mc, g_c = 0, None, None
+        if decorrelate:
+            t_mc, g_mc, _ = timeseries.detect_equilibration(logposteriors)
+            logger.info(f"First equilibration sample is {t_mc} of {len(logposteriors)}")
+            equil = logposteriors[t_mc:]
+            g_mc = timeseries.statistical_inefficiency(equil)
+            if verbose:
+                logger.info(f"Statistical inefficiency of log posterior is {g_mc:.3g}")
+            g_c = np.array([timeseries.statistical_inefficiency(csamples[i, t_mc:]) for i in range(len(c))])
+            if verbose:
+                logger.info(f"Time series for spline parameters are : {g_c}")
+            indices = timeseries.subsample_correlated_data(equil, g=g_mc)
+            logposteriors = equil[indices]
+            csamples = csamples[:, t_mc:][:, indices]
+            if verbose:
+                logger.info(f"samples after decorrelation : {csamples.shape[1]}")
+        self.mc_data.update(bspline=BSpline(t, c, kdeg), samples=csamples, logposteriors=logposteriors, mc_parameters=mc,
+                            acceptance_ratio=self.mc_data["naccept"] / niterations, nequil=t_mc, g_logposterior=g_mc,
+                            g_parameters=g_c, g=g_mc)
+        if verbose:
+            logger.info(f"Acceptance rate : {self.mc_data['acceptance_ratio']:5.3f}")
+
+    def get_confidence_intervals(self, xplot, plow, phigh, reference="zero"):
+        """Percentiles of the sampled surfaces at xplot (pymbar/fes.py:1835-1902)."""
+        from scipy.interpolate import BSpline
+
+        if self.mc_data is None:
+            raise DataError("No MC sampling has been done, cannot construct confidence intervals")
+        xplot = np.asarray(xplot, dtype=np.float64)
+        base = self.mc_data["original_spline"]
+        csamples = self.mc_data["samples"]
+        yvals = base(xplot)
+        samplevals = np.stack([BSpline(base.t, csamples[:, n], base.k)(xplot) for n in range(csamples.shape[1])], axis=-1)
+        if reference == "zero":
+            ref = np.min(yvals)
+        elif reference is None:
+            ref = 0
+        else:
+            raise ParameterError(f"{reference} is not a valid value for 'reference'")
+        return dict(plow=np.percentile(samplevals, plow, axis=-1) - ref, phigh=np.percentile(samplevals, phigh, axis=-1) - ref,
+                    median=np.percentile(samplevals, 50, axis=-1) - ref, values=yvals - ref)
+
+    def get_mc_data(self):
+        """The Monte Carlo results of :meth:`sample_parameter_distribution` (pymbar/fes.py:1904-1929)."""
+        if self.mc_data is None:
+            raise DataError("No MC sampling has been done, cannot construct confidence intervals")
+        return self.mc_data
 
     # ---- accessors --------------------------------------------------------------------------------------------------------
     def get_mbar(self):
