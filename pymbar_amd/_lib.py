@@ -237,3 +237,40 @@ def require_device():
         raise BackendUnavailable(
             "no HIP device visible: pymbar_amd computes only on an MI355X (gfx950) through "
             "libmbar_hip.so and has no CPU fallback")
+
+
+def default_device(device=None):
+    """``device``, or this process's GPU when it is None: the local rank modulo the visible devices."""
+    if device is None:
+        device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, device_count())
+    return int(device)
+
+
+def ptr(a, t=_dp):
+    """ctypes pointer to the data of a numpy array (None for None)."""
+    return a.ctypes.data_as(t) if a is not None else None
+
+
+class Handle:
+    """Owner of one library handle ``_h``: released by ``close``, at the end of a ``with`` block or when collected.
+    Subclasses name the library function that releases it in ``_destroy``."""
+
+    _destroy = None
+    _h = None
+
+    def close(self):
+        if self._h:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -7,7 +7,6 @@ is a dot product with the moment vector ``m_i = sum_n w_n B_i(x_n)``.  :class:`D
 ``csrc/libmbar_hip.so`` (``mbar_bspline_*`` of include/mbar_hip.h, kernels in ``csrc/mbar_k_bspline.hip``), per sample group
 and per weight column, exactly and reproducibly; ``B_i`` is ``scipy.interpolate.BSpline(t, e_i, k)`` with extrapolation."""
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -17,12 +16,6 @@ from .utils import DataError, ParameterError
 MAX_DEGREE = 7
 MAX_BASIS = 1024
 MAX_GROUPS = 1024
-
-_dp = C.POINTER(C.c_double)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(_dp)
 
 
 def check_spline_shape(t, k):
@@ -39,10 +32,12 @@ def check_spline_shape(t, k):
     return t, k, nbasis
 
 
-class DeviceBSplineMoments:
+class DeviceBSplineMoments(_lib.Handle):
     """N samples resident on one device, with optional group labels and C weight columns (an ``mbar_bspline`` handle).
 
     ``moments(t, k)[g, c, i] = sum over the samples n of group g of V[n, c] B_{i,k,t}(x_n)``."""
+
+    _destroy = "mbar_bspline_destroy"
 
     def __init__(self, x, groups=None, n_groups=None, device=None):
         x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
@@ -53,11 +48,9 @@ class DeviceBSplineMoments:
         _lib.require_device()
         self._lib = _lib.load_library()
         self.n_samples = len(x)
-        if device is None:
-            device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _lib.device_count())
-        self.device = int(device)
+        self.device = _lib.default_device(device)
         self._h = C.c_void_p()
-        _lib.check(self._lib.mbar_bspline_create(C.byref(self._h), self.device, self.n_samples, _ptr(x)))
+        _lib.check(self._lib.mbar_bspline_create(C.byref(self._h), self.device, self.n_samples, _lib.ptr(x)))
         self.n_groups = 1
         self.n_columns = 1
         if groups is not None:
@@ -85,13 +78,13 @@ class DeviceBSplineMoments:
             raise ParameterError("weights must be (n_samples, C)")
         if not np.all(np.isfinite(V)):
             raise DataError("weights must be finite")
-        _lib.check(self._lib.mbar_bspline_set_weights(self._h, V.shape[1], _ptr(V)))
+        _lib.check(self._lib.mbar_bspline_set_weights(self._h, V.shape[1], _lib.ptr(V)))
         self.n_columns = V.shape[1]
 
     def moments(self, t, k):
         t, k, nbasis = check_spline_shape(t, k)
         out = np.empty((self.n_groups, self.n_columns, nbasis), dtype=np.float64)
-        _lib.check(self._lib.mbar_bspline_moments(self._h, k, nbasis, _ptr(t), _ptr(out)))
+        _lib.check(self._lib.mbar_bspline_moments(self._h, k, nbasis, _lib.ptr(t), _lib.ptr(out)))
         return out
 
     def kernel_ms(self):
@@ -99,20 +92,3 @@ class DeviceBSplineMoments:
         ms = C.c_double(0.0)
         _lib.check(self._lib.mbar_bspline_kernel_ms(self._h, C.byref(ms)))
         return ms.value
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.mbar_bspline_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

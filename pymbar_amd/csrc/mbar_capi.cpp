@@ -653,13 +653,13 @@ int mbar_ctx_create(mbar_ctx** out, int device, int64_t K, int64_t N_local) {
     // (N_local = 0 is a legal shard: with more ranks than 16-sample tiles a rank owns no column, yet it must take part in every
     // collective of the loop; it keeps one all-padding tile so that every kernel has something to launch on)
     if (K < 1 || N_local < 0) return fail(nullptr, MBAR_ERR_ARG, "K must be >= 1 and N_local >= 0");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-        return fail(nullptr, MBAR_ERR_NODEVICE, "no HIP device visible (libmbar_hip needs an MI355X / gfx950 GPU)");
-    if (device < 0 || device >= n) return fail(nullptr, MBAR_ERR_ARG, "device index out of range");
+    DevInfo di;
+    int rc = open_device(device, &di);
+    if (rc) return rc;
     mbar_ctx* c = new mbar_ctx();
     g_live_contexts.fetch_add(1);
     c->device = device;
+    c->num_cu = di.num_cu;
     c->K = K;
     c->Kp = padded_K(K);
     c->N = N_local;
@@ -675,33 +675,14 @@ int mbar_ctx_create(mbar_ctx** out, int device, int64_t K, int64_t N_local) {
             return rc_;                                                                             \
         }                                                                                           \
     } while (0)
-    CRT(hipSetDevice(device));
-    // (hipGetDeviceProperties and stream creation cost milliseconds: properties are looked up once per device, streams of
-    // destroyed contexts are kept for the next one)
-    DevInfo di;
+    // (stream creation costs milliseconds: streams of destroyed contexts are kept for the next one)
     {
         std::lock_guard<std::mutex> lock(g_dev_mu);
-        auto it = g_dev_info.find(device);
-        if (it == g_dev_info.end()) {
-            hipDeviceProp_t p;
-            CRT(hipGetDeviceProperties(&p, device));
-            di.num_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-            di.arch = p.gcnArchName;
-            g_dev_info[device] = di;
-        } else {
-            di = it->second;
-        }
         auto& pool = g_stream_pool[device];
         if (!pool.empty()) {
             c->stream = pool.back();
             pool.pop_back();
         }
-    }
-    c->num_cu = di.num_cu;
-    if (std::strncmp(di.arch.c_str(), "gfx950", 6) != 0) {
-        int rc = fail(nullptr, MBAR_ERR_NODEVICE, std::string("device is ") + di.arch + ", this library is built for gfx950 only");
-        mbar_ctx_destroy(c);
-        return rc;
     }
     if (!c->stream) CRT(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const size_t ubytes = (size_t)c->Kp * c->ld * sizeof(double);

@@ -2,6 +2,8 @@
 // helpers the translation units of the host side share -- mbar_capi.cpp (contexts, uploads, options, evaluations), mbar_loops.cpp
 // (the solver loops the reference writes in Python), mbar_comm.cpp (RCCL loader, in-process transport, all-reduce),
 // mbar_host.cpp (allocator state, host-side K x K linear algebra, content digest).
+// The handles of the other backends (mbar_kde.cpp, mbar_acf.cpp, mbar_bar.cpp, mbar_bspline.cpp) share the layer below the
+// context: Handle, DevBuf, create_handle / destroy_handle, ColumnPasses.
 #pragma once
 #include "../../include/mbar_hip.h"
 #include "mbar_internal.h"
@@ -350,6 +352,127 @@ int fail(mbar_ctx* c, int code, const std::string& msg);
         if (_e != hipSuccess)                                                                    \
             return fail(ctx, MBAR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
     } while (0)
+inline int bad_arg(const std::string& msg) { return fail(nullptr, MBAR_ERR_ARG, msg); }
+
+// ---- the handles of the other backends (mbar_kde, mbar_acf, mbar_bar, mbar_bspline) -----------------------------------------
+// A handle derives from Handle, holds its device memory in DevBuf members, is made by create_handle and released by
+// destroy_handle: no buffer list to keep in step with the struct.
+
+// One block of the cache, owned: freed when the owner goes
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;  // capacity in elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) {
+        o.p = nullptr;
+        o.n = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    void reset() {
+        if (p) (void)cache_free(p);
+        p = nullptr;
+        n = 0;
+    }
+    // at least `want` elements (contents are not kept)
+    auto grow(size_t want) -> hipError_t {
+        if (n >= want) return hipSuccess;
+        if (p) {
+            hipError_t e = cache_free(p);
+            if (e != hipSuccess) return e;
+        }
+        p = nullptr;
+        n = 0;
+        hipError_t e = cache_malloc((void**)&p, want * sizeof(T));
+        if (e == hipSuccess) n = want;
+        return e;
+    }
+};
+
+// Makes `device` current after checking that it exists and is a gfx950; its properties are looked up once per process
+int open_device(int device, DevInfo* out);
+
+// Device and stream of a handle, and its place among the live contexts (the last one to go trims the cache)
+struct Handle {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    Handle() { g_live_contexts.fetch_add(1); }
+    Handle(const Handle&) = delete;
+    Handle& operator=(const Handle&) = delete;
+    ~Handle() {
+        if (stream) (void)hipStreamDestroy(stream);
+        if (g_live_contexts.fetch_sub(1) == 1) g_mem.trim_to(g_mem.idle_limit());
+    }
+};
+
+// The stream is drained before the members give their blocks back: the pool is shared, and no block may return to it while a
+// kernel still uses it
+template <class H>
+void destroy_handle(H* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    delete h;
+}
+
+// Opens the device, makes the handle with its own stream and runs init(h, device info); on a failure the handle is destroyed
+// and the first error stays the last one
+template <class H, class Init>
+int create_handle(H** out, int device, Init&& init) {
+    DevInfo di;
+    int rc = open_device(device, &di);
+    if (rc) return rc;
+    H* h = new H();
+    h->device = device;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    rc = e == hipSuccess ? init(h, di)
+                         : fail(nullptr, MBAR_ERR_HIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e));
+    if (rc != MBAR_OK) {
+        const std::string msg = g_last_error;
+        destroy_handle(h);
+        return fail(nullptr, rc, msg);
+    }
+    *out = h;
+    return MBAR_OK;
+}
+
+// Weight columns: the host copy of every column and the device buffer of one pass of cb columns ([pitch][cb], zero on the
+// padding columns and rows).  `widths` are the pass widths the kernels are instantiated for, ascending.
+struct ColumnPasses {
+    std::vector<int> widths;
+    std::vector<double> host;  // [rows][C]
+    int64_t rows = 0, C = 0;
+    DevBuf<double> dev;
+    int64_t pass = -1;  // first column of the pass the device buffer holds (-1: none)
+    int cb = 0;
+    explicit ColumnPasses(std::vector<int> w) : widths(std::move(w)) {}
+    // the smallest width that holds `cols` columns
+    int width(int64_t cols) const {
+        for (int w : widths)
+            if (w >= cols) return w;
+        return widths.back();
+    }
+    // new columns ([rows][C]): a copy of v, or (v NULL) a host copy for the caller to fill; nothing is on the device
+    double* reset(int64_t rows_, int64_t C_, const double* v = nullptr) {
+        rows = rows_;
+        C = C_;
+        if (v) host.assign(v, v + rows * C);
+        else host.resize((size_t)rows * C);
+        pass = -1;
+        return host.data();
+    }
+    bool holds(int64_t c0, int width_) const { return pass == c0 && cb == width_; }
+    // columns [c0, c0 + cv) as a pass of width w, rows padded to `pitch` (no copy when the buffer holds them)
+    int upload(int64_t c0, int cv, int w, int64_t pitch);
+};
 
 
 hipEvent_t get_event(mbar_ctx* c);

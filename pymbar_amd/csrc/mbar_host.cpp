@@ -1,7 +1,8 @@
 // Host-only parts of libmbar_hip.so: the state of the caching allocator, the K x K linear algebra of the host-driven loop (Cholesky
 // factorisation of the gauge-fixed Hessian -- blocked and threaded from 320 / 448 unknowns -- with a Jacobi pseudo-inverse
 // fallback: the minimum-norm semantics of numpy.linalg.lstsq, mbar_solvers.py:582-583), the content digest behind the resident
-// cache of host matrices, and the host face of the bootstrap stream.  Nothing here touches a kernel.
+// cache of host matrices, the host face of the bootstrap stream, and the out-of-line parts of the handle layer (open_device,
+// ColumnPasses::upload).  Nothing here touches a kernel.
 #include "mbar_ctx.h"
 
 using namespace mbar;
@@ -16,6 +17,45 @@ std::atomic<int> g_live_contexts{0};
 std::mutex g_dev_mu;
 std::map<int, DevInfo> g_dev_info;
 std::map<int, std::vector<hipStream_t>> g_stream_pool;
+
+int open_device(int device, DevInfo* out) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+        return fail(nullptr, MBAR_ERR_NODEVICE, "no HIP device visible (libmbar_hip needs an MI355X / gfx950 GPU)");
+    if (device < 0 || device >= n) return bad_arg("device index out of range");
+    HIPCHK(nullptr, hipSetDevice(device));
+    // (hipGetDeviceProperties costs milliseconds)
+    DevInfo di;
+    {
+        std::lock_guard<std::mutex> lock(g_dev_mu);
+        auto it = g_dev_info.find(device);
+        if (it == g_dev_info.end()) {
+            hipDeviceProp_t p;
+            HIPCHK(nullptr, hipGetDeviceProperties(&p, device));
+            di.num_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+            di.arch = p.gcnArchName;
+            g_dev_info[device] = di;
+        } else {
+            di = it->second;
+        }
+    }
+    if (std::strncmp(di.arch.c_str(), "gfx950", 6) != 0)
+        return fail(nullptr, MBAR_ERR_NODEVICE, "device is " + di.arch + ", this library is built for gfx950 only");
+    *out = di;
+    return MBAR_OK;
+}
+
+int ColumnPasses::upload(int64_t c0, int cv, int w, int64_t pitch) {
+    if (holds(c0, w)) return MBAR_OK;
+    HIPCHK(nullptr, dev.grow((size_t)pitch * w));
+    std::vector<double> stage((size_t)pitch * w, 0.0);
+    for (int64_t n = 0; n < rows; ++n)
+        for (int c = 0; c < cv; ++c) stage[(size_t)n * w + c] = host[(size_t)n * C + c0 + c];
+    HIPCHK(nullptr, hipMemcpy(dev, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
+    pass = c0;
+    cb = w;
+    return MBAR_OK;
+}
 
 double now_ms() {
     using namespace std::chrono;

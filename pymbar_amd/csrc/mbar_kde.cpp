@@ -1,5 +1,5 @@
-// Host side of the weighted kernel-density sums (include/mbar_hip.h, "weighted kernel-density sums"): the mbar_kde handle, its
-// device buffers (taken from the block cache of mbar_ctx.h), the column passes and the exact recomputation of the rare
+// Host side of the weighted kernel-density sums (include/mbar_hip.h, "weighted kernel-density sums"): the mbar_kde handle (on the
+// handle layer of mbar_ctx.h), the per-column scaling of the weights and their passes, and the exact recomputation of the rare
 // (query, column) pairs the combine kernel flags.  Kernels: mbar_k_kde.hip.
 #include <cmath>
 
@@ -8,58 +8,22 @@
 using namespace mbar;
 using namespace mbar::host;
 
-struct mbar_kde {
-    int device = 0, kernel = 0, d = 1, num_cu = 256;
+struct mbar_kde : Handle {
+    int kernel = 0, d = 1, num_cu = 256;
     int64_t N = 0, ldx = 0;
     double h = 1.0, lognorm = 0.0;
-    hipStream_t stream = nullptr;
-    double* X = nullptr;             // [d][ldx]
-    // weights: host copy of every column (scaled by a power of two per column, so that its largest entry lies in [1, 2)),
-    // log of the column totals, and the device buffer of one pass
-    int64_t C = 0;
-    std::vector<double> Vh;          // [N][C]
+    DevBuf<double> X;                // [d][ldx]
+    // weights: every column scaled by a power of two, so that its largest entry lies in [1, 2), and the log of the column totals
+    ColumnPasses V{{1, 4, 8, 16, 24, 32}};
     std::vector<double> logW;        // [C]
-    double* V = nullptr;
-    size_t v_doubles = 0;
-    int64_t v_pass = -1;             // first column of the pass the device buffer holds (-1: none)
-    int v_cb = 0;
-    double* logW_d = nullptr;        // [KDE_MAX_CB]
-    double* part = nullptr;
-    size_t part_doubles = 0;
-    double* Q = nullptr;
-    size_t q_doubles = 0;
-    double* out = nullptr;           // [M][cb] log densities of a pass, then the recomputed pairs
-    size_t out_doubles = 0;
-    int* flag = nullptr;
-    size_t flag_ints = 0;
-    int64_t* pq = nullptr;
-    size_t pq_words = 0;
+    DevBuf<double> logW_d;           // [KDE_MAX_CB] of the pass on the device
+    DevBuf<double> part, Q;
+    DevBuf<double> out;              // [M][cb] log densities of a pass, then the recomputed pairs
+    DevBuf<int> flag;
+    DevBuf<int64_t> pq;
 };
 
 namespace {
-
-int kfail(const std::string& msg, int code = MBAR_ERR_ARG) { return fail(nullptr, code, msg); }
-
-#define KHIP(expr)                                                                                        \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) return kfail(std::string(#expr) + ": " + hipGetErrorString(_e), MBAR_ERR_HIP); \
-    } while (0)
-
-// grow a cached device buffer (contents are not kept)
-template <typename T>
-hipError_t grow(T** p, size_t* have, size_t want) {
-    if (*have >= want) return hipSuccess;
-    if (*p) {
-        hipError_t e = cache_free(*p);
-        if (e != hipSuccess) return e;
-    }
-    *p = nullptr;
-    *have = 0;
-    hipError_t e = cache_malloc((void**)p, want * sizeof(T));
-    if (e == hipSuccess) *have = want;
-    return e;
-}
 
 // log of the normaliser 1 / integral over R^d of k(|x| / h), k the kernel on the unit scale.  With V_d = pi^(d/2) / Gamma(d/2 + 1)
 // the volume of the unit d-ball and S_(d-1) = d V_d its surface, the integral is S_(d-1) int_0^1 r^(d-1) k(r) dr h^d:
@@ -92,13 +56,6 @@ double log_norm(int kernel, int d, double h) {
     }
 }
 
-int pass_width(int64_t cols) {
-    static const int cbs[] = {1, 4, 8, 16, 24, 32};
-    for (int cb : cbs)
-        if (cb >= cols) return cb;
-    return KDE_MAX_CB;
-}
-
 // Neumaier-compensated sum (the column totals: N up to 1e9 positive terms)
 double csum(const double* v, int64_t n, int64_t stride) {
     double s = 0.0, comp = 0.0;
@@ -111,20 +68,13 @@ double csum(const double* v, int64_t n, int64_t stride) {
     return s + comp;
 }
 
-// upload the weights of columns [c0, c0 + cv) as a pass of width cb: [ldx][cb], zero on the padding columns and rows
+// the weights and log column totals of columns [c0, c0 + cv) as a pass of width cb
 int upload_pass(mbar_kde* k, int64_t c0, int cv, int cb) {
-    if (k->v_pass == c0 && k->v_cb == cb) return MBAR_OK;
-    KHIP(grow(&k->V, &k->v_doubles, (size_t)k->ldx * cb));
-    std::vector<double> stage((size_t)k->ldx * cb, 0.0);
-    for (int64_t n = 0; n < k->N; ++n)
-        for (int c = 0; c < cv; ++c) stage[(size_t)n * cb + c] = k->Vh[(size_t)n * k->C + c0 + c];
-    KHIP(hipMemcpy(k->V, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (k->V.holds(c0, cb)) return MBAR_OK;
     std::vector<double> lw(KDE_MAX_CB, 0.0);
     for (int c = 0; c < cv; ++c) lw[c] = k->logW[c0 + c];
-    KHIP(hipMemcpy(k->logW_d, lw.data(), lw.size() * sizeof(double), hipMemcpyHostToDevice));
-    k->v_pass = c0;
-    k->v_cb = cb;
-    return MBAR_OK;
+    HIPCHK(nullptr, hipMemcpy(k->logW_d, lw.data(), lw.size() * sizeof(double), hipMemcpyHostToDevice));
+    return k->V.upload(c0, cv, cb, k->ldx);
 }
 
 }  // namespace
@@ -132,123 +82,86 @@ int upload_pass(mbar_kde* k, int64_t c0, int cv, int cb) {
 extern "C" {
 
 int mbar_kde_log_norm(int kernel, int d, double bandwidth, double* out) {
-    if (!out) return kfail("out is NULL");
-    if (kernel < 0 || kernel > KDE_COSINE) return kfail("unknown kernel");
-    if (d < 1 || d > KDE_MAX_D) return kfail("d must be 1 .. 8");
-    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth)) return kfail("bandwidth must be positive and finite");
+    if (!out) return bad_arg("out is NULL");
+    if (kernel < 0 || kernel > KDE_COSINE) return bad_arg("unknown kernel");
+    if (d < 1 || d > KDE_MAX_D) return bad_arg("d must be 1 .. 8");
+    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth)) return bad_arg("bandwidth must be positive and finite");
     *out = log_norm(kernel, d, bandwidth);
     return MBAR_OK;
 }
 
 int mbar_kde_create(mbar_kde** out, int device, int kernel, int d, int64_t N, const double* x, double bandwidth) {
-    if (!out) return kfail("out is NULL");
+    if (!out) return bad_arg("out is NULL");
     *out = nullptr;
-    if (kernel < 0 || kernel > KDE_COSINE) return kfail("unknown kernel");
-    if (d < 1 || d > KDE_MAX_D) return kfail("d must be 1 .. 8");
-    if (N < 1 || !x) return kfail("need at least one sample");
-    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth)) return kfail("bandwidth must be positive and finite");
+    if (kernel < 0 || kernel > KDE_COSINE) return bad_arg("unknown kernel");
+    if (d < 1 || d > KDE_MAX_D) return bad_arg("d must be 1 .. 8");
+    if (N < 1 || !x) return bad_arg("need at least one sample");
+    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth)) return bad_arg("bandwidth must be positive and finite");
     for (int64_t i = 0; i < N * d; ++i)
-        if (!std::isfinite(x[i])) return kfail("sample coordinates must be finite");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-        return kfail("no HIP device visible (libmbar_hip needs an MI355X / gfx950 GPU)", MBAR_ERR_NODEVICE);
-    if (device < 0 || device >= n) return kfail("device index out of range");
-    KHIP(hipSetDevice(device));
-    hipDeviceProp_t p;
-    KHIP(hipGetDeviceProperties(&p, device));
-    if (std::strncmp(p.gcnArchName, "gfx950", 6) != 0)
-        return kfail(std::string("device is ") + p.gcnArchName + ", this library is built for gfx950 only", MBAR_ERR_NODEVICE);
-    mbar_kde* k = new mbar_kde();
-    g_live_contexts.fetch_add(1);
-    k->device = device;
-    k->kernel = kernel;
-    k->d = d;
-    k->N = N;
-    k->h = bandwidth;
-    k->lognorm = log_norm(kernel, d, bandwidth);
-    k->num_cu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-    k->ldx = (N + KDE_TILE - 1) / KDE_TILE * KDE_TILE;
-    int rc = MBAR_OK;
-    auto hip = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == MBAR_OK) rc = kfail(std::string(what) + ": " + hipGetErrorString(e), MBAR_ERR_HIP);
-        return rc == MBAR_OK;
-    };
-    if (hip(hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking), "hipStreamCreateWithFlags") &&
-        hip(cache_malloc((void**)&k->X, (size_t)d * k->ldx * sizeof(double)), "cache_malloc") &&
-        hip(cache_malloc((void**)&k->logW_d, KDE_MAX_CB * sizeof(double)), "cache_malloc")) {
+        if (!std::isfinite(x[i])) return bad_arg("sample coordinates must be finite");
+    return create_handle(out, device, [&](mbar_kde* k, const DevInfo& di) {
+        k->kernel = kernel;
+        k->d = d;
+        k->N = N;
+        k->h = bandwidth;
+        k->lognorm = log_norm(kernel, d, bandwidth);
+        k->num_cu = di.num_cu;
+        k->ldx = (N + KDE_TILE - 1) / KDE_TILE * KDE_TILE;
+        HIPCHK(nullptr, k->X.grow((size_t)d * k->ldx));
+        HIPCHK(nullptr, k->logW_d.grow(KDE_MAX_CB));
         // coordinate-major, padded with copies of the last sample (weight zero: they add nothing, and they never hold a
         // query's running shift above what a real sample gives)
         std::vector<double> stage((size_t)d * k->ldx);
         for (int j = 0; j < d; ++j)
             for (int64_t i = 0; i < k->ldx; ++i) stage[(size_t)j * k->ldx + i] = x[(i < N ? i : N - 1) * d + j];
-        hip(hipMemcpy(k->X, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-    }
-    if (rc == MBAR_OK) {
+        HIPCHK(nullptr, hipMemcpy(k->X, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
         std::vector<double> ones((size_t)N, 1.0);
-        rc = mbar_kde_set_weights(k, 1, ones.data());
-    }
-    if (rc != MBAR_OK) {
-        const std::string msg = mbar_last_error(nullptr);
-        mbar_kde_destroy(k);
-        return kfail(msg, rc);
-    }
-    *out = k;
-    return MBAR_OK;
+        return mbar_kde_set_weights(k, 1, ones.data());
+    });
 }
 
-void mbar_kde_destroy(mbar_kde* k) {
-    if (!k) return;
-    (void)hipSetDevice(k->device);
-    if (k->stream) (void)hipStreamSynchronize(k->stream);
-    for (void* p : {(void*)k->X, (void*)k->V, (void*)k->logW_d, (void*)k->part, (void*)k->Q, (void*)k->out, (void*)k->flag, (void*)k->pq})
-        if (p) (void)cache_free(p);
-    if (k->stream) (void)hipStreamDestroy(k->stream);
-    delete k;
-    if (g_live_contexts.fetch_sub(1) == 1) g_mem.trim_to(g_mem.idle_limit());
-}
+void mbar_kde_destroy(mbar_kde* k) { destroy_handle(k); }
 
 int mbar_kde_set_weights(mbar_kde* k, int64_t C, const double* v) {
-    if (!k) return kfail("kde is NULL");
-    if (C < 1 || !v) return kfail("need at least one weight column");
+    if (!k) return bad_arg("kde is NULL");
+    if (C < 1 || !v) return bad_arg("need at least one weight column");
     const int64_t N = k->N;
     std::vector<double> colmax((size_t)C, 0.0);
     for (int64_t n = 0; n < N; ++n)
         for (int64_t c = 0; c < C; ++c) {
             const double w = v[n * C + c];
-            if (!std::isfinite(w) || w < 0.0) return kfail("weights must be finite and non-negative");
+            if (!std::isfinite(w) || w < 0.0) return bad_arg("weights must be finite and non-negative");
             if (w > colmax[c]) colmax[c] = w;
         }
     // a power-of-two scale per column (exact): the largest weight lies in [1, 2), so that N 2^257 bounds every device sum
     std::vector<double> scale((size_t)C, 1.0);
     for (int64_t c = 0; c < C; ++c)
         if (colmax[c] > 0.0) scale[c] = std::ldexp(1.0, -std::ilogb(colmax[c]));
-    k->Vh.resize((size_t)N * C);
+    double* Vh = k->V.reset(N, C);
     for (int64_t n = 0; n < N; ++n)
-        for (int64_t c = 0; c < C; ++c) k->Vh[(size_t)n * C + c] = v[n * C + c] * scale[c];
+        for (int64_t c = 0; c < C; ++c) Vh[(size_t)n * C + c] = v[n * C + c] * scale[c];
     k->logW.assign((size_t)C, 0.0);
-    for (int64_t c = 0; c < C; ++c) k->logW[c] = std::log(csum(k->Vh.data() + c, N, C));  // (log 0 = -inf: a column without weight)
-    k->C = C;
-    k->v_pass = -1;
-    KHIP(hipSetDevice(k->device));
-    if (C <= KDE_MAX_CB) return upload_pass(k, 0, (int)C, pass_width(C));  // (one pass: stays resident between calls)
+    for (int64_t c = 0; c < C; ++c) k->logW[c] = std::log(csum(Vh + c, N, C));  // (log 0 = -inf: a column without weight)
+    HIPCHK(nullptr, hipSetDevice(k->device));
+    if (C <= KDE_MAX_CB) return upload_pass(k, 0, (int)C, k->V.width(C));  // (one pass: stays resident between calls)
     return MBAR_OK;
 }
 
 int mbar_kde_eval(mbar_kde* k, int64_t M, const double* q, double* out) {
-    if (!k) return kfail("kde is NULL");
-    if (M < 0 || (M > 0 && (!q || !out))) return kfail("bad query arguments");
+    if (!k) return bad_arg("kde is NULL");
+    if (M < 0 || (M > 0 && (!q || !out))) return bad_arg("bad query arguments");
     if (M == 0) return MBAR_OK;
     const int d = k->d;
     for (int64_t i = 0; i < M * d; ++i)
-        if (!std::isfinite(q[i])) return kfail("query coordinates must be finite");
-    KHIP(hipSetDevice(k->device));
+        if (!std::isfinite(q[i])) return bad_arg("query coordinates must be finite");
+    HIPCHK(nullptr, hipSetDevice(k->device));
     const int64_t qblocks = (M + 255) / 256, ldq = qblocks * 256;
     {
         std::vector<double> stage((size_t)d * ldq);
         for (int j = 0; j < d; ++j)
             for (int64_t i = 0; i < ldq; ++i) stage[(size_t)j * ldq + i] = q[(i < M ? i : M - 1) * d + j];
-        KHIP(grow(&k->Q, &k->q_doubles, stage.size()));
-        KHIP(hipMemcpy(k->Q, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, k->Q.grow(stage.size()));
+        HIPCHK(nullptr, hipMemcpy(k->Q, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     // grid: 256 queries x one chunk of whole tiles per workgroup, about four workgroups per CU (their LDS allows four)
     const int64_t ntiles = k->ldx / KDE_TILE;
@@ -277,24 +190,25 @@ int mbar_kde_eval(mbar_kde* k, int64_t M, const double* q, double* out) {
     a.chunk = chunk;
     std::vector<double> hout;
     std::vector<int> hflag;
-    for (int64_t c0 = 0; c0 < k->C; c0 += KDE_MAX_CB) {
-        const int cv = (int)std::min<int64_t>(KDE_MAX_CB, k->C - c0);
-        const int cb = pass_width(cv);
+    const int64_t C = k->V.C;
+    for (int64_t c0 = 0; c0 < C; c0 += KDE_MAX_CB) {
+        const int cv = (int)std::min<int64_t>(KDE_MAX_CB, C - c0);
+        const int cb = k->V.width(cv);
         int rc = upload_pass(k, c0, cv, cb);
         if (rc) return rc;
         a.cb = cb;
-        a.V = k->V;
-        KHIP(grow(&k->part, &k->part_doubles, (size_t)nchunks * (cb + 1) * ldq));
-        KHIP(grow(&k->out, &k->out_doubles, (size_t)M * cv));
-        KHIP(grow(&k->flag, &k->flag_ints, (size_t)M * cv));
+        a.V = k->V.dev;
+        HIPCHK(nullptr, k->part.grow((size_t)nchunks * (cb + 1) * ldq));
+        HIPCHK(nullptr, k->out.grow((size_t)M * cv));
+        HIPCHK(nullptr, k->flag.grow((size_t)M * cv));
         a.part = k->part;
-        KHIP(launch_kde(k->stream, a));
-        KHIP(launch_kde_combine(k->stream, a, cv, k->logW_d, k->lognorm, k->out, k->flag));
+        HIPCHK(nullptr, launch_kde(k->stream, a));
+        HIPCHK(nullptr, launch_kde_combine(k->stream, a, cv, k->logW_d, k->lognorm, k->out, k->flag));
         hout.resize((size_t)M * cv);
         hflag.resize((size_t)M * cv);
-        KHIP(hipMemcpyAsync(hout.data(), k->out, hout.size() * sizeof(double), hipMemcpyDeviceToHost, k->stream));
-        KHIP(hipMemcpyAsync(hflag.data(), k->flag, hflag.size() * sizeof(int), hipMemcpyDeviceToHost, k->stream));
-        KHIP(hipStreamSynchronize(k->stream));
+        HIPCHK(nullptr, hipMemcpyAsync(hout.data(), k->out, hout.size() * sizeof(double), hipMemcpyDeviceToHost, k->stream));
+        HIPCHK(nullptr, hipMemcpyAsync(hflag.data(), k->flag, hflag.size() * sizeof(int), hipMemcpyDeviceToHost, k->stream));
+        HIPCHK(nullptr, hipStreamSynchronize(k->stream));
         std::vector<int64_t> pairs;
         for (int64_t i = 0; i < M; ++i)
             for (int c = 0; c < cv; ++c)
@@ -304,16 +218,16 @@ int mbar_kde_eval(mbar_kde* k, int64_t M, const double* q, double* out) {
                 }
         const int64_t np = (int64_t)pairs.size() / 2;
         if (np > 0) {  // every term of these pairs underflowed against the shared shift: their own maximum, in log space
-            KHIP(grow(&k->pq, &k->pq_words, pairs.size()));
-            KHIP(hipMemcpy(k->pq, pairs.data(), pairs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-            KHIP(launch_kde_exact(k->stream, a, k->N, np, k->pq, k->logW_d, k->lognorm, k->out));
+            HIPCHK(nullptr, k->pq.grow(pairs.size()));
+            HIPCHK(nullptr, hipMemcpy(k->pq, pairs.data(), pairs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+            HIPCHK(nullptr, launch_kde_exact(k->stream, a, k->N, np, k->pq, k->logW_d, k->lognorm, k->out));
             std::vector<double> redo((size_t)np);
-            KHIP(hipMemcpyAsync(redo.data(), k->out, redo.size() * sizeof(double), hipMemcpyDeviceToHost, k->stream));
-            KHIP(hipStreamSynchronize(k->stream));
+            HIPCHK(nullptr, hipMemcpyAsync(redo.data(), k->out, redo.size() * sizeof(double), hipMemcpyDeviceToHost, k->stream));
+            HIPCHK(nullptr, hipStreamSynchronize(k->stream));
             for (int64_t p = 0; p < np; ++p) hout[(size_t)pairs[2 * p] * cv + pairs[2 * p + 1]] = redo[p];
         }
         for (int64_t i = 0; i < M; ++i)
-            for (int c = 0; c < cv; ++c) out[i * k->C + c0 + c] = hout[(size_t)i * cv + c];
+            for (int c = 0; c < cv; ++c) out[i * C + c0 + c] = hout[(size_t)i * cv + c];
     }
     return MBAR_OK;
 }

@@ -13,8 +13,7 @@ import numpy as np
 from . import _lib
 
 
-def _dptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+_dptr = _lib.ptr
 
 
 class DeviceMatrix:
@@ -25,11 +24,7 @@ class DeviceMatrix:
         self._lib = _lib.load_library()
         self.K = int(K)
         self.N_local = int(N_local)
-        if device is None:
-            import os
-
-            device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _lib.device_count())
-        self.device = int(device)
+        self.device = _lib.default_device(device)
         self._ctx = C.c_void_p()
         rc = self._lib.mbar_ctx_create(C.byref(self._ctx), self.device, self.K, self.N_local)
         if rc != _lib.MBAR_OK:

@@ -11,7 +11,6 @@ the data).  ``algorithm``, ``leaf_size``, ``breadth_first``, ``atol`` and ``rtol
 bootstrap replicates of a KDE free energy surface (pymbar_amd.fes.FES).
 """
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -24,12 +23,6 @@ MAX_DIM = 8
 # the constructor parameters of sklearn.neighbors.KernelDensity (what get_params returns)
 SKLEARN_PARAMS = ("algorithm", "atol", "bandwidth", "breadth_first", "kernel", "leaf_size", "metric", "metric_params", "rtol")
 
-_dp = C.POINTER(C.c_double)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(_dp)
-
 
 def log_normaliser(kernel, d, bandwidth):
     """``log(1 / integral of k_h over R^d)``, the constant the library adds (``mbar_kde_log_norm``; host only, no GPU needed)."""
@@ -38,21 +31,21 @@ def log_normaliser(kernel, d, bandwidth):
     return out.value
 
 
-class DeviceKDE:
+class DeviceKDE(_lib.Handle):
     """N samples of dimension d resident on one device with C columns of sample weights (an ``mbar_kde`` handle).
 
     ``log_density(Q)[m, c] = log sum_n V[n, c] k_h(|Q_m - X_n|) - log sum_n V[n, c] + log-normaliser``."""
+
+    _destroy = "mbar_kde_destroy"
 
     def __init__(self, X, kernel, bandwidth, device=None):
         _lib.require_device()
         self._lib = _lib.load_library()
         X = np.ascontiguousarray(X, dtype=np.float64)
         self.n_samples, self.dim = X.shape
-        if device is None:
-            device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _lib.device_count())
-        self.device = int(device)
+        self.device = _lib.default_device(device)
         self._h = C.c_void_p()
-        _lib.check(self._lib.mbar_kde_create(C.byref(self._h), self.device, _KERNEL_ID[kernel], self.dim, self.n_samples, _ptr(X),
+        _lib.check(self._lib.mbar_kde_create(C.byref(self._h), self.device, _KERNEL_ID[kernel], self.dim, self.n_samples, _lib.ptr(X),
                                              float(bandwidth)))
         self.n_columns = 1
 
@@ -64,32 +57,15 @@ class DeviceKDE:
         V = np.ascontiguousarray(V)
         if V.shape[0] != self.n_samples:
             raise ValueError("one weight row per sample is needed")
-        _lib.check(self._lib.mbar_kde_set_weights(self._h, V.shape[1], _ptr(V)))
+        _lib.check(self._lib.mbar_kde_set_weights(self._h, V.shape[1], _lib.ptr(V)))
         self.n_columns = V.shape[1]
 
     def log_density(self, Q):
         Q = np.ascontiguousarray(Q, dtype=np.float64)
         out = np.empty((Q.shape[0], self.n_columns), dtype=np.float64)
         if Q.shape[0]:
-            _lib.check(self._lib.mbar_kde_eval(self._h, Q.shape[0], _ptr(Q), _ptr(out)))
+            _lib.check(self._lib.mbar_kde_eval(self._h, Q.shape[0], _lib.ptr(Q), _lib.ptr(out)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.mbar_kde_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _check_2d(X, what):

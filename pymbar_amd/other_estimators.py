@@ -16,7 +16,6 @@ logs only the final line; array-likes and float32 input are accepted (as fp64).
 """
 import ctypes as C
 import logging
-import os
 
 import numpy as np
 
@@ -32,14 +31,9 @@ CHUNK = 4096  # MBAR_BAR_CHUNK
 RUNNING, DONE, NAN_BRACKET, BOUNDS, NOT_CONVERGED = 0, 1, 2, 3, 4
 METHODS = {"false-position": 0, "bisection": 1, "self-consistent-iteration": 2}
 
-_dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
 _POOR_OVERLAP = ("BAR is likely to be inaccurate because of poor overlap. Improve the sampling, or decrease the spacing between "
                  "states.  For now, guessing that the free energy difference is 0 with no uncertainty.")
-
-
-def _ptr(a, t=_dp):
-    return a.ctypes.data_as(t) if a is not None else None
 
 
 def _work(w, what):
@@ -50,24 +44,24 @@ def _work(w, what):
     return a
 
 
-class DeviceBAR:
+class DeviceBAR(_lib.Handle):
     """P problems' forward and reverse work values resident on one device (an ``mbar_bar`` handle).
 
     ``w_F_list``, ``w_R_list``: sequences of P arrays (``w_R_list`` None: one-sided, for the EXP moments only).  Values are
     uploaded once; every evaluation, the bracket, the uncertainty sums and the EXP moments read that copy."""
 
+    _destroy = "mbar_bar_destroy"
+
     def __init__(self, w_F_list, w_R_list=None, device=None):
         self._setup(w_F_list, w_R_list)
         _lib.require_device()
         self._lib = _lib.load_library()
-        if device is None:
-            device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _lib.device_count())
-        self.device = int(device)
+        self.device = _lib.default_device(device)
         wf = np.concatenate(self.w_F)
         wr = np.concatenate(self.w_R)
         self._h = C.c_void_p()
-        _lib.check(self._lib.mbar_bar_create(C.byref(self._h), self.device, self.P, _ptr(self.n_F, _ip), _ptr(wf),
-                                             _ptr(self.n_R, _ip), _ptr(wr) if wr.size else None))
+        _lib.check(self._lib.mbar_bar_create(C.byref(self._h), self.device, self.P, _lib.ptr(self.n_F, _ip), _lib.ptr(wf),
+                                             _lib.ptr(self.n_R, _ip), _lib.ptr(wr) if wr.size else None))
 
     def _setup(self, w_F_list, w_R_list):
         """The input rules: fp64 copies, no NaN or -inf, no empty side (one-sided: no empty forward side)."""
@@ -94,7 +88,7 @@ class DeviceBAR:
         """[P][5]: (F, log_numer, log_denom, log_numer2, log_denom2) at DeltaF[p], one pass."""
         d = np.ascontiguousarray(np.broadcast_to(np.asarray(DeltaF, dtype=np.float64), (self.P,)))
         out = np.empty((self.P, 5))
-        _lib.check(self._lib.mbar_bar_zero(self._h, _ptr(d), _ptr(out)))
+        _lib.check(self._lib.mbar_bar_zero(self._h, _lib.ptr(d), _lib.ptr(out)))
         return out
 
     def solve(self, states):
@@ -107,25 +101,8 @@ class DeviceBAR:
         """[P][2][5]: per side (forward, reverse) logsumexp(-w), sum x, sum (x - mean)^2 with x = exp(-w - max(-w)), sum w,
         sum (w - mean)^2."""
         out = np.empty((self.P, 2, 5))
-        _lib.check(self._lib.mbar_bar_moments(self._h, _ptr(out)))
+        _lib.check(self._lib.mbar_bar_moments(self._h, _lib.ptr(out)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.mbar_bar_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _exp_delta_f(lse, T):

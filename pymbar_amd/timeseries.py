@@ -15,7 +15,6 @@ statsmodels).  The fft formula's cost is O(N * ind): quadratic for a series whos
 import ctypes as C
 import logging
 import math
-import os
 
 import numpy as np
 
@@ -43,12 +42,7 @@ logger.warning(LongWarning)
 STOPPED, ZERO_VARIANCE, END = 1, 2, 3
 _ZERO_COV = "Sample covariance sigma_AB^2 = 0 -- cannot compute statistical inefficiency"
 
-_dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
-
-
-def _ptr(a, t=_dp):
-    return a.ctypes.data_as(t) if a is not None else None
 
 
 def lag_schedule(fast, tmax):
@@ -62,11 +56,13 @@ def lag_schedule(fast, tmax):
     return out
 
 
-class DeviceACF:
+class DeviceACF(_lib.Handle):
     """One series (or the concatenation of K segments) resident on one device (an ``mbar_acf`` handle).
 
     ``a``, ``b``: fp64 values (``b`` None: the autocorrelation); ``seg``: segment lengths; the device holds ``a - shift_a`` and
     ``b - shift_b``."""
+
+    _destroy = "mbar_acf_destroy"
 
     def __init__(self, a, b=None, seg=None, shift_a=0.0, shift_b=0.0, device=None):
         _lib.require_device()
@@ -75,19 +71,17 @@ class DeviceACF:
         self.b = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
         self.T = self.a.size
         self.seg = np.ascontiguousarray([self.T] if seg is None else seg, dtype=np.int64)
-        if device is None:
-            device = int(os.environ.get("LOCAL_RANK", "0")) % max(1, _lib.device_count())
-        self.device = int(device)
+        self.device = _lib.default_device(device)
         self._h = C.c_void_p()
-        _lib.check(self._lib.mbar_acf_create(C.byref(self._h), self.device, self.T, _ptr(self.a), _ptr(self.b), self.seg.size,
-                                             _ptr(self.seg, _ip), float(shift_a), float(shift_b)))
+        _lib.check(self._lib.mbar_acf_create(C.byref(self._h), self.device, self.T, _lib.ptr(self.a), _lib.ptr(self.b), self.seg.size,
+                                             _lib.ptr(self.seg, _ip), float(shift_a), float(shift_b)))
 
     def suffix_g(self, nskip, fast, mintime, fft=False):
         """(g, stop, status) of the origins 0, nskip, ... < T - 1 (one segment)."""
         n = (self.T - 2) // nskip + 1
         g, stop, st = np.empty(n), np.empty(n, np.int64), np.empty(n, np.int32)
-        _lib.check(self._lib.mbar_acf_suffix_g(self._h, int(nskip), int(bool(fast)), int(mintime), int(bool(fft)), _ptr(g),
-                                               _ptr(stop, _ip), st.ctypes.data_as(C.POINTER(C.c_int32))))
+        _lib.check(self._lib.mbar_acf_suffix_g(self._h, int(nskip), int(bool(fast)), int(mintime), int(bool(fft)), _lib.ptr(g),
+                                               _lib.ptr(stop, _ip), st.ctypes.data_as(C.POINTER(C.c_int32))))
         return g, stop, st
 
     def multiple_g(self, fast, mintime, want_ct=False):
@@ -98,8 +92,8 @@ class DeviceACF:
             n = C.c_int64(0)
             _lib.check(self._lib.mbar_acf_schedule_length(int(bool(fast)), int(self.seg.max()), C.byref(n)))
             ct = np.zeros(n.value)
-        _lib.check(self._lib.mbar_acf_multiple_g(self._h, int(bool(fast)), int(mintime), _ptr(g), _ptr(stop, _ip),
-                                                 st.ctypes.data_as(C.POINTER(C.c_int32)), 0 if ct is None else ct.size, _ptr(ct)))
+        _lib.check(self._lib.mbar_acf_multiple_g(self._h, int(bool(fast)), int(mintime), _lib.ptr(g), _lib.ptr(stop, _ip),
+                                                 st.ctypes.data_as(C.POINTER(C.c_int32)), 0 if ct is None else ct.size, _lib.ptr(ct)))
         return float(g[0]), int(stop[0]), int(st[0]), ct
 
     def lag_sums(self, lags, origins, segments=False):
@@ -109,26 +103,9 @@ class DeviceACF:
         origins = np.ascontiguousarray(origins, dtype=np.int64)
         xab = np.empty((lags.size, origins.size))
         xba = np.empty((lags.size, origins.size))
-        _lib.check(self._lib.mbar_acf_lag_sums(self._h, lags.size, _ptr(lags, _ip), origins.size, _ptr(origins, _ip),
-                                               int(bool(segments)), _ptr(xab), _ptr(xba)))
+        _lib.check(self._lib.mbar_acf_lag_sums(self._h, lags.size, _lib.ptr(lags, _ip), origins.size, _lib.ptr(origins, _ip),
+                                               int(bool(segments)), _lib.ptr(xab), _lib.ptr(xba)))
         return xab, xba
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.mbar_acf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _f64(x):
