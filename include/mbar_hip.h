@@ -494,6 +494,46 @@ int mbar_bspline_moments(mbar_bspline* bs, int k, int nbasis, const double* t, d
 /* Device time of the last mbar_bspline_moments call's kernels (all passes, HIP events), in ms. */
 int mbar_bspline_kernel_ms(mbar_bspline* bs, double* ms);
 
+/* ---- many small MBAR problems in one call (pymbar_amd.mbar_batch) -----------------------------------------------------------
+ * A handle holds P independent problems resident on one device: problem p is a K[p] x N[p] row-major block of reduced
+ * potentials (1 <= K[p] <= MBAR_BATCH_MAX_K, N[p] >= 1; u: the blocks concatenated in order; +inf allowed, NaN and -inf
+ * rejected).  Each problem's columns are cut into chunks of MBAR_BATCH_CHUNK, fixed whatever the other problems are; chunk
+ * partials merge in a fixed order without atomics, so two identical calls return identical bits and a problem's answer does
+ * not depend on the batch it is in.  The adaptive loop of mbar_solvers.py:575-640 runs per problem as a resumable state machine
+ * (mbar_batch_step_host on the host, the same function on the device).  Errors: mbar_last_error(NULL).  Not thread-safe (one
+ * handle per caller thread). */
+#define MBAR_BATCH_MAX_K 64
+#define MBAR_BATCH_CHUNK 256
+/* One problem's solve.  Callers fill K, Nk (samples per state, zeros allowed, at least one > 0), f (the start), tol, gamma,
+ * maxiter, min_sc_iter; everything else zero.  lognum[k] = log sum_n exp(-logden_n - u_kn) at f for every state k and
+ * psum[k] = N_k exp(f_k + lognum_k) when the solve has ended.  status: 0 running, 1 ended (success: converged), 2 a Newton pivot
+ * counted as zero or was not finite (the caller finishes the problem on the host). */
+typedef struct mbar_batch_state {
+    double f[MBAR_BATCH_MAX_K];
+    double req[2][MBAR_BATCH_MAX_K];  /* the f vectors the next pass evaluates (nreq of them; [0] f_sci, [1] f_nr) */
+    double lognum[MBAR_BATCH_MAX_K];
+    double psum[MBAR_BATCH_MAX_K];
+    double Nk[MBAR_BATCH_MAX_K];
+    double x[MBAR_BATCH_MAX_K];       /* Newton direction of the live states (between the two halves of a step) */
+    double tol, gamma, max_delta, max_diff, gnorm_sci, gnorm_nr;
+    int64_t K, maxiter, min_sc_iter, iterations, nr_iter, sci_iter, choices; /* choices: bit i = 1 when iteration i took NR */
+    int64_t phase, status, success, nreq, gram_req, gram_w, newton_bad;
+} mbar_batch_state;
+typedef struct mbar_batch mbar_batch;
+/* u[p]: host pointer to problem p's K[p] x N[p] row-major block. */
+int mbar_batch_create(mbar_batch** out, int device, int64_t P, const int64_t* K, const int64_t* N, const double* const* u);
+void mbar_batch_destroy(mbar_batch* b);
+/* Runs every problem's solve to its end: states[P] in (initial), out (final); passes: evaluation passes enqueued (or NULL).
+ * The host reads one int per problem between groups of passes. */
+int mbar_batch_solve(mbar_batch* b, mbar_batch_state* states, int64_t* passes);
+/* For the problems with mask[p] != 0, at f[p][0 .. K[p]) (the final free energies, every state): gram = W^T W (K[p] x K[p]) and
+ * wsum = sum_n W_nk, packed problem after problem (K[p]^2 resp. K[p] doubles each; entries of masked-out problems untouched). */
+int mbar_batch_gram_w(mbar_batch* b, const double* f, const int32_t* mask, double* gram, double* wsum);
+/* One step of a state on the host with the same state machine the device runs: lognum[r][K] = lognum at req[r] for the nreq
+ * requests of the last pass (ignored in the first call, which issues the first requests), gram[K][K] = sum_n p_ni p_nj
+ * (p_nk = N_k W_nk) at req[gram_req] (NULL when gram_req < 0).  Returns the status.  Needs no GPU. */
+int mbar_batch_step_host(mbar_batch_state* state, const double* lognum, const double* gram);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,18 @@ class BarState(C.Structure):
                                  "want_moments", "moments_pending")]
 
 
+MBAR_BATCH_MAX_K = 64
+
+
+class BatchState(C.Structure):
+    """``mbar_batch_state`` of include/mbar_hip.h: one problem's adaptive loop in ``mbar_batch``."""
+    _fields_ = [(n, C.c_double * MBAR_BATCH_MAX_K) for n in ("f",)] + [("req", (C.c_double * MBAR_BATCH_MAX_K) * 2)] + [
+        (n, C.c_double * MBAR_BATCH_MAX_K) for n in ("lognum", "psum", "Nk", "x")] + [
+        (n, C.c_double) for n in ("tol", "gamma", "max_delta", "max_diff", "gnorm_sci", "gnorm_nr")] + [
+        (n, C.c_int64) for n in ("K", "maxiter", "min_sc_iter", "iterations", "nr_iter", "sci_iter", "choices", "phase", "status",
+                                 "success", "nreq", "gram_req", "gram_w", "newton_bad")]
+
+
 class SolveResult(C.Structure):
     _fields_ = [
         ("iterations", C.c_int64),
@@ -142,6 +154,11 @@ SIGNATURES = {
     "mbar_bspline_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "mbar_bspline_moments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "mbar_bspline_kernel_ms": (C.c_int, [C.c_void_p, _dp]),
+    "mbar_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, _ip, _ip, C.POINTER(_dp)]),
+    "mbar_batch_destroy": (None, [C.c_void_p]),
+    "mbar_batch_solve": (C.c_int, [C.c_void_p, C.POINTER(BatchState), _ip]),
+    "mbar_batch_gram_w": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_int32), _dp, _dp]),
+    "mbar_batch_step_host": (C.c_int, [C.POINTER(BatchState), _dp, _dp]),
 }
 
 _lib = None

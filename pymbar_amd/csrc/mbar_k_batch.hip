@@ -1,0 +1,306 @@
+// gfx950 (CDNA4 / MI355X) kernels of mbar_batch: many small MBAR problems (K <= 64 states each) solved side by side.  One of the
+// translation units of libmbar_hip.so: launchers declared in mbar_internal.h, C ABI in mbar_batch.cpp, design and numbers in
+// DESIGN.md ("Many small MBAR problems").
+//
+// Every problem's columns are cut into chunks of MBAR_BATCH_CHUNK samples; one workgroup of 256 threads handles one chunk, one
+// sample per thread, with the sample's K reduced potentials in registers.  Chunks are launched in four width classes (8, 16, 32,
+// 64 states) so that a problem of 5 states does not carry 64 registers of padding; a problem always lands in the same class.
+//   k_batch_eval   at each f the problem's state requests (one or two): the log-denominator of every sample, then per state the
+//                  chunk maximum of -logden_n - u_kn and the sum of exp(. - maximum) (log space: no term is lost to underflow
+//                  that is not below 2^-1074 of the chunk's largest), and at one request the K x K Gram partial of
+//                  p_nk = N_k W_nk (or of W itself for the covariance).  The per-state sums go through an LDS transposition,
+//                  16 states at a time; the Gram matrix is VALU outer products of 64-sample tiles staged in LDS, each thread
+//                  owning a 1x1, 2x2 or 4x4 block.
+//   k_batch_step   one workgroup per problem: merges the chunk partials in chunk order, advances the problem's adaptive loop
+//                  (batch_advance, mbar_internal.h) and, when it asks for one, factors the gauge-fixed Newton system in LDS
+//                  (LDL^T, one barrier pair per pivot).
+// No atomics: every sum has a fixed order that depends on the problem alone, so two identical calls return identical bits and a
+// problem's answer does not depend on the other problems of the batch.
+#include "mbar_device.h"
+
+namespace mbar {
+
+namespace {
+
+constexpr int TP = MBAR_BATCH_CHUNK + 1;  // pitch of the per-state transposition tile (16 states x 256 samples)
+
+template <int KB>
+__global__ void __launch_bounds__(BATCH_WG) k_batch_eval(BatchData d, const int* __restrict__ list,
+                                                         const mbar_batch_state* __restrict__ states) {
+    constexpr int GS = KB < 16 ? KB : 16;   // states per transposition group
+    constexpr int BS = KB >= 64 ? 4 : (KB >= 32 ? 2 : 1);  // Gram block per thread
+    constexpr int NBD = KB / BS;            // Gram blocks per dimension (NBD^2 <= 256)
+    constexpr int GP = KB + 1;              // pitch of the Gram operand tile (64 samples x KB states)
+    __shared__ double buf[64 * 65];         // (the two tiles share one buffer)
+    static_assert(64 * 65 >= 16 * TP && 64 * 65 >= 64 * GP, "tile sizes");
+    __shared__ double sa[2][KB];
+    __shared__ double sg[KB];
+    __shared__ int info[4];
+    const int tid = threadIdx.x;
+    const int c = list[blockIdx.x];
+    const int p = d.cprob[c];
+    const mbar_batch_state* st = states + p;
+    if (tid == 0) {
+        info[0] = (int)st->nreq;
+        info[1] = (int)st->gram_req;
+        info[2] = (int)st->K;
+        info[3] = (int)st->gram_w;
+    }
+    __syncthreads();
+    const int nreq = info[0] > 2 ? 2 : info[0], greq = info[1], K = info[2], gw = info[3];
+    if (nreq <= 0) return;  // (the problem has ended: the whole workgroup leaves)
+    if (tid < KB) {
+        const bool on = tid < K && st->Nk[tid] > 0;
+        const double lnN = on ? log(st->Nk[tid]) : 0.0;
+        for (int r = 0; r < nreq; ++r) sa[r][tid] = on ? st->req[r][tid] + lnN : -INFINITY;
+        if (greq >= 0 && greq < nreq)
+            sg[tid] = tid >= K ? -INFINITY : (gw ? st->req[greq][tid] : (on ? st->req[greq][tid] + lnN : -INFINITY));
+    }
+    const int64_t Np = d.N[p];
+    const int64_t n0 = d.cn0[c];
+    const int ncols = (int)(Np - n0 < MBAR_BATCH_CHUNK ? Np - n0 : MBAR_BATCH_CHUNK);
+    const bool valid = tid < ncols;
+    const double* __restrict__ up = d.u + d.uoff[p] + n0 + tid;
+    double u[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) u[k] = (valid && k < K) ? up[(int64_t)k * Np] : INFINITY;
+    double* __restrict__ rec = d.part + d.coff[c];
+    __syncthreads();
+    for (int r = 0; r < nreq; ++r) {
+        // log-denominator of this sample: log sum_k N_k exp(f_k - u_kn)
+        double m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < KB; ++k) m = fmax(m, sa[r][k] - u[k]);
+        double ld = INFINITY;  // (a padding column, or one with no finite sampled entry: every term below is exp(-inf) = 0)
+        if (m != -INFINITY) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < KB; ++k) s += exp((sa[r][k] - u[k]) - m);
+            ld = m + log(s);
+        }
+        // per state: maximum over the chunk of v_k = -logden - u_k and the sum of exp(v_k - maximum)
+#pragma unroll
+        for (int g0 = 0; g0 < KB; g0 += GS) {
+            if (g0 >= K) break;
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < GS; ++j) buf[j * TP + tid] = -ld - u[g0 + j];
+            __syncthreads();
+            const int kk = tid >> 4, q = tid & 15;
+            double mx = -INFINITY;
+            if (kk < GS)
+#pragma unroll 4
+                for (int i = 0; i < MBAR_BATCH_CHUNK / 16; ++i) mx = fmax(mx, buf[kk * TP + q + 16 * i]);
+            mx = row16_max(mx);
+            double sm = 0.0;
+            if (kk < GS && mx != -INFINITY)
+#pragma unroll 4
+                for (int i = 0; i < MBAR_BATCH_CHUNK / 16; ++i) sm += exp(buf[kk * TP + q + 16 * i] - mx);
+            sm = row16_sum(sm);
+            if (q == 0 && kk < GS && g0 + kk < K) {
+                rec[r * K + g0 + kk] = mx;
+                rec[2 * K + r * K + g0 + kk] = sm;
+            }
+        }
+        if (r != greq) continue;
+        // Gram partial: sum over the chunk's samples of q q^T, q_k = exp(sg_k - u_k - logden), 64 samples at a time
+        const int wv = tid >> 6, lane = tid & 63;
+        const int bi = tid / NBD, bj = tid % NBD;
+        double acc[BS][BS];
+#pragma unroll
+        for (int a = 0; a < BS; ++a)
+#pragma unroll
+            for (int b = 0; b < BS; ++b) acc[a][b] = 0.0;
+        for (int w = 0; w < BATCH_WG / 64; ++w) {
+            if (w * 64 >= ncols) break;
+            __syncthreads();
+            if (wv == w)
+#pragma unroll
+                for (int k = 0; k < KB; ++k) buf[lane * GP + k] = exp((sg[k] - u[k]) - ld);
+            __syncthreads();
+            if (tid < NBD * NBD) {
+                const int cols = ncols - w * 64 < 64 ? ncols - w * 64 : 64;
+                for (int j = 0; j < cols; ++j) {
+                    double x[BS], y[BS];
+#pragma unroll
+                    for (int a = 0; a < BS; ++a) {
+                        x[a] = buf[j * GP + bi * BS + a];
+                        y[a] = buf[j * GP + bj * BS + a];
+                    }
+#pragma unroll
+                    for (int a = 0; a < BS; ++a)
+#pragma unroll
+                        for (int b = 0; b < BS; ++b) acc[a][b] += x[a] * y[b];
+                }
+            }
+        }
+        if (tid < NBD * NBD)
+#pragma unroll
+            for (int a = 0; a < BS; ++a)
+#pragma unroll
+                for (int b = 0; b < BS; ++b) {
+                    const int i = bi * BS + a, j = bj * BS + b;
+                    if (i < K && j < K) rec[4 * K + i * K + j] = acc[a][b];
+                }
+    }
+}
+
+__global__ void __launch_bounds__(BATCH_WG) k_batch_step(BatchData d, mbar_batch_state* __restrict__ states, int* __restrict__ active,
+                                                         double* __restrict__ out_gram, double* __restrict__ out_wsum,
+                                                         const int64_t* __restrict__ goff, const int64_t* __restrict__ woff) {
+    constexpr int MK = MBAR_BATCH_MAX_K;
+    __shared__ mbar_batch_state st;
+    __shared__ double G[MK * MK];
+    __shared__ double ln[2 * MK];
+    __shared__ double b[MK];
+    __shared__ int idx[MK];
+    __shared__ int sh_m;
+    __shared__ double sh_thr, sh_gbar;
+    const int tid = threadIdx.x;
+    const int p = blockIdx.x;
+    {
+        static_assert(sizeof(mbar_batch_state) % 8 == 0, "state copied as 8-byte words");
+        constexpr int W = (int)(sizeof(mbar_batch_state) / 8);
+        const uint64_t* src = reinterpret_cast<const uint64_t*>(states + p);
+        uint64_t* dst = reinterpret_cast<uint64_t*>(&st);
+        for (int i = tid; i < W; i += BATCH_WG) dst[i] = src[i];
+    }
+    __syncthreads();
+    const int nreq = (int)(st.nreq > 2 ? 2 : st.nreq);
+    if (nreq <= 0) {
+        if (tid == 0) active[p] = 0;
+        return;
+    }
+    const int K = (int)st.K, greq = (int)st.gram_req;
+    const int64_t cb = d.cbeg[p], ce = d.cbeg[p + 1];
+    // merge in chunk order: per state the maximum of the chunk maxima, then the rescaled sums
+    for (int r = 0; r < nreq; ++r)
+        if (tid < K) {
+            double M = -INFINITY;
+            for (int64_t c = cb; c < ce; ++c) M = fmax(M, d.part[d.coff[c] + r * K + tid]);
+            double S = 0.0;
+            if (M != -INFINITY)
+                for (int64_t c = cb; c < ce; ++c) {
+                    const double* rec = d.part + d.coff[c];
+                    const double s = rec[2 * K + r * K + tid];
+                    if (s != 0.0) S += s * exp(rec[r * K + tid] - M);
+                }
+            ln[r * K + tid] = M == -INFINITY ? -INFINITY : M + log(S);
+        }
+    if (greq >= 0 && greq < nreq)
+        for (int e = tid; e < K * K; e += BATCH_WG) {
+            double s = 0.0;
+            for (int64_t c = cb; c < ce; ++c) s += d.part[d.coff[c] + 4 * K + e];
+            G[(e / K) * MK + e % K] = s;
+        }
+    __syncthreads();
+    if (st.phase == BATCH_PH_FINAL) {
+        // the covariance inputs at the final f: W^T W and sum_n W_nk = exp(f_k + lognum_k)
+        for (int e = tid; e < K * K; e += BATCH_WG) out_gram[goff[p] + e] = G[(e / K) * MK + e % K];
+        if (tid < K) out_wsum[woff[p] + tid] = exp(st.req[0][tid] + ln[tid]);
+        if (tid == 0) {
+            states[p].nreq = 0;
+            states[p].phase = BATCH_PH_IDLE;
+            active[p] = 0;
+        }
+        return;
+    }
+    if (tid == 0) batch_advance(st, ln);
+    __syncthreads();
+    if (st.phase == BATCH_PH_NEWTON) {
+        if (tid == 0) {
+            const int s0 = batch_first_sampled(st);
+            int m = 0;
+            for (int k = 0; k < K; ++k)
+                if (st.Nk[k] > 0 && k != s0) idx[m++] = k;
+            sh_m = m;
+            sh_thr = batch_pivot_threshold(st, m);
+            sh_gbar = batch_gradient_mean(st);
+        }
+        __syncthreads();
+        const int m = sh_m;
+        const double thr = sh_thr;
+        // H = diag(psum) - G of the live states, compacted in place through registers; b = the gradient psum - N_k less its mean
+        double v[MK * MK / BATCH_WG];
+#pragma unroll
+        for (int j = 0; j < MK * MK / BATCH_WG; ++j) {
+            const int e = tid + j * BATCH_WG;
+            if (e < m * m) {
+                const int i = e / m, jj = e % m;
+                v[j] = (i == jj ? st.psum[idx[i]] : 0.0) - G[idx[i] * MK + idx[jj]];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < MK * MK / BATCH_WG; ++j) {
+            const int e = tid + j * BATCH_WG;
+            if (e < m * m) G[(e / m) * MK + e % m] = v[j];
+        }
+        if (tid < m) b[tid] = (st.psum[idx[tid]] - st.Nk[idx[tid]]) - sh_gbar;
+        __syncthreads();
+        // LDL^T (the serial batch_ldlt_solve, one pivot per barrier pair) with the forward substitution folded in
+        bool ok = true;
+        for (int j = 0; j < m; ++j) {
+            const double dj = G[j * MK + j];
+            if (!(dj > thr) || !isfinite(dj)) {
+                ok = false;
+                break;
+            }
+            const int n = m - j - 1;
+            for (int e = tid; e < n * n; e += BATCH_WG) {
+                const int i = j + 1 + e / n, k = j + 1 + e % n;
+                if (k <= i) G[i * MK + k] = G[i * MK + k] - (G[i * MK + j] / dj) * G[k * MK + j];
+            }
+            if (tid > j && tid < m) b[tid] = b[tid] - (G[tid * MK + j] / dj) * b[j];
+            __syncthreads();
+            if (tid > j && tid < m) G[tid * MK + j] = G[tid * MK + j] / dj;
+            __syncthreads();
+        }
+        if (ok) {
+            if (tid < m) b[tid] = b[tid] / G[tid * MK + tid];
+            __syncthreads();
+            for (int j = m - 1; j > 0; --j) {
+                if (tid < j) b[tid] = b[tid] - G[j * MK + tid] * b[j];
+                __syncthreads();
+            }
+        }
+        if (tid == 0) {
+            st.newton_bad = ok ? 0 : 1;
+            for (int k = 0; k < K; ++k) st.x[k] = 0.0;
+            if (ok)
+                for (int i = 0; i < m; ++i) st.x[idx[i]] = b[i];
+            batch_advance(st, nullptr);
+        }
+    }
+    __syncthreads();
+    {
+        constexpr int W = (int)(sizeof(mbar_batch_state) / 8);
+        const uint64_t* src = reinterpret_cast<const uint64_t*>(&st);
+        uint64_t* dst = reinterpret_cast<uint64_t*>(states + p);
+        for (int i = tid; i < W; i += BATCH_WG) dst[i] = src[i];
+    }
+    if (tid == 0) active[p] = st.nreq > 0 ? 1 : 0;
+}
+
+}  // namespace
+
+hipError_t launch_batch_eval(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n, const mbar_batch_state* states) {
+    if (n == 0) return hipSuccess;
+    switch (kb) {
+    case 8: hipLaunchKernelGGL(k_batch_eval<8>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 16: hipLaunchKernelGGL(k_batch_eval<16>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 32: hipLaunchKernelGGL(k_batch_eval<32>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 64: hipLaunchKernelGGL(k_batch_eval<64>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_step(hipStream_t st, const BatchData& d, mbar_batch_state* states, int* active, double* out_gram,
+                             double* out_wsum, const int64_t* goff, const int64_t* woff) {
+    if (d.P == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_batch_step, dim3((unsigned)d.P), dim3(BATCH_WG), 0, st, d, states, active, out_gram, out_wsum, goff, woff);
+    return hipGetLastError();
+}
+
+}  // namespace mbar

@@ -555,12 +555,12 @@ def solve_mbar(u_kn_nonzero, N_k_nonzero, f_k_nonzero, solver_protocol=None):
         return _solve_protocol_resident(h, N_k_f, f_k_nonzero - f_k_nonzero[0], sampled, solver_protocol)[:2]
 
 
-def solve_mbar_for_all_states(u_kn, N_k, f_k, states_with_samples, solver_protocol):
+def solve_mbar_for_all_states(u_kn, N_k, f_k, states_with_samples, solver_protocol, results_out=None):
     """Solve on the states with samples, then one all-state self-consistent update gives the
     unsampled states and ``f_k[0]`` is re-zeroed (mbar_solvers.py:977-1017).
 
     Unlike the reference no ``u_kn[states_with_samples]`` copy is made: unsampled rows are masked by
-    ``N_k = 0`` on the device."""
+    ``N_k = 0`` on the device.  ``results_out`` (extension): a list that receives the results of every protocol stage run."""
     states_with_samples = np.asarray(states_with_samples, dtype=np.int64)
     N_k = np.asarray(N_k)
     f_k = np.array(f_k, dtype=np.float64)
@@ -573,8 +573,10 @@ def solve_mbar_for_all_states(u_kn, N_k, f_k, states_with_samples, solver_protoc
             f_start[states_with_samples] -= f_start[states_with_samples[0]]
         psum_solved = None
         if len(states_with_samples) != 1:
-            f_solved, _, psum_solved = _solve_protocol_resident(h, Nf, f_start, states_with_samples,
-                                                                copy.deepcopy(solver_protocol) if solver_protocol is not None else None)
+            f_solved, stage_results, psum_solved = _solve_protocol_resident(
+                h, Nf, f_start, states_with_samples, copy.deepcopy(solver_protocol) if solver_protocol is not None else None)
+            if results_out is not None:
+                results_out.extend(stage_results)
             f_k[states_with_samples] = f_solved[states_with_samples]
         h.set_Nk(Nf)
         if np.all(Nf > 0):
