@@ -136,6 +136,9 @@ int mbar_device_synchronize(int device);
  *   "pcache"         1 = the resident probability matrix outlives the solve that built it: a later adaptive solve on the same
  *                    matrix whose start lies within 200 kT of its anchor (bootstrap replicates, protocol stages) starts with
  *                    one fused sweep instead of the build sweep (default); 0 = every solve builds (cold-solve timings)
+ *   "debug_download_p" test-only hook: 1 = mbar_ctx_download_u hands back the resident probability matrix P of the last
+ *                    device-resident adaptive solve (K <= 256) instead of u, and fails with MBAR_ERR_STATE when the context
+ *                    holds none; 0 = u (default).  tests/test_gpu_device_math.py checks P entry by entry through it
  *   "merge_select"   1 = the selection of iteration i and the Newton solve of iteration i + 1 share a launch (default)
  *   "light_last"     fused loop: when BOTH candidates of the coming sweep already meet the stop test of
  *                    mbar_solvers.py:627-636 against the current f, the iteration is the last whichever of them wins and the Gram

@@ -100,7 +100,12 @@ __device__ __forceinline__ double wave_max(double x) {
 // 2^(t/S) for t = S x log2(e), S = 2^EXP2_BITS = 2048:   s = rint(max(t, EXP2_CLAMP));  z = t - s in [-1/2, 1/2];
 //   j = s & (S-1), q = s >> EXP2_BITS;   result = ldexp(T[j] * P(z), q),  T[j] = 2^(j/S) from a 16 KB LDS table at
 //   LDS offset 0, P = degree-3 polynomial of 2^(z/S) (error 9e-18; tools/gen_exp2_table.py).  Nine fp64 + three
-//   integer instructions (the library exp needs ~25).  exp(-inf) = 0 through the clamp, overflow gives inf through
+//   integer instructions (the library exp needs ~25).  Relative error of the whole function <= 3.1 x 2^-53 (1.55 ulp: half an ulp
+//   each from the table entry, the last fma of the polynomial and the product; measured 2.82 x 2^-53); results below 2^-1022 are NOT
+//   flushed: v_ldexp_f64 rounds them once, to nearest-even, into the subnormal range.  The table entries (correctly rounded), the
+//   polynomial's 9e-18 and the 3.1 x 2^-53 are asserted by tests/test_device_math_tables.py against a step-by-step model of this
+//   function; tests/test_gpu_device_math.py asserts that the device returns the model's bits.
+//   exp(-inf) = 0 through the clamp, overflow gives inf through
 //   ldexp; NaN arguments are laundered to 0 by the clamp, which is why NaN / -inf entries of u_kn and non-finite f_k
 //   are detected at the boundary instead (mbar_capi.cpp).
 #include "exp2_table.inc"
@@ -161,8 +166,12 @@ __device__ __forceinline__ double exp2s_fast(double ts) {  // 2^(ts / S)
 // log s for positive finite s (the per-sample sums of the evaluation sweep), 12 fp64 + 2 integer instructions
 // (the library log is ~50 and keeps a dozen constants in registers):  s = 2^e m, m in [1/2, 1); the top 7 mantissa
 // bits pick c_j with |m / c_j - 1| <= 2^-8 from the 2 KB LDS table behind the exp table (tools/gen_log_table.py);
-// log s = e ln2 + log c_j + log1p(r), r = m / c_j - 1, log1p by its degree-6 Taylor polynomial (error 2e-18).
-// Absolute error ~2e-16 (it is added to a shift of order one or more).  s = 0 / negative are not supported.
+// log s = e ln2 + log c_j + log1p(r), r = m / c_j - 1, log1p by its degree-6 Taylor polynomial (absolute error 2e-18).
+// Absolute error <= (1.6 + |e| / 2) x 2^-53 + one ulp of the result: ~2e-16 (measured 1.8 x 2^-53) for s in [1, 2), but the two half
+// ulps of the result -- fma(e, LN2, log c_j) and the closing fma, which hipcc contracts from "+ q * r" -- dominate from s = 4 on
+// (1.1e-15 = 10 x 2^-53 at s = 1000).  log_pos(1) is 4.3e-17, not 0 (1 = 2^1 x 1/2 goes through bucket 0).  The table pairs, the
+// 2e-18 and the bound are asserted by tests/test_device_math_tables.py; the device's bits by tests/test_gpu_device_math.py.
+// s = 0 / negative are not supported.
 typedef double v2d __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double log_pos(double s) {
     const double m = __builtin_amdgcn_frexp_mant(s);
@@ -238,7 +247,9 @@ __device__ __forceinline__ void exp2s_batch2(double (&x0)[N], double (&x1)[N]) {
 // be formed non-negative EXACTLY): floor and fraction come straight from the argument -- n = -trunc(w) (one conversion with a
 // negated source), z = fract(w) in [0, 1) (one instruction) -- instead of rint / subtract / convert, and no clamp is needed below:
 //   2^(-w/S) = 2^(n/S) 2^(-z/S) = ldexp(T[n & (S-1)] * Q(z), n >> EXP2_BITS),  Q = degree-3 polynomial of 2^(-z/S) on [0, 1]
-// (error 8.8e-18, tools/gen_exp2_poly.py).  Eight fp64 + three integer instructions (exp2s_batch: nine + three, + the clamp).  Huge
+// (error 8.8e-18; generated by tools/gen_exp2n_poly.py, which reproduces the four coefficients below bit for bit; the 8.8e-18 and
+// the function's relative error <= 3.1 x 2^-53, measured 2.49 x 2^-53, are asserted by tests/test_device_math_tables.py).
+// Eight fp64 + three integer instructions (exp2s_batch: nine + three, + the clamp).  Huge
 // finite w is safe (v_cvt_i32_f64 saturates, ldexp(.., -2^20) = 0); CLAMP = true also takes w = +inf (matrices with +inf entries).
 constexpr double EXP2N_POLY[4] = {1.0, -0x1.62e42fefa3028p-12, 0x1.ebfbdf9648000p-25, -0x1.c69cea0000000p-38};
 template <int N, bool CLAMP>
@@ -298,7 +309,9 @@ __device__ __forceinline__ void exp2s_neg_batch2(double (&w0)[N], double (&w1)[N
         w1[i] = ldexp(T1[i] * w1[i], q1[i]);
     }
 }
-// 1 / s for s > 0: hardware estimate + two Newton steps (the divide expansion costs twice as many instructions)
+// 1 / s for s > 0: hardware estimate + two Newton steps (the divide expansion costs twice as many instructions).  Measured, not
+// proved: from the correctly rounded seed and from a seed 2^-20 off the model ends within 0.5000 ulp and at the same bits on 71 000
+// arguments (tests/test_device_math_tables.py); the device's P equals the model's bits on every probe entry (tests/test_gpu_device_math.py)
 __device__ __forceinline__ double recip_fast(double s) {
     double r = __builtin_amdgcn_rcp(s);
     r = fma(fma(-s, r, 1.0), r, r);

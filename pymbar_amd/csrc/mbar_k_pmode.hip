@@ -16,8 +16,10 @@ namespace mbar {
 // instead of the 14-instruction table exponential -- on gfx950 the fp64 matrix instructions and the fp64 VALU share
 // one pipe, so every VALU instruction removed from the Gram sweep is kernel time (profiles/r2_gram_ceiling.txt).
 // Costs one extra K x N array in HBM (288 GB are there for that) and one build sweep per solve.  Entries of P below
-// 1e-308 are flushed to zero: with |a - a0| <= 250 enforced by k_newton (hand-back, then the host rebuilds at the
-// current f) the mass lost that way is below 1e-199 of a sample's normaliser.
+// the normal range (2^-1022 = 2.2e-308) carry no relative accuracy: the two build sweeps of this file keep them as subnormals
+// (rounded once by v_ldexp_f64 and once by the product with 1 / s), k_gram_quad and k_make_p flush them to zero; with
+// |a - a0| <= 250 enforced by k_newton (hand-back, then the host rebuilds at the current f) the mass lost either way is below
+// 1e-199 of a sample's normaliser.  (Pinned entry by entry for all four builders by tests/test_gpu_device_math.py.)
 // ---------------------------------------------------------------------------------------------
 // out[n] = rinv[slot][n] * sqrt(cw[n]): per-sample multiplicities folded into both MFMA operands of the P-mode Gram sweep
 __global__ void __launch_bounds__(256)

@@ -183,9 +183,9 @@ __device__ __forceinline__ void gram_quad_body(const double* __restrict__ u, int
                 }
             }
             if constexpr (!PMODE) exp2s_batch<GROUPS * NQ>(x);
-            if constexpr (STOREP) {  // (what is kept as P: entries below the normal range are flushed to zero)
+            if constexpr (STOREP) {  // (what is kept as P: entries below the normal range, 2^-1022, are flushed to zero)
 #pragma unroll
-                for (int e = 0; e < GROUPS * NQ; ++e) x[e] = x[e] >= 2.3e-308 ? x[e] : 0.0;
+                for (int e = 0; e < GROUPS * NQ; ++e) x[e] = x[e] >= 0x1p-1022 ? x[e] : 0.0;
             }
 #pragma unroll
             for (int g = 0; g < GROUPS; ++g)

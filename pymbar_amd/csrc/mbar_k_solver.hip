@@ -320,8 +320,10 @@ k_make_p(const double* __restrict__ u, int64_t ld, int64_t N, int64_t rows, cons
         double2 pv;
         pv.x = (n < N) ? exp(a - uv.x - logden[n]) : 0.0;
         pv.y = (n + 1 < N) ? exp(a - uv.y - logden[n + 1]) : 0.0;
-        if (!(pv.x >= 2.3e-308)) pv.x = 0.0;  // (also a = -inf: unsampled / padded state)
-        if (!(pv.y >= 2.3e-308)) pv.y = 0.0;
+        // (flush below the normal range -- the bound is 2^-1022 itself: 2.3e-308 used to zero the normal entries in [2^-1022, 2.3e-308)
+        // as well; also a = -inf: unsampled / padded state)
+        if (!(pv.x >= 0x1p-1022)) pv.x = 0.0;
+        if (!(pv.y >= 0x1p-1022)) pv.y = 0.0;
         *reinterpret_cast<double2*>(P + k * ld + n) = pv;
     }
 }
