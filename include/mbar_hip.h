@@ -148,6 +148,12 @@ int mbar_device_synchronize(int device);
  *                    states and 5e7 matrix entries per rank on (default: elsewhere the
  *                    idle launch per iteration costs more than the lighter sweep saves -- with 64 states and fewer both sweeps
  *                    are HBM-bound), 2 = always, 0 = never
+ *   "fused_general"  fused loop up to 128 states: 0 = a context without sample weights runs the fused sweep specialised for unit
+ *                    multiplicities (no weights in the tile, no multiplications by one, the multipliers of the normalisers'
+ *                    matrix steps in registers; default);
+ *                    1 = it runs the general kernel, which a weighted context (bootstrap draw counts, observable weights)
+ *                    always runs.  Same grid, same partial records, same order of every sum: the results are identical to the
+ *                    bit (tests/test_gpu_fused_variants.py) -- the A/B arm of tools/ab_fused_general.py
  *   "direct_results" 1 = mbar_eval on one rank without the Gram matrix: the last reduction level writes the sums into pinned host
  *                    memory itself instead of a device buffer + a copy (default); 0 = always through the device buffer
  *   "sci_merged"     1 = pure self-consistent iteration, K <= 32, one rank: update + sweep of an iteration in ONE launch
@@ -331,7 +337,8 @@ typedef struct mbar_solve_result {
     int32_t builds;      /* ... that built it (build sweep)                       */
     int32_t light_sweeps; /* fused loop: iterations whose sweep ran WITHOUT the speculated Gram matrix because both candidates already
                            * met the stop test against the current f (the last iteration of a solve; option "light_last") */
-    int32_t reserved_;
+    int32_t fused_unit;   /* device-resident loop entries whose fused sweep was the kernel specialised for unit sample multiplicities
+                           * (a context without sample weights, up to 128 states, option "fused_general" = 0); 0: the general kernel */
 } mbar_solve_result;
 
 /* Adaptive NR/SCI on the states with N_k > 0 (others are left untouched).  f_inout[K].

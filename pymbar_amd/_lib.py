@@ -62,7 +62,7 @@ class SolveResult(C.Structure):
         ("warm_starts", C.c_int32),
         ("builds", C.c_int32),
         ("light_sweeps", C.c_int32),
-        ("reserved_", C.c_int32),
+        ("fused_unit", C.c_int32),
     ]
 
 

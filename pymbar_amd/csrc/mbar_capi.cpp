@@ -786,6 +786,10 @@ int mbar_ctx_set_option(mbar_ctx* c, const char* key, int64_t value) {
     else if (k == "pcache") c->opt_pcache = value;
     else if (k == "merge_select") c->opt_merge_select = value;
     else if (k == "light_last") c->opt_light_last = value;
+    else if (k == "fused_general") {
+        c->opt_fused_general = value ? 1 : 0;
+        (void)drop_graphs(c);  // (a captured batch holds the launches of the other kernel)
+    }
     else if (k == "debug_download_p") c->opt_debug_download_p = value;
     else if (k == "direct_results") c->opt_direct_results = value;
     else if (k == "sci_merged") c->opt_sci_merged = value;

@@ -279,9 +279,11 @@ hipError_t launch_psweep(hipStream_t s, int nb, int nf, const LaunchGeom& g, con
                          const double* cmul, const double* cw, double* rinv0, double* rinv1, double* psum_part,
                          const LoopCtl& lc = LoopCtl());
 // fused sweep: both candidates' normalisers / per-state sums + the Gram matrix of the second (Newton-Raphson) candidate
-LaunchGeom fused_geometry(int nb, int num_cu, int64_t ntiles, int64_t grid_override);
+// unit: cw is all ones (a context without sample weights) -- up to 128 states the kernel specialised for it runs (same grid, same
+// sums to the bit); the geometry and the launch must be given the same value
+LaunchGeom fused_geometry(int nb, int num_cu, int64_t ntiles, int64_t grid_override, bool unit = false);
 hipError_t launch_fused(hipStream_t s, int nb, const LaunchGeom& g, const double* P, int64_t ld, int64_t N, const double* cmul,
-                        const double* cw, const double* wsq, double* rinv_base, double* gram_part, double* psum_part,
+                        const double* cw, const double* wsq, bool unit, double* rinv_base, double* gram_part, double* psum_part,
                         const LoopCtl& lc);
 // fused build: the single-candidate sweep at the anchor point (psum partial records [nwaves][16 nb]) that also writes P and
 // fills the reciprocal slot with ones

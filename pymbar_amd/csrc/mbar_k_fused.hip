@@ -24,6 +24,13 @@ namespace mbar {
 //     all four groups' operands alive), and the loop body is ONE basic block (the register allocator handles the pinned
 //     accumulators only then).
 // wsq: sqrt of the per-sample multiplicities (= cw itself for plain 0 / 1 weights).
+// UNIT: every sample counts once (a context without sample weights: cw is a vector of ones) -- the tile carries no weights' piece,
+// no group reads or multiplies by w / sw (x * 1.0 is exact: the results are the general kernel's to the bit), and the 4 NB
+// multiplier operands of the 4x4x4 steps, which never change during a launch, sit in registers instead of being read from LDS
+// every tile (full panel: 52 -> 32 LDS read instructions, 17 -> 16 LDS-DMA pieces and 40 -> 32 multiplications per tile, 452
+// of 512 registers).  A sample beyond N, which the general kernel drops through its multiplicity of zero, gets the reciprocal
+// zero there (store_rinv: one select per tile) -- its column of P is NOT zero when k_build_sweep built the matrix.  Option
+// "fused_general" runs the general kernel instead.
 // ---------------------------------------------------------------------------------------------
 // (Measured dead end, twice: the diagonal 16 x 16 blocks of the full panel as three v_mfma_f64_4x4x4_4b_f64 each -- 48 matrix-pipe
 // cycles instead of 64, half of the 16x16x4 block lies below the diagonal.  Round 2, with DPP-rotated copies of the scaled operand:
@@ -44,7 +51,7 @@ __host__ __device__ constexpr int fused_steps_done(int I) {
     const int rows = NB - 2 - r1;     // rows r1 + 1 .. NB - 2 share the second batch
     return NB + (NB * (I - r1) + rows - 1) / rows;
 }
-template <int NB, bool WIDE>
+template <int NB, bool WIDE, bool UNIT>
 __global__ void __launch_bounds__(256, 1)
 k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, const double* __restrict__ cmul,
         const double* __restrict__ cw, const double* __restrict__ wsq, double* __restrict__ rinv0,
@@ -58,9 +65,9 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
         rinv0 = rinv0 + (int64_t)((s + 1) % 3) * slot_stride;
     }
     constexpr int ROWS = NB * 16;
-    constexpr int NDMA = ROWS / 8 + 1;            // tile rows + one piece for the two weight vectors
+    constexpr int NDMA = ROWS / 8 + (UNIT ? 0 : 1);         // tile rows + one piece for the two weight vectors
     constexpr int U_BYTES = ROWS * TS * 8;
-    constexpr int TILE_BYTES = U_BYTES + 1024;    // (the weights' piece is a full-wave LDS-DMA too: no exec-masked branch)
+    constexpr int TILE_BYTES = U_BYTES + (UNIT ? 0 : 1024);  // (the weights' piece is a full-wave LDS-DMA too: no exec-masked branch)
     constexpr int NBLK = NB * (NB + 1) / 2;
     constexpr bool PINNED = NBLK > GRAM_AGPR_BLOCKS;
     // Full panel: the per-state sums of the SECOND candidate are not accumulated here -- the rows of p sum to one, so they are
@@ -93,9 +100,19 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
     // j + 4 b + 16 k, D lane = j + 4 b + 16 i), so with the tile read a SECOND time as A(sample = lane & 15, state = 4 step +
     // (lane >> 4)) and the multipliers as B(candidate = lane & 3, same state) 32 instructions of 16 cycles leave
     // s[sample (lane >> 4) + 4 ((lane >> 2) & 3)][candidate lane & 3] in one register -- in place of 64 FMAs, 128 DPP moves,
-    // 32 adds and eight reciprocals.  The multiplier operand is a 4 KB table behind the wave buffers.
+    // 32 adds and eight reciprocals.  The multiplier operand is a 4 KB table behind the wave buffers (UNIT: NSTEP registers, made
+    // opaque so that the compiler cannot load them again inside the loop).
     constexpr int NSTEP = ROWS / 4;
-    {
+    double cb[UNIT ? NSTEP : 1];
+    if constexpr (UNIT) {
+#pragma unroll
+        for (int st = 0; st < NSTEP; ++st) {
+            // (lanes of candidates 2 and 3 load candidate (lane & 1)'s entry and drop it: no exec-masked branch per load)
+            const double cv = cmul[(lane & 1) * ROWS + 4 * st + (lane >> 4)];
+            cb[st] = (lane & 3) < 2 ? cv : 0.0;
+            asm volatile("" : "+v"(cb[st]));
+        }
+    } else {
         double* ctab = reinterpret_cast<double*>(smem + nwv * (2 * TILE_BYTES));
         for (int e = threadIdx.x; e < NSTEP * 16; e += blockDim.x) ctab[e] = (e & 3) < 2 ? cmul[(e & 3) * ROWS + (e >> 2)] : 0.0;
         __syncthreads();
@@ -122,19 +139,22 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
     };
     auto stage = [&](int64_t tile, char* dst) {
         stage_tile<ROWS, true, 0, 1>(P, ld, tile * TS, dst, lane, so, rows);
-        stage_w(tile, dst);
+        if constexpr (!UNIT) stage_w(tile, dst);
     };
     // operands of group g in the Gram layout (state 16 I + ks, sample 4 g + ns) + the sample's multiplicity and its root
     auto read_group = [&](const char* tb, int g, double (&x)[NB], double& wg, double& swg) {
-        wg = *reinterpret_cast<const double*>(tb + U_BYTES + (4 * g + ns) * 8);
-        swg = *reinterpret_cast<const double*>(tb + U_BYTES + TS * 8 + (4 * g + ns) * 8);
+        if constexpr (!UNIT) {
+            wg = *reinterpret_cast<const double*>(tb + U_BYTES + (4 * g + ns) * 8);
+            swg = *reinterpret_cast<const double*>(tb + U_BYTES + TS * 8 + (4 * g + ns) * 8);
+        }
 #pragma unroll
         for (int I = 0; I < NB; ++I) x[I] = *reinterpret_cast<const double*>(tb + I * (16 * TS * 8) + rd_base + pos[g]);
     };
     uint32_t cop_off = (uint32_t)(nwv * (2 * TILE_BYTES) + (lane >> 4) * 32 + (lane & 3) * 8);
     auto read_step = [&](const char* tb, int st, double& a, double& b) {
         a = *reinterpret_cast<const double*>(tb + st * (4 * TS * 8) + apos[st & 3]);
-        b = *reinterpret_cast<const double*>(smem + cop_off + st * 128);
+        if constexpr (UNIT) b = cb[st];
+        else b = *reinterpret_cast<const double*>(smem + cop_off + st * 128);
     };
     // (first: the accumulator starts from the inline constant 0 -- a register zeroed by a VALU move right in front of an asm
     // matrix instruction, where the hazard recogniser cannot see it, gave wrong sums)
@@ -148,10 +168,14 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
             d = __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, first ? 0.0 : d, 0, 0, 0);
         }
     };
-    auto store_rinv = [&](int64_t tile, double r) {
+    auto store_rinv = [&](int64_t tile, double& r) {
         // exactly ONE store instruction per tile and wave (sample 0 of every tile exists): the vmcnt bookkeeping needs it
         const int64_t n = tile * TS + sq;
         double* out = fq ? rinv1 : rinv0;
+        // (UNIT: no multiplicity of zero takes a sample beyond N out of the sums, and its column of P is zero only after
+        // k_build_gram / k_make_p -- k_build_sweep normalises the zero energies of the padding like any sample's.  Its reciprocal
+        // is zeroed instead: the same products w r = 0 and r sw = 0 as in the general kernel, once per tile rather than per group.)
+        if constexpr (UNIT) r = n < N ? r : 0.0;
         if (n < N && fq < 2) out[n] = r;
     };
     // Software pipeline over the wave's tiles t_0, t_1, ... (two LDS buffers): while the Gram blocks of tile t_i issue, the
@@ -191,7 +215,7 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
         const int64_t tn = t + W, tnn = t + 2 * W;
         const int64_t tstage = tnn < ntiles ? tnn : t;
         // (the multiplier table never changes: without this the compiler keeps all of it in 8 NB registers)
-        asm volatile("" : "+v"(cop_off));
+        if constexpr (!UNIT) asm volatile("" : "+v"(cop_off));
         // (four accumulators in rotation: the asm 4x4x4 blocks are invisible to the hazard recogniser, and a dependent one
         // needs four wait states after its predecessor)
         double sacc[4];
@@ -206,7 +230,7 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
                 case 2: r0 = row16_bcast<8>(rcur); r1 = row16_bcast<9>(rcur); break;
                 default: r0 = row16_bcast<12>(rcur); r1 = row16_bcast<13>(rcur); break;
             }
-            const double q0 = w[gc] * r0, q1 = w[gc] * r1;
+            const double q0 = UNIT ? r0 : w[gc] * r0, q1 = UNIT ? r1 : w[gc] * r1;
 #pragma unroll
             for (int I = 0; I < NB; ++I) {
                 acc[0][I] = fma(uv[gc][I], q0, acc[0][I]);
@@ -216,8 +240,8 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
                 settle(acc[0][I]);
                 if constexpr (ACC1) settle(acc[1][I]);
             }
-            // (a padded sample needs no mask: its multiplicity and the root of it are stored as zeros)
-            const double rin = r1 * sw[gc];  // operand of the Newton-Raphson candidate's Gram matrix
+            // (a padded sample needs no mask: its multiplicity and the root of it are stored as zeros; UNIT: its reciprocal is)
+            const double rin = UNIT ? r1 : r1 * sw[gc];  // operand of the Newton-Raphson candidate's Gram matrix
             double p[NB];
 #pragma unroll
             for (int I = 0; I < NB; ++I) p[I] = uv[gc][I] * rin;
@@ -285,7 +309,7 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
                             if constexpr (PINNED) __builtin_amdgcn_sched_barrier(0);
                             if (j < ROWS / 8)
                                 stage_piece<true>(P + rows(8 * j) * ld + rows.cols(j, tstage * TS), so.off[j & 1], cbuf + j * 1024, lane);
-                            else
+                            else if constexpr (!UNIT)
                                 stage_w(tstage, cbuf);
                             if constexpr (PINNED) __builtin_amdgcn_sched_barrier(0);
                         }
@@ -350,7 +374,9 @@ k_fused(const double* __restrict__ P, int64_t ld, int64_t N, int64_t ntiles, con
 // ---------------------------------------------------------------------------------------------
 
 // Fused sweep (P mode): geometry of the full Gram panel -- one workgroup of four waves per CU, two tile buffers per wave.
-LaunchGeom fused_geometry(int nb, int num_cu, int64_t ntiles, int64_t grid_override) {
+// unit: the launch is k_fused<.., UNIT> (no weights' piece, no multiplier table in LDS); the grid -- and with it the partial
+// records and the order of every sum -- is that of the general kernel, so that the two agree to the bit.
+LaunchGeom fused_geometry(int nb, int num_cu, int64_t ntiles, int64_t grid_override, bool unit) {
     LaunchGeom g;
     g.waves = 4;
     g.variant = 1;
@@ -365,12 +391,15 @@ LaunchGeom fused_geometry(int nb, int num_cu, int64_t ntiles, int64_t grid_overr
         return g;
     }
     const size_t tile = (size_t)nb * 16 * TS * 8 + 1024;    // + one LDS-DMA piece for the two weight vectors
-    g.lds_bytes = (size_t)4 * 2 * tile + (size_t)nb * 512;  // + the candidates' multipliers as a 4x4x4 MFMA operand
+    // The GRID is derived from the general kernel's LDS size in both forms (by_lds below): the unit form needs less, but a grid
+    // of its own would change the partial records and the order of the sums, and the two forms would no longer agree to the bit.
+    const size_t lds_general = (size_t)4 * 2 * tile + (size_t)nb * 512;  // + the candidates' multipliers as a 4x4x4 MFMA operand
+    g.lds_bytes = unit ? (size_t)4 * 2 * (tile - 1024) : lds_general;    // what the launch asks for
     int64_t want = (ntiles + 3) / 4;
     int64_t cap = num_cu;
     if (nb <= 5) {  // narrow panels: few accumulators, several workgroups per CU (cf. gram_geometry)
         static const int occ[6] = {1, 4, 4, 3, 2, 2};
-        const int by_lds = blocks_per_cu_for(g.lds_bytes);
+        const int by_lds = blocks_per_cu_for(lds_general);
         cap = (int64_t)num_cu * (by_lds < occ[nb] ? by_lds : occ[nb]);
         // ... but every wave leaves a partial record (NB (NB + 1) / 2 blocks of 2 KB + the per-state sums) and pays a prologue:
         // a second workgroup per CU only once a wave has ~32 tiles to work on (config 5, K = 40, N = 95 000: 58 instead of
@@ -388,7 +417,7 @@ LaunchGeom fused_geometry(int nb, int num_cu, int64_t ntiles, int64_t grid_overr
 }
 template <int NB>
 static hipError_t launch_fused_nb(hipStream_t s, const LaunchGeom& g, const double* P, int64_t ld, int64_t N, const double* cmul,
-                                  const double* cw, const double* wsq, double* rinv0, double* gp, double* pp, const LoopCtl& lc) {
+                                  const double* cw, const double* wsq, bool unit, double* rinv0, double* gp, double* pp, const LoopCtl& lc) {
     auto go = [&](auto kern) -> hipError_t {
         if (g.lds_bytes > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -405,16 +434,17 @@ static hipError_t launch_fused_nb(hipStream_t s, const LaunchGeom& g, const doub
                                lc.ctl, lc.slot_stride);
         return hipGetLastError();
     };
-    return stage_offsets_wide(ld) ? go(k_fused<NB, true>) : go(k_fused<NB, false>);
+    if (unit) return stage_offsets_wide(ld) ? go(k_fused<NB, true, true>) : go(k_fused<NB, false, true>);
+    return stage_offsets_wide(ld) ? go(k_fused<NB, true, false>) : go(k_fused<NB, false, false>);
 }
 hipError_t launch_fused(hipStream_t s, int nb, const LaunchGeom& g, const double* P, int64_t ld, int64_t N, const double* cmul,
-                        const double* cw, const double* wsq, double* rinv_base, double* gram_part, double* psum_part,
+                        const double* cw, const double* wsq, bool unit, double* rinv_base, double* gram_part, double* psum_part,
                         const LoopCtl& lc) {
     if (!lc.ctl) return hipErrorInvalidValue;  // (the slot vectors are addressed through the control words)
     if (nb == 12 || nb == 16) return launch_fused_quad(s, nb, g, P, ld, N, cmul, cw, wsq, rinv_base, gram_part, psum_part, lc);
     switch (nb) {
 #define MBAR_CASE(NB_) \
-    case NB_: return launch_fused_nb<NB_>(s, g, P, ld, N, cmul, cw, wsq, rinv_base, gram_part, psum_part, lc);
+    case NB_: return launch_fused_nb<NB_>(s, g, P, ld, N, cmul, cw, wsq, unit, rinv_base, gram_part, psum_part, lc);
         MBAR_CASE(1) MBAR_CASE(2) MBAR_CASE(3) MBAR_CASE(4) MBAR_CASE(5) MBAR_CASE(6) MBAR_CASE(7) MBAR_CASE(8)
 #undef MBAR_CASE
         default: return hipErrorInvalidValue;

@@ -392,7 +392,8 @@ int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_
     // geometry and buffers are fixed for the whole solve (nothing may allocate inside a capture)
     LaunchGeom gg = wide ? gram_quad_geometry(nb, c->num_cu, ntiles, c->opt_grid)
                          : gram_geometry(nb * 16, true, c->num_cu, ntiles, c->opt_grid);
-    LaunchGeom gl = fused ? fused_geometry(nb, c->num_cu, ntiles, c->opt_grid)
+    const bool unit = !c->weighted && !c->opt_fused_general;  // (k_fused without the x 1.0 work of unit multiplicities)
+    LaunchGeom gl = fused ? fused_geometry(nb, c->num_cu, ntiles, c->opt_grid, unit)
                     : pmode ? psweep_geometry(nb, c->num_cu, ntiles, c->opt_grid)
                             : lse_geometry(nb, 2, c->num_cu, ntiles, c->opt_grid, lse_variant_for(c));
     if (wide) gg.live_blocks = gl.live_blocks = quad_live_blocks(c);
@@ -477,8 +478,8 @@ int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_
         HIPCHK(c, hipMemsetAsync(c->red, 0, off_gram * sizeof(double), c->stream));
         {
             ScopedTimer t(c, MBAR_TIMER_OTHER);
-            HIPCHK(c, launch_fused(c->stream, nb, gl, c->P, c->ld, c->N, d_aden(c), c->cw, c->weighted ? c->cwsq : c->cw, c->logden[0],
-                                   c->part_g, c->part, lc_slot));
+            HIPCHK(c, launch_fused(c->stream, nb, gl, c->P, c->ld, c->N, d_aden(c), c->cw, c->weighted ? c->cwsq : c->cw, unit,
+                                   c->logden[0], c->part_g, c->part, lc_slot));
         }
         HIPCHK(c, launch_reduce2(c->stream, c->part, (int64_t)rec_l, c->part_g, (int64_t)rec_g, gl.nwaves, c->scratch, c->red,
                                  c->red + off_gram));
@@ -731,7 +732,7 @@ int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_
             if (ext) { lcb.ev_start = tp.a; lcb.ev_stop = tp.b; }
             if (tp.a && tp.b && !ext) (void)hipEventRecord(tp.a, c->stream);
             if (fused) {
-                HIPCHK(c, launch_fused(c->stream, nb, gl, c->P, c->ld, c->N, d_aden(c), c->cw, c->weighted ? c->cwsq : c->cw,
+                HIPCHK(c, launch_fused(c->stream, nb, gl, c->P, c->ld, c->N, d_aden(c), c->cw, c->weighted ? c->cwsq : c->cw, unit,
                                        c->logden[0], gram_part, psum_part, lcb));
                 if (light && !wide) {  // (idle unless k_newton found that this iteration is the last: then the fused sweep is the idle one)
                     LoopCtl lcl = lc_slot;
@@ -907,6 +908,7 @@ int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_
     res.nr_iter = c->h_ctl[CTL_NR];
     res.gram_sweeps += fused ? gram_sweeps : (int32_t)(it - it_start);
     res.light_sweeps += c->h_ctl[CTL_LIGHTS];
+    if (fused && !wide && unit) res.fused_unit += 1;  // (what launch_fused was told: k_fused<.., UNIT>)
     if (handed_back) {
         c->P_valid = false;  // (the continuation re-anchors: a state whose weights underflow at this anchor has a zero row in P)
         static const char* why[] = {"", "the Newton system is not positive definite", "a candidate is too far from the point the sweeps are anchored at",
