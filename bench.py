@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """Benchmark of the MBAR solver hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and nothing else: it generates the workload, warms up, times the K steps, writes
+``--dump-outputs`` and prints the JSON line (``value``, ``ms_per_step``, and the roofline of the sweep from the HIP-event timers
+of the timed steps themselves).  ``--full`` adds, after that and in the same line, every other measurement described below: the
+solves to convergence (``per_solve``), the measured fp64 matrix peak, the CPU baseline, the class end to end, configs 2, 4 and 5
+and the strong-scaling model -- about half a minute more on one GPU.  The line says which of the two it is (``"full"``).
 
 Workload (BASELINE.json metric "MBAR solver iterations/sec + wallclock-to-converge, K=128 N=1e7, 1/2/4/8 GPUs"): the
 synthetic harmonic ladder O_k = linspace(0,4,K), K_k = linspace(1,3,K), equal N_k, K = 128, fp64, generated directly
@@ -11,7 +17,7 @@ in HBM from a counter RNG keyed by (seed, global sample index), so every shardin
 
     --gpus 1, 2, 4, 8 : config 3 -- the configuration the metric is quoted on -- N = 1e7 samples in TOTAL, column-sharded over the
                         GPUs (strong scaling: `value` at N GPUs against N x `value` at one is the scaling efficiency)
-    --gpus 8          : ALSO measures config 4 (N = 1e8 in total = 1.25e7 per GPU) after the headline run and reports it as the
+    --gpus 8 --full   : ALSO measures config 4 (N = 1e8 in total = 1.25e7 per GPU) after the headline run and reports it as the
                         `config4` object of the same JSON line (`--config4 0` skips it, `--config4 1` forces it at any count)
 
 A step is ONE adaptive iteration (pymbar/mbar_solvers.py:575-640): the K x K Newton solve from the Hessian at the current f,
@@ -22,7 +28,7 @@ call of exactly K iterations with the convergence test disabled, including the s
 gradient and Hessian at the start point).  From f = 0 this workload converges in 5 iterations, so most of the K timed steps
 run at the fixed point; they cost the same ONE sweep as the steps before it as long as no speculation is rejected
 (``separate_gram_sweeps_in_timed_region`` counts the rejected ones: each costs one more sweep, and none occurs here).  What
-the steady-state rate hides is the build sweep, amortised over K steps instead of a real solve's 5: ``per_solve`` reports the
+the steady-state rate hides is the build sweep, amortised over K steps instead of a real solve's 5: ``per_solve`` (``--full``) reports the
 solve from f = 0 to tol 1e-12 -- iterations, wall clock, ms per iteration and the fraction of the fp64 matrix peak over the
 WHOLE solve -- for min_sc_iter = 0 (BASELINE's adaptive configuration) and for the reference's default min_sc_iter = 2.
 ``value`` = solver iterations per second of the whole job (NOT multiplied by the number of GPUs).
@@ -36,7 +42,7 @@ code 3, the RCCL error on stderr): a number over the host transport is not the m
 run go on as a diagnosis of the node -- its line then says ``"valid": false``, ``config.allreduce == "host-fallback"`` with the
 RCCL error beside it (``config.rccl_error``), carries no config 4, and the process still exits with code 4.
 
-At ``--gpus 1`` the line also carries ``config4_one_device`` (BASELINE.json config 4's WHOLE matrix, K=128, N=1e8, on the one
+At ``--gpus 1 --full`` the line also carries ``config4_one_device`` (BASELINE.json config 4's WHOLE matrix, K=128, N=1e8, on the one
 288 GB device: 102 GB of u + 102 GB of resident probabilities -- NOT the 8-GPU metric) and ``scaling_model``: the pieces of
 one iteration measured on ONE GPU at the shard sizes of 1, 2, 4 and 8 ranks, and what they predict for the strong-scaling
 curve -- a model, labelled as such, since no multi-GPU run can be made from here.
@@ -503,6 +509,125 @@ def scaling_model_object(dev, K, N_total, seed, steps, warmup):
     }
 
 
+def full_measurements(args, dm, group, rank, world, dev, info, allreduce, K, N_total, n_loc, O_k, K_k, N_k):
+    """``--full``: what the line carries beyond the headline run, measured after the timed steps (and after ``--dump-outputs``) --
+    the solves to convergence, the measured fp64 matrix peak, config 4, the CPU baseline, the class end to end, configs 2 and 5,
+    the strong-scaling model and config 4's whole matrix on one device; the options that skip or force a leg apply as before.
+    ``dm`` is the matrix of the headline run; the one-GPU legs that need the device to themselves close it.  Returns
+    ``(keys of the line, measured matrix peak, dm or None)``."""
+    from pymbar_amd import _lib
+    from pymbar_amd import testsystems as ts
+    from pymbar_amd.device import DeviceMatrix
+
+    f0 = np.zeros(K)
+
+    def barrier_sync():
+        if group is not None:
+            group.barrier()
+        dm.device_synchronize()
+
+    # ---- wall-clock to converge from f = 0 (reported, not the headline value): whole solves, build sweep included ----
+    def timed_solve(min_sc_iter, warm=False):
+        # cold: the solver call builds its resident probability matrix (what a first solve on a matrix costs); warm: the matrix
+        # of the previous call is re-used (bootstrap replicates, protocol stages: one fused sweep instead of the build sweep)
+        dm.set_option("pcache", 1 if warm else 0)
+        barrier_sync()
+        t0 = time.perf_counter()
+        f_c, r_c = dm.solve_adaptive(f0, tol=1e-12, maxiter=10000, min_sc_iter=min_sc_iter, check_convergence=True)
+        barrier_sync()
+        t = time.perf_counter() - t0
+        if group is not None:
+            tt = np.array([t])
+            group.allreduce(tt, "max")
+            t = float(tt[0])
+        return f_c, r_c, t
+
+    f_conv, conv, t_conv = timed_solve(0)
+    _, conv2, t_conv2 = timed_solve(2)   # the reference's default for adaptive() (mbar_solvers.py:545; "robust" protocol)
+    dm.set_option("pcache", 1)
+    dm.solve_adaptive(f0, tol=1e-12, maxiter=10000, min_sc_iter=0)  # (leaves its probability matrix behind)
+    _, conv_w, t_conv_w = timed_solve(0, warm=True)
+    err_analytic = float(np.max(np.abs(f_conv - ts.harmonic_free_energies(K_k))))
+
+    mfma_peak = dm.mfma_f64_peak() if rank == 0 else None
+
+    # ---- config 4 (K = 128, N = 1e8 in total, sharded): BASELINE.json's eight-GPU configuration, next to the headline run ----
+    config4 = None
+    if (args.config4 == 1 or (args.config4 < 0 and world >= 8)) and N_total != 100_000_000 and allreduce != "host-fallback":
+        config4 = config4_object(dev, K, args, rank, world, group)
+
+    cpu = None
+    if rank == 0 and world == 1 and args.cpu_sample > 0:
+        def factory(n):
+            return DeviceMatrix.harmonic(O_k, K_k, N_k, seed=args.seed, n_global0=0, N_local=n, device=dev)
+        cpu = cpu_baseline(factory, K, N_total, min(args.cpu_sample, n_loc), args.seed)
+
+    e2e = None
+    if rank == 0 and world == 1 and args.api_e2e:
+        dm.close()  # the end-to-end run owns its own device copy
+        dm = None
+        e2e = api_end_to_end(K, N_total, args.seed, dev, O_k, K_k, N_k)
+
+    config2 = config5 = None
+    if rank == 0 and world == 1 and args.small_configs:
+        if dm is not None:
+            dm.close()
+            dm = None
+        config2 = config2_object(dev, args.seed)
+        config5 = config5_object(dev)
+
+    scaling_model = config4_one = None
+    if rank == 0 and world == 1 and N_total == 10_000_000 and args.device_loop and args.pmode and args.fused:
+        if args.scaling_model:
+            if dm is not None:
+                dm.close()
+                dm = None
+            scaling_model = scaling_model_object(dev, K, N_total, args.seed, args.steps, args.warmup)
+        want4 = args.config4_one_device
+        if want4 == 1 or (want4 < 0 and info["total_mem_bytes"] >= 230 * (1 << 30)):
+            if dm is not None:
+                dm.close()
+                dm = None
+            _lib.load_library().mbar_cache_trim()  # (205 GB of 288: the parked blocks of the runs above go back to the driver first)
+            try:
+                config4_one = config4_object(dev, K, args, 0, 1, None)
+            except Exception as exc:  # (a shared or smaller device: the headline line must still be printed)
+                config4_one = {"skipped": f"{type(exc).__name__}: {exc}"}
+
+    flops = float(n_loc) * K * (K + 1)  # one Hessian's matrix flop on this rank's shard
+    keys = {
+        "cpu_baseline": cpu,
+        "wallclock_to_converge_s": t_conv,
+        "iterations_to_converge": int(conv["iterations"]),
+        "converged": bool(conv["success"]),
+        "nr_iterations": int(conv["nr_iter"]), "sci_iterations": int(conv["sci_iter"]),
+        "separate_gram_sweeps_to_converge": int(conv.get("gram_sweeps", -1)),
+        # whole solves from f = 0 to tol 1e-12 (build sweep included): `frac` = one Hessian's matrix flop per iteration
+        # over the wall clock of the solve, against the fp64 matrix peak
+        "per_solve": {
+            name: {"min_sc_iter": msc, "iterations": int(r["iterations"]), "nr_iterations": int(r["nr_iter"]),
+                   "sci_iterations": int(r["sci_iter"]), "converged": bool(r["success"]), "wallclock_ms": 1e3 * t,
+                   "ms_per_iteration": 1e3 * t / max(1, int(r["iterations"])),
+                   "iterations_per_s": int(r["iterations"]) / t,
+                   "separate_gram_sweeps": int(r.get("gram_sweeps", -1)),
+                   # (the last iteration's sweep when both candidates already met the stop test: no Hessian accumulated, none needed)
+                   "sweeps_without_gram_matrix": int(r.get("light_sweeps", -1)),
+                   "build_sweeps": int(r.get("builds", -1)), "warm_starts": int(r.get("warm_starts", -1)),
+                   "frac": int(r["iterations"]) * flops * world / t * 1e-12 / (FP64_MFMA_PEAK_TFLOPS * world)}
+            for name, msc, r, t in (("adaptive_min_sc_iter_0", 0, conv, t_conv), ("adaptive_min_sc_iter_2", 2, conv2, t_conv2),
+                                    ("adaptive_min_sc_iter_0_warm_start", 0, conv_w, t_conv_w))},
+        "max_abs_error_vs_analytic_f": err_analytic,
+        "gnorm_at_solution": float(conv["gnorm"]),
+        "api_end_to_end": e2e,
+        "config2": config2,
+        "config4": config4,
+        "config4_one_device": config4_one,
+        "config5": config5,
+        "scaling_model": scaling_model,
+    }
+    return keys, mfma_peak, dm
+
+
 def dump_outputs(out_dir, f_end, res):
     """What the timed solver call hands its caller after its last step, as ``out_dir/<name>.npy`` (float64, ~2 kB at K = 128):
     the free energies, the per-state sums at them, the step's stopping statistics and its iteration counts."""
@@ -567,11 +692,16 @@ def main():
     ap.add_argument("--n-total", type=int, default=0,
                     help="samples in total (default: 1e7 = config 3 for 1, 2, 4 GPUs; 1e8 = config 4 for 8 GPUs)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the line can carry: the solves to convergence, the measured "
+                         "fp64 matrix peak, the CPU baseline, MBAR(u_kn_host, N_k) end to end, configs 2, 4 and 5 and the strong-scaling "
+                         "model.  Off by default: a plain run sets up, warms up, times the steps and prints the line.  The options "
+                         "marked (--full) below choose among these extra measurements and do nothing without it")
     ap.add_argument("--cpu-sample", type=int, default=1_600_000,
-                    help="columns for the CPU baseline: ~10-15 s of CPU work on the GPU host (0 = skip)")
-    ap.add_argument("--api-e2e", type=int, default=1, help="also time MBAR(u_kn_host, N_k) end to end (1 GPU only; 0 = skip)")
+                    help="(--full) columns for the CPU baseline: ~10-15 s of CPU work on the GPU host (0 = skip)")
+    ap.add_argument("--api-e2e", type=int, default=1, help="(--full) also time MBAR(u_kn_host, N_k) end to end (1 GPU only; 0 = skip)")
     ap.add_argument("--small-configs", type=int, default=1,
-                    help="also measure BASELINE.json configs 2 and 5 (1 GPU only, < 1 s of GPU time together; 0 = skip)")
+                    help="(--full) also measure BASELINE.json configs 2 and 5 (1 GPU only, < 1 s of GPU time together; 0 = skip)")
     ap.add_argument("--device-loop", type=int, default=1, help="0 = host-driven adaptive loop (A/B)")
     ap.add_argument("--pmode", type=int, default=1,
                     help="1 = the device-resident loop sweeps the resident probability matrix P = exp(a0 - u - logden(a0)) "
@@ -586,12 +716,12 @@ def main():
                     help="testing only: let --gpus N spawn more ranks than the box has GPUs (ranks share devices; RCCL refuses that, so "
                          "this needs --allow-host-allreduce and proves nothing but that the multi-rank bench path executes)")
     ap.add_argument("--config4-one-device", type=int, default=-1,
-                    help="--gpus 1: also measure config 4's WHOLE matrix (K=128, N=1e8) on the one device as `config4_one_device`: "
+                    help="(--full) --gpus 1: also measure config 4's WHOLE matrix (K=128, N=1e8) on the one device as `config4_one_device`: "
                          "-1 = when the device has 230 GB or more (default), 0 = never, 1 = always")
     ap.add_argument("--scaling-model", type=int, default=1,
-                    help="--gpus 1: also measure the pieces of an iteration at the shard sizes of 1/2/4/8 ranks and emit `scaling_model` (0 = skip)")
+                    help="(--full) --gpus 1: also measure the pieces of an iteration at the shard sizes of 1/2/4/8 ranks and emit `scaling_model` (0 = skip)")
     ap.add_argument("--config4", type=int, default=-1,
-                    help="also measure config 4 (K=128, N=1e8 in total, sharded) after the headline run: -1 = only with 8 or more "
+                    help="(--full) also measure config 4 (K=128, N=1e8 in total, sharded) after the headline run: -1 = only with 8 or more "
                          "GPUs (default), 0 = never, 1 = always (needs 205 GB on a single GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed solver call returned in its last step as DIR/<name>.npy "
@@ -693,73 +823,10 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, f_end, res)
 
-    # ---- wall-clock to converge from f = 0 (reported, not the headline value): whole solves, build sweep included ----
-    def timed_solve(min_sc_iter, warm=False):
-        # cold: the solver call builds its resident probability matrix (what a first solve on a matrix costs); warm: the matrix
-        # of the previous call is re-used (bootstrap replicates, protocol stages: one fused sweep instead of the build sweep)
-        dm.set_option("pcache", 1 if warm else 0)
-        barrier_sync()
-        t0 = time.perf_counter()
-        f_c, r_c = dm.solve_adaptive(f0, tol=1e-12, maxiter=10000, min_sc_iter=min_sc_iter, check_convergence=True)
-        barrier_sync()
-        t = time.perf_counter() - t0
-        if group is not None:
-            tt = np.array([t])
-            group.allreduce(tt, "max")
-            t = float(tt[0])
-        return f_c, r_c, t
-
-    f_conv, conv, t_conv = timed_solve(0)
-    _, conv2, t_conv2 = timed_solve(2)   # the reference's default for adaptive() (mbar_solvers.py:545; "robust" protocol)
-    dm.set_option("pcache", 1)
-    dm.solve_adaptive(f0, tol=1e-12, maxiter=10000, min_sc_iter=0)  # (leaves its probability matrix behind)
-    _, conv_w, t_conv_w = timed_solve(0, warm=True)
-    err_analytic = float(np.max(np.abs(f_conv - ts.harmonic_free_energies(K_k))))
-
-    mfma_peak = dm.mfma_f64_peak() if rank == 0 else None
-
-    # ---- config 4 (K = 128, N = 1e8 in total, sharded): BASELINE.json's eight-GPU configuration, next to the headline run ----
-    config4 = None
-    if (args.config4 == 1 or (args.config4 < 0 and world >= 8)) and N_total != 100_000_000 and allreduce != "host-fallback":
-        config4 = config4_object(dev, K, args, rank, world, group)
-
-    cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
-        def factory(n):
-            return DeviceMatrix.harmonic(O_k, K_k, N_k, seed=args.seed, n_global0=0, N_local=n, device=dev)
-        cpu = cpu_baseline(factory, K, N_total, min(args.cpu_sample, n_loc), args.seed)
-
-    e2e = None
-    if rank == 0 and world == 1 and args.api_e2e:
-        dm.close()  # the end-to-end run owns its own device copy
-        dm = None
-        e2e = api_end_to_end(K, N_total, args.seed, dev, O_k, K_k, N_k)
-
-    config2 = config5 = None
-    if rank == 0 and world == 1 and args.small_configs:
-        if dm is not None:
-            dm.close()
-            dm = None
-        config2 = config2_object(dev, args.seed)
-        config5 = config5_object(dev)
-
-    scaling_model = config4_one = None
-    if rank == 0 and world == 1 and N_total == 10_000_000 and args.device_loop and args.pmode and args.fused:
-        if args.scaling_model:
-            if dm is not None:
-                dm.close()
-                dm = None
-            scaling_model = scaling_model_object(dev, K, N_total, args.seed, args.steps, args.warmup)
-        want4 = args.config4_one_device
-        if want4 == 1 or (want4 < 0 and info["total_mem_bytes"] >= 230 * (1 << 30)):
-            if dm is not None:
-                dm.close()
-                dm = None
-            _lib.load_library().mbar_cache_trim()  # (205 GB of 288: the parked blocks of the runs above go back to the driver first)
-            try:
-                config4_one = config4_object(dev, K, args, 0, 1, None)
-            except Exception as exc:  # (a shared or smaller device: the headline line must still be printed)
-                config4_one = {"skipped": f"{type(exc).__name__}: {exc}"}
+    # ---- everything beyond the headline run: only with --full ----
+    more, mfma_peak = None, None
+    if args.full:
+        more, mfma_peak, dm = full_measurements(args, dm, group, rank, world, dev, info, allreduce, K, N_total, n_loc, O_k, K_k, N_k)
 
     if rank == 0:
         it_per_s = args.steps / elapsed
@@ -832,7 +899,8 @@ def main():
             }
             outside = ms_step - gram_avg - lse_avg
             extra = {}
-        roof["measured_mfma_f64_peak_tflops"] = mfma_peak
+        if args.full:
+            roof["measured_mfma_f64_peak_tflops"] = mfma_peak
         ghz, ghz_src = measured_kernel_clock()
         if ghz and roof.get("bound") == "mfma":
             # (the share of the gap to the spec-sheet peak that is the power limit, not the kernel: 78.6 TFLOP/s is 2.4 GHz)
@@ -872,35 +940,10 @@ def main():
             "roofline": roof,
             "roofline_lse": roof2,
             "ms_per_step_outside_the_sweeps": outside,
-            "cpu_baseline": cpu,
-            "wallclock_to_converge_s": t_conv,
-            "iterations_to_converge": int(conv["iterations"]),
-            "converged": bool(conv["success"]),
-            "nr_iterations": int(conv["nr_iter"]), "sci_iterations": int(conv["sci_iter"]),
-            "separate_gram_sweeps_to_converge": int(conv.get("gram_sweeps", -1)),
-            # whole solves from f = 0 to tol 1e-12 (build sweep included): `frac` = one Hessian's matrix flop per iteration
-            # over the wall clock of the solve, against the fp64 matrix peak
-            "per_solve": {
-                name: {"min_sc_iter": msc, "iterations": int(r["iterations"]), "nr_iterations": int(r["nr_iter"]),
-                       "sci_iterations": int(r["sci_iter"]), "converged": bool(r["success"]), "wallclock_ms": 1e3 * t,
-                       "ms_per_iteration": 1e3 * t / max(1, int(r["iterations"])),
-                       "iterations_per_s": int(r["iterations"]) / t,
-                       "separate_gram_sweeps": int(r.get("gram_sweeps", -1)),
-                       # (the last iteration's sweep when both candidates already met the stop test: no Hessian accumulated, none needed)
-                       "sweeps_without_gram_matrix": int(r.get("light_sweeps", -1)),
-                       "build_sweeps": int(r.get("builds", -1)), "warm_starts": int(r.get("warm_starts", -1)),
-                       "frac": int(r["iterations"]) * flops * world / t * 1e-12 / (FP64_MFMA_PEAK_TFLOPS * world)}
-                for name, msc, r, t in (("adaptive_min_sc_iter_0", 0, conv, t_conv), ("adaptive_min_sc_iter_2", 2, conv2, t_conv2),
-                                        ("adaptive_min_sc_iter_0_warm_start", 0, conv_w, t_conv_w))},
-            "max_abs_error_vs_analytic_f": err_analytic,
-            "gnorm_at_solution": float(conv["gnorm"]),
-            "api_end_to_end": e2e,
-            "config2": config2,
-            "config4": config4,
-            "config4_one_device": config4_one,
-            "config5": config5,
-            "scaling_model": scaling_model,
+            "full": bool(args.full),
         }
+        if more is not None:
+            out.update(more)
         if allreduce == "host-fallback":
             out["valid"] = False
             out["invalid_because"] = "RCCL could not be initialised on every rank; measured over the host transport (diagnosis only)"
@@ -917,13 +960,14 @@ def main():
                 "reduce": per_launch("reduce"), "all_reduce": per_launch("comm"), "newton_and_select": per_launch("newton"),
                 "all_reduce_doubles": int(2 * K + 2 + (K // 16) * (K // 16 + 1) // 2 * 256) if fused else None,
             }
+        cpu = more["cpu_baseline"] if more is not None else None
         if cpu is not None:
             out["speedup_vs_cpu_baseline"] = it_per_s / cpu["value"]
             if "reference_on_gpu_host" in cpu:
                 rg = cpu["reference_on_gpu_host"]
                 out["speedup_vs_reference_on_gpu_host"] = it_per_s / rg["value"]
                 if "wallclock_to_converge_s" in rg:
-                    out["wallclock_to_converge_speedup_vs_reference_on_gpu_host"] = rg["wallclock_to_converge_s"] / t_conv
+                    out["wallclock_to_converge_speedup_vs_reference_on_gpu_host"] = rg["wallclock_to_converge_s"] / more["wallclock_to_converge_s"]
             if "reference_on_build_container" in cpu:
                 out["speedup_vs_reference_on_build_container"] = it_per_s / cpu["reference_on_build_container"]["value"]
         json_out.write(json.dumps(out) + "\n")
