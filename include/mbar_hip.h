@@ -510,8 +510,9 @@ int mbar_bspline_kernel_ms(mbar_bspline* bs, double* ms);
  * rejected).  Each problem's columns are cut into chunks of MBAR_BATCH_CHUNK, fixed whatever the other problems are; chunk
  * partials merge in a fixed order without atomics, so two identical calls return identical bits and a problem's answer does
  * not depend on the batch it is in.  The adaptive loop of mbar_solvers.py:575-640 runs per problem as a resumable state machine
- * (mbar_batch_step_host on the host, the same function on the device).  Errors: mbar_last_error(NULL).  Not thread-safe (one
- * handle per caller thread). */
+ * (mbar_batch_step_host on the host, the same function on the device).  Bootstrap replicates of the problems are solved as
+ * replica slots over the same resident blocks (below).  Errors: mbar_last_error(NULL).  Not thread-safe (one handle per caller
+ * thread). */
 #define MBAR_BATCH_MAX_K 64
 #define MBAR_BATCH_CHUNK 256
 /* One problem's solve.  Callers fill K, Nk (samples per state, zeros allowed, at least one > 0), f (the start), tol, gamma,
@@ -543,6 +544,29 @@ int mbar_batch_gram_w(mbar_batch* b, const double* f, const int32_t* mask, doubl
  * requests of the last pass (ignored in the first call, which issues the first requests), gram[K][K] = sum_n p_ni p_nj
  * (p_nk = N_k W_nk) at req[gram_req] (NULL when gram_req < 0).  Returns the status.  Needs no GPU. */
 int mbar_batch_step_host(mbar_batch_state* state, const double* lognum, const double* gram);
+
+/* ---- replica slots: bootstrap replicates solved next to the problems they resample ------------------------------------------
+ * A slot is a solve that shares the resident block, K, N and chunking of a base problem and has its own chunk records, its own
+ * mbar_batch_state and per-sample multiplicities c_n >= 0: every sum over samples becomes sum_n c_n (...), the log-denominator of
+ * a sample is unchanged, and a chunk with no drawn sample contributes nothing.  A bootstrap replicate (mbar.py:417-449) is the
+ * vector of draw counts: nothing is gathered, no block is copied.  The state machine is that of the problems (mbar_batch_step_host).
+ * A slot's result depends on its problem, its multiplicities and its start alone; two identical calls return identical bits.
+ *
+ * mbar_batch_set_replicas declares R slots (replacing earlier ones; R = 0 releases them): base[s] is slot s's problem,
+ * Nk[p][MBAR_BATCH_MAX_K] the samples per state of problem p (read for the problems that are some slot's base; they must sum
+ * to N[p]), which fix the default layout of the draws -- the states' runs in order.  Multiplicities start as 1.  The device memory of
+ * the multiplicities (N doubles per slot), records and states is checked up front (MBAR_ERR_ARG with the sizes in the message). */
+int mbar_batch_set_replicas(mbar_batch* b, int64_t R, const int64_t* base, const int64_t* Nk);
+/* Slot `slot`'s multiplicities from a host vector of N[base[slot]] doubles, finite and >= 0 (as mbar_ctx_set_sample_weights). */
+int mbar_batch_replica_set_weights(mbar_batch* b, int64_t slot, const double* c_n);
+/* The multiplicities of the slots first .. first + count drawn ON THE DEVICE in one launch: slot first + i gets the draw counts of
+ * replicate replicate[i] of the counter-based stream seed[i] over the default layout -- the draws mbar_bootstrap_draws(seed[i],
+ * replicate[i], cumN, K, NULL, .) returns on the host.  Counts are exact integers held as doubles (sums of 1.0). */
+int mbar_batch_replicas_draw(mbar_batch* b, int64_t first, int64_t count, const uint64_t* seed, const int64_t* replicate);
+/* mbar_batch_solve for the slots: states[R] in (initial), out (final). */
+int mbar_batch_replicas_solve(mbar_batch* b, mbar_batch_state* states, int64_t* passes);
+/* mbar_batch_gram_w for the slots: gram = sum_n c_n W_ni W_nj and wsum = sum_n c_n W_nk at f[s][0 .. K), packed slot after slot. */
+int mbar_batch_replicas_gram_w(mbar_batch* b, const double* f, const int32_t* mask, double* gram, double* wsum);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@ class BarState(C.Structure):
 
 
 MBAR_BATCH_MAX_K = 64
+MBAR_BATCH_CHUNK = 256
 
 
 class BatchState(C.Structure):
@@ -159,6 +160,11 @@ SIGNATURES = {
     "mbar_batch_solve": (C.c_int, [C.c_void_p, C.POINTER(BatchState), _ip]),
     "mbar_batch_gram_w": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_int32), _dp, _dp]),
     "mbar_batch_step_host": (C.c_int, [C.POINTER(BatchState), _dp, _dp]),
+    "mbar_batch_set_replicas": (C.c_int, [C.c_void_p, C.c_int64, _ip, _ip]),
+    "mbar_batch_replica_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
+    "mbar_batch_replicas_draw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), _ip]),
+    "mbar_batch_replicas_solve": (C.c_int, [C.c_void_p, C.POINTER(BatchState), _ip]),
+    "mbar_batch_replicas_gram_w": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_int32), _dp, _dp]),
 }
 
 _lib = None

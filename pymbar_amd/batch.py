@@ -7,6 +7,10 @@ the same iteration count and Newton / self-consistent choices, ``f_k`` within th
 states filled in as ``solve_mbar_for_all_states`` does.  The adaptive loops of all problems run on the device
 (``csrc/mbar_k_batch.hip``); the host reads one status int per problem between groups of passes.  A problem whose Newton system
 has a pivot that counts as zero is finished on the host by the single-problem path and flagged in ``host_fallback``.
+
+With ``n_bootstraps = B`` every problem's B bootstrap replicates are solved in the same call: a replicate is a replica slot of the
+device batch -- the problem's resident block with per-sample draw counts, drawn on the device from the counter-based stream of
+``MBAR(bootstrap_rng="device")`` -- started from the problem's solved ``f_k``; nothing is gathered and no block is copied.
 """
 import ctypes as C
 import logging
@@ -24,6 +28,8 @@ MAX_K = _lib.MBAR_BATCH_MAX_K
 RUNNING, DONE, FALLBACK = 0, 1, 2
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
+# Device memory one group of replica slots may take for its multiplicities (8 N bytes per slot), chunk records and states
+BOOTSTRAP_GROUP_BYTES = 2 << 30
 
 
 class DeviceBatch(_lib.Handle):
@@ -60,6 +66,67 @@ class DeviceBatch(_lib.Handle):
         _lib.check(self._lib.mbar_batch_gram_w(self._h, _lib.ptr(F), mask.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(gram),
                                                _lib.ptr(wsum)))
         return gram, wsum
+
+    # ---- replica slots (bootstrap replicates) ----
+    def set_replicas(self, base, N_k_list):
+        """Declares ``len(base)`` replica slots: slot s shares problem ``base[s]``'s block; ``N_k_list[p]`` (every problem's samples
+        per state) fixes the layout of the draws.  An empty ``base`` releases the slots."""
+        base = np.ascontiguousarray(base, dtype=np.int64)
+        Nk = np.zeros((self.P, MAX_K), dtype=np.int64)
+        for p in range(self.P):
+            Nk[p, :self.K[p]] = N_k_list[p]
+        rc = self._lib.mbar_batch_set_replicas(self._h, len(base), _lib.ptr(base, _ip), _lib.ptr(Nk, _ip))
+        if rc == -1:
+            raise ParameterError(_lib.last_error(None))
+        _lib.check(rc)
+        self.base = base
+
+    def replica_set_weights(self, slot, c_n):
+        """Slot ``slot``'s per-sample multiplicities from a host vector (finite, >= 0)."""
+        c_n = np.ascontiguousarray(c_n, dtype=np.float64)
+        if c_n.shape != (int(self.N[self.base[slot]]),):
+            raise ValueError(f"sample weights must have shape ({int(self.N[self.base[slot]])},)")
+        rc = self._lib.mbar_batch_replica_set_weights(self._h, int(slot), _lib.ptr(c_n))
+        if rc == -1:
+            raise ParameterError(_lib.last_error(None))
+        _lib.check(rc)
+
+    def replicas_draw(self, first, seeds, replicates):
+        """Draw counts of the slots ``first .. first + len(seeds)`` on the device: replicate ``replicates[i]`` of stream ``seeds[i]``."""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        replicates = np.ascontiguousarray(replicates, dtype=np.int64)
+        _lib.check(self._lib.mbar_batch_replicas_draw(self._h, int(first), len(seeds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                      _lib.ptr(replicates, _ip)))
+
+    def replicas_solve(self, states):
+        passes = C.c_int64(0)
+        _lib.check(self._lib.mbar_batch_replicas_solve(self._h, states, C.byref(passes)))
+        return passes.value
+
+    def replicas_gram_w(self, F, mask):
+        """``gram_w`` of the slots: packed ``sum_n c_n W_ni W_nj`` and ``sum_n c_n W_nk`` at ``F[s, :K]``."""
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        Ks = self.K[self.base]
+        gram = np.zeros(int(np.sum(Ks * Ks)), dtype=np.float64)
+        wsum = np.zeros(int(np.sum(Ks)), dtype=np.float64)
+        _lib.check(self._lib.mbar_batch_replicas_gram_w(self._h, _lib.ptr(F), mask.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                        _lib.ptr(gram), _lib.ptr(wsum)))
+        return gram, wsum
+
+
+def bootstrap_indices(seed, b, N_k):
+    """The resampled sample indices of replicate ``b`` of the stream ``seed`` over the default layout (the states' runs in order):
+    the reference's ``bootstrap_rints`` row, and the draws whose counts the device uses (``_lib.bootstrap_draws``; no GPU)."""
+    cumN = np.concatenate(([0], np.cumsum(np.asarray(N_k, dtype=np.int64)))).astype(np.int64)
+    return _lib.bootstrap_draws(seed, b, cumN)
+
+
+def bootstrap_ddelta_f(f_k_boots):
+    """``dDelta_f`` of ``MBAR.compute_free_energy_differences(uncertainty_method="bootstrap")`` from the (B, K) replicates."""
+    f_k_boots = np.asarray(f_k_boots, dtype=np.float64)
+    diffm = f_k_boots[:, np.newaxis, :] - f_k_boots[:, :, np.newaxis]
+    return np.std(diffm, axis=0)
 
 
 def _states_view(states):
@@ -133,6 +200,98 @@ def _host_solve(u, N_k, f_k, protocol, device):
     return f, G, ws, res
 
 
+def _host_solve_replicas(u, N_k, f_start, protocol, device, seed, bs):
+    """The single-problem path for the replicates ``bs`` of a problem: its own matrix with the draw counts as sample weights."""
+    from . import mbar_solvers
+    from .device import DeviceMatrix
+
+    sws = np.where(N_k != 0)[0].astype(np.int64)
+    out = []
+    with DeviceMatrix.from_host(u, device=device) as dm:
+        for b in bs:
+            dm.set_sample_weights(np.bincount(bootstrap_indices(seed, b, N_k), minlength=u.shape[1]))
+            results = []
+            try:
+                f = mbar_solvers.solve_mbar_for_all_states(dm, N_k, f_start.copy(), sws, protocol, results_out=results)
+            finally:
+                dm.set_sample_weights(None)
+            res = results[-1] if results else dict(iterations=0, success=True)
+            out.append((f, int(res["iterations"]), bool(res["success"])))
+    return out
+
+
+def _slot_bytes(K, N):
+    chunks = -(-int(N) // _lib.MBAR_BATCH_CHUNK)
+    return 8 * int(N) + chunks * (8 * (4 * K + K * K) + 32) + C.sizeof(_lib.BatchState) + 96
+
+
+def _solve_replicas(h, blocks, Nks, f_out, fallback, seeds, B, settings, protocol):
+    """The P x B replicates: slots on the device in groups of at most BOOTSTRAP_GROUP_BYTES, each started from its problem's f_k;
+    slots the device hands back, and every replicate of a problem that itself fell back, go through the single-problem path."""
+    P = len(blocks)
+    tol, gamma, maximum_iterations, min_sc_iter = settings
+    f_boots = [np.zeros((B, b.shape[0])) for b in blocks]
+    iters = np.zeros((P, B), dtype=np.int64)
+    success = np.zeros((P, B), dtype=bool)
+    host = np.zeros((P, B), dtype=bool)
+    passes = 0
+    slots = [(p, b) for p in range(P) if not fallback[p] for b in range(B)]
+    cost = np.array([_slot_bytes(blocks[p].shape[0], blocks[p].shape[1]) for p, _ in slots], dtype=np.int64)
+    start = 0
+    while start < len(slots):
+        end = start + max(1, int(np.searchsorted(np.cumsum(cost[start:]), BOOTSTRAP_GROUP_BYTES, side="right")))
+        group = slots[start:end]
+        R = len(group)
+        gp = np.array([p for p, _ in group], dtype=np.int64)
+        gb = np.array([b for _, b in group], dtype=np.int64)
+        h.set_replicas(gp, Nks)
+        h.replicas_draw(0, seeds[gp], gb)
+        states = (_lib.BatchState * R)()
+        sv = _states_view(states)
+        Kg = h.K[gp]
+        sv["K"] = Kg
+        sv["tol"] = tol
+        sv["gamma"] = gamma
+        sv["maxiter"] = maximum_iterations
+        sv["min_sc_iter"] = min_sc_iter
+        cuts = np.concatenate(([0], np.flatnonzero(np.diff(gp)) + 1, [R]))  # (a problem's slots are consecutive)
+        for s0, s1 in zip(cuts[:-1], cuts[1:]):
+            p = gp[s0]
+            K = int(h.K[p])
+            sv["Nk"][s0:s1, :K] = Nks[p]
+            sv["f"][s0:s1, :K] = f_out[p]
+        passes += h.replicas_solve(states)
+        sv = _states_view(states)
+        # the all-state update of the problems (mbar_batch below) with the weighted psum and lognum, every slot at once
+        cols = np.arange(MAX_K)[None, :] < Kg[:, None]
+        Nk = np.where(cols, sv["Nk"], 1.0)
+        sampled = np.all(Nk > 0, axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f_all = np.where(sampled[:, None], sv["f"] - np.log(np.where(cols, sv["psum"], 1.0) / Nk), -1.0 * sv["lognum"])
+        f_all = f_all - f_all[:, :1]
+        back = sv["status"] == FALLBACK
+        for s0, s1 in zip(cuts[:-1], cuts[1:]):
+            p = gp[s0]
+            ok = ~back[s0:s1]
+            bs = gb[s0:s1][ok]
+            f_boots[p][bs] = f_all[s0:s1][ok, :int(h.K[p])]
+            iters[p, bs] = sv["iterations"][s0:s1][ok]
+            success[p, bs] = sv["success"][s0:s1][ok] != 0
+            host[p, gb[s0:s1][~ok]] = True
+        start = end
+    h.set_replicas(np.zeros(0, dtype=np.int64), Nks)
+    host[fallback, :] = True
+    for p in np.where(host.any(axis=1))[0]:
+        bs = np.where(host[p])[0]
+        for b, (f, it, ok) in zip(bs, _host_solve_replicas(blocks[p], Nks[p], f_out[p], protocol, h.device, int(seeds[p]), bs)):
+            f_boots[p][b] = f
+            iters[p, b] = it
+            success[p, b] = ok
+    if not success.all():
+        logger.warning(f"{int((~success).sum())} bootstrap replicates did not converge to within specified tolerance.")
+    return f_boots, iters, success, host, passes
+
+
 def _pseudoinverse_stack(A, tol=1.0e-10):
     """``MBAR._pseudoinverse`` of every matrix of the stack ``A`` (B, K, K)."""
     out = np.empty_like(A)
@@ -177,13 +336,25 @@ def _error_of_differences_stack(cov, warning_cutoff):
 
 
 def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterations=10000, min_sc_iter=0, gamma=1.0,
-               compute_uncertainty=True, uncertainty_method=None, warning_cutoff=1e-10, device=None):
+               compute_uncertainty=True, uncertainty_method=None, warning_cutoff=1e-10, device=None, n_bootstraps=0, rseed=None,
+               bootstrap_seeds=None):
     """Solve P independent MBAR problems (``u_kn_list[p]``: K_p x N_p, ``N_k_list[p]``: K_p, 1 <= K_p <= 64) in one device call.
 
     Returns a dict of per-problem entries: ``f_k``, ``Delta_f`` and ``dDelta_f`` (lists of arrays; ``dDelta_f`` only with
     ``compute_uncertainty``), ``iterations``, ``nr_iterations``, ``sci_iterations`` (int arrays), ``success`` and
     ``host_fallback`` (bool arrays), and ``choices`` (per problem the Newton-Raphson flag of each of the first 63 iterations).
-    ``uncertainty_method``: None / "svd-ew" or "approximate"."""
+    ``uncertainty_method``: None / "svd-ew", "approximate" or "bootstrap".
+
+    ``n_bootstraps = B > 0``: after the P problems (solved exactly as with ``B = 0``) their P x B bootstrap replicates are solved
+    on the device as well, each from its problem's ``f_k`` with the same ``tol``, ``maximum_iterations``, ``min_sc_iter`` and
+    ``gamma``, in groups of replica slots that take at most ``BOOTSTRAP_GROUP_BYTES`` (2 GiB) of device memory for their draw counts
+    (8 bytes per sample and slot), chunk records and states.  Replicate b of problem p is replicate b of the counter-based stream
+    ``bootstrap_seeds[p]`` (``bootstrap_indices(seed, b, N_k)`` gives its resampled indices); without ``bootstrap_seeds`` the P seeds
+    come from ``np.random.default_rng(rseed)``.  Added entries: ``bootstrap_seeds``, ``f_k_boots`` (list of (B, K_p) arrays),
+    ``boot_iterations``, ``boot_success`` and ``boot_host_fallback`` ((P, B) arrays; replicates the device handed back, and all
+    those of a problem in ``host_fallback``, are solved by the single-problem path).  ``uncertainty_method="bootstrap"`` gives
+    ``dDelta_f`` as ``MBAR.compute_free_energy_differences`` does, the standard deviation over the replicates of every difference,
+    and skips the covariance pass; the other methods give the analytical ``dDelta_f`` next to ``f_k_boots``."""
     P = len(u_kn_list)
     if P == 0:
         raise ParameterError("mbar_batch needs at least one problem")
@@ -191,8 +362,22 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
         raise ParameterError(f"mbar_batch: {P} matrices but {len(N_k_list)} N_k vectors")
     if initial_f_k is not None and len(initial_f_k) != P:
         raise ParameterError(f"mbar_batch: {P} matrices but {len(initial_f_k)} initial_f_k vectors")
-    if uncertainty_method not in (None, "svd-ew", "approximate"):
-        raise ParameterError(f"mbar_batch: uncertainty_method {uncertainty_method!r} is not supported (None, 'svd-ew', 'approximate')")
+    if uncertainty_method not in (None, "svd-ew", "approximate", "bootstrap"):
+        raise ParameterError(f"mbar_batch: uncertainty_method {uncertainty_method!r} is not supported (None, 'svd-ew', 'approximate', "
+                             "'bootstrap')")
+    if isinstance(n_bootstraps, bool) or not isinstance(n_bootstraps, (int, np.integer)) or n_bootstraps < 0:
+        raise ParameterError(f"mbar_batch: n_bootstraps must be an integer >= 0, it was set to {n_bootstraps!r}")
+    B = int(n_bootstraps)
+    if uncertainty_method == "bootstrap" and B == 0:
+        raise ParameterError("Cannot request bootstrap sampling of free energy differences without any bootstraps.")
+    seeds = None
+    if bootstrap_seeds is not None:
+        seeds = np.asarray(bootstrap_seeds)
+        if seeds.shape != (P,) or not np.issubdtype(seeds.dtype, np.integer) or np.any(seeds < 0):
+            raise ParameterError(f"mbar_batch: bootstrap_seeds must be {P} non-negative integers, one per problem")
+        seeds = seeds.astype(np.uint64)
+    elif B > 0:
+        seeds = np.random.default_rng(rseed).integers(np.iinfo(np.int64).max, size=P).astype(np.uint64)
     tol = float(tol)
     maximum_iterations = int(maximum_iterations)
     min_sc_iter = int(min_sc_iter)
@@ -256,9 +441,14 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
             f_out.append(f)
         gram = wsum = None
         t4 = time.perf_counter()
-        if compute_uncertainty:
+        analytical = compute_uncertainty and uncertainty_method != "bootstrap"
+        if analytical:
             gram, wsum = h.gram_w(F, ~fallback)
         t5 = time.perf_counter()
+        boots = None
+        if B > 0:
+            boots = _solve_replicas(h, blocks, Nks, f_out, fallback, seeds, B, (tol, gamma, maximum_iterations, min_sc_iter), protocol)
+        t6 = time.perf_counter()
 
     out = dict(f_k=f_out, Delta_f=[np.array(f - np.vstack(f)) for f in f_out])
     out["iterations"] = np.array([r[0] for r in results], dtype=np.int64)
@@ -270,7 +460,13 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
     out["passes"] = int(passes)
     # wall-clock split (s): input checks, upload, the device loop, host work between them, the covariance pass, host covariance
     out["timing"] = dict(checks=t1 - t0, upload=t2 - t1, solve=t3 - t2, host=t4 - t3, gram=t5 - t4, covariance=0.0)
-    if not compute_uncertainty:
+    if B > 0:
+        out["bootstrap_seeds"] = seeds.copy()
+        out["f_k_boots"], out["boot_iterations"], out["boot_success"], out["boot_host_fallback"], out["boot_passes"] = boots
+        out["timing"]["bootstrap"] = t6 - t5
+    if compute_uncertainty and uncertainty_method == "bootstrap":
+        out["dDelta_f"] = [bootstrap_ddelta_f(fb) for fb in out["f_k_boots"]]
+    if not analytical:
         return out
     goff = np.concatenate(([0], np.cumsum(Ks * Ks)))
     woff = np.concatenate(([0], np.cumsum(Ks)))
@@ -299,5 +495,5 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
         for i, p in enumerate(sel):
             dDelta_f[p] = err[i]
     out["dDelta_f"] = dDelta_f
-    out["timing"]["covariance"] = time.perf_counter() - t5
+    out["timing"]["covariance"] = time.perf_counter() - (t6 if B > 0 else t5)
     return out

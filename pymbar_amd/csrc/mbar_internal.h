@@ -794,6 +794,9 @@ MBAR_HD inline bool batch_ldlt_solve(double* A, int lda, double* b, int m, doubl
 // Device side.  Problem p: rows of K[p] states, N[p] samples at u + uoff[p] (row-major, ld N[p]); its chunks cbeg[p] ..
 // cbeg[p + 1] of MBAR_BATCH_CHUNK columns each (the last one shorter), chunk c's partial record at part + coff[c]:
 // [2][K] maxima, [2][K] scaled sums, [K][K] Gram.  Chunks are launched in four width classes (8, 16, 32, 64 states).
+// The same struct describes a set of replica slots (bootstrap replicates): "problem" s is then a slot, uoff[s] and N[s] are those
+// of its base problem (the block is shared, nothing is copied), its chunks, partial records and state are its own, and sample n
+// counts cw[cwoff[s] + n] times (the weighted instantiation of the evaluation kernel; cw is NULL for the problems themselves).
 constexpr int BATCH_WG = 256;
 struct BatchData {
     const double* u;
@@ -805,9 +808,19 @@ struct BatchData {
     const int64_t* coff;     // [nchunks] offset of the chunk's partial record
     double* part;
     int64_t P, nchunks;
+    const double* cw;        // per-sample multiplicities of replica slots, or NULL
+    const int64_t* cwoff;    // [P] offset of slot s's multiplicities in cw
 };
 // evaluation pass over the chunks list[0 .. n) of one width class kb
 hipError_t launch_batch_eval(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n, const mbar_batch_state* states);
+// the weighted form (d.cw, d.cwoff): every sum over samples becomes sum_n c_n (...)
+hipError_t launch_batch_eval_weighted(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n,
+                                      const mbar_batch_state* states);
+// Draw counts of the slots first .. first + count of the replica set d into d.cw (zeroed by the caller): position j of slot s
+// draws bootstrap_draw(seed[s], replicate[s], j, n_k) within the run of its state, cum[base[s]][0 .. K] being the runs' bounds
+// (rows of MBAR_BATCH_MAX_K + 1).  One workgroup per chunk; chunk0 / nchunk: the chunks of those slots.
+hipError_t launch_batch_draw(hipStream_t st, const BatchData& d, int64_t chunk0, int64_t nchunk, const int64_t* base,
+                             const int64_t* Kp, const int64_t* cum, const uint64_t* seed, const int64_t* replicate, double* cw);
 // merge + one step of every running problem; FINAL problems: out_gram / out_wsum at their packed offsets goff / woff
 hipError_t launch_batch_step(hipStream_t st, const BatchData& d, mbar_batch_state* states, int* active, double* out_gram,
                              double* out_wsum, const int64_t* goff, const int64_t* woff);

@@ -14,8 +14,14 @@
 //   k_batch_step   one workgroup per problem: merges the chunk partials in chunk order, advances the problem's adaptive loop
 //                  (batch_advance, mbar_internal.h) and, when it asks for one, factors the gauge-fixed Newton system in LDS
 //                  (LDL^T, one barrier pair per pivot).
-// No atomics: every sum has a fixed order that depends on the problem alone, so two identical calls return identical bits and a
-// problem's answer does not depend on the other problems of the batch.
+//   k_batch_draw   bootstrap draw counts of many replica slots in one launch (the counter-based stream of mbar_internal.h).
+// Replica slots (bootstrap replicates, BatchData in mbar_internal.h) share their base problem's block and run the weighted
+// instantiation of k_batch_eval: sample n counts c_n >= 0 times.  Its log-denominator is unchanged; the chunk maximum of a state
+// is taken over the samples with c_n > 0 and its sum is sum_n c_n exp(. - maximum); the Gram operands are scaled by sqrt(c_n) when
+// the tile is staged, so that sum_n c_n q q^T stays bit-symmetric.  k_batch_step does not know about multiplicities.
+// No floating-point atomics but one: the draw counts, sums of 1.0 (exact, whatever the order).  Every other sum has a fixed order
+// that depends on the problem alone, so two identical calls return identical bits and a problem's (or a slot's) answer does not
+// depend on the other problems of the batch.
 #include "mbar_device.h"
 
 namespace mbar {
@@ -24,7 +30,7 @@ namespace {
 
 constexpr int TP = MBAR_BATCH_CHUNK + 1;  // pitch of the per-state transposition tile (16 states x 256 samples)
 
-template <int KB>
+template <int KB, bool WT = false>
 __global__ void __launch_bounds__(BATCH_WG) k_batch_eval(BatchData d, const int* __restrict__ list,
                                                          const mbar_batch_state* __restrict__ states) {
     constexpr int GS = KB < 16 ? KB : 16;   // states per transposition group
@@ -36,6 +42,7 @@ __global__ void __launch_bounds__(BATCH_WG) k_batch_eval(BatchData d, const int*
     __shared__ double sa[2][KB];
     __shared__ double sg[KB];
     __shared__ int info[4];
+    __shared__ double sc[WT ? MBAR_BATCH_CHUNK : 1];  // (weighted form: the chunk's multiplicities)
     const int tid = threadIdx.x;
     const int c = list[blockIdx.x];
     const int p = d.cprob[c];
@@ -65,6 +72,12 @@ __global__ void __launch_bounds__(BATCH_WG) k_batch_eval(BatchData d, const int*
 #pragma unroll
     for (int k = 0; k < KB; ++k) u[k] = (valid && k < K) ? up[(int64_t)k * Np] : INFINITY;
     double* __restrict__ rec = d.part + d.coff[c];
+    double cq = 1.0;  // sqrt(c_n)
+    if constexpr (WT) {
+        const double cn = valid ? d.cw[d.cwoff[p] + n0 + tid] : 0.0;
+        sc[tid] = cn;
+        cq = sqrt(cn);
+    }
     __syncthreads();
     for (int r = 0; r < nreq; ++r) {
         // log-denominator of this sample: log sum_k N_k exp(f_k - u_kn)
@@ -84,7 +97,10 @@ __global__ void __launch_bounds__(BATCH_WG) k_batch_eval(BatchData d, const int*
             if (g0 >= K) break;
             __syncthreads();
 #pragma unroll
-            for (int j = 0; j < GS; ++j) buf[j * TP + tid] = -ld - u[g0 + j];
+            for (int j = 0; j < GS; ++j) {
+                if constexpr (WT) buf[j * TP + tid] = cq > 0.0 ? -ld - u[g0 + j] : -INFINITY;  // (a sample not drawn: no term)
+                else buf[j * TP + tid] = -ld - u[g0 + j];
+            }
             __syncthreads();
             const int kk = tid >> 4, q = tid & 15;
             double mx = -INFINITY;
@@ -95,7 +111,10 @@ __global__ void __launch_bounds__(BATCH_WG) k_batch_eval(BatchData d, const int*
             double sm = 0.0;
             if (kk < GS && mx != -INFINITY)
 #pragma unroll 4
-                for (int i = 0; i < MBAR_BATCH_CHUNK / 16; ++i) sm += exp(buf[kk * TP + q + 16 * i] - mx);
+                for (int i = 0; i < MBAR_BATCH_CHUNK / 16; ++i) {
+                    if constexpr (WT) sm += sc[q + 16 * i] * exp(buf[kk * TP + q + 16 * i] - mx);
+                    else sm += exp(buf[kk * TP + q + 16 * i] - mx);
+                }
             sm = row16_sum(sm);
             if (q == 0 && kk < GS && g0 + kk < K) {
                 rec[r * K + g0 + kk] = mx;
@@ -116,7 +135,10 @@ __global__ void __launch_bounds__(BATCH_WG) k_batch_eval(BatchData d, const int*
             __syncthreads();
             if (wv == w)
 #pragma unroll
-                for (int k = 0; k < KB; ++k) buf[lane * GP + k] = exp((sg[k] - u[k]) - ld);
+                for (int k = 0; k < KB; ++k) {
+                    if constexpr (WT) buf[lane * GP + k] = cq > 0.0 ? cq * exp((sg[k] - u[k]) - ld) : 0.0;
+                    else buf[lane * GP + k] = exp((sg[k] - u[k]) - ld);
+                }
             __syncthreads();
             if (tid < NBD * NBD) {
                 const int cols = ncols - w * 64 < 64 ? ncols - w * 64 : 64;
@@ -282,7 +304,50 @@ __global__ void __launch_bounds__(BATCH_WG) k_batch_step(BatchData d, mbar_batch
     if (tid == 0) active[p] = st.nreq > 0 ? 1 : 0;
 }
 
+// Draw counts of replica slots.  Chunk c of slot s = cprob[c]: thread t holds position j = cn0[c] + t of the slot's N[s] draws, in
+// the run [cum[k], cum[k + 1]) of its state k, and adds 1.0 to the count of the sample it draws (exact in any order).
+__global__ void __launch_bounds__(BATCH_WG) k_batch_draw(BatchData d, int64_t chunk0, const int64_t* __restrict__ base,
+                                                         const int64_t* __restrict__ Kp, const int64_t* __restrict__ cum,
+                                                         const uint64_t* __restrict__ seed, const int64_t* __restrict__ replicate,
+                                                         double* __restrict__ cw) {
+    const int64_t c = chunk0 + blockIdx.x;
+    const int s = d.cprob[c];
+    const int64_t j = d.cn0[c] + threadIdx.x;
+    if (j >= d.N[s]) return;
+    const int64_t b = base[s];
+    const int64_t* __restrict__ cm = cum + b * (MBAR_BATCH_MAX_K + 1);
+    int64_t lo = 0, hi = Kp[b];  // the state k with cum[k] <= j < cum[k + 1] (empty states have empty runs)
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (cm[mid] <= j) lo = mid; else hi = mid;
+    }
+    const int64_t start = cm[lo], nk = cm[lo + 1] - start;
+    const int64_t pos = start + bootstrap_draw(seed[s], (uint64_t)replicate[s], (uint64_t)j, (uint64_t)nk);
+    if (pos >= 0 && pos < d.N[s]) atomicAdd(cw + d.cwoff[s] + pos, 1.0);
+}
+
 }  // namespace
+
+hipError_t launch_batch_eval_weighted(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n,
+                                      const mbar_batch_state* states) {
+    if (n == 0) return hipSuccess;
+    if (!d.cw || !d.cwoff) return hipErrorInvalidValue;
+    switch (kb) {
+    case 8: hipLaunchKernelGGL((k_batch_eval<8, true>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 16: hipLaunchKernelGGL((k_batch_eval<16, true>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 32: hipLaunchKernelGGL((k_batch_eval<32, true>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 64: hipLaunchKernelGGL((k_batch_eval<64, true>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_draw(hipStream_t st, const BatchData& d, int64_t chunk0, int64_t nchunk, const int64_t* base,
+                             const int64_t* Kp, const int64_t* cum, const uint64_t* seed, const int64_t* replicate, double* cw) {
+    if (nchunk == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_batch_draw, dim3((unsigned)nchunk), dim3(BATCH_WG), 0, st, d, chunk0, base, Kp, cum, seed, replicate, cw);
+    return hipGetLastError();
+}
 
 hipError_t launch_batch_eval(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n, const mbar_batch_state* states) {
     if (n == 0) return hipSuccess;
