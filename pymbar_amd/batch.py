@@ -32,6 +32,13 @@ _ip = C.POINTER(C.c_int64)
 BOOTSTRAP_GROUP_BYTES = 2 << 30
 
 
+def _check_inputs(rc):
+    """MBAR_ERR_ARG is about the inputs (NaN / -inf entries, a batch larger than the device, bad weights): a ParameterError."""
+    if rc == -1:
+        raise ParameterError(_lib.last_error(None))
+    _lib.check(rc)
+
+
 class DeviceBatch(_lib.Handle):
     """P problems' reduced potentials resident on one device (``mbar_batch_*`` of include/mbar_hip.h)."""
 
@@ -46,26 +53,29 @@ class DeviceBatch(_lib.Handle):
         self.N = np.array([b.shape[1] for b in blocks], dtype=np.int64)
         ptrs = (_dp * self.P)(*[b.ctypes.data_as(_dp) for b in blocks])
         h = C.c_void_p()
-        rc = self._lib.mbar_batch_create(C.byref(h), self.device, self.P, _lib.ptr(self.K, _ip), _lib.ptr(self.N, _ip), ptrs)
-        if rc == -1:  # MBAR_ERR_ARG: the inputs (NaN / -inf entries, a batch larger than the device)
-            raise ParameterError(_lib.last_error(None))
-        _lib.check(rc)
+        _check_inputs(self._lib.mbar_batch_create(C.byref(h), self.device, self.P, _lib.ptr(self.K, _ip), _lib.ptr(self.N, _ip), ptrs))
         self._h = h
 
-    def solve(self, states):
+    # The problems and the replica slots are two sets of solves over the same blocks: `fn` is the set's entry point, Ks its widths
+    def _solve(self, fn, states):
         passes = C.c_int64(0)
-        _lib.check(self._lib.mbar_batch_solve(self._h, states, C.byref(passes)))
+        _lib.check(fn(self._h, states, C.byref(passes)))
         return passes.value
+
+    def _gram_w(self, fn, Ks, F, mask):
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        gram = np.zeros(int(np.sum(Ks * Ks)), dtype=np.float64)
+        wsum = np.zeros(int(np.sum(Ks)), dtype=np.float64)
+        _lib.check(fn(self._h, _lib.ptr(F), mask.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(gram), _lib.ptr(wsum)))
+        return gram, wsum
+
+    def solve(self, states):
+        return self._solve(self._lib.mbar_batch_solve, states)
 
     def gram_w(self, F, mask):
         """Packed ``W^T W`` and ``sum_n W_nk`` at ``F[p, :K[p]]`` for the problems with ``mask[p]``."""
-        F = np.ascontiguousarray(F, dtype=np.float64)
-        mask = np.ascontiguousarray(mask, dtype=np.int32)
-        gram = np.zeros(int(np.sum(self.K * self.K)), dtype=np.float64)
-        wsum = np.zeros(int(np.sum(self.K)), dtype=np.float64)
-        _lib.check(self._lib.mbar_batch_gram_w(self._h, _lib.ptr(F), mask.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(gram),
-                                               _lib.ptr(wsum)))
-        return gram, wsum
+        return self._gram_w(self._lib.mbar_batch_gram_w, self.K, F, mask)
 
     # ---- replica slots (bootstrap replicates) ----
     def set_replicas(self, base, N_k_list):
@@ -75,10 +85,7 @@ class DeviceBatch(_lib.Handle):
         Nk = np.zeros((self.P, MAX_K), dtype=np.int64)
         for p in range(self.P):
             Nk[p, :self.K[p]] = N_k_list[p]
-        rc = self._lib.mbar_batch_set_replicas(self._h, len(base), _lib.ptr(base, _ip), _lib.ptr(Nk, _ip))
-        if rc == -1:
-            raise ParameterError(_lib.last_error(None))
-        _lib.check(rc)
+        _check_inputs(self._lib.mbar_batch_set_replicas(self._h, len(base), _lib.ptr(base, _ip), _lib.ptr(Nk, _ip)))
         self.base = base
 
     def replica_set_weights(self, slot, c_n):
@@ -86,10 +93,7 @@ class DeviceBatch(_lib.Handle):
         c_n = np.ascontiguousarray(c_n, dtype=np.float64)
         if c_n.shape != (int(self.N[self.base[slot]]),):
             raise ValueError(f"sample weights must have shape ({int(self.N[self.base[slot]])},)")
-        rc = self._lib.mbar_batch_replica_set_weights(self._h, int(slot), _lib.ptr(c_n))
-        if rc == -1:
-            raise ParameterError(_lib.last_error(None))
-        _lib.check(rc)
+        _check_inputs(self._lib.mbar_batch_replica_set_weights(self._h, int(slot), _lib.ptr(c_n)))
 
     def replicas_draw(self, first, seeds, replicates):
         """Draw counts of the slots ``first .. first + len(seeds)`` on the device: replicate ``replicates[i]`` of stream ``seeds[i]``."""
@@ -99,20 +103,11 @@ class DeviceBatch(_lib.Handle):
                                                       _lib.ptr(replicates, _ip)))
 
     def replicas_solve(self, states):
-        passes = C.c_int64(0)
-        _lib.check(self._lib.mbar_batch_replicas_solve(self._h, states, C.byref(passes)))
-        return passes.value
+        return self._solve(self._lib.mbar_batch_replicas_solve, states)
 
     def replicas_gram_w(self, F, mask):
         """``gram_w`` of the slots: packed ``sum_n c_n W_ni W_nj`` and ``sum_n c_n W_nk`` at ``F[s, :K]``."""
-        F = np.ascontiguousarray(F, dtype=np.float64)
-        mask = np.ascontiguousarray(mask, dtype=np.int32)
-        Ks = self.K[self.base]
-        gram = np.zeros(int(np.sum(Ks * Ks)), dtype=np.float64)
-        wsum = np.zeros(int(np.sum(Ks)), dtype=np.float64)
-        _lib.check(self._lib.mbar_batch_replicas_gram_w(self._h, _lib.ptr(F), mask.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                        _lib.ptr(gram), _lib.ptr(wsum)))
-        return gram, wsum
+        return self._gram_w(self._lib.mbar_batch_replicas_gram_w, self.K[self.base], F, mask)
 
 
 def bootstrap_indices(seed, b, N_k):
@@ -132,6 +127,35 @@ def bootstrap_ddelta_f(f_k_boots):
 def _states_view(states):
     """A structured numpy view of a ctypes array of ``BatchState`` (no copy)."""
     return np.ctypeslib.as_array(states)
+
+
+def _new_states(prob, Ks, Nks, fs, settings):
+    """A ``BatchState`` array for one solve of a set: entry e is problem ``prob[e]``'s (ascending), with its K, N_k and start
+    ``fs[prob[e]]``; ``settings``: tol, gamma, maxiter, min_sc_iter."""
+    n = len(prob)
+    states = (_lib.BatchState * n)()
+    sv = _states_view(states)
+    sv["K"] = Ks[prob]
+    sv["tol"], sv["gamma"], sv["maxiter"], sv["min_sc_iter"] = settings
+    cuts = np.concatenate(([0], np.flatnonzero(np.diff(prob)) + 1, [n]))  # (the entries of one problem are consecutive)
+    for e0, e1 in zip(cuts[:-1], cuts[1:]):
+        p = prob[e0]
+        K = int(Ks[p])
+        sv["Nk"][e0:e1, :K] = Nks[p]
+        sv["f"][e0:e1, :K] = fs[p]
+    return states
+
+
+def _all_states_update(sv):
+    """The all-state update of ``solve_mbar_for_all_states`` (mbar_solvers.py) on every entry of a solved state array: every
+    state sampled -- f - log(psum / N_k) with the per-state sums at the solution; otherwise -lognum over all states; then
+    f_0 = 0.  Returns (len(sv), MAX_K); row e is meaningful in its first K[e] columns."""
+    cols = np.arange(MAX_K)[None, :] < sv["K"][:, None]
+    Nk = np.where(cols, sv["Nk"], 1.0)
+    sampled = np.all(Nk > 0, axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f_all = np.where(sampled[:, None], sv["f"] - np.log(np.where(cols, sv["psum"], 1.0) / Nk), -1.0 * sv["lognum"])
+    return f_all - f_all[:, :1]
 
 
 def step_host(state, lognum=None, gram=None):
@@ -229,7 +253,6 @@ def _solve_replicas(h, blocks, Nks, f_out, fallback, seeds, B, settings, protoco
     """The P x B replicates: slots on the device in groups of at most BOOTSTRAP_GROUP_BYTES, each started from its problem's f_k;
     slots the device hands back, and every replicate of a problem that itself fell back, go through the single-problem path."""
     P = len(blocks)
-    tol, gamma, maximum_iterations, min_sc_iter = settings
     f_boots = [np.zeros((B, b.shape[0])) for b in blocks]
     iters = np.zeros((P, B), dtype=np.int64)
     success = np.zeros((P, B), dtype=bool)
@@ -246,30 +269,12 @@ def _solve_replicas(h, blocks, Nks, f_out, fallback, seeds, B, settings, protoco
         gb = np.array([b for _, b in group], dtype=np.int64)
         h.set_replicas(gp, Nks)
         h.replicas_draw(0, seeds[gp], gb)
-        states = (_lib.BatchState * R)()
-        sv = _states_view(states)
-        Kg = h.K[gp]
-        sv["K"] = Kg
-        sv["tol"] = tol
-        sv["gamma"] = gamma
-        sv["maxiter"] = maximum_iterations
-        sv["min_sc_iter"] = min_sc_iter
-        cuts = np.concatenate(([0], np.flatnonzero(np.diff(gp)) + 1, [R]))  # (a problem's slots are consecutive)
-        for s0, s1 in zip(cuts[:-1], cuts[1:]):
-            p = gp[s0]
-            K = int(h.K[p])
-            sv["Nk"][s0:s1, :K] = Nks[p]
-            sv["f"][s0:s1, :K] = f_out[p]
+        states = _new_states(gp, h.K, Nks, f_out, settings)
         passes += h.replicas_solve(states)
         sv = _states_view(states)
-        # the all-state update of the problems (mbar_batch below) with the weighted psum and lognum, every slot at once
-        cols = np.arange(MAX_K)[None, :] < Kg[:, None]
-        Nk = np.where(cols, sv["Nk"], 1.0)
-        sampled = np.all(Nk > 0, axis=1)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            f_all = np.where(sampled[:, None], sv["f"] - np.log(np.where(cols, sv["psum"], 1.0) / Nk), -1.0 * sv["lognum"])
-        f_all = f_all - f_all[:, :1]
+        f_all = _all_states_update(sv)  # (with the weighted psum and lognum)
         back = sv["status"] == FALLBACK
+        cuts = np.concatenate(([0], np.flatnonzero(np.diff(gp)) + 1, [R]))  # (a problem's slots are consecutive)
         for s0, s1 in zip(cuts[:-1], cuts[1:]):
             p = gp[s0]
             ok = ~back[s0:s1]
@@ -393,17 +398,8 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
         f0s.append(f_k)
     Ks = np.array([b.shape[0] for b in blocks], dtype=np.int64)
 
-    states = (_lib.BatchState * P)()
-    sv = _states_view(states)
-    sv["K"] = Ks
-    sv["tol"] = tol
-    sv["gamma"] = gamma
-    sv["maxiter"] = maximum_iterations
-    sv["min_sc_iter"] = min_sc_iter
-    for p in range(P):
-        K = Ks[p]
-        sv["Nk"][p, :K] = Nks[p]
-        sv["f"][p, :K] = f0s[p]
+    settings = (tol, gamma, maximum_iterations, min_sc_iter)
+    states = _new_states(np.arange(P), Ks, Nks, f0s, settings)
 
     t1 = time.perf_counter()
     with DeviceBatch(blocks, device=device) as h:
@@ -413,6 +409,7 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
         sv = _states_view(states)
         status = sv["status"].copy()
         fallback = status == FALLBACK
+        f_all = _all_states_update(sv)
         f_out, results = [], []
         F = np.zeros((P, MAX_K), dtype=np.float64)
         host_gram = {}
@@ -425,14 +422,7 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
                 host_gram[p] = (G, ws)
                 results.append((int(res["iterations"]), int(res["nr_iter"]), int(res["sci_iter"]), bool(res["success"]), 0))
             else:
-                # the all-state update of solve_mbar_for_all_states (mbar_solvers.py): every state sampled -- f - log(psum / N_k)
-                # with the per-state sums at the solution; otherwise -lognum over all states; then f_0 = 0
-                f = sv["f"][p, :K].copy()
-                if np.all(N_k > 0):
-                    f = f - np.log(sv["psum"][p, :K] / N_k)
-                else:
-                    f = -1.0 * sv["lognum"][p, :K]
-                f -= f[0]
+                f = f_all[p, :K].copy()
                 results.append((int(sv["iterations"][p]), int(sv["nr_iter"][p]), int(sv["sci_iter"][p]), bool(sv["success"][p]),
                                 int(sv["choices"][p])))
                 if results[-1][3] is False:
@@ -447,7 +437,7 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
         t5 = time.perf_counter()
         boots = None
         if B > 0:
-            boots = _solve_replicas(h, blocks, Nks, f_out, fallback, seeds, B, (tol, gamma, maximum_iterations, min_sc_iter), protocol)
+            boots = _solve_replicas(h, blocks, Nks, f_out, fallback, seeds, B, settings, protocol)
         t6 = time.perf_counter()
 
     out = dict(f_k=f_out, Delta_f=[np.array(f - np.vstack(f)) for f in f_out])

@@ -206,17 +206,12 @@ int mbar_acf_create(mbar_acf** out, int device, int64_t T, const double* a, cons
         for (int64_t i = 0; i + 1 < T; ++i)
             if (a[i] != a[i + 1] || (b && b[i] != b[i + 1])) h->last_change = i;
         const size_t ldx = (size_t)h->ldx;
-        HIPCHK(nullptr, h->A.grow(ldx));
-        HIPCHK(nullptr, h->rem.grow(ldx));
         HIPCHK(nullptr, h->SA.grow(ldx));
         HIPCHK(nullptr, h->tot.grow((size_t)ACF_MAX_LAGS * 2 * h->ntiles));
         HIPCHK(nullptr, h->off.grow((size_t)ACF_MAX_LAGS * 2 * h->ntiles));
         HIPCHK(nullptr, h->active.grow((size_t)h->ntiles));
         HIPCHK(nullptr, h->oid.grow(ldx));
-        if (b) {
-            HIPCHK(nullptr, h->b_own.grow(ldx));
-            HIPCHK(nullptr, h->sb_own.grow(ldx));
-        }
+        if (b) HIPCHK(nullptr, h->sb_own.grow(ldx));
         // x - shift exactly, as the rounded difference and its error (TwoSum)
         std::vector<double2> stage(ldx, double2{0.0, 0.0});
         auto shifted = [&](const double* x, double m) {
@@ -226,16 +221,16 @@ int mbar_acf_create(mbar_acf** out, int device, int64_t T, const double* a, cons
             }
         };
         shifted(a, shift_a);
-        HIPCHK(nullptr, hipMemcpy(h->A, stage.data(), ldx * sizeof(double2), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, h->A.upload(stage.data(), ldx));
         if (b) {
             shifted(b, shift_b);
-            HIPCHK(nullptr, hipMemcpy(h->b_own, stage.data(), ldx * sizeof(double2), hipMemcpyHostToDevice));
+            HIPCHK(nullptr, h->b_own.upload(stage.data(), ldx));
         }
         std::vector<int> rem(ldx, 0);
         int64_t pos = 0;
         for (int64_t k = 0; k < K; ++k)
             for (int64_t i = 0; i < seg[k]; ++i, ++pos) rem[pos] = (int)(seg[k] - i);
-        HIPCHK(nullptr, hipMemcpy(h->rem, rem.data(), ldx * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, h->rem.upload(rem.data(), ldx));
         HIPCHK(nullptr, hipMemset(h->active, 0, (size_t)h->ntiles * sizeof(int)));
         // suffix sums of A' (and B'): the plain term at lag 0 over every tile, stored at every position
         for (int which = 0; which < (b ? 2 : 1); ++which) {
@@ -308,8 +303,7 @@ int mbar_acf_lag_sums(mbar_acf* h, int64_t nlags, const int64_t* lags, int64_t n
     // positions whose suffix sums are stored: the origins and T (segment mode: the end of the last range)
     std::vector<int64_t> pos(origins, origins + norig);
     pos.push_back(h->T);
-    HIPCHK(nullptr, h->orig.grow(pos.size()));
-    HIPCHK(nullptr, hipMemcpy(h->orig, pos.data(), pos.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, h->orig.upload(pos.data(), pos.size()));
     HIPCHK(nullptr, launch_acf_fill_int(h->stream, h->oid, h->ldx, -1));
     HIPCHK(nullptr, launch_acf_scatter_oid(h->stream, h->oid, h->orig, (int64_t)pos.size()));
     const int64_t ldo = norig + 1;

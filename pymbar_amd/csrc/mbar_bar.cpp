@@ -107,9 +107,6 @@ int mbar_bar_create(mbar_bar** out, int device, int64_t P, const int64_t* n_f, c
         HIPCHK(nullptr, h->len.grow(nc));
         HIPCHK(nullptr, h->seg.grow(nc));
         HIPCHK(nullptr, h->wmin.grow(nc));
-        HIPCHK(nullptr, h->cbeg.grow((size_t)(2 * P + 1)));
-        HIPCHK(nullptr, h->dM.grow((size_t)P));
-        HIPCHK(nullptr, h->dnside.grow((size_t)(2 * P)));
         HIPCHK(nullptr, h->part.grow(2 * nc));
         HIPCHK(nullptr, h->states.grow((size_t)P));
         HIPCHK(nullptr, h->active.grow((size_t)P));
@@ -123,9 +120,9 @@ int mbar_bar_create(mbar_bar** out, int device, int64_t P, const int64_t* n_f, c
             HIPCHK(nullptr, hipMemcpy(h->seg, seg.data(), seg.size() * sizeof(int), hipMemcpyHostToDevice));
             HIPCHK(nullptr, hipMemcpy(h->wmin, wmin.data(), wmin.size() * sizeof(double), hipMemcpyHostToDevice));
         }
-        HIPCHK(nullptr, hipMemcpy(h->cbeg, cbeg.data(), cbeg.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        HIPCHK(nullptr, hipMemcpy(h->dM, h->M.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(nullptr, hipMemcpy(h->dnside, nside.data(), (size_t)(2 * P) * sizeof(int64_t), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, h->cbeg.upload(cbeg.data(), cbeg.size()));
+        HIPCHK(nullptr, h->dM.upload(h->M.data(), (size_t)P));
+        HIPCHK(nullptr, h->dnside.upload(nside.data(), (size_t)(2 * P)));
         HIPCHK(nullptr, hipMemset(h->scratch, 0, (2 * nc + (size_t)(6 * P)) * sizeof(double)));
         return MBAR_OK;
     });
@@ -174,32 +171,15 @@ int mbar_bar_solve(mbar_bar* h, mbar_bar_state* states, int64_t* passes) {
     }
     HIPCHK(nullptr, hipSetDevice(h->device));
     const BarData d = data_of(h);
-    HIPCHK(nullptr, hipMemcpyAsync(h->states, states, (size_t)h->P * sizeof(mbar_bar_state), hipMemcpyHostToDevice, h->stream));
-    // Passes in groups of 4, 8, 16, 16, ...: between groups the host reads one int per problem.  A finished problem costs one
-    // early-exiting workgroup per chunk.  The reference's loops all end (the widening overflows to NaN after ~1100 steps); the
-    // limit below only guards the host against a state machine that would not.
+    // The reference's loops all end (the widening overflows to NaN after ~1100 steps); the limit below only guards the host
+    // against a state machine that would not.
     const int64_t limit = maxit + 1 + 4096;
-    std::vector<int> act((size_t)h->P);
-    int64_t done = 0;
-    int group = 4;
-    for (;;) {
-        for (int k = 0; k < group; ++k) {
-            HIPCHK(nullptr, launch_bar_eval(h->stream, d, h->states, h->part));
-            HIPCHK(nullptr, launch_bar_step(h->stream, d, h->states, h->part, 1, h->out, h->active));
-        }
-        done += group;
-        HIPCHK(nullptr, hipMemcpyAsync(act.data(), h->active, act.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(nullptr, hipStreamSynchronize(h->stream));
-        bool any = false;
-        for (int a : act) any = any || a != 0;
-        if (!any) break;
-        if (done > limit) return fail(nullptr, MBAR_ERR_NUMERIC, "the root find did not end within the pass limit");
-        group = std::min(16, group * 2);
-    }
-    HIPCHK(nullptr, hipMemcpyAsync(states, h->states, (size_t)h->P * sizeof(mbar_bar_state), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(nullptr, hipStreamSynchronize(h->stream));
-    if (passes) *passes = done;
-    return MBAR_OK;
+    return run_passes(h->stream, states, h->states.p, h->active.p, h->P, limit, "the root find did not end within the pass limit",
+                      passes, [&]() -> int {
+                          HIPCHK(nullptr, launch_bar_eval(h->stream, d, h->states, h->part));
+                          HIPCHK(nullptr, launch_bar_step(h->stream, d, h->states, h->part, 1, h->out, h->active));
+                          return MBAR_OK;
+                      });
 }
 
 int mbar_bar_moments(mbar_bar* h, double* out) {

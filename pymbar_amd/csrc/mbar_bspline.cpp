@@ -36,9 +36,8 @@ int mbar_bspline_create(mbar_bspline** out, int device, int64_t N, const double*
         b->N = N;
         HIPCHK(nullptr, hipEventCreate(&b->ev0));
         HIPCHK(nullptr, hipEventCreate(&b->ev1));
-        HIPCHK(nullptr, b->X.grow((size_t)N));
+        HIPCHK(nullptr, b->X.upload(x, (size_t)N));
         HIPCHK(nullptr, b->t.grow((size_t)(BSP_MAX_BASIS + BSP_MAX_K + 1)));
-        HIPCHK(nullptr, hipMemcpy(b->X, x, (size_t)N * sizeof(double), hipMemcpyHostToDevice));
         std::vector<double> ones((size_t)N, 1.0);
         return mbar_bspline_set_weights(b, 1, ones.data());
     });
@@ -58,8 +57,7 @@ int mbar_bspline_set_groups(mbar_bspline* b, int G, const int* g) {
     }
     for (int64_t n = 0; n < b->N; ++n)
         if (g[n] < 0 || g[n] >= G) return bad_arg("group labels must lie in [0, G)");
-    HIPCHK(nullptr, b->g.grow((size_t)b->N));
-    HIPCHK(nullptr, hipMemcpy(b->g, g, (size_t)b->N * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, b->g.upload(g, (size_t)b->N));
     b->G = G;
     return MBAR_OK;
 }

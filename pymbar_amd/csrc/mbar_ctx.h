@@ -2,8 +2,8 @@
 // helpers the translation units of the host side share -- mbar_capi.cpp (contexts, uploads, options, evaluations), mbar_loops.cpp
 // (the solver loops the reference writes in Python), mbar_comm.cpp (RCCL loader, in-process transport, all-reduce),
 // mbar_host.cpp (allocator state, host-side K x K linear algebra, content digest).
-// The handles of the other backends (mbar_kde.cpp, mbar_acf.cpp, mbar_bar.cpp, mbar_bspline.cpp) share the layer below the
-// context: Handle, DevBuf, create_handle / destroy_handle, ColumnPasses.
+// The handles of the other backends (mbar_kde.cpp, mbar_acf.cpp, mbar_bar.cpp, mbar_bspline.cpp, mbar_batch.cpp) share the layer
+// below the context: Handle, DevBuf, create_handle / destroy_handle, ColumnPasses, run_passes.
 #pragma once
 #include "../../include/mbar_hip.h"
 #include "mbar_internal.h"
@@ -354,7 +354,7 @@ int fail(mbar_ctx* c, int code, const std::string& msg);
     } while (0)
 inline int bad_arg(const std::string& msg) { return fail(nullptr, MBAR_ERR_ARG, msg); }
 
-// ---- the handles of the other backends (mbar_kde, mbar_acf, mbar_bar, mbar_bspline) -----------------------------------------
+// ---- the handles of the other backends (mbar_kde, mbar_acf, mbar_bar, mbar_bspline, mbar_batch) -----------------------------
 // A handle derives from Handle, holds its device memory in DevBuf members, is made by create_handle and released by
 // destroy_handle: no buffer list to keep in step with the struct.
 
@@ -394,6 +394,11 @@ struct DevBuf {
         hipError_t e = cache_malloc((void**)&p, want * sizeof(T));
         if (e == hipSuccess) n = want;
         return e;
+    }
+    // grow(count), then the synchronous copy of `count` elements from the host to the buffer's start
+    auto upload(const T* src, size_t count) -> hipError_t {
+        hipError_t e = grow(count);
+        return e != hipSuccess ? e : hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
     }
 };
 
@@ -441,6 +446,37 @@ int create_handle(H** out, int device, Init&& init) {
         return fail(nullptr, rc, msg);
     }
     *out = h;
+    return MBAR_OK;
+}
+
+// The pass driver of the batched state machines (mbar_batch, mbar_bar), with the handle's device current: the P host states go
+// to `dev`, then pass() runs in groups of 4, 8, 16, 16, ...: between groups the host reads one int per problem (`active`).  A
+// finished problem costs one early-exiting workgroup per chunk.  More than `limit` passes with a problem still active:
+// MBAR_ERR_NUMERIC with `over_limit`.  At the end the states come back and *passes (if any) is the number of passes.
+template <class State, class Pass>
+int run_passes(hipStream_t stream, State* host, State* dev, const int* active, int64_t P, int64_t limit, const char* over_limit,
+               int64_t* passes, Pass&& pass) {
+    HIPCHK(nullptr, hipMemcpyAsync(dev, host, (size_t)P * sizeof(State), hipMemcpyHostToDevice, stream));
+    std::vector<int> act((size_t)P);
+    int64_t done = 0;
+    int group = 4;
+    for (;;) {
+        for (int k = 0; k < group; ++k) {
+            int rc = pass();
+            if (rc) return rc;
+        }
+        done += group;
+        HIPCHK(nullptr, hipMemcpyAsync(act.data(), active, act.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIPCHK(nullptr, hipStreamSynchronize(stream));
+        bool any = false;
+        for (int a : act) any = any || a != 0;
+        if (!any) break;
+        if (done > limit) return fail(nullptr, MBAR_ERR_NUMERIC, over_limit);
+        group = std::min(16, group * 2);
+    }
+    HIPCHK(nullptr, hipMemcpyAsync(host, dev, (size_t)P * sizeof(State), hipMemcpyDeviceToHost, stream));
+    HIPCHK(nullptr, hipStreamSynchronize(stream));
+    if (passes) *passes = done;
     return MBAR_OK;
 }
 

@@ -811,11 +811,9 @@ struct BatchData {
     const double* cw;        // per-sample multiplicities of replica slots, or NULL
     const int64_t* cwoff;    // [P] offset of slot s's multiplicities in cw
 };
-// evaluation pass over the chunks list[0 .. n) of one width class kb
+// evaluation pass over the chunks list[0 .. n) of one width class kb; with d.cw (and d.cwoff) the weighted form: every sum over
+// samples becomes sum_n c_n (...)
 hipError_t launch_batch_eval(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n, const mbar_batch_state* states);
-// the weighted form (d.cw, d.cwoff): every sum over samples becomes sum_n c_n (...)
-hipError_t launch_batch_eval_weighted(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n,
-                                      const mbar_batch_state* states);
 // Draw counts of the slots first .. first + count of the replica set d into d.cw (zeroed by the caller): position j of slot s
 // draws bootstrap_draw(seed[s], replicate[s], j, n_k) within the run of its state, cum[base[s]][0 .. K] being the runs' bounds
 // (rows of MBAR_BATCH_MAX_K + 1).  One workgroup per chunk; chunk0 / nchunk: the chunks of those slots.

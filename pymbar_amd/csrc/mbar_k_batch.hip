@@ -326,38 +326,30 @@ __global__ void __launch_bounds__(BATCH_WG) k_batch_draw(BatchData d, int64_t ch
     if (pos >= 0 && pos < d.N[s]) atomicAdd(cw + d.cwoff[s] + pos, 1.0);
 }
 
-}  // namespace
-
-hipError_t launch_batch_eval_weighted(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n,
-                                      const mbar_batch_state* states) {
-    if (n == 0) return hipSuccess;
-    if (!d.cw || !d.cwoff) return hipErrorInvalidValue;
+template <bool WT>
+hipError_t launch_eval(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n, const mbar_batch_state* states) {
     switch (kb) {
-    case 8: hipLaunchKernelGGL((k_batch_eval<8, true>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
-    case 16: hipLaunchKernelGGL((k_batch_eval<16, true>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
-    case 32: hipLaunchKernelGGL((k_batch_eval<32, true>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
-    case 64: hipLaunchKernelGGL((k_batch_eval<64, true>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 8: hipLaunchKernelGGL((k_batch_eval<8, WT>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 16: hipLaunchKernelGGL((k_batch_eval<16, WT>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 32: hipLaunchKernelGGL((k_batch_eval<32, WT>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
+    case 64: hipLaunchKernelGGL((k_batch_eval<64, WT>), dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_batch_eval(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n, const mbar_batch_state* states) {
+    if (n == 0) return hipSuccess;
+    if (d.cw && !d.cwoff) return hipErrorInvalidValue;
+    return d.cw ? launch_eval<true>(st, kb, d, list, n, states) : launch_eval<false>(st, kb, d, list, n, states);
 }
 
 hipError_t launch_batch_draw(hipStream_t st, const BatchData& d, int64_t chunk0, int64_t nchunk, const int64_t* base,
                              const int64_t* Kp, const int64_t* cum, const uint64_t* seed, const int64_t* replicate, double* cw) {
     if (nchunk == 0) return hipSuccess;
     hipLaunchKernelGGL(k_batch_draw, dim3((unsigned)nchunk), dim3(BATCH_WG), 0, st, d, chunk0, base, Kp, cum, seed, replicate, cw);
-    return hipGetLastError();
-}
-
-hipError_t launch_batch_eval(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n, const mbar_batch_state* states) {
-    if (n == 0) return hipSuccess;
-    switch (kb) {
-    case 8: hipLaunchKernelGGL(k_batch_eval<8>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
-    case 16: hipLaunchKernelGGL(k_batch_eval<16>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
-    case 32: hipLaunchKernelGGL(k_batch_eval<32>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
-    case 64: hipLaunchKernelGGL(k_batch_eval<64>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, list, states); break;
-    default: return hipErrorInvalidValue;
-    }
     return hipGetLastError();
 }
 

@@ -107,14 +107,13 @@ int mbar_kde_create(mbar_kde** out, int device, int kernel, int d, int64_t N, co
         k->lognorm = log_norm(kernel, d, bandwidth);
         k->num_cu = di.num_cu;
         k->ldx = (N + KDE_TILE - 1) / KDE_TILE * KDE_TILE;
-        HIPCHK(nullptr, k->X.grow((size_t)d * k->ldx));
         HIPCHK(nullptr, k->logW_d.grow(KDE_MAX_CB));
         // coordinate-major, padded with copies of the last sample (weight zero: they add nothing, and they never hold a
         // query's running shift above what a real sample gives)
         std::vector<double> stage((size_t)d * k->ldx);
         for (int j = 0; j < d; ++j)
             for (int64_t i = 0; i < k->ldx; ++i) stage[(size_t)j * k->ldx + i] = x[(i < N ? i : N - 1) * d + j];
-        HIPCHK(nullptr, hipMemcpy(k->X, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, k->X.upload(stage.data(), stage.size()));
         std::vector<double> ones((size_t)N, 1.0);
         return mbar_kde_set_weights(k, 1, ones.data());
     });
@@ -160,8 +159,7 @@ int mbar_kde_eval(mbar_kde* k, int64_t M, const double* q, double* out) {
         std::vector<double> stage((size_t)d * ldq);
         for (int j = 0; j < d; ++j)
             for (int64_t i = 0; i < ldq; ++i) stage[(size_t)j * ldq + i] = q[(i < M ? i : M - 1) * d + j];
-        HIPCHK(nullptr, k->Q.grow(stage.size()));
-        HIPCHK(nullptr, hipMemcpy(k->Q, stage.data(), stage.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(nullptr, k->Q.upload(stage.data(), stage.size()));
     }
     // grid: 256 queries x one chunk of whole tiles per workgroup, about four workgroups per CU (their LDS allows four)
     const int64_t ntiles = k->ldx / KDE_TILE;
@@ -218,8 +216,7 @@ int mbar_kde_eval(mbar_kde* k, int64_t M, const double* q, double* out) {
                 }
         const int64_t np = (int64_t)pairs.size() / 2;
         if (np > 0) {  // every term of these pairs underflowed against the shared shift: their own maximum, in log space
-            HIPCHK(nullptr, k->pq.grow(pairs.size()));
-            HIPCHK(nullptr, hipMemcpy(k->pq, pairs.data(), pairs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+            HIPCHK(nullptr, k->pq.upload(pairs.data(), pairs.size()));
             HIPCHK(nullptr, launch_kde_exact(k->stream, a, k->N, np, k->pq, k->logW_d, k->lognorm, k->out));
             std::vector<double> redo((size_t)np);
             HIPCHK(nullptr, hipMemcpyAsync(redo.data(), k->out, redo.size() * sizeof(double), hipMemcpyDeviceToHost, k->stream));

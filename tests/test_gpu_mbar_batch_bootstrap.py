@@ -124,7 +124,8 @@ def _long_double_sums(u_kn, N_k, f, c):
 @pytest.fixture(scope="module")
 def shape_run():
     """Every (K, N) problem in one device batch, one replica slot per multiplicity pattern: the slots' per-state log sums (a solve
-    that takes no iteration evaluates them at the start) and their covariance inputs at the same f; likewise the problems' own."""
+    that takes no iteration evaluates them at the start) and their covariance inputs at the same f; likewise the problems' own,
+    once before the slots exist, again after the slots' calls, and once more after the slots are released."""
     rng = np.random.default_rng(31)
     probs = [_shape_problem(K, N, seed=100 + i) for i, (K, N) in enumerate((K, N) for K in SHAPE_K for N in SHAPE_N)]
     blocks = [p[0] for p in probs]
@@ -152,11 +153,13 @@ def shape_run():
             F[i, :K] = fs[p]
         return st, F
 
-    with batch.DeviceBatch(blocks) as h:
+    def problems_run(h):
         st, F = states_for(range(P))
         h.solve(st)
-        base_lognum = batch._states_view(st)["lognum"].copy()
-        base_gram, base_wsum = h.gram_w(F, np.ones(P, dtype=bool))
+        return (batch._states_view(st)["lognum"].copy(),) + h.gram_w(F, np.ones(P, dtype=bool))
+
+    with batch.DeviceBatch(blocks) as h:
+        base_lognum, base_gram, base_wsum = problems_run(h)
         h.set_replicas(base, Nks)
         for s, c in enumerate(cs):
             h.replica_set_weights(s, c)
@@ -168,8 +171,11 @@ def shape_run():
         assert (sv["status"] == batch.DONE).all() and (sv["iterations"] == 0).all()
         lognum = sv["lognum"].copy()
         gram, wsum = h.replicas_gram_w(F, np.ones(len(slots), dtype=bool))
+        repeats = [problems_run(h)]
+        h.set_replicas(np.zeros(0, dtype=np.int64), Nks)
+        repeats.append(problems_run(h))
     return dict(probs=probs, fs=fs, slots=slots, cs=cs, lognum=lognum, gram=gram, wsum=wsum, base_lognum=base_lognum,
-                base_gram=base_gram, base_wsum=base_wsum)
+                base_gram=base_gram, base_wsum=base_wsum, repeats=repeats)
 
 
 def _unpack(Ks, gram, wsum):
@@ -218,6 +224,16 @@ def test_unit_multiplicities_reproduce_the_unweighted_kernel(shape_run):
         np.testing.assert_allclose(slots[s][1], plain[p][1], rtol=1e-13, atol=0.0)
         seen += 1
     assert seen == P
+
+
+def test_problems_and_slots_stay_apart_when_their_calls_interleave(shape_run):
+    """The problems' records, states and outputs are their own: the same bits after the slots' solve and covariance pass, and
+    after the slots are released."""
+    d = shape_run
+    for lognum, gram, wsum in d["repeats"]:
+        assert np.array_equal(lognum, d["base_lognum"])
+        assert np.array_equal(gram, d["base_gram"])
+        assert np.array_equal(wsum, d["base_wsum"])
 
 
 # ---- bits ----------------------------------------------------------------------------------------------------------------

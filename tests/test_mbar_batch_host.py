@@ -120,6 +120,42 @@ def test_state_machine_hands_back_a_singular_system():
     assert st.status == batch.FALLBACK and st.newton_bad == 1 and st.nreq == 0
 
 
+def test_all_states_update_equals_the_formula_per_problem():
+    """The shared all-state update on a whole state array against ``solve_mbar_for_all_states``'s update written out per problem:
+    ragged widths, an unsampled state in one row, sums over hundreds of orders of magnitude (one subnormal), f of both signs.
+    The same expression per element: no tolerance."""
+    rng = np.random.default_rng(5)
+    Ks = [1, 2, 8, 9, 64]
+    states = (_lib.BatchState * len(Ks))()
+    sv = batch._states_view(states)
+    for name in ("f", "psum", "lognum", "Nk"):   # what lies behind column K must not matter
+        sv[name] = rng.normal(size=sv[name].shape)
+    Nks = []
+    for e, K in enumerate(Ks):
+        N_k = rng.integers(1, 1000, size=K)
+        if K == 8:
+            N_k[3] = 0                               # an unsampled state: this row takes -lognum
+        Nks.append(N_k)
+        sv["K"][e] = K
+        sv["Nk"][e, :K] = N_k
+        sv["f"][e, :K] = rng.normal(scale=30.0, size=K)
+        sv["psum"][e, :K] = 10.0 ** rng.uniform(-300, 300, size=K)
+        sv["lognum"][e, :K] = rng.normal(scale=30.0, size=K)
+    sv["psum"][4, 7] = 1e-310                        # (subnormal, and still so after the division by N_k < 1000)
+    assert (sv["f"] < 0).any() and (sv["f"] > 0).any()
+    got = batch._all_states_update(sv)
+    for e, K in enumerate(Ks):
+        N_k = Nks[e]
+        f = sv["f"][e, :K].copy()
+        if np.all(N_k > 0):
+            f = f - np.log(sv["psum"][e, :K] / N_k)
+        else:
+            f = -1.0 * sv["lognum"][e, :K]
+        f -= f[0]
+        assert np.all(np.isfinite(f)) and (K == 8) == (not np.all(N_k > 0))
+        assert np.array_equal(got[e, :K], f), (K, got[e, :K] - f)
+
+
 def test_input_rules():
     u = np.zeros((3, 10))
     with pytest.raises(ParameterError, match="at least one problem"):
