@@ -568,6 +568,32 @@ int mbar_batch_replicas_solve(mbar_batch* b, mbar_batch_state* states, int64_t* 
 /* mbar_batch_gram_w for the slots: gram = sum_n c_n W_ni W_nj and wsum = sum_n c_n W_nk at f[s][0 .. K), packed slot after slot. */
 int mbar_batch_replicas_gram_w(mbar_batch* b, const double* f, const int32_t* mask, double* gram, double* wsum);
 
+/* ---- extension rows: the expectation family of a batch (pymbar_amd.MBARBatch) --------------------------------------------------
+ * Problem p gets R[p] >= 0 extension rows, an R[p] x N[p] row-major block of reduced potentials e_rn resident next to its own
+ * block: new states and observables written as states with no samples (expectations.py), which do not enter the log-denominator.
+ * K[p] + R[p] <= MBAR_BATCH_MAX_AUG; +inf allowed, NaN and -inf rejected.  The two passes below read N_k from the problems' states
+ * as mbar_batch_solve left them on the device (as mbar_batch_gram_w does) and take f[p][0 .. K[p]) in rows of MBAR_BATCH_MAX_K;
+ * per-row values (lognum_ext, f_ext) are packed problem after problem, R[p] doubles each.  Same rules as the passes above: chunks
+ * of MBAR_BATCH_CHUNK samples, no atomics, partials merged in chunk order, so two identical calls return identical bits and a
+ * problem's bits depend neither on the batch it is in nor on the grouping of the Gram pass.
+ *
+ * mbar_batch_set_ext replaces any earlier rows (R = NULL releases them); e[p] may be NULL where R[p] = 0.  The
+ * device memory of the rows and their chunk records is checked up front (MBAR_ERR_ARG with the sizes in the message); a call
+ * that is rejected (MBAR_ERR_ARG) leaves the earlier rows in place. */
+#define MBAR_BATCH_MAX_AUG 128
+int mbar_batch_set_ext(mbar_batch* b, const int64_t* R, const double* const* e);
+/* lognum_ext[p][r] = log sum_n exp(-logden_n(f) - e_rn) for the problems with mask[p] != 0 (log space, the chunk maximum as the
+ * shift; a row whose terms are all zero gives -inf; entries of masked-out problems untouched). */
+int mbar_batch_ext_lognum(mbar_batch* b, const double* f, const int32_t* mask, double* lognum_ext);
+/* gram = Q^T Q ((K[p] + R[p])^2 doubles per problem, bit-symmetric) and wsum = the column sums of Q (K[p] + R[p] doubles), packed
+ * problem after problem, for the problems with mask[p] != 0.  Q_nk = exp(f_k - u_kn - logden_n) for the K[p] states (W of
+ * mbar_batch_gram_w), then exp(f_ext_r - e_rn - logden_n) for the rows (f_ext finite).  A workgroup owns MBAR_BATCH_EXT_RUN
+ * consecutive chunks of a problem and writes one partial record for them; the problems are swept in groups whose records take at
+ * most group_bytes of device memory (at least one problem per group; <= 0: no limit). */
+#define MBAR_BATCH_EXT_RUN 4
+int mbar_batch_ext_gram(mbar_batch* b, const double* f, const double* f_ext, const int32_t* mask, int64_t group_bytes, double* gram,
+                        double* wsum);
+
 #ifdef __cplusplus
 }
 #endif

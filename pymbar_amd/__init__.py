@@ -7,12 +7,13 @@ does not load the library or touch a GPU; the first computation does, and fails 
 """
 from . import mbar_solvers, other_estimators, testsystems, utils
 from ._lib import BackendUnavailable, MbarHipError, trim_device_cache
-from .batch import mbar_batch
+from .batch import MBARBatch, mbar_batch
 from .fes import FES
 from .mbar import MBAR
 from .other_estimators import bar, bar_batch, bar_overlap, bar_zero, exp, exp_gauss
 from .utils import ParameterError
 
 __all__ = ["MBAR", "FES", "mbar_solvers", "other_estimators", "testsystems", "utils", "ParameterError", "BackendUnavailable",
-           "MbarHipError", "trim_device_cache", "mbar_batch", "bar", "bar_batch", "bar_overlap", "bar_zero", "exp", "exp_gauss"]
+           "MbarHipError", "trim_device_cache", "mbar_batch", "MBARBatch", "bar", "bar_batch", "bar_overlap", "bar_zero", "exp",
+           "exp_gauss"]
 __version__ = "0.1.0"

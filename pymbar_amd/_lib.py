@@ -39,6 +39,8 @@ class BarState(C.Structure):
 
 MBAR_BATCH_MAX_K = 64
 MBAR_BATCH_CHUNK = 256
+MBAR_BATCH_MAX_AUG = 128
+MBAR_BATCH_EXT_RUN = 4
 
 
 class BatchState(C.Structure):
@@ -165,6 +167,9 @@ SIGNATURES = {
     "mbar_batch_replicas_draw": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), _ip]),
     "mbar_batch_replicas_solve": (C.c_int, [C.c_void_p, C.POINTER(BatchState), _ip]),
     "mbar_batch_replicas_gram_w": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_int32), _dp, _dp]),
+    "mbar_batch_set_ext": (C.c_int, [C.c_void_p, _ip, C.POINTER(_dp)]),
+    "mbar_batch_ext_lognum": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_int32), _dp]),
+    "mbar_batch_ext_gram": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(C.c_int32), C.c_int64, _dp, _dp]),
 }
 
 _lib = None

@@ -11,6 +11,10 @@ has a pivot that counts as zero is finished on the host by the single-problem pa
 With ``n_bootstraps = B`` every problem's B bootstrap replicates are solved in the same call: a replicate is a replica slot of the
 device batch -- the problem's resident block with per-sample draw counts, drawn on the device from the counter-based stream of
 ``MBAR(bootstrap_rng="device")`` -- started from the problem's solved ``f_k``; nothing is gathered and no block is copied.
+
+``MBARBatch`` keeps the solved batch resident and answers the expectation family of ``MBAR`` for every problem at once: new states
+and observables become extension rows of the resident blocks, swept by one device pass for their normalisers and one for the
+augmented Gram matrices.
 """
 import ctypes as C
 import logging
@@ -25,11 +29,14 @@ from .utils import ParameterError, check_w_sums
 logger = logging.getLogger(__name__)
 
 MAX_K = _lib.MBAR_BATCH_MAX_K
+MAX_AUG = _lib.MBAR_BATCH_MAX_AUG
 RUNNING, DONE, FALLBACK = 0, 1, 2
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
 # Device memory one group of replica slots may take for its multiplicities (8 N bytes per slot), chunk records and states
 BOOTSTRAP_GROUP_BYTES = 2 << 30
+# Device memory the partial records of one group of problems may take in the augmented Gram pass of MBARBatch
+EXT_GRAM_GROUP_BYTES = 1 << 30
 
 
 def _check_inputs(rc):
@@ -51,6 +58,7 @@ class DeviceBatch(_lib.Handle):
         self.P = len(blocks)
         self.K = np.array([b.shape[0] for b in blocks], dtype=np.int64)
         self.N = np.array([b.shape[1] for b in blocks], dtype=np.int64)
+        self.R = np.zeros(self.P, dtype=np.int64)  # extension rows per problem (set_ext)
         ptrs = (_dp * self.P)(*[b.ctypes.data_as(_dp) for b in blocks])
         h = C.c_void_p()
         _check_inputs(self._lib.mbar_batch_create(C.byref(h), self.device, self.P, _lib.ptr(self.K, _ip), _lib.ptr(self.N, _ip), ptrs))
@@ -108,6 +116,46 @@ class DeviceBatch(_lib.Handle):
     def replicas_gram_w(self, F, mask):
         """``gram_w`` of the slots: packed ``sum_n c_n W_ni W_nj`` and ``sum_n c_n W_nk`` at ``F[s, :K]``."""
         return self._gram_w(self._lib.mbar_batch_replicas_gram_w, self.K[self.base], F, mask)
+
+    # ---- extension rows (the expectation family) ----
+    def set_ext(self, rows):
+        """Problem p's extension rows ``rows[p]`` (R_p x N_p; None: no rows), resident until replaced; ``rows=None`` releases them."""
+        if rows is None:
+            self.R = np.zeros(self.P, dtype=np.int64)
+            _check_inputs(self._lib.mbar_batch_set_ext(self._h, None, None))
+            return
+        rows = [None if r is None or len(r) == 0 else np.ascontiguousarray(r, dtype=np.float64) for r in rows]
+        for p, r in enumerate(rows):
+            if r is not None and (r.ndim != 2 or r.shape[1] != self.N[p]):
+                raise ValueError(f"problem {p}: extension rows must have shape (R, {int(self.N[p])})")
+        R = np.array([0 if r is None else r.shape[0] for r in rows], dtype=np.int64)
+        ptrs = (_dp * self.P)(*[_lib.ptr(r) for r in rows])
+        _check_inputs(self._lib.mbar_batch_set_ext(self._h, _lib.ptr(R, _ip), ptrs))  # (rejected: the earlier rows stay)
+        self.R = R
+
+    def ext_lognum(self, F, mask):
+        """Packed ``log sum_n exp(-logden_n(F[p]) - e_rn)`` of the extension rows of the problems with ``mask[p]``."""
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        out = np.zeros(int(self.R.sum()), dtype=np.float64)
+        if out.size:
+            _check_inputs(self._lib.mbar_batch_ext_lognum(self._h, _lib.ptr(F), mask.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(out)))
+        return out
+
+    def ext_gram(self, F, f_ext, mask, group_bytes=0):
+        """Packed ``Q^T Q`` ((K + R)^2 per problem) and column sums of ``Q = [W | exp(f_ext_r - e_rn - logden_n)]`` at ``F`` for the
+        problems with ``mask[p]``; the records of one group of problems take at most ``group_bytes`` of device memory."""
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        f_ext = np.ascontiguousarray(f_ext, dtype=np.float64)
+        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        if f_ext.shape != (int(self.R.sum()),):
+            raise ValueError(f"f_ext must have shape ({int(self.R.sum())},)")
+        A = self.K + self.R
+        gram = np.zeros(int(np.sum(A * A)), dtype=np.float64)
+        wsum = np.zeros(int(np.sum(A)), dtype=np.float64)
+        _check_inputs(self._lib.mbar_batch_ext_gram(self._h, _lib.ptr(F), _lib.ptr(f_ext), mask.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    int(group_bytes), _lib.ptr(gram), _lib.ptr(wsum)))
+        return gram, wsum
 
 
 def bootstrap_indices(seed, b, N_k):
@@ -340,6 +388,114 @@ def _error_of_differences_stack(cov, warning_cutoff):
     return np.sqrt(d2)
 
 
+def _check_lengths(who, u_kn_list, N_k_list, initial_f_k):
+    P = len(u_kn_list)
+    if P == 0:
+        raise ParameterError(f"{who} needs at least one problem")
+    if len(N_k_list) != P:
+        raise ParameterError(f"{who}: {P} matrices but {len(N_k_list)} N_k vectors")
+    if initial_f_k is not None and len(initial_f_k) != P:
+        raise ParameterError(f"{who}: {P} matrices but {len(initial_f_k)} initial_f_k vectors")
+    return P
+
+
+def _settings(tol, maximum_iterations, min_sc_iter, gamma):
+    """The solver settings of a batch as the states take them, and as the protocol of the single-problem path."""
+    tol = float(tol)
+    maximum_iterations = int(maximum_iterations)
+    min_sc_iter = int(min_sc_iter)
+    gamma = float(gamma)
+    if tol < 4.0 * np.finfo(float).eps:
+        logger.info("Tolerance may be too close to machine precision to converge.")
+    return (tol, gamma, maximum_iterations, min_sc_iter), _protocol(tol, maximum_iterations, min_sc_iter, gamma)
+
+
+def _check_problems(u_kn_list, N_k_list, initial_f_k, settings):
+    """Every problem checked and made contiguous (``_check_problem``), and the state array that starts their solves."""
+    P = len(u_kn_list)
+    blocks, Nks, f0s = [], [], []
+    for p in range(P):
+        u, N_k, f_k = _check_problem(p, u_kn_list[p], N_k_list[p], None if initial_f_k is None else initial_f_k[p])
+        blocks.append(u)
+        Nks.append(N_k)
+        f0s.append(f_k)
+    Ks = np.array([b.shape[0] for b in blocks], dtype=np.int64)
+    return blocks, Nks, f0s, _new_states(np.arange(P), Ks, Nks, f0s, settings)
+
+
+def _solve_problems(h, states, blocks, Nks, f0s, protocol):
+    """The problems' solves on the handle ``h``, the all-state update, and the single-problem path for the problems the device
+    handed back.  Returns (passes, time after the device loop, fallback, f_k per problem, the same in rows of MAX_K, per problem
+    (iterations, nr, sci, success, choices), {p: (W^T W, sum_n W_nk)} of the problems that fell back)."""
+    P = len(blocks)
+    passes = h.solve(states)
+    t3 = time.perf_counter()
+    sv = _states_view(states)
+    status = sv["status"].copy()
+    fallback = status == FALLBACK
+    f_all = _all_states_update(sv)
+    f_out, results = [], []
+    F = np.zeros((P, MAX_K), dtype=np.float64)
+    host_gram = {}
+    for p in range(P):
+        K = blocks[p].shape[0]
+        N_k = Nks[p]
+        if fallback[p]:
+            f, G, ws, res = _host_solve(blocks[p], N_k, f0s[p], protocol, h.device)
+            host_gram[p] = (G, ws)
+            results.append((int(res["iterations"]), int(res["nr_iter"]), int(res["sci_iter"]), bool(res["success"]), 0))
+        else:
+            f = f_all[p, :K].copy()
+            results.append((int(sv["iterations"][p]), int(sv["nr_iter"][p]), int(sv["sci_iter"][p]), bool(sv["success"][p]),
+                            int(sv["choices"][p])))
+            if results[-1][3] is False:
+                logger.warning(f"problem {p}: WARNING: Did not converge to within specified tolerance.")
+        F[p, :K] = f
+        f_out.append(f)
+    return passes, t3, fallback, f_out, F, results, host_gram
+
+
+def _unpack_gram(Ks, gram, wsum, fallback, host_gram):
+    """Per problem ``(W^T W, sum_n W_nk)`` from the packed covariance pass (or the single-problem path), the sums checked."""
+    goff = np.concatenate(([0], np.cumsum(Ks * Ks)))
+    woff = np.concatenate(([0], np.cumsum(Ks)))
+    Gs, Ws = [], []
+    for p in range(len(Ks)):
+        K = int(Ks[p])
+        if fallback[p]:
+            G, ws = host_gram[p]
+        else:
+            G = gram[goff[p]:goff[p + 1]].reshape(K, K)
+            ws = wsum[woff[p]:woff[p + 1]]
+        try:
+            check_w_sums(ws, 0.0)
+        except ParameterError as exc:
+            raise ParameterError(f"problem {p}: {exc}") from exc
+        Gs.append(G)
+        Ws.append(ws)
+    return Gs, Ws
+
+
+def _theta_stacks(Gs, Nks, method):
+    """``_theta_stack`` of the problems, those of one size as one stack: ``Gs[p]`` (A_p, A_p), ``Nks[p]`` (A_p,).  Yields
+    (the problems of a size, their Theta stack)."""
+    sizes = np.array([G.shape[0] for G in Gs], dtype=np.int64)
+    for A in np.unique(sizes):
+        sel = np.where(sizes == A)[0]
+        G = np.stack([Gs[p] for p in sel])
+        Nk = np.stack([Nks[p] for p in sel]).astype(np.float64)
+        yield sel, _theta_stack(G, Nk, method)
+
+
+def _ddelta_f(Nks, Gs, uncertainty_method, warning_cutoff):
+    dDelta_f = [None] * len(Gs)
+    for sel, theta in _theta_stacks(Gs, Nks, "svd-ew" if uncertainty_method is None else uncertainty_method):
+        err = _error_of_differences_stack(theta, warning_cutoff)
+        for i, p in enumerate(sel):
+            dDelta_f[p] = err[i]
+    return dDelta_f
+
+
 def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterations=10000, min_sc_iter=0, gamma=1.0,
                compute_uncertainty=True, uncertainty_method=None, warning_cutoff=1e-10, device=None, n_bootstraps=0, rseed=None,
                bootstrap_seeds=None):
@@ -360,13 +516,7 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
     those of a problem in ``host_fallback``, are solved by the single-problem path).  ``uncertainty_method="bootstrap"`` gives
     ``dDelta_f`` as ``MBAR.compute_free_energy_differences`` does, the standard deviation over the replicates of every difference,
     and skips the covariance pass; the other methods give the analytical ``dDelta_f`` next to ``f_k_boots``."""
-    P = len(u_kn_list)
-    if P == 0:
-        raise ParameterError("mbar_batch needs at least one problem")
-    if len(N_k_list) != P:
-        raise ParameterError(f"mbar_batch: {P} matrices but {len(N_k_list)} N_k vectors")
-    if initial_f_k is not None and len(initial_f_k) != P:
-        raise ParameterError(f"mbar_batch: {P} matrices but {len(initial_f_k)} initial_f_k vectors")
+    P = _check_lengths("mbar_batch", u_kn_list, N_k_list, initial_f_k)
     if uncertainty_method not in (None, "svd-ew", "approximate", "bootstrap"):
         raise ParameterError(f"mbar_batch: uncertainty_method {uncertainty_method!r} is not supported (None, 'svd-ew', 'approximate', "
                              "'bootstrap')")
@@ -383,52 +533,15 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
         seeds = seeds.astype(np.uint64)
     elif B > 0:
         seeds = np.random.default_rng(rseed).integers(np.iinfo(np.int64).max, size=P).astype(np.uint64)
-    tol = float(tol)
-    maximum_iterations = int(maximum_iterations)
-    min_sc_iter = int(min_sc_iter)
-    gamma = float(gamma)
-    if tol < 4.0 * np.finfo(float).eps:
-        logger.info("Tolerance may be too close to machine precision to converge.")
     t0 = time.perf_counter()
-    blocks, Nks, f0s = [], [], []
-    for p in range(P):
-        u, N_k, f_k = _check_problem(p, u_kn_list[p], N_k_list[p], None if initial_f_k is None else initial_f_k[p])
-        blocks.append(u)
-        Nks.append(N_k)
-        f0s.append(f_k)
+    settings, protocol = _settings(tol, maximum_iterations, min_sc_iter, gamma)
+    blocks, Nks, f0s, states = _check_problems(u_kn_list, N_k_list, initial_f_k, settings)
     Ks = np.array([b.shape[0] for b in blocks], dtype=np.int64)
-
-    settings = (tol, gamma, maximum_iterations, min_sc_iter)
-    states = _new_states(np.arange(P), Ks, Nks, f0s, settings)
 
     t1 = time.perf_counter()
     with DeviceBatch(blocks, device=device) as h:
         t2 = time.perf_counter()
-        passes = h.solve(states)
-        t3 = time.perf_counter()
-        sv = _states_view(states)
-        status = sv["status"].copy()
-        fallback = status == FALLBACK
-        f_all = _all_states_update(sv)
-        f_out, results = [], []
-        F = np.zeros((P, MAX_K), dtype=np.float64)
-        host_gram = {}
-        protocol = _protocol(tol, maximum_iterations, min_sc_iter, gamma)
-        for p in range(P):
-            K = int(Ks[p])
-            N_k = Nks[p]
-            if fallback[p]:
-                f, G, ws, res = _host_solve(blocks[p], N_k, f0s[p], protocol, h.device)
-                host_gram[p] = (G, ws)
-                results.append((int(res["iterations"]), int(res["nr_iter"]), int(res["sci_iter"]), bool(res["success"]), 0))
-            else:
-                f = f_all[p, :K].copy()
-                results.append((int(sv["iterations"][p]), int(sv["nr_iter"][p]), int(sv["sci_iter"][p]), bool(sv["success"][p]),
-                                int(sv["choices"][p])))
-                if results[-1][3] is False:
-                    logger.warning(f"problem {p}: WARNING: Did not converge to within specified tolerance.")
-            F[p, :K] = f
-            f_out.append(f)
+        passes, t3, fallback, f_out, F, results, host_gram = _solve_problems(h, states, blocks, Nks, f0s, protocol)
         gram = wsum = None
         t4 = time.perf_counter()
         analytical = compute_uncertainty and uncertainty_method != "bootstrap"
@@ -458,32 +571,396 @@ def mbar_batch(u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterati
         out["dDelta_f"] = [bootstrap_ddelta_f(fb) for fb in out["f_k_boots"]]
     if not analytical:
         return out
-    goff = np.concatenate(([0], np.cumsum(Ks * Ks)))
-    woff = np.concatenate(([0], np.cumsum(Ks)))
-    Gs, Ws = [], []
-    for p in range(P):
-        K = int(Ks[p])
-        if fallback[p]:
-            G, ws = host_gram[p]
-        else:
-            G = gram[goff[p]:goff[p + 1]].reshape(K, K)
-            ws = wsum[woff[p]:woff[p + 1]]
-        try:
-            check_w_sums(ws, 0.0)
-        except ParameterError as exc:
-            raise ParameterError(f"problem {p}: {exc}") from exc
-        Gs.append(G)
-        Ws.append(ws)
-    method = "svd-ew" if uncertainty_method is None else uncertainty_method
-    dDelta_f = [None] * P
-    for K in np.unique(Ks):
-        sel = np.where(Ks == K)[0]
-        G = np.stack([Gs[p] for p in sel])
-        Nk = np.stack([Nks[p] for p in sel]).astype(np.float64)
-        theta = _theta_stack(G, Nk, method)
-        err = _error_of_differences_stack(theta, warning_cutoff)
-        for i, p in enumerate(sel):
-            dDelta_f[p] = err[i]
-    out["dDelta_f"] = dDelta_f
+    Gs, Ws = _unpack_gram(Ks, gram, wsum, fallback, host_gram)
+    out["dDelta_f"] = _ddelta_f(Nks, Gs, uncertainty_method, warning_cutoff)
     out["timing"]["covariance"] = time.perf_counter() - (t6 if B > 0 else t5)
     return out
+
+
+def _check_method(who, uncertainty_method):
+    if uncertainty_method not in (None, "svd-ew", "approximate"):
+        raise ParameterError(f"{who}: uncertainty_method {uncertainty_method!r} is not supported (None, 'svd-ew', 'approximate')")
+    return "svd-ew" if uncertainty_method is None else uncertainty_method
+
+
+class MBARBatch:
+    """P independent MBAR problems solved in one device call and kept resident for the expectation family (DESIGN.md section 15,
+    INTEGRATION.md section 7).
+
+    Construction checks, uploads and solves exactly as ``mbar_batch(..., n_bootstraps=0)`` does (the same ``f_k`` bits); the handle
+    stays on the device until ``close()``, the end of a ``with`` block or collection.  Attributes: ``P``, ``K``, ``N`` (arrays),
+    ``N_k``, ``f_k`` (lists), ``iterations``, ``success``, ``host_fallback``.  Every method returns a dict of per-problem lists
+    under the key names of the ``MBAR`` method it mirrors; entry p is what ``MBAR(u_p, N_p, solver_protocol=<adaptive, tol>)``
+    and the same method return.  New states and observables become extension rows of the resident blocks (states with no samples,
+    as in expectations.py): their normalisers and the augmented Gram matrices of all problems come from one device pass each, the
+    covariances from eigendecompositions stacked over the problems that share an augmented size.  ``uncertainty_method``: None /
+    "svd-ew" or "approximate".  A problem in ``host_fallback`` is answered by the single-problem ``MBAR``."""
+
+    def __init__(self, u_kn_list, N_k_list, initial_f_k=None, tol=1e-12, maximum_iterations=10000, min_sc_iter=0, gamma=1.0,
+                 device=None):
+        self._h = None
+        self._mbars = {}
+        P = _check_lengths("MBARBatch", u_kn_list, N_k_list, initial_f_k)
+        settings, self._protocol = _settings(tol, maximum_iterations, min_sc_iter, gamma)
+        self._maxiter = settings[2]
+        self._blocks, self.N_k, self._f0s, states = _check_problems(u_kn_list, N_k_list, initial_f_k, settings)
+        self.P = P
+        self.K = np.array([b.shape[0] for b in self._blocks], dtype=np.int64)
+        self.N = np.array([b.shape[1] for b in self._blocks], dtype=np.int64)
+        self._h = DeviceBatch(self._blocks, device=device)
+        try:
+            _, _, self.host_fallback, self.f_k, self._F, results, self._host_gram = _solve_problems(
+                self._h, states, self._blocks, self.N_k, self._f0s, self._protocol)
+        except BaseException:
+            self.close()
+            raise
+        self.iterations = np.array([r[0] for r in results], dtype=np.int64)
+        self.success = np.array([r[3] for r in results], dtype=bool)
+        self._gram = None
+
+    # ---- lifetime ----
+    def close(self):
+        """Release the device copy of the problems (and the single-problem objects of those that fell back)."""
+        if self._h is not None:
+            self._h.close()
+            self._h = None
+        for m in self._mbars.values():
+            m.close()
+        self._mbars = {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if self._h is None:
+            raise ParameterError("MBARBatch: the batch is closed")
+        return self._h
+
+    def _mbar(self, p):
+        """The single-problem object of a problem that fell back."""
+        from .mbar import MBAR
+
+        if p not in self._mbars:
+            self._mbars[p] = MBAR(self._blocks[p], self.N_k[p], initial_f_k=self._f0s[p], solver_protocol=self._protocol,
+                                  maximum_iterations=self._maxiter, device=self._handle().device)
+        return self._mbars[p]
+
+    def _gram_w(self):
+        """Per problem ``(W^T W, sum_n W_nk)`` at ``f_k`` (one device pass, kept)."""
+        h = self._handle()
+        if self._gram is None:
+            gram, wsum = h.gram_w(self._F, ~self.host_fallback)
+            self._gram = _unpack_gram(self.K, gram, wsum, self.host_fallback, self._host_gram)
+        return self._gram
+
+    def _ErrorOfDifferences(self, cov, warning_cutoff=1.0e-10):
+        from .mbar import error_of_differences
+
+        return error_of_differences(cov, warning_cutoff)
+
+    # ---- the methods of MBAR ----
+    def compute_free_energy_differences(self, compute_uncertainty=True, uncertainty_method=None, warning_cutoff=1.0e-10):
+        """``Delta_f`` and ``dDelta_f`` per problem: the numbers of ``mbar_batch``."""
+        _check_method("MBARBatch", uncertainty_method)
+        self._handle()
+        out = dict(Delta_f=[np.array(f - np.vstack(f)) for f in self.f_k])
+        if compute_uncertainty:
+            Gs, _ = self._gram_w()
+            out["dDelta_f"] = _ddelta_f(self.N_k, Gs, uncertainty_method, warning_cutoff)
+        return out
+
+    def compute_overlap(self):
+        """``scalar``, ``eigenvalues`` and ``matrix`` of ``MBAR.compute_overlap`` per problem."""
+        Gs, _ = self._gram_w()
+        out = dict(scalar=[], eigenvalues=[], matrix=[])
+        for p in range(self.P):
+            O = self.N_k[p] * Gs[p]
+            eigenvals = np.sort(np.linalg.eigvals(O))[::-1]
+            out["scalar"].append(1 - eigenvals[1])
+            out["eigenvalues"].append(eigenvals)
+            out["matrix"].append(O)
+        return out
+
+    def compute_expectations(self, A_n_list, u_kn_list=None, output="averages", state_dependent=False, compute_uncertainty=True,
+                             uncertainty_method=None, warning_cutoff=1.0e-10):
+        """``mu`` and ``sigma`` of ``MBAR.compute_expectations`` per problem: ``A_n_list[p]`` is (N_p,), or (K_p, N_p) with
+        ``state_dependent`` (one observable per state); ``u_kn_list[p]`` optional new states (L_p, N_p)."""
+        from . import expectations as ex
+
+        _check_method("MBARBatch", uncertainty_method)
+        if output not in ("averages", "differences"):
+            raise ParameterError(f"MBARBatch: output must be 'averages' or 'differences', it was {output!r}")
+        self._check_list("A_n_list", A_n_list)
+        u_ln = self._check_new_states(u_kn_list)
+        A, maps = [], []
+        for p in range(self.P):
+            Kout = int(self.K[p]) if u_ln[p] is None else u_ln[p].shape[0]
+            a = np.asarray(A_n_list[p], dtype=np.float64)
+            want = (Kout, int(self.N[p])) if state_dependent else (int(self.N[p]),)
+            if a.shape != want:
+                raise ParameterError(f"problem {p}: the observable must have shape {want}, it has {a.shape}")
+            if not np.all(np.isfinite(a)):
+                raise ParameterError(f"problem {p}: the observable is not finite")
+            A.append(np.atleast_2d(a))
+            sm = np.zeros([2, Kout], int)
+            sm[0, :] = np.arange(Kout)
+            if state_dependent:
+                sm[1, :] = np.arange(Kout)
+            maps.append(sm)
+        inner = self.compute_expectations_inner(A, u_ln, maps, uncertainty_method=uncertainty_method, warning_cutoff=warning_cutoff,
+                                                return_theta=compute_uncertainty)
+        out = dict(mu=[])
+        if compute_uncertainty:
+            out["sigma"] = []
+        for p in range(self.P):
+            Kout = maps[p].shape[1]
+            cov = ex._difference_covariance(inner[p], Kout)[1] if compute_uncertainty else None
+            r = ex._expectations_result(self, inner[p], None, cov, Kout, output, compute_uncertainty, uncertainty_method,
+                                        warning_cutoff)
+            for key in out:
+                out[key].append(r[key])
+        return out
+
+    def compute_perturbed_free_energies(self, u_ln_list, compute_uncertainty=True, uncertainty_method=None, warning_cutoff=1.0e-10):
+        """``Delta_f`` and ``dDelta_f`` among the new states ``u_ln_list[p]`` (L_p, N_p) per problem."""
+        from . import expectations as ex
+
+        _check_method("MBARBatch", uncertainty_method)
+        u_ln = self._check_new_states(u_ln_list, required=True)
+        maps = [np.arange(u.shape[0]) for u in u_ln]
+        inner = self.compute_expectations_inner([None] * self.P, u_ln, maps, uncertainty_method=uncertainty_method,
+                                                warning_cutoff=warning_cutoff, return_theta=compute_uncertainty)
+        out = dict(Delta_f=[])
+        if compute_uncertainty:
+            out["dDelta_f"] = []
+        for p in range(self.P):
+            r = ex._perturbed_result(self, inner[p], compute_uncertainty, uncertainty_method, warning_cutoff)
+            for key in out:
+                out[key].append(r[key])
+        return out
+
+    def compute_entropy_and_enthalpy(self, uncertainty_method=None, warning_cutoff=1.0e-10):
+        """``Delta_f``, ``Delta_u``, ``Delta_s`` and their uncertainties per problem (``MBAR.compute_entropy_and_enthalpy``)."""
+        from . import expectations as ex
+
+        _check_method("MBARBatch", uncertainty_method)
+        self._handle()
+        for p in np.where(~self.host_fallback)[0]:   # (the potentials are the observables; a problem that fell back is MBAR's)
+            if not np.all(np.isfinite(self._blocks[p])):
+                raise ParameterError(f"problem {p}: the potentials hold +inf: no entropy / enthalpy decomposition")
+        maps = [np.vstack([np.arange(K), np.arange(K)]) for K in self.K]
+        inner = self.compute_expectations_inner(self._blocks, [None] * self.P, maps, uncertainty_method=uncertainty_method,
+                                                warning_cutoff=warning_cutoff, return_theta=True)
+        keys = ("Delta_f", "dDelta_f", "Delta_u", "dDelta_u", "Delta_s", "dDelta_s")
+        out = {key: [] for key in keys}
+        for p in range(self.P):
+            r = ex._entropy_and_enthalpy_result(self, inner[p], int(self.K[p]), uncertainty_method, warning_cutoff)
+            for key in keys:
+                out[key].append(r[key])
+        return out
+
+    # ---- input rules ----
+    def _check_list(self, name, lst):
+        if len(lst) != self.P:
+            raise ParameterError(f"MBARBatch: {self.P} problems but {len(lst)} entries in {name}")
+
+    def _check_new_states(self, u_list, required=False):
+        """Per problem the new states as a contiguous (L_p, N_p) array, or None for the resident states."""
+        if u_list is None:
+            if required:
+                raise ParameterError("MBARBatch: the new states are missing")
+            return [None] * self.P
+        self._check_list("the list of new states", u_list)
+        out = []
+        for p in range(self.P):
+            u = np.ascontiguousarray(u_list[p], dtype=np.float64)
+            if u.ndim == 1:
+                u = u.reshape(1, -1)
+            if u.ndim != 2 or u.shape[0] < 1:
+                raise ParameterError(f"problem {p}: the new states must be an L x N array")
+            if u.shape[1] < self.N[p]:
+                raise ParameterError(f"problem {p}: the new states have {u.shape[1]} columns, fewer than the {int(self.N[p])} samples: "
+                                     "evaluate the new potentials at all of the samples used originally")
+            if u.shape[1] != self.N[p]:
+                raise ParameterError(f"problem {p}: the new states must have shape (L, {int(self.N[p])}), they have {u.shape}")
+            if np.any(np.isnan(u)) or np.any(u == -np.inf):
+                raise ParameterError(f"problem {p}: the new states hold NaN or -inf")
+            out.append(u)
+        return out
+
+    # ---- the one pass underneath ----
+    # ---- the one pass underneath ----
+    def compute_expectations_inner(self, A_list, u_ln_list, state_maps, uncertainty_method=None, warning_cutoff=1.0e-10,
+                                   return_theta=False):
+        """``expectations.compute_expectations_inner`` of every problem: ``A_list[p]`` the observables (n_obs, N_p) (None: no
+        observables), ``u_ln_list[p]`` the states (L_p, N_p) (None: the resident states), ``state_maps[p]`` as there.  Returns
+        per problem the dict of ``observables``, ``f``, ``Theta``, ``Amin``.
+
+        The augmented matrix of problem p is its resident block plus extension rows, built as ``_augmented_matrix`` builds them:
+        resident states are not duplicated (their copies of the reference's layout are columns scaled by exp(f_l - f_k[l]): the
+        ``dedup`` algebra), new states are rows with N = 0, observable s is the row u_{l(s),n} - log(A_sn - shift_s) with the shift
+        of ``rows_logshift`` taken on the host.  A problem that needs no rows at all (resident states, no observables) is answered
+        from the kept covariance pass at ``f_k``.  ``self.timing`` holds the wall-clock split (s) of the last call: the rows built on
+        the host, upload and device passes, covariances and results."""
+        method = _check_method("MBARBatch", uncertainty_method)
+        h = self._handle()
+        plans = self._plan_inner(A_list, u_ln_list, state_maps)   # (every input rule, before any device work)
+        device = ~self.host_fallback
+        t0 = time.perf_counter()
+        rows = [_extension_rows(pl) if device[p] and pl["R"] > 0 else None for p, pl in enumerate(plans)]
+        t1 = time.perf_counter()
+        R = np.array([0 if r is None else r.shape[0] for r in rows], dtype=np.int64)
+        mask = R > 0
+        # the kept pass at f_k: the normalisers of resident states, and the Gram matrix of a problem without rows
+        kept = any(device[p] and (pl["resident"] or (return_theta and pl["R"] == 0)) for p, pl in enumerate(plans))
+        Gs, Ws = self._gram_w() if kept else (None, None)
+        lognum_ext, gram, wsum = np.zeros(0), None, None
+        if mask.any():
+            h.set_ext(rows)
+            try:
+                lognum_ext = h.ext_lognum(self._F, mask)
+                if return_theta:
+                    if not np.all(np.isfinite(lognum_ext[np.repeat(mask, R)])):
+                        roff = np.concatenate(([0], np.cumsum(R)))
+                        bad = [p for p in np.where(mask)[0] if not np.all(np.isfinite(lognum_ext[roff[p]:roff[p + 1]]))]
+                        raise ParameterError(f"problem {bad[0]}: a new state or an observable has no weight on any sample")
+                    gram, wsum = h.ext_gram(self._F, -lognum_ext, mask, EXT_GRAM_GROUP_BYTES)
+            finally:
+                h.set_ext(None)
+        t2 = time.perf_counter()
+        roff = np.concatenate(([0], np.cumsum(R)))
+        Aug = self.K + R
+        goff = np.concatenate(([0], np.cumsum(Aug * Aug)))
+        woff = np.concatenate(([0], np.cumsum(Aug)))
+        sel = np.where(device)[0]
+        thetas = {}
+        if return_theta:
+            Gaug, Naug = [], []
+            for p in sel:
+                if mask[p]:
+                    a = int(Aug[p])
+                    try:
+                        check_w_sums(wsum[woff[p]:woff[p + 1]], 0.0)
+                    except ParameterError as exc:
+                        raise ParameterError(f"problem {p}: {exc}") from exc
+                    Gaug.append(gram[goff[p]:goff[p + 1]].reshape(a, a))
+                else:
+                    Gaug.append(Gs[p])
+                Naug.append(np.concatenate((self.N_k[p], np.zeros(int(R[p]), dtype=np.int64))))
+            thetas = {sel[i]: t for idx, stack in _theta_stacks(Gaug, Naug, method) for i, t in zip(idx, stack)}
+        out = [None] * self.P
+        for p in sel:
+            ln_resident = None
+            if plans[p]["resident"]:
+                with np.errstate(divide="ignore"):
+                    ln_resident = np.log(Ws[p]) - self.f_k[p]   # (from sum_n W_nk = exp(f_k + lognum_k))
+            out[p] = _assemble_inner(plans[p], int(self.K[p]), self.f_k[p], ln_resident, lognum_ext[roff[p]:roff[p + 1]],
+                                     thetas.get(p))
+        for p in np.where(self.host_fallback)[0]:
+            pl, m = plans[p], self._mbar(p)
+            A = np.array([0]) if pl["A"] is None else (m.u_kn if pl["A"] is self._blocks[p] else pl["A"])
+            out[p] = m.compute_expectations_inner(A, m.u_kn if pl["resident"] else pl["u_ln"], state_maps[p],
+                                                  uncertainty_method=uncertainty_method, warning_cutoff=warning_cutoff,
+                                                  return_theta=return_theta)
+        self.timing = dict(rows=t1 - t0, device=t2 - t1, covariance=time.perf_counter() - t2)
+        return out
+
+    def _plan_inner(self, A_list, u_ln_list, state_maps):
+        """Per problem what ``compute_expectations_inner`` is asked for, checked: the states and observables of the state map, the
+        distinct states ``L_list``, the extension rows ``R`` it takes (the observables at resident states; the distinct new
+        states and the observables otherwise)."""
+        self._check_list("A_list", A_list)
+        self._check_list("u_ln_list", u_ln_list)
+        self._check_list("state_maps", state_maps)
+        plans = []
+        for p in range(self.P):
+            K, N = int(self.K[p]), int(self.N[p])
+            sm = np.asarray(state_maps[p])
+            if sm.ndim < 2:
+                state_list, obs_list = np.array(sm, dtype=int), np.zeros(0, dtype=int)
+            else:
+                state_list, obs_list = np.array(sm[0, :], dtype=int), np.array(sm[1, :], dtype=int)
+            resident = u_ln_list[p] is None
+            u_ln = self._blocks[p] if resident else u_ln_list[p]
+            A = A_list[p]
+            S = len(obs_list)
+            if u_ln.ndim != 2 or u_ln.shape[1] != N or (S > 0 and (A is None or A.ndim != 2 or A.shape[1] != N)):
+                raise ParameterError(f"problem {p}: states and observables must be arrays of {N} columns")
+            if np.any(state_list < 0) or np.any(state_list >= u_ln.shape[0]) or (
+                    S > 0 and (np.any(obs_list < 0) or np.any(obs_list >= A.shape[0]))):
+                raise ParameterError(f"problem {p}: the state map names a state or an observable that is not there")
+            if not self.host_fallback[p]:   # (a problem that fell back is MBAR's, with MBAR's answer to such input)
+                for i in np.unique(obs_list):
+                    if not np.all(np.isfinite(A[i])):
+                        raise ParameterError(f"problem {p}: observable {int(i)} is not finite")
+            L_list = np.unique(state_list)
+            NL = len(L_list)
+            R = S if resident else NL + S
+            if K + R > MAX_AUG:
+                raise ParameterError(f"problem {p}: K + extra rows = {K + R} > {MAX_AUG}: use MBAR")
+            plans.append(dict(state_list=state_list, obs_list=obs_list, L_list=L_list, NL=NL, S=S, R=R, resident=resident, u_ln=u_ln,
+                              A=A))
+        return plans
+
+
+def _extension_rows(pl):
+    """The extension rows of one planned problem, and its observables' shifts (``pl["shift"]``): the distinct new states (none
+    where the states are resident), then per observable s the row u_{l(s),n} - log(A_sn - shift), shift = amin - |4 eps amin|."""
+    A, u_ln, S = pl["A"], pl["u_ln"], pl["S"]
+    eps4 = 4.0 * np.finfo(np.float64).eps
+    shift = np.zeros(len(A) if S > 0 else 0, dtype=np.float64)
+    logA = {}
+    for i in np.unique(pl["obs_list"]):
+        amin = A[i].min()
+        shift[i] = amin - np.abs(eps4 * amin)
+        with np.errstate(divide="ignore"):
+            logA[int(i)] = np.log(A[i] - shift[i])
+    block = np.empty((pl["R"], u_ln.shape[1]), dtype=np.float64)
+    r0 = 0
+    if not pl["resident"]:
+        block[:pl["NL"]] = u_ln[pl["L_list"]]
+        r0 = pl["NL"]
+    for s in range(S):
+        block[r0 + s] = u_ln[pl["state_list"][s]] - logA[int(pl["obs_list"][s])]
+    pl["shift"] = shift
+    return block
+
+
+def _assemble_inner(pl, K, f_k, ln_resident, ln_ext, theta):
+    """The result dict of one planned problem from the normalisers of its rows ``ln_ext``, those of the resident rows as states
+    ``ln_resident`` (where its states are resident) and Theta of its K + R distinct columns (None: not asked for)."""
+    S, NL, L_list, state_list, obs_list = pl["S"], pl["NL"], pl["L_list"], pl["state_list"], pl["obs_list"]
+    if pl["resident"]:
+        ln_state, obs0 = ln_resident, 0
+    else:
+        ln_state = np.full(pl["u_ln"].shape[0], np.nan)
+        ln_state[L_list] = ln_ext[:NL]
+        obs0 = NL
+    res = dict()
+    if S > 0:
+        res["observables"] = np.exp(ln_ext[obs0:obs0 + S] - ln_state[state_list[:S]]) + pl["shift"][obs_list]
+    res["f"] = -ln_state[state_list]
+    if theta is not None:
+        if pl["resident"]:
+            # (the layout [K | NL state copies | S observables] from the K + S distinct columns: copy l is column l scaled by
+            # c_l = exp(f_l - f_k[l]), and Theta is bilinear in the columns)
+            src = np.concatenate((np.arange(K), L_list, K + np.arange(S))).astype(int)
+            scale = np.concatenate((np.ones(K), np.exp(-ln_state[L_list] - f_k[L_list]), np.ones(S)))
+            theta = (scale[:, None] * theta[np.ix_(src, src)]) * scale[None, :]
+        col_of_state = {int(l): j for j, l in enumerate(L_list)}
+        si = K + NL + np.arange(S)
+        li = K + np.array([col_of_state[int(l)] for l in state_list], dtype=int)
+        idx = np.concatenate((si, li)).astype(int)
+        res["Theta"] = theta[np.ix_(idx, idx)]
+        if S > 0:
+            res["Amin"] = pl["shift"][obs_list]
+    return res

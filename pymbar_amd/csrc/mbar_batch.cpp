@@ -1,8 +1,9 @@
 // Host side of mbar_batch (include/mbar_hip.h, "many small MBAR problems in one call"): the handle (on the handle layer of
 // mbar_ctx.h), which keeps P problems' reduced potentials resident on a device, cut into chunks, and drives their adaptive loops.
 // Replica slots (bootstrap replicates: solves that share a problem's block and weigh its samples by draw counts) are a second
-// set of chunks, records and states over the same blocks.  Kernels: mbar_k_batch.hip; the loop's state machine: batch_advance in
-// mbar_internal.h.
+// set of chunks, records and states over the same blocks.  Extension rows (the expectation family: new states and observables as
+// states with no samples) lie next to the blocks, with the two passes over them.  Kernels: mbar_k_batch.hip; the loop's state
+// machine: batch_advance in mbar_internal.h.
 #include <cmath>
 
 #include "mbar_ctx.h"
@@ -50,12 +51,24 @@ struct BatchReplicas : BatchSet {
     DevBuf<int64_t> cum, dK;                   // per problem: the bounds of the states' runs (MBAR_BATCH_MAX_K + 1 each) and K
 };
 
+// Extension rows of the problems (the expectation family): the rows, the chunk records of their sums, the arguments of a pass and
+// the packed outputs of the augmented Gram pass
+struct BatchExtRows {
+    int64_t nrows = 0, ngram = 0, nwsum = 0;   // sum of R, of (K + R)^2, of K + R
+    std::vector<int64_t> R, roff_h, ogoff_h, owoff_h;
+    DevBuf<double> e, lpart, f, Nk, fext, olognum, gpart, ogram, owsum;
+    DevBuf<int64_t> eoff, dK, dR, roff, lcoff, ogoff, owoff, wgoff, gbase;
+    DevBuf<int32_t> mask;
+    DevBuf<int> wprob, wrun, gprob, nrun;
+};
+
 struct mbar_batch : Handle {
     std::vector<int64_t> uoff_h;
     size_t need = 0;                           // device bytes of the problems themselves
     DevBuf<double> u;                          // the problems' blocks, concatenated
     BatchSet prob;
     std::unique_ptr<BatchReplicas> rep;
+    std::unique_ptr<BatchExtRows> ext;
 };
 
 namespace {
@@ -372,6 +385,251 @@ int mbar_batch_replicas_gram_w(mbar_batch* h, const double* f, const int32_t* ma
     if (!h->rep) return bad_arg("mbar_batch_replicas_gram_w: no replica slots (mbar_batch_set_replicas first)");
     if (!f || !mask || !gram || !wsum) return bad_arg("f / mask / gram / wsum is NULL");
     return gram_w_set(h, *h->rep, "slot", f, mask, gram, wsum);
+}
+
+int mbar_batch_set_ext(mbar_batch* h, const int64_t* R, const double* const* e) {
+    if (!h) return bad_arg("batch is NULL");
+    HIPCHK(nullptr, hipSetDevice(h->device));
+    HIPCHK(nullptr, hipStreamSynchronize(h->stream));
+    if (!R) {
+        h->ext.reset();
+        return MBAR_OK;
+    }
+    const BatchSet& s = h->prob;
+    const int64_t P = s.count;
+    auto x = std::make_unique<BatchExtRows>();
+    x->R.assign((size_t)P, 0);
+    x->roff_h.resize((size_t)P);
+    x->ogoff_h.resize((size_t)P);
+    x->owoff_h.resize((size_t)P);
+    std::vector<int64_t> eoff((size_t)P), lcoff((size_t)s.nchunks);
+    int64_t total = 0, lrec = 0;
+    for (int64_t p = 0; p < P; ++p) {
+        const int64_t r = R[p];
+        if (r < 0 || s.K[p] + r > MBAR_BATCH_MAX_AUG)
+            return bad_arg("problem " + std::to_string(p) + ": K + extension rows = " + std::to_string(s.K[p] + r) + " is outside " +
+                           std::to_string(s.K[p]) + " .. " + std::to_string(MBAR_BATCH_MAX_AUG));
+        if (r > 0) {
+            if (!e || !e[p]) return bad_arg("problem " + std::to_string(p) + ": extension rows are NULL");
+            const double* v = e[p];
+            for (int64_t i = 0; i < r * s.N[p]; ++i)
+                if (std::isnan(v[i]) || v[i] == -INFINITY)
+                    return bad_arg("problem " + std::to_string(p) + ": extension rows hold NaN or -inf");
+        }
+        x->R[p] = r;
+        x->roff_h[p] = x->nrows;
+        x->nrows += r;
+        x->ogoff_h[p] = x->ngram;
+        x->ngram += (s.K[p] + r) * (s.K[p] + r);
+        x->owoff_h[p] = x->nwsum;
+        x->nwsum += s.K[p] + r;
+        eoff[p] = total;
+        total += r * s.N[p];
+        for (int64_t c = s.cbeg_h[p]; c < s.cbeg_h[p + 1]; ++c) {
+            lcoff[c] = lrec;
+            lrec += 2 * r;
+        }
+    }
+    size_t free_b = 0, total_b = 0;
+    const size_t need = ((size_t)total + (size_t)lrec + 2 * (size_t)x->nrows + (size_t)(x->ngram + x->nwsum) +
+                         2 * (size_t)P * MBAR_BATCH_MAX_K) * sizeof(double) + (size_t)P * 64 + (size_t)s.nchunks * 8;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + h->need > total_b)
+        return fail(nullptr, MBAR_ERR_ARG, "the extension rows need " + std::to_string(need >> 20) + " MB of device memory for " +
+                    std::to_string(x->nrows) + " rows, their chunk records and outputs on top of the batch's " +
+                    std::to_string(h->need >> 20) + " MB; the device has " + std::to_string(total_b >> 20) + " MB");
+    (void)hipGetLastError();
+    h->ext.reset();  // (the new rows passed every check: only now do the earlier ones go)
+    HIPCHK(nullptr, x->e.grow((size_t)std::max<int64_t>(total, 1)));  // (a batch may have no rows at all: the passes still run)
+    for (int64_t p = 0; p < P; ++p)
+        if (x->R[p] > 0)
+            HIPCHK(nullptr, hipMemcpy(x->e + eoff[p], e[p], (size_t)(x->R[p] * s.N[p]) * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(nullptr, x->eoff.upload(eoff.data(), (size_t)P));
+    HIPCHK(nullptr, x->dK.upload(s.K.data(), (size_t)P));
+    HIPCHK(nullptr, x->dR.upload(x->R.data(), (size_t)P));
+    HIPCHK(nullptr, x->roff.upload(x->roff_h.data(), (size_t)P));
+    HIPCHK(nullptr, x->lcoff.upload(lcoff.data(), lcoff.size()));
+    HIPCHK(nullptr, x->ogoff.upload(x->ogoff_h.data(), (size_t)P));
+    HIPCHK(nullptr, x->owoff.upload(x->owoff_h.data(), (size_t)P));
+    HIPCHK(nullptr, x->lpart.grow((size_t)std::max<int64_t>(lrec, 1)));
+    HIPCHK(nullptr, x->f.grow((size_t)P * MBAR_BATCH_MAX_K));
+    HIPCHK(nullptr, x->Nk.grow((size_t)P * MBAR_BATCH_MAX_K));
+    HIPCHK(nullptr, x->fext.grow((size_t)std::max<int64_t>(x->nrows, 1)));
+    HIPCHK(nullptr, x->olognum.grow((size_t)std::max<int64_t>(x->nrows, 1)));
+    HIPCHK(nullptr, x->mask.grow((size_t)P));
+    h->ext = std::move(x);
+    return MBAR_OK;
+}
+
+namespace {
+
+// The arguments of a pass over the extension rows on the device: f, the problems' N_k as the last solve left them in their
+// states, and the mask
+int ext_arguments(mbar_batch* h, const double* f, const int32_t* mask, BatchExt* out) {
+    BatchSet& s = h->prob;
+    BatchExtRows& x = *h->ext;
+    const int64_t P = s.count;
+    std::vector<mbar_batch_state> st((size_t)P);
+    HIPCHK(nullptr, hipSetDevice(h->device));
+    HIPCHK(nullptr, hipMemcpyAsync(st.data(), s.states, st.size() * sizeof(mbar_batch_state), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(nullptr, hipStreamSynchronize(h->stream));
+    std::vector<double> fv((size_t)P * MBAR_BATCH_MAX_K, 0.0), nk((size_t)P * MBAR_BATCH_MAX_K, 0.0);
+    for (int64_t p = 0; p < P; ++p) {
+        if (!mask[p]) continue;
+        double n = 0.0;
+        for (int64_t k = 0; k < s.K[p]; ++k) {
+            const double v = f[p * MBAR_BATCH_MAX_K + k];
+            if (!std::isfinite(v)) return bad_arg("problem " + std::to_string(p) + ": f is not finite");
+            fv[(size_t)(p * MBAR_BATCH_MAX_K + k)] = v;
+            nk[(size_t)(p * MBAR_BATCH_MAX_K + k)] = st[(size_t)p].Nk[k];
+            n += st[(size_t)p].Nk[k];
+        }
+        if (st[(size_t)p].K != s.K[p] || n != (double)s.N[p])
+            return bad_arg("problem " + std::to_string(p) + ": its state holds no N_k (mbar_batch_solve first)");
+    }
+    HIPCHK(nullptr, hipMemcpyAsync(x.f, fv.data(), fv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(nullptr, hipMemcpyAsync(x.Nk, nk.data(), nk.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(nullptr, hipMemcpyAsync(x.mask, mask, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(nullptr, hipStreamSynchronize(h->stream));  // (the host vectors go)
+    BatchExt d{};
+    d.e = x.e;
+    d.eoff = x.eoff;
+    d.K = x.dK;
+    d.R = x.dR;
+    d.roff = x.roff;
+    d.lcoff = x.lcoff;
+    d.lpart = x.lpart;
+    d.f = x.f;
+    d.Nk = x.Nk;
+    d.fext = x.fext;
+    d.mask = x.mask;
+    *out = d;
+    return MBAR_OK;
+}
+
+constexpr int NEXT = 4;
+constexpr int EXT_AB[NEXT] = {16, 32, 64, 128};
+
+}  // namespace
+
+int mbar_batch_ext_lognum(mbar_batch* h, const double* f, const int32_t* mask, double* lognum_ext) {
+    if (!h) return bad_arg("batch is NULL");
+    if (!f || !mask || !lognum_ext) return bad_arg("f / mask / lognum_ext is NULL");
+    if (!h->ext) return bad_arg("mbar_batch_ext_lognum: no extension rows (mbar_batch_set_ext first)");
+    BatchExtRows& x = *h->ext;
+    if (x.nrows == 0) return MBAR_OK;
+    BatchExt d;
+    int rc = ext_arguments(h, f, mask, &d);
+    if (rc) return rc;
+    HIPCHK(nullptr, launch_batch_ext_lognum(h->stream, data(h->prob, h->u), d, x.olognum));
+    std::vector<double> out((size_t)x.nrows);
+    HIPCHK(nullptr, hipMemcpyAsync(out.data(), x.olognum, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(nullptr, hipStreamSynchronize(h->stream));
+    for (int64_t p = 0; p < h->prob.count; ++p)
+        if (mask[p]) std::copy(out.begin() + x.roff_h[p], out.begin() + x.roff_h[p] + x.R[p], lognum_ext + x.roff_h[p]);
+    return MBAR_OK;
+}
+
+int mbar_batch_ext_gram(mbar_batch* h, const double* f, const double* f_ext, const int32_t* mask, int64_t group_bytes, double* gram,
+                        double* wsum) {
+    if (!h) return bad_arg("batch is NULL");
+    if (!f || !mask || !gram || !wsum) return bad_arg("f / mask / gram / wsum is NULL");
+    if (!h->ext) return bad_arg("mbar_batch_ext_gram: no extension rows (mbar_batch_set_ext first)");
+    BatchSet& s = h->prob;
+    BatchExtRows& x = *h->ext;
+    if (!f_ext && x.nrows > 0) return bad_arg("f_ext is NULL");
+    const int64_t P = s.count;
+    // work items: run after run of every masked-in problem, in groups of problems whose records take at most group_bytes
+    struct Group {
+        size_t w0[NEXT + 1];  // its items of each width class in the class's list
+        size_t q0, q1;        // its problems in gprob
+    };
+    std::vector<int> wprob[NEXT], wrun[NEXT], gprob, nrun;
+    std::vector<int64_t> wgoff[NEXT], gbase;
+    std::vector<Group> groups;
+    int64_t used = 0, most = 0;
+    for (int64_t p = 0; p < P; ++p) {
+        if (!mask[p]) continue;
+        for (int64_t r = 0; r < x.R[p]; ++r)
+            if (!std::isfinite(f_ext[x.roff_h[p] + r]))
+                return bad_arg("problem " + std::to_string(p) + ": f_ext of row " + std::to_string(r) + " is not finite");
+        const int64_t A = s.K[p] + x.R[p], sz = A * A + A;
+        const int64_t chunks = s.cbeg_h[p + 1] - s.cbeg_h[p];
+        const int64_t runs = (chunks + MBAR_BATCH_EXT_RUN - 1) / MBAR_BATCH_EXT_RUN;
+        if (groups.empty() || (group_bytes > 0 && used > 0 && (used + runs * sz) * (int64_t)sizeof(double) > group_bytes)) {
+            Group g{};
+            for (int i = 0; i < NEXT; ++i) g.w0[i] = wprob[i].size();
+            g.q0 = g.q1 = gprob.size();
+            groups.push_back(g);
+            used = 0;
+        }
+        int cls = 0;
+        while (EXT_AB[cls] < A) ++cls;
+        gprob.push_back((int)p);
+        gbase.push_back(used);
+        nrun.push_back((int)runs);
+        for (int64_t r = 0; r < runs; ++r) {
+            wprob[cls].push_back((int)p);
+            wrun[cls].push_back((int)r);
+            wgoff[cls].push_back(used + r * sz);
+        }
+        used += runs * sz;
+        most = std::max(most, used);
+        groups.back().q1 = gprob.size();
+    }
+    if (groups.empty()) return MBAR_OK;
+    BatchExt d;
+    int rc = ext_arguments(h, f, mask, &d);
+    if (rc) return rc;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)most * sizeof(double) > total_b)
+        return fail(nullptr, MBAR_ERR_ARG, "the Gram records of one group need " + std::to_string(((size_t)most * sizeof(double)) >> 20) +
+                    " MB of device memory; the device has " + std::to_string(total_b >> 20) + " MB");
+    (void)hipGetLastError();
+    if (x.nrows > 0)
+        HIPCHK(nullptr, hipMemcpyAsync(x.fext, f_ext, (size_t)x.nrows * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(nullptr, hipStreamSynchronize(h->stream));
+    // one list per table, the classes one after the other
+    std::vector<int> wp, wr;
+    std::vector<int64_t> wg;
+    size_t cbase[NEXT];
+    for (int i = 0; i < NEXT; ++i) {
+        cbase[i] = wp.size();
+        wp.insert(wp.end(), wprob[i].begin(), wprob[i].end());
+        wr.insert(wr.end(), wrun[i].begin(), wrun[i].end());
+        wg.insert(wg.end(), wgoff[i].begin(), wgoff[i].end());
+    }
+    HIPCHK(nullptr, x.wprob.upload(wp.data(), wp.size()));
+    HIPCHK(nullptr, x.wrun.upload(wr.data(), wr.size()));
+    HIPCHK(nullptr, x.wgoff.upload(wg.data(), wg.size()));
+    HIPCHK(nullptr, x.gprob.upload(gprob.data(), gprob.size()));
+    HIPCHK(nullptr, x.gbase.upload(gbase.data(), gbase.size()));
+    HIPCHK(nullptr, x.nrun.upload(nrun.data(), nrun.size()));
+    HIPCHK(nullptr, x.gpart.grow((size_t)most));
+    HIPCHK(nullptr, x.ogram.grow((size_t)x.ngram));
+    HIPCHK(nullptr, x.owsum.grow((size_t)x.nwsum));
+    const BatchData bd = data(s, h->u);
+    for (size_t g = 0; g < groups.size(); ++g) {
+        const Group& gr = groups[g];
+        for (int i = 0; i < NEXT; ++i) {
+            const size_t w1 = g + 1 < groups.size() ? groups[g + 1].w0[i] : wprob[i].size();
+            const size_t o = cbase[i] + gr.w0[i];
+            HIPCHK(nullptr, launch_batch_ext_gram(h->stream, EXT_AB[i], bd, d, (int64_t)(w1 - gr.w0[i]), x.wprob + o, x.wrun + o,
+                                                  x.wgoff + o, x.gpart));
+        }
+        HIPCHK(nullptr, launch_batch_ext_gram_merge(h->stream, d, (int64_t)(gr.q1 - gr.q0), x.gprob + gr.q0, x.gbase + gr.q0,
+                                                    x.nrun + gr.q0, x.gpart, x.ogram, x.owsum, x.ogoff, x.owoff));
+    }
+    std::vector<double> og((size_t)x.ngram), ow((size_t)x.nwsum);
+    HIPCHK(nullptr, hipMemcpyAsync(og.data(), x.ogram, og.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(nullptr, hipMemcpyAsync(ow.data(), x.owsum, ow.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(nullptr, hipStreamSynchronize(h->stream));
+    for (int64_t p = 0; p < P; ++p) {
+        if (!mask[p]) continue;
+        const int64_t A = s.K[p] + x.R[p];
+        std::copy(og.begin() + x.ogoff_h[p], og.begin() + x.ogoff_h[p] + A * A, gram + x.ogoff_h[p]);
+        std::copy(ow.begin() + x.owoff_h[p], ow.begin() + x.owoff_h[p] + A, wsum + x.owoff_h[p]);
+    }
+    return MBAR_OK;
 }
 
 int mbar_batch_step_host(mbar_batch_state* state, const double* lognum, const double* gram) {

@@ -823,4 +823,34 @@ hipError_t launch_batch_draw(hipStream_t st, const BatchData& d, int64_t chunk0,
 hipError_t launch_batch_step(hipStream_t st, const BatchData& d, mbar_batch_state* states, int* active, double* out_gram,
                              double* out_wsum, const int64_t* goff, const int64_t* woff);
 
+// Extension rows of the problems (mbar_batch_set_ext): problem p has R[p] rows of N[p] reduced potentials at e + eoff[p] (row-major,
+// ld N[p]); its per-row values (f_ext, lognum_ext) are packed at roff[p].  Chunk c's record of the rows' sums is at lpart + lcoff[c]:
+// [R] maxima, [R] scaled sums.  f and Nk: rows of MBAR_BATCH_MAX_K per problem; problems with mask[p] == 0 are skipped.
+struct BatchExt {
+    const double* e;
+    const int64_t* eoff;     // [P]
+    const int64_t* K;        // [P]
+    const int64_t* R;        // [P]
+    const int64_t* roff;     // [P]
+    const int64_t* lcoff;    // [nchunks]
+    double* lpart;
+    const double* f;         // [P][MBAR_BATCH_MAX_K]
+    const double* Nk;        // [P][MBAR_BATCH_MAX_K]
+    const double* fext;      // packed like lognum_ext (the Gram pass only)
+    const int32_t* mask;     // [P]
+};
+// The rows' sums: one workgroup per chunk of d, then one per problem that merges the chunk records in chunk order into
+// lognum_ext (device, packed)
+hipError_t launch_batch_ext_lognum(hipStream_t st, const BatchData& d, const BatchExt& x, double* lognum_ext);
+// The augmented Gram pass over n work items of the width class ab (16, 32, 64, 128 >= K + R): item w is run wrun[w] of problem
+// wprob[w] -- the chunks wrun[w] * MBAR_BATCH_EXT_RUN .. of that problem -- and writes the record ((K + R)^2 Gram, K + R column
+// sums) at gpart + wgoff[w]
+hipError_t launch_batch_ext_gram(hipStream_t st, int ab, const BatchData& d, const BatchExt& x, int64_t n, const int* wprob,
+                                 const int* wrun, const int64_t* wgoff, double* gpart);
+// Merge of the records of the n problems gprob[0 .. n): problem gprob[q]'s nrun[q] records start at gpart + gbase[q]; the sums, in
+// run order, go to ogram + ogoff[p] and owsum + owoff[p]
+hipError_t launch_batch_ext_gram_merge(hipStream_t st, const BatchExt& x, int64_t n, const int* gprob, const int64_t* gbase,
+                                       const int* nrun, const double* gpart, double* ogram, double* owsum, const int64_t* ogoff,
+                                       const int64_t* owoff);
+
 }  // namespace mbar

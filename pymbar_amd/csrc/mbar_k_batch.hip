@@ -15,6 +15,11 @@
 //                  (batch_advance, mbar_internal.h) and, when it asks for one, factors the gauge-fixed Newton system in LDS
 //                  (LDL^T, one barrier pair per pivot).
 //   k_batch_draw   bootstrap draw counts of many replica slots in one launch (the counter-based stream of mbar_internal.h).
+//   k_batch_ext_*  the extension rows of the problems (new states and observables of the expectation family, MBARBatch): per row
+//                  the chunk maximum and scaled sum in log space (k_batch_ext_sums, merged by k_batch_ext_sums_merge), and the
+//                  augmented Gram matrix Q^T Q of up to 128 columns, Q = [W | the rows' weight columns] (k_batch_ext_gram: 32-sample
+//                  tiles in LDS, each thread a block of up to 8x8, one record per run of MBAR_BATCH_EXT_RUN chunks, merged in run
+//                  order by k_batch_ext_gram_merge).
 // Replica slots (bootstrap replicates, BatchData in mbar_internal.h) share their base problem's block and run the weighted
 // instantiation of k_batch_eval: sample n counts c_n >= 0 times.  Its log-denominator is unchanged; the chunk maximum of a state
 // is taken over the samples with c_n > 0 and its sum is sum_n c_n exp(. - maximum); the Gram operands are scaled by sqrt(c_n) when
@@ -326,6 +331,190 @@ __global__ void __launch_bounds__(BATCH_WG) k_batch_draw(BatchData d, int64_t ch
     if (pos >= 0 && pos < d.N[s]) atomicAdd(cw + d.cwoff[s] + pos, 1.0);
 }
 
+// ---- extension rows (mbar_batch_set_ext): the expectation family of a batch -------------------------------------------------
+// The augmented matrix of a problem has up to MBAR_BATCH_MAX_AUG = 128 columns, twice what a thread of k_batch_eval can keep in
+// registers, so these kernels hold nothing per sample but its log-denominator and read the rows where they use them.
+
+// sa[k] = f_k + log N_k of the sampled states, -inf otherwise (thread k < K; the caller synchronises)
+__device__ __forceinline__ void ext_load_sa(const BatchExt& x, int p, int K, double* sa) {
+    const int tid = threadIdx.x;
+    if (tid < K) {
+        const double nk = x.Nk[(int64_t)p * MBAR_BATCH_MAX_K + tid];
+        sa[tid] = nk > 0 ? x.f[(int64_t)p * MBAR_BATCH_MAX_K + tid] + log(nk) : -INFINITY;
+    }
+}
+
+// log sum_k N_k exp(f_k - u_kn) of the sample at `up` (its column, rows Np apart): the expression and the order of k_batch_eval
+__device__ __forceinline__ double ext_logden(const double* __restrict__ up, int64_t Np, int K, const double* sa) {
+    double m = -INFINITY;
+    for (int k = 0; k < K; ++k) m = fmax(m, sa[k] - up[(int64_t)k * Np]);
+    if (m == -INFINITY) return INFINITY;  // (no finite sampled entry: every term of this sample is exp(-inf) = 0)
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += exp((sa[k] - up[(int64_t)k * Np]) - m);
+    return m + log(s);
+}
+
+// Per extension row the chunk maximum of v_r = -logden_n - e_rn and the sum of exp(v_r - maximum): k_batch_eval's per-state sums,
+// 16 rows at a time through the same transposition tile.  One workgroup per chunk of the problems.
+__global__ void __launch_bounds__(BATCH_WG) k_batch_ext_sums(BatchData d, BatchExt x) {
+    __shared__ double buf[16 * TP];
+    __shared__ double sa[MBAR_BATCH_MAX_K];
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x;
+    const int p = d.cprob[c];
+    const int R = (int)x.R[p], K = (int)x.K[p];
+    if (!x.mask[p] || R == 0) return;  // (the whole workgroup)
+    ext_load_sa(x, p, K, sa);
+    __syncthreads();
+    const int64_t Np = d.N[p];
+    const int64_t n0 = d.cn0[c];
+    const int ncols = (int)(Np - n0 < MBAR_BATCH_CHUNK ? Np - n0 : MBAR_BATCH_CHUNK);
+    const bool valid = tid < ncols;
+    const double ld = valid ? ext_logden(d.u + d.uoff[p] + n0 + tid, Np, K, sa) : INFINITY;
+    const double* __restrict__ ep = x.e + x.eoff[p] + n0 + tid;
+    double* __restrict__ rec = x.lpart + x.lcoff[c];
+    const int kk = tid >> 4, q = tid & 15;
+    for (int g0 = 0; g0 < R; g0 += 16) {
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < 16; ++j) buf[j * TP + tid] = (valid && g0 + j < R) ? -ld - ep[(int64_t)(g0 + j) * Np] : -INFINITY;
+        __syncthreads();
+        double mx = -INFINITY;
+#pragma unroll 4
+        for (int i = 0; i < MBAR_BATCH_CHUNK / 16; ++i) mx = fmax(mx, buf[kk * TP + q + 16 * i]);
+        mx = row16_max(mx);
+        double sm = 0.0;
+        if (mx != -INFINITY)
+#pragma unroll 4
+            for (int i = 0; i < MBAR_BATCH_CHUNK / 16; ++i) sm += exp(buf[kk * TP + q + 16 * i] - mx);
+        sm = row16_sum(sm);
+        if (q == 0 && g0 + kk < R) {
+            rec[g0 + kk] = mx;
+            rec[R + g0 + kk] = sm;
+        }
+    }
+}
+
+// One workgroup per problem: the chunk records of its rows merged in chunk order, as k_batch_step merges the states'
+__global__ void __launch_bounds__(BATCH_WG) k_batch_ext_sums_merge(BatchData d, BatchExt x, double* __restrict__ out) {
+    const int p = blockIdx.x;
+    const int R = (int)x.R[p];
+    if (!x.mask[p]) return;
+    const int64_t cb = d.cbeg[p], ce = d.cbeg[p + 1];
+    for (int r = threadIdx.x; r < R; r += BATCH_WG) {
+        double M = -INFINITY;
+        for (int64_t c = cb; c < ce; ++c) M = fmax(M, x.lpart[x.lcoff[c] + r]);
+        double S = 0.0;
+        if (M != -INFINITY)
+            for (int64_t c = cb; c < ce; ++c) {
+                const double* rec = x.lpart + x.lcoff[c];
+                const double s = rec[R + r];
+                if (s != 0.0) S += s * exp(rec[r] - M);
+            }
+        out[x.roff[p] + r] = M == -INFINITY ? -INFINITY : M + log(S);
+    }
+}
+
+// Q^T Q and the column sums of Q over one run of MBAR_BATCH_EXT_RUN consecutive chunks of a problem, Q = [W | exp(f_ext_r - e_rn -
+// logden_n)], A = K + R <= AB columns.  Tiles of 32 samples x A columns are staged in LDS (33 KB at AB = 128); the 256 threads form
+// a 16 x 16 grid and thread (bi, bj) owns the (AB/16)^2 entries (bi + 16 a, bj + 16 b), so that a half-wave reads 16 consecutive
+// doubles of a tile row (no bank conflict) and 2 broadcast ones.  Entries (i, j) and (j, i) add the same products x_i x_j in the
+// same sample order: G is bit-symmetric.  The accumulators live in registers across the run, whose record is written once.
+template <int AB>
+__global__ void __launch_bounds__(BATCH_WG) k_batch_ext_gram(BatchData d, BatchExt x, const int* __restrict__ wprob,
+                                                             const int* __restrict__ wrun, const int64_t* __restrict__ wgoff,
+                                                             double* __restrict__ gpart) {
+    constexpr int BS = AB / 16;  // entries per thread and dimension
+    constexpr int TS = 32;       // samples per tile
+    constexpr int GP = AB + 1;   // pitch of a tile row
+    __shared__ double buf[TS * GP];
+    __shared__ double sa[MBAR_BATCH_MAX_K];
+    __shared__ double sg[AB];
+    __shared__ double sld[MBAR_BATCH_CHUNK];
+    const int tid = threadIdx.x;
+    const int p = wprob[blockIdx.x];
+    const int K = (int)x.K[p], R = (int)x.R[p], A = K + R;
+    ext_load_sa(x, p, K, sa);
+    if (tid < AB) sg[tid] = tid < K ? x.f[(int64_t)p * MBAR_BATCH_MAX_K + tid] : (tid < A ? x.fext[x.roff[p] + tid - K] : 0.0);
+    const int64_t Np = d.N[p];
+    const double* __restrict__ ub = d.u + d.uoff[p];
+    const double* __restrict__ eb = R > 0 ? x.e + x.eoff[p] : ub;
+    const int64_t c0 = d.cbeg[p] + (int64_t)wrun[blockIdx.x] * MBAR_BATCH_EXT_RUN;
+    const int64_t c1 = c0 + MBAR_BATCH_EXT_RUN < d.cbeg[p + 1] ? c0 + MBAR_BATCH_EXT_RUN : d.cbeg[p + 1];
+    const int bi = tid >> 4, bj = tid & 15;
+    const int sj = tid & (TS - 1), sc0 = tid / TS;  // staging: sample sj of the tile, columns sc0, sc0 + 8, ...
+    double acc[BS][BS];
+#pragma unroll
+    for (int a = 0; a < BS; ++a)
+#pragma unroll
+        for (int b = 0; b < BS; ++b) acc[a][b] = 0.0;
+    double cs = 0.0;  // column sum of column tid
+    __syncthreads();
+    for (int64_t c = c0; c < c1; ++c) {
+        const int64_t n0 = d.cn0[c];
+        const int ncols = (int)(Np - n0 < MBAR_BATCH_CHUNK ? Np - n0 : MBAR_BATCH_CHUNK);
+        // (the last reads of sld for the chunk before lie ahead of the barrier that precedes its last tile's products)
+        sld[tid] = tid < ncols ? ext_logden(ub + n0 + tid, Np, K, sa) : INFINITY;
+        for (int t0 = 0; t0 < ncols; t0 += TS) {
+            __syncthreads();
+            const bool in = t0 + sj < ncols;
+            const double ldn = sld[t0 + sj];
+            const int64_t n = n0 + t0 + sj;
+            for (int col = sc0; col < AB; col += BATCH_WG / TS) {
+                double v = 0.0;
+                if (in && col < A) {
+                    const double e = col < K ? ub[(int64_t)col * Np + n] : eb[(int64_t)(col - K) * Np + n];
+                    v = exp((sg[col] - e) - ldn);
+                }
+                buf[sj * GP + col] = v;
+            }
+            __syncthreads();
+            const int cols = ncols - t0 < TS ? ncols - t0 : TS;
+            for (int j = 0; j < cols; ++j) {
+                double xr[BS], yr[BS];
+#pragma unroll
+                for (int a = 0; a < BS; ++a) {
+                    xr[a] = buf[j * GP + bi + 16 * a];
+                    yr[a] = buf[j * GP + bj + 16 * a];
+                }
+#pragma unroll
+                for (int a = 0; a < BS; ++a)
+#pragma unroll
+                    for (int b = 0; b < BS; ++b) acc[a][b] += xr[a] * yr[b];
+            }
+            if (tid < A)
+                for (int j = 0; j < cols; ++j) cs += buf[j * GP + tid];
+        }
+    }
+    double* __restrict__ rec = gpart + wgoff[blockIdx.x];
+#pragma unroll
+    for (int a = 0; a < BS; ++a)
+#pragma unroll
+        for (int b = 0; b < BS; ++b) {
+            const int i = bi + 16 * a, j = bj + 16 * b;
+            if (i < A && j < A) rec[i * A + j] = acc[a][b];
+        }
+    if (tid < A) rec[A * A + tid] = cs;
+}
+
+// One workgroup per problem of the group: its runs' records summed in run order
+__global__ void __launch_bounds__(BATCH_WG) k_batch_ext_gram_merge(BatchExt x, const int* __restrict__ gprob,
+                                                                   const int64_t* __restrict__ gbase, const int* __restrict__ nrun,
+                                                                   const double* __restrict__ gpart, double* __restrict__ ogram,
+                                                                   double* __restrict__ owsum, const int64_t* __restrict__ ogoff,
+                                                                   const int64_t* __restrict__ owoff) {
+    const int p = gprob[blockIdx.x];
+    const int A = (int)(x.K[p] + x.R[p]);
+    const int sz = A * A + A, nr = nrun[blockIdx.x];
+    const double* __restrict__ rec = gpart + gbase[blockIdx.x];
+    for (int e = threadIdx.x; e < sz; e += BATCH_WG) {
+        double s = 0.0;
+        for (int r = 0; r < nr; ++r) s += rec[(int64_t)r * sz + e];
+        if (e < A * A) ogram[ogoff[p] + e] = s;
+        else owsum[owoff[p] + e - A * A] = s;
+    }
+}
+
 template <bool WT>
 hipError_t launch_eval(hipStream_t st, int kb, const BatchData& d, const int* list, int64_t n, const mbar_batch_state* states) {
     switch (kb) {
@@ -357,6 +546,35 @@ hipError_t launch_batch_step(hipStream_t st, const BatchData& d, mbar_batch_stat
                              double* out_wsum, const int64_t* goff, const int64_t* woff) {
     if (d.P == 0) return hipSuccess;
     hipLaunchKernelGGL(k_batch_step, dim3((unsigned)d.P), dim3(BATCH_WG), 0, st, d, states, active, out_gram, out_wsum, goff, woff);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_ext_lognum(hipStream_t st, const BatchData& d, const BatchExt& x, double* lognum_ext) {
+    if (d.P == 0 || d.nchunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_batch_ext_sums, dim3((unsigned)d.nchunks), dim3(BATCH_WG), 0, st, d, x);
+    hipLaunchKernelGGL(k_batch_ext_sums_merge, dim3((unsigned)d.P), dim3(BATCH_WG), 0, st, d, x, lognum_ext);
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_ext_gram(hipStream_t st, int ab, const BatchData& d, const BatchExt& x, int64_t n, const int* wprob,
+                                 const int* wrun, const int64_t* wgoff, double* gpart) {
+    if (n == 0) return hipSuccess;
+    switch (ab) {
+    case 16: hipLaunchKernelGGL(k_batch_ext_gram<16>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, x, wprob, wrun, wgoff, gpart); break;
+    case 32: hipLaunchKernelGGL(k_batch_ext_gram<32>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, x, wprob, wrun, wgoff, gpart); break;
+    case 64: hipLaunchKernelGGL(k_batch_ext_gram<64>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, x, wprob, wrun, wgoff, gpart); break;
+    case 128: hipLaunchKernelGGL(k_batch_ext_gram<128>, dim3((unsigned)n), dim3(BATCH_WG), 0, st, d, x, wprob, wrun, wgoff, gpart); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_batch_ext_gram_merge(hipStream_t st, const BatchExt& x, int64_t n, const int* gprob, const int64_t* gbase,
+                                       const int* nrun, const double* gpart, double* ogram, double* owsum, const int64_t* ogoff,
+                                       const int64_t* owoff) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_batch_ext_gram_merge, dim3((unsigned)n), dim3(BATCH_WG), 0, st, x, gprob, gbase, nrun, gpart, ogram, owsum,
+                       ogoff, owoff);
     return hipGetLastError();
 }
 

@@ -389,13 +389,21 @@ def compute_expectations(mbar, A_n, u_kn=None, output="averages", state_dependen
         state_map[1, :] = np.arange(K)
     inner = compute_expectations_inner(mbar, A_n, u_kn, state_map, return_theta=compute_uncertainty,
                                        uncertainty_method=uncertainty_method, warning_cutoff=warning_cutoff)
-    result_vals = dict()
     Theta = covA_ij = None
     if (compute_uncertainty and uncertainty_method != "bootstrap") or return_theta:
         if "Theta" not in inner:
             inner = compute_expectations_inner(mbar, A_n, u_kn, state_map, return_theta=True,
                                                uncertainty_method=uncertainty_method, warning_cutoff=warning_cutoff)
         Theta, covA_ij = _difference_covariance(inner, K)
+    return _expectations_result(mbar, inner, Theta, covA_ij, K, output, compute_uncertainty, uncertainty_method, warning_cutoff,
+                                return_theta)
+
+
+def _expectations_result(mbar, inner, Theta, covA_ij, K, output, compute_uncertainty, uncertainty_method, warning_cutoff,
+                         return_theta=False):
+    """``mu`` / ``sigma`` of ``compute_expectations`` from the inner result and its difference covariance (mbar.py:1283-1312);
+    ``mbar`` gives ``_ErrorOfDifferences``."""
+    result_vals = dict()
     if output == "averages":
         result_vals["mu"] = inner["observables"]
         if compute_uncertainty:
@@ -458,6 +466,11 @@ def compute_perturbed_free_energies(mbar, u_ln, compute_uncertainty=True, uncert
                         "of the samples used originally.")
     inner = compute_expectations_inner(mbar, np.array([0]), u_ln, np.arange(L), return_theta=compute_uncertainty,
                                        uncertainty_method=uncertainty_method, warning_cutoff=warning_cutoff)
+    return _perturbed_result(mbar, inner, compute_uncertainty, uncertainty_method, warning_cutoff)
+
+
+def _perturbed_result(mbar, inner, compute_uncertainty, uncertainty_method, warning_cutoff):
+    """``Delta_f`` / ``dDelta_f`` of ``compute_perturbed_free_energies`` from the inner result (mbar.py:1505-1521)."""
     f_k = inner["f"]
     result_vals = dict(Delta_f=f_k - np.vstack(f_k))
     if compute_uncertainty:
@@ -482,6 +495,11 @@ def compute_entropy_and_enthalpy(mbar, u_kn=None, uncertainty_method=None, verbo
     state_map = np.vstack([np.arange(K), np.arange(K)])
     inner = compute_expectations_inner(mbar, u_kn, u_kn, state_map, return_theta=True,  # (the observables are copied there)
                                        uncertainty_method=uncertainty_method, warning_cutoff=warning_cutoff)
+    return _entropy_and_enthalpy_result(mbar, inner, K, uncertainty_method, warning_cutoff)
+
+
+def _entropy_and_enthalpy_result(mbar, inner, K, uncertainty_method, warning_cutoff):
+    """The six ``Delta_*`` / ``dDelta_*`` entries of ``compute_entropy_and_enthalpy`` from the inner result (mbar.py:1600-1681)."""
     # covariance of (ln c_Ua, ln c_a, ln c_a again) -> u, f and s = u - f   (mbar.py:1600-1610)
     Theta = np.zeros([3 * K, 3 * K], dtype=np.float64)
     Theta[0 : 2 * K, 0 : 2 * K] = inner["Theta"]

@@ -97,6 +97,20 @@ def _sample_groups(x_kindices, K):
     return state_index_groups(x_kindices, K)
 
 
+def error_of_differences(cov, warning_cutoff=1.0e-10):
+    """``sqrt(cov_ii + cov_jj - 2 cov_ij)`` of a covariance matrix; small negative squares are zeroed (mbar.py:1687-1715).
+    ``MBAR._ErrorOfDifferences``, and ``MBARBatch``'s."""
+    diag = cov.diagonal()
+    d2 = diag + np.vstack(diag) - 2 * cov
+    cutoff = -abs(warning_cutoff)
+    if np.any(d2 < 0.0):
+        if np.any(d2 < cutoff):
+            logger.warning("A squared uncertainty is negative. Largest Magnitude = {0:f}".format(abs(np.min(d2[d2 < cutoff]))))
+        else:
+            d2[np.logical_and(0 > d2, d2 > cutoff)] = 0.0
+    return np.sqrt(np.array(d2))
+
+
 class MBAR:
     """Multistate Bennett acceptance ratio estimator; free energies are solved on construction.
 
@@ -426,15 +440,7 @@ class MBAR:
     # ---- private -----------------------------------------------------------------------------------
     def _ErrorOfDifferences(self, cov, warning_cutoff=1.0e-10):
         """``sqrt(cov_ii + cov_jj - 2 cov_ij)``; small negative squares are zeroed (mbar.py:1687-1715)."""
-        diag = cov.diagonal()
-        d2 = diag + np.vstack(diag) - 2 * cov
-        cutoff = -abs(warning_cutoff)
-        if np.any(d2 < 0.0):
-            if np.any(d2 < cutoff):
-                logger.warning("A squared uncertainty is negative. Largest Magnitude = {0:f}".format(abs(np.min(d2[d2 < cutoff]))))
-            else:
-                d2[np.logical_and(0 > d2, d2 > cutoff)] = 0.0
-        return np.sqrt(np.array(d2))
+        return error_of_differences(cov, warning_cutoff)
 
     @staticmethod
     def _pseudoinverse(A, tol=1.0e-10):
