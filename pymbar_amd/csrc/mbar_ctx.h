@@ -512,13 +512,15 @@ struct ColumnPasses {
 
 
 hipEvent_t get_event(mbar_ctx* c);
+// Event pair around the work enqueued in its scope (when the "timing" option is set, or when `enable` says so)
 struct ScopedTimer {
     mbar_ctx* c;
     TimerPair tp;
     bool on;
-    ScopedTimer(mbar_ctx* c_, int which) : c(c_), on(false) {
+    ScopedTimer(mbar_ctx* c_, int which) : ScopedTimer(c_, which, c_->opt_timing != 0) {}
+    ScopedTimer(mbar_ctx* c_, int which, bool enable) : c(c_), on(false) {
         tp.a = tp.b = nullptr;
-        if (!c->opt_timing) return;
+        if (!enable) return;
         tp.a = get_event(c);
         tp.b = get_event(c);
         tp.which = which;
@@ -531,6 +533,31 @@ struct ScopedTimer {
             (void)hipEventRecord(tp.b, c->stream);
             c->pending.push_back(tp);
         }
+    }
+};
+// Event pair for ONE sweep of the device-resident loop, made before its launch.  "timing" 2: the events ride on the kernel dispatch
+// itself, bound to it through `lc` (the LoopCtl the launch is about to get); otherwise event records around the launch(es) in scope.
+struct LaunchTimer {
+    mbar_ctx* c;
+    TimerPair tp;
+    bool armed, ext;
+    LaunchTimer(mbar_ctx* c_, int which, bool timed, LoopCtl& lc) : c(c_), tp{nullptr, nullptr, which} {
+        if (timed) {
+            tp.a = get_event(c);
+            tp.b = get_event(c);
+        }
+        armed = tp.a && tp.b;
+        ext = armed && c->opt_timing == 2;
+        if (ext) {
+            lc.ev_start = tp.a;
+            lc.ev_stop = tp.b;
+        } else if (armed) {
+            (void)hipEventRecord(tp.a, c->stream);
+        }
+    }
+    ~LaunchTimer() {
+        if (armed && !ext) (void)hipEventRecord(tp.b, c->stream);
+        if (armed) c->pending.push_back(tp);
     }
 };
 

@@ -880,6 +880,59 @@ def test_resident_probability_matrix_is_reused_across_solves(DM):
         assert rn["builds"] == 1 and rn["warm_starts"] == 0
 
 
+@pytest.mark.parametrize("K", [40, 144, 200])
+def test_every_start_form_of_the_device_loop(DM, K):
+    """The four ways the device-resident loop arrives at its first gradient and Gram matrix -- the classic evaluation sweep, the
+    build sweep of the two-sweep P mode, the build of the fused loop (one launch up to 128 states, evaluation + Gram sweep writing P
+    above), and the warm start on the kept probability matrix -- give the host-driven loop's free energies and iteration count,
+    unweighted and with per-sample multiplicities, at a shard length that is no multiple of the 16-sample tile and with a state
+    without samples.  (Above 128 states P mode exists in its fused form only: fused=0 runs the classic sweeps there.)"""
+    N = 3001 + K
+    u_kn, N_k, _ = random_problem(K, N, seed=500 + K, unsampled=(K // 3,))
+    sws = np.where(N_k > 0)[0]
+    tol = 1e-12 if K <= 128 else 1e-10  # (as in test_adaptive_loop_variants_agree)
+    rng = np.random.default_rng(K)
+    c_n = np.zeros(N)
+    start = 0
+    for n_k in N_k:
+        if n_k > 0:
+            c_n[start:start + n_k] = np.bincount(rng.integers(0, n_k, size=n_k), minlength=n_k)
+        start += n_k
+    with DM.from_host(u_kn) as dm, DM.from_host(u_kn) as host:
+        dm.set_option("pcache", 1)
+        host.set_option("pcache", 0)
+        host.set_option("device_loop", 0)
+        for d in (dm, host):
+            d.set_Nk(N_k)
+
+        def agree(tag, fs, builds, warm_starts, **opts):
+            for k, v in opts.items():
+                dm.set_option(k, v)
+            fa, ra = dm.solve_adaptive(fs, tol=tol, min_sc_iter=0)
+            fb, rb = host.solve_adaptive(fs, tol=tol, min_sc_iter=0)
+            assert rb["success"] and ra["success"] == rb["success"], tag
+            assert ra["iterations"] == rb["iterations"], (tag, ra["iterations"], rb["iterations"])
+            np.testing.assert_allclose(fa[sws], fb[sws], rtol=1e-11, atol=1e-11, err_msg=tag)
+            assert (ra["builds"], ra["warm_starts"]) == (builds, warm_starts), (tag, ra["builds"], ra["warm_starts"])
+            return fa
+
+        try:
+            for weights in (None, c_n):
+                tag = f"K={K} {'unweighted' if weights is None else 'weighted'}"
+                for d in (dm, host):
+                    d.set_sample_weights(weights)
+                agree(tag + " classic", np.zeros(K), 0, 0, pmode=0, fused=0)
+                agree(tag + " two-sweep P mode", np.zeros(K), 1 if K <= 128 else 0, 0, pmode=1, fused=0)
+                dm.upload_rows(3, u_kn[3])  # (an unchanged row: the matrix counts as changed, the kept P is dropped)
+                f1 = agree(tag + " fused build", np.zeros(K), 1, 0, pmode=1, fused=1)
+                f_start = f1 + 0.3 * np.cos(np.arange(K))
+                f_start[sws[0]] = 0.0
+                agree(tag + " warm start", f_start, 0, 1, pmode=1, fused=1)
+        finally:
+            for d in (dm, host):
+                d.set_sample_weights(None)
+
+
 @pytest.mark.parametrize("K,N,unsampled", [(5, 3000, ()), (48, 20000, (9,)), (128, 30000, ()), (200, 16000, (11,)), (300, 12000, ())])
 def test_solve_hands_back_the_per_state_sums_at_its_result(DM, K, N, unsampled):
     """mbar_ctx_last_solve_psum: the sums the adaptive loop ends with are those of the f it returns (every loop form: the fused
