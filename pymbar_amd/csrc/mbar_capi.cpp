@@ -3,6 +3,8 @@
 // eval_core).  Owns the device-resident shard of u_kn and drives the gfx950 kernels of mbar_k_*.hip.  No PyTorch, no BLAS/LAPACK.
 #include "mbar_ctx.h"
 
+#include <cassert>
+
 using namespace mbar;
 using namespace mbar::host;
 
@@ -59,18 +61,31 @@ int drop_graphs(mbar_ctx* c) {  // captured batches hold buffer pointers, sizes 
     }
     return MBAR_OK;
 }
-int ensure(mbar_ctx* c, double** p, size_t* have, size_t want) {
-    if (*have >= want) return MBAR_OK;
-    {
-        int rc = drop_graphs(c);
-        if (rc) return rc;
-    }
-    if (*p) HIPCHK(c, cache_free(*p));
-    *p = nullptr;
-    *have = 0;
-    HIPCHK(c, cache_malloc((void**)p, want * sizeof(double)));
-    *have = want;
+int ensure(mbar_ctx* c, DevBuf<double>& buf, size_t want) {
+    if (buf.n >= want) return MBAR_OK;
+    int rc = drop_graphs(c);
+    if (rc) return rc;
+    HIPCHK(c, buf.grow(want));
     return MBAR_OK;
+}
+// One vector of ld doubles, allocated and zeroed at its first use (what is written later stops at N: the padding stays zero)
+int need_zeroed_vec(mbar_ctx* c, DevBuf<double>& v) {
+    if (v) return MBAR_OK;
+    HIPCHK(c, v.grow((size_t)c->ld));
+    HIPCHK(c, hipMemsetAsync(v, 0, (size_t)c->ld * sizeof(double), c->stream));
+    return MBAR_OK;
+}
+// ... and the two that only a weighted context has: lden_eff, cwsq
+static int need_weight_vecs(mbar_ctx* c) {
+    int rc = need_zeroed_vec(c, c->lden_eff);
+    return rc ? rc : need_zeroed_vec(c, c->cwsq);
+}
+// What every writer of the matrix leaves behind: the poison flags (and with them the log-denominators kept in slot 0, see
+// refresh_poison), the resident probability matrix and the last solve's sums all describe the matrix as it was
+static void matrix_touched(mbar_ctx* c) {
+    c->u_checked = false;
+    c->P_valid = false;
+    c->last_psum.clear();
 }
 int refresh_poison(mbar_ctx* c) {
     if (c->u_checked) return MBAR_OK;
@@ -138,9 +153,9 @@ int run_lse(mbar_ctx* c, int nf, int64_t rows, double* ld0, double* ld1, bool us
         LaunchGeom g = lse_geometry(nb, nf, c->num_cu, ntiles, c->opt_grid, lse_variant_for(c));
         g.balanced = c->opt_small_balanced ? 1 : 0;
         const size_t rec = (size_t)nf * rows;
-        int rc = ensure(c, &c->part, &c->part_doubles, (size_t)g.nwaves * (rec + nf));
+        int rc = ensure(c, c->part, (size_t)g.nwaves * (rec + nf));
         if (rc) return rc;
-        rc = ensure(c, &c->scratch, &c->scratch_doubles, ((size_t)g.nwaves / 32 + 1) * (rec + nf));
+        rc = ensure(c, c->scratch, ((size_t)g.nwaves / 32 + 1) * (rec + nf));
         if (rc) return rc;
         double* psum_part = c->part;
         double* obj_part = c->part + (size_t)g.nwaves * rec;
@@ -162,9 +177,9 @@ int run_lse(mbar_ctx* c, int nf, int64_t rows, double* ld0, double* ld1, bool us
     // matrix twice per candidate: log-sum-exp pass + column-sum pass)
     if (split_sweep_ok(c, rows)) {
         int blocks = 0;
-        int rc = ensure(c, &c->part, &c->part_doubles, (size_t)c->num_cu * nf * (rows + 1));
+        int rc = ensure(c, c->part, (size_t)c->num_cu * nf * (rows + 1));
         if (rc) return rc;
-        rc = ensure(c, &c->scratch, &c->scratch_doubles, (size_t)(c->num_cu / 32 + 2) * nf * (rows + 1));
+        rc = ensure(c, c->scratch, (size_t)(c->num_cu / 32 + 2) * nf * (rows + 1));
         if (rc) return rc;
         double* obj_part = c->part + (size_t)c->num_cu * nf * rows;
         {
@@ -180,9 +195,9 @@ int run_lse(mbar_ctx* c, int nf, int64_t rows, double* ld0, double* ld1, bool us
     // generic: one f at a time
     for (int i = 0; i < nf; ++i) {
         int blocks = 0, cblocks = 0;
-        int rc = ensure(c, &c->part, &c->part_doubles, (size_t)c->num_cu * 8 + (size_t)512 * c->K);
+        int rc = ensure(c, c->part, (size_t)c->num_cu * 8 + (size_t)512 * c->K);
         if (rc) return rc;
-        rc = ensure(c, &c->scratch, &c->scratch_doubles, (size_t)64 * (c->K + 8));
+        rc = ensure(c, c->scratch, (size_t)64 * (c->K + 8));
         if (rc) return rc;
         double* ldst = i == 0 ? ld0 : ld1;
         if (!ldst) ldst = c->logden[i];  // the column-sum kernel needs logden even if the caller does not
@@ -209,51 +224,47 @@ int run_lse(mbar_ctx* c, int nf, int64_t rows, double* ld0, double* ld1, bool us
     return MBAR_OK;
 }
 
+// Shared by the two plans below: Kp (a multiple of 64 wherever there is more than one panel) split into panels of `width`
+// states and a shorter last one; the panels' diagonal items (upper-triangular blocks, one launch each) open the plan
+struct Panel { int64_t r0; int nb; };
+static std::vector<Panel> diag_panels(int64_t Kp, int width, GramPlan& p) {
+    std::vector<Panel> panels;
+    for (int64_t r = 0; r < Kp;) {
+        const int nb = Kp - r >= width ? width / 16 : (int)((Kp - r) / 16);
+        panels.push_back({r, nb});
+        r += 16 * nb;
+    }
+    for (const auto& a : panels) {
+        const int nblk = a.nb * (a.nb + 1) / 2;
+        p.items.push_back({true, a.r0, a.r0, a.nb, a.nb, nblk, p.total_blocks});
+        p.total_blocks += nblk;
+    }
+    return panels;
+}
+static void add_rect(GramPlan& p, int64_t ri, int64_t rj, int nbi, int nbj) {
+    p.items.push_back({false, ri, rj, nbi, nbj, nbi * nbj, p.total_blocks});
+    p.total_blocks += (size_t)nbi * nbj;
+}
+
 // Gram-pass geometry: list of launches and where their 16 x 16 blocks land.  Up to 128 states: one diagonal panel.
 // Beyond: 128-state panels (+ one trailing 64-state panel); a diagonal panel is one launch (upper-triangular blocks),
 // a pair of panels is covered by 64 x 128 rectangles (nbi = 4 block rows of the I panel x nbj = 8 block columns of the
 // J panel = 32 blocks, the most one wave's register file holds next to the operands).
 GramPlan gram_plan(int64_t Kp, bool quad) {
     GramPlan p;
-    if (Kp <= 128 || quad) {  // (quad: 129 .. 256 states as ONE panel, its blocks split over the four waves of a workgroup)
-        int nb = (int)(Kp / 16);
-        p.items.push_back({true, 0, 0, nb, nb, nb * (nb + 1) / 2, 0});
-        p.total_blocks = (size_t)nb * (nb + 1) / 2;
-        return p;
-    }
-    struct Panel { int64_t r0; int nb; };
-    std::vector<Panel> panels;
-    for (int64_t r = 0; r < Kp;) {
-        const int nb = Kp - r >= 128 ? 8 : (int)((Kp - r) / 16);  // Kp is a multiple of PANEL = 64 here
-        panels.push_back({r, nb});
-        r += 16 * nb;
-    }
-    size_t off = 0;
-    for (const auto& a : panels) {
-        const int nblk = a.nb * (a.nb + 1) / 2;
-        p.items.push_back({true, a.r0, a.r0, a.nb, a.nb, nblk, off});
-        off += nblk;
-    }
+    // (quad: 129 .. 256 states as ONE panel, its blocks split over the four waves of a workgroup)
+    const std::vector<Panel> panels = diag_panels(Kp, Kp <= 128 || quad ? (int)Kp : 128, p);
+    // beyond 128 states padded_K gives multiples of 64: every panel has 128 states but the last, which may have 64
     for (size_t ia = 0; ia < panels.size(); ++ia)
         for (size_t ib = ia + 1; ib < panels.size(); ++ib) {
             const Panel &a = panels[ia], &b = panels[ib];
             if (b.nb == 8) {  // 128 x 128: two 64 x 128 rectangles
-                for (int h = 0; h < 2; ++h) {
-                    p.items.push_back({false, a.r0 + 64 * h, b.r0, 4, 8, 32, off});
-                    off += 32;
-                }
-            } else if (b.nb == 4) {  // the trailing 64-state panel against a 128-state one: I = the short panel
-                p.items.push_back({false, b.r0, a.r0, 4, 8, 32, off});
-                off += 32;
-            } else {  // (cannot happen for Kp a multiple of 64; kept correct anyway: 64 x 64 squares)
-                for (int64_t ri = a.r0; ri < a.r0 + 16 * a.nb; ri += 64)
-                    for (int64_t rj = b.r0; rj < b.r0 + 16 * b.nb; rj += 64) {
-                        p.items.push_back({false, ri, rj, 4, 4, 16, off});
-                        off += 16;
-                    }
+                for (int h = 0; h < 2; ++h) add_rect(p, a.r0 + 64 * h, b.r0, 4, 8);
+            } else {  // the trailing 64-state panel against a 128-state one: I = the short panel
+                assert(b.nb == 4 && "gram_plan: beyond 128 states Kp must be a multiple of 64");
+                add_rect(p, b.r0, a.r0, 4, 8);
             }
         }
-    p.total_blocks = off;
     return p;
 }
 
@@ -263,31 +274,17 @@ GramPlan gram_plan(int64_t Kp, bool quad) {
 // 4 + 12 launches that read 5632 rows of the matrix (gram_plan above: 64 launches, 11776 rows).
 GramPlan gram_plan_pmode(int64_t Kp) {
     GramPlan p;
-    struct Panel { int64_t r0; int nb; };
-    std::vector<Panel> panels;
-    for (int64_t r = 0; r < Kp;) {
-        const int nb = Kp - r >= 256 ? 16 : (int)((Kp - r) / 16);  // Kp is a multiple of 64 here
-        panels.push_back({r, nb});
-        r += 16 * nb;
-    }
-    size_t off = 0;
-    for (const auto& a : panels) {
-        const int nblk = a.nb * (a.nb + 1) / 2;
-        p.items.push_back({true, a.r0, a.r0, a.nb, a.nb, nblk, off});
-        off += nblk;
-    }
+    const std::vector<Panel> panels = diag_panels(Kp, 256, p);
     for (size_t ia = 0; ia < panels.size(); ++ia)
         for (size_t ib = ia + 1; ib < panels.size(); ++ib) {
             const Panel &a = panels[ia], &b = panels[ib];  // a is a 256-state panel; b one too, or the remainder
             const Panel &rows = b.nb == 16 ? a : b, &cols = b.nb == 16 ? b : a;
             for (int done = 0; done < rows.nb;) {
                 const int nbi = rows.nb - done >= 8 ? 8 : 4;
-                p.items.push_back({false, rows.r0 + 16 * done, cols.r0, nbi, 16, nbi * 16, off});
-                off += (size_t)nbi * 16;
+                add_rect(p, rows.r0 + 16 * done, cols.r0, nbi, 16);
                 done += nbi;
             }
         }
-    p.total_blocks = off;
     return p;
 }
 
@@ -297,6 +294,24 @@ GramPlan plan_for(const mbar_ctx* c) { return gram_plan(c->Kp, use_quad(c)); }
 // blocks of 16 states of the 192- / 256-row panel that hold real states: up to 160 / 224 states the one-read kernels leave the
 // last two blocks (padding rows only) out of the staging, the operand step and the matrix instructions
 int quad_live_blocks(const mbar_ctx* c) { return c->opt_quad_trim ? (int)((c->K + 15) / 16) : 0; }
+
+// One Gram launch and the reduction of its per-wave records: `nwaves` records of `rec` doubles, which launch() (a callable that
+// returns an MBAR code) leaves in c->part, summed into `dst`.  Sizes `part` and the level-1 scratch first.
+template <class Launch>
+static int launch_and_reduce(mbar_ctx* c, int nwaves, size_t rec, double* dst, Launch&& launch) {
+    int rc = ensure(c, c->part, (size_t)nwaves * rec);
+    if (rc) return rc;
+    rc = ensure(c, c->scratch, ((size_t)nwaves / 32 + 1) * rec);
+    if (rc) return rc;
+    {
+        ScopedTimer t(c, MBAR_TIMER_GRAM);
+        rc = launch();
+        if (rc) return rc;
+    }
+    ScopedTimer t(c, MBAR_TIMER_REDUCE);
+    HIPCHK(c, launch_reduce(c->stream, c->part, nwaves, (int64_t)rec, c->scratch, dst));
+    return MBAR_OK;
+}
 
 // Gram pass with operand exp(anum_k - u_kn - logden_n); anum (device) has Kp entries.
 // Results: gram blocks at red + red_off (plan order).  The per-state operand sums are not accumulated on the
@@ -312,6 +327,9 @@ int run_gram(mbar_ctx* c, const double* anum_dev, const double* logden, size_t r
         logden = c->lden_eff;
     }
     for (const auto& it : plan.items) {
+        const size_t rec = (size_t)it.nblk * 256;
+        double* dst = c->red + red_off + it.off * 256;
+        int rc;
         if (!it.diag && it.nbj == 16) {  // P mode: rectangle against a 256-state panel, four waves on one shared tile stream
             if (!pmat) return fail(c, MBAR_ERR_STATE, "run_gram: the 256-column rectangles exist on the probability matrix only");
             LaunchGeom g = gram_quad_geometry(it.nbi + 16, c->num_cu, ntiles, c->opt_grid);
@@ -319,63 +337,36 @@ int run_gram(mbar_ctx* c, const double* anum_dev, const double* logden, size_t r
                 g.waves = 8;
                 g.lds_bytes += 2 * 4 * 1024;
             }
-            const size_t rec = (size_t)it.nblk * 256;
-            int rc = ensure(c, &c->part, &c->part_doubles, (size_t)g.nwaves * rec);
-            if (rc) return rc;
-            rc = ensure(c, &c->scratch, &c->scratch_doubles, ((size_t)g.nwaves / 32 + 1) * rec);
-            if (rc) return rc;
-            {
-                ScopedTimer t(c, MBAR_TIMER_GRAM);
+            rc = launch_and_reduce(c, g.nwaves, rec, dst, [&]() -> int {
                 HIPCHK(c, launch_gram_rect(c->stream, it.nbi, g, pmat, c->ld, c->N, it.ri, it.rj, logden, c->part));
-            }
-            ScopedTimer t(c, MBAR_TIMER_REDUCE);
-            HIPCHK(c, launch_reduce(c->stream, c->part, g.nwaves, (int64_t)rec, c->scratch, c->red + red_off + it.off * 256));
-            continue;
-        }
-        if (it.diag && it.nbi > 8) {  // one read of the matrix: the four waves of a workgroup split the panel's blocks
+                return MBAR_OK;
+            });
+        } else if (it.diag && it.nbi > 8) {  // one read of the matrix: the four waves of a workgroup split the panel's blocks
             LaunchGeom g = gram_quad_geometry(it.nbi, c->num_cu, ntiles, c->opt_grid);
             g.live_blocks = pmat ? 0 : quad_live_blocks(c);
-            const size_t rec = (size_t)it.nblk * 256;
-            int rc = ensure(c, &c->part, &c->part_doubles, (size_t)g.nwaves * rec);
-            if (rc) return rc;
-            rc = ensure(c, &c->scratch, &c->scratch_doubles, ((size_t)g.nwaves / 32 + 1) * rec);
-            if (rc) return rc;
-            {
-                ScopedTimer t(c, MBAR_TIMER_GRAM);
-                LoopCtl lo;
-                lo.pmode = pmat != nullptr;  // (then: the panel's rows of the probability matrix, `logden` = reciprocals)
+            LoopCtl lo;
+            lo.pmode = pmat != nullptr;  // (then: the panel's rows of the probability matrix, `logden` = reciprocals)
+            rc = launch_and_reduce(c, g.nwaves, rec, dst, [&]() -> int {
                 HIPCHK(c, launch_gram_quad(c->stream, it.nbi, g, mat + it.ri * c->ld, c->ld, c->N, anum_dev + it.ri, logden, c->part, lo));
-            }
-            ScopedTimer t(c, MBAR_TIMER_REDUCE);
-            HIPCHK(c, launch_reduce(c->stream, c->part, g.nwaves, (int64_t)rec, c->scratch, c->red + red_off + it.off * 256));
-            continue;
+                return MBAR_OK;
+            });
+        } else {
+            const int tile_rows = it.diag ? it.nbi * 16 : (it.nbi + it.nbj) * 16;
+            LaunchGeom g = gram_geometry(tile_rows, it.diag, c->num_cu, ntiles, c->opt_grid);
+            LoopCtl lo;
+            lo.unclamped = c->u_checked && !c->u_posinf;
+            lo.pmode = pmat != nullptr;
+            rc = launch_and_reduce(c, g.nwaves, rec, dst, [&]() -> int {
+                if (it.diag)
+                    HIPCHK(c, launch_gram_diag(c->stream, it.nbi, g, mat, c->ld, c->N, anum_dev + it.ri, logden,
+                                               it.ri, c->part, nullptr, lo));
+                else
+                    HIPCHK(c, launch_gram_off(c->stream, it.nbj, g, mat, c->ld, c->N, anum_dev + it.ri, anum_dev + it.rj,
+                                              logden, it.ri, it.rj, c->part, pmat != nullptr));
+                return MBAR_OK;
+            });
         }
-        const int tile_rows = it.diag ? it.nbi * 16 : (it.nbi + it.nbj) * 16;
-        LaunchGeom g = gram_geometry(tile_rows, it.diag, c->num_cu, ntiles, c->opt_grid);
-        const size_t rec = (size_t)it.nblk * 256;
-        int rc = ensure(c, &c->part, &c->part_doubles, (size_t)g.nwaves * rec);
         if (rc) return rc;
-        rc = ensure(c, &c->scratch, &c->scratch_doubles, ((size_t)g.nwaves / 32 + 1) * rec);
-        if (rc) return rc;
-        double* gp = c->part;
-        {
-            ScopedTimer t(c, MBAR_TIMER_GRAM);
-            if (it.diag)
-            {
-                LoopCtl lo;
-                lo.unclamped = c->u_checked && !c->u_posinf;
-                lo.pmode = pmat != nullptr;
-                HIPCHK(c, launch_gram_diag(c->stream, it.nbi, g, mat, c->ld, c->N, anum_dev + it.ri, logden,
-                                           it.ri, gp, nullptr, lo));
-            }
-            else
-                HIPCHK(c, launch_gram_off(c->stream, it.nbj, g, mat, c->ld, c->N, anum_dev + it.ri, anum_dev + it.rj,
-                                          logden, it.ri, it.rj, gp, pmat != nullptr));
-        }
-        {
-            ScopedTimer t(c, MBAR_TIMER_REDUCE);
-            HIPCHK(c, launch_reduce(c->stream, gp, g.nwaves, (int64_t)rec, c->scratch, c->red + red_off + it.off * 256));
-        }
     }
     return MBAR_OK;
 }
@@ -467,26 +458,26 @@ void unpack_gram_to_hessian(const GramPlan& plan, const double* blocks, int64_t 
     });
 }
 
-int ensure_red(mbar_ctx* c, size_t want) {
-    if (c->red_doubles >= want) return MBAR_OK;
-    {
-        int rc = drop_graphs(c);
-        if (rc) return rc;
-    }
-    if (c->red) HIPCHK(c, cache_free(c->red));
-    if (c->hred) HIPCHK(c, cache_host_free(c->hred));
-    c->red = nullptr;
-    c->hred = nullptr;
-    c->red_doubles = 0;
-    HIPCHK(c, cache_malloc((void**)&c->red, want * sizeof(double)));
-    HIPCHK(c, cache_host_malloc((void**)&c->hred, want * sizeof(double)));
-    c->red_doubles = want;
+int ensure_red(mbar_ctx* c, size_t want) {  // red and its pinned mirror grow together
+    if (c->red.n >= want && c->hred.n >= want) return MBAR_OK;
+    int rc = drop_graphs(c);
+    if (rc) return rc;
+    HIPCHK(c, c->red.grow(want));
+    HIPCHK(c, c->hred.grow(want));
     return MBAR_OK;
 }
 
 // Row pitch of the aden / psum vectors: the padded state count (padded_K() only produces values
 // for which the fused kernel has an instantiation: 16..128 step 16, 192, 256).
 int64_t lse_rows(const mbar_ctx* c) { return c->Kp; }
+
+// A NaN or -inf entry of the matrix, or a non-finite f_k of a state with samples, makes every sum NaN (the reference's logsumexp
+// over all samples propagates it into every f_k): no sweep runs, eval_core and the entry points built on it fill their outputs
+// with NaN and return MBAR_OK
+static bool unusable(const mbar_ctx* c, const double* f, int nf = 1) { return c->u_poison || !f_is_finite(c, f, nf); }
+static void fill_nan(double* out, size_t n) {
+    if (out) std::fill(out, out + n, std::numeric_limits<double>::quiet_NaN());
+}
 
 // Core of mbar_eval: f points to nf*K doubles on the host.  Leaves logden in ld0/ld1.
 int eval_core(mbar_ctx* c, const double* f, int nf, unsigned flags, double* ld0, double* ld1, double* psum,
@@ -500,11 +491,10 @@ int eval_core(mbar_ctx* c, const double* f, int nf, unsigned flags, double* ld0,
     {
         int prc = refresh_poison(c);
         if (prc) return prc;
-        if (c->u_poison || !f_is_finite(c, f, nf)) {
-            const double qnan = std::numeric_limits<double>::quiet_NaN();
-            if (psum) std::fill(psum, psum + (size_t)nf * c->K, qnan);
-            if (sumlogden) std::fill(sumlogden, sumlogden + nf, qnan);
-            if (want_gram && gram) std::fill(gram, gram + (size_t)c->K * c->K, qnan);
+        if (unusable(c, f, nf)) {
+            fill_nan(psum, (size_t)nf * c->K);
+            fill_nan(sumlogden, nf);
+            if (want_gram) fill_nan(gram, (size_t)c->K * c->K);
             c->error = c->u_poison ? "u_kn contains NaN or -inf: all sums are NaN" : "f_k is not finite: all sums are NaN";
             return MBAR_OK;
         }
@@ -551,7 +541,7 @@ int eval_core(mbar_ctx* c, const double* f, int nf, unsigned flags, double* ld0,
     }
     // (pinned staging: the copy is stream-ordered before the sweep and the host only touches the buffer again after
     // the sweep's results have been read back, so no synchronisation is needed here)
-    std::copy(h.begin(), h.end(), c->hstage);
+    std::copy(h.begin(), h.end(), c->hstage.p);
     HIPCHK(c, hipMemcpyAsync(d_aden(c), c->hstage, h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     // One rank, sums only: the last level of the reduction writes into the pinned host buffer itself (it is mapped into the
     // device's address space) -- one copy kernel less per evaluation; the scipy-driven protocol stages call this thirty times
@@ -559,8 +549,8 @@ int eval_core(mbar_ctx* c, const double* f, int nf, unsigned flags, double* ld0,
     const bool direct = c->opt_direct_results && c->nranks <= 1 && !c->comm && !stream_transport(c) && use_fast(c) && !want_gram;
     struct RedSwap {
         mbar_ctx* c; double* saved;
-        RedSwap(mbar_ctx* c_, bool on) : c(c_), saved(nullptr) { if (on) { saved = c->red; c->red = c->hred; } }
-        ~RedSwap() { if (saved) c->red = saved; }
+        RedSwap(mbar_ctx* c_, bool on) : c(c_), saved(nullptr) { if (on) { saved = c->red.p; c->red.p = c->hred.p; } }
+        ~RedSwap() { if (saved) c->red.p = saved; }
     };
     {
         RedSwap swap(c, direct);
@@ -647,6 +637,26 @@ int mbar_device_info(int device, char* name, int name_len, int* compute_units, i
     return MBAR_OK;
 }
 
+// The two context constructors: a HIP error destroys the half-made context `c` and is the call's error
+#define CRT(expr)                                                                                   \
+    do {                                                                                            \
+        hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess) {                                                                     \
+            int rc_ = fail(nullptr, MBAR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+            mbar_ctx_destroy(c);                                                                    \
+            return rc_;                                                                             \
+        }                                                                                           \
+    } while (0)
+// (stream creation costs milliseconds: streams of destroyed contexts are kept for the next one on the device; null: none is kept)
+static hipStream_t take_pooled_stream(int device) {
+    std::lock_guard<std::mutex> lock(g_dev_mu);
+    auto& pool = g_stream_pool[device];
+    if (pool.empty()) return nullptr;
+    hipStream_t s = pool.back();
+    pool.pop_back();
+    return s;
+}
+
 int mbar_ctx_create(mbar_ctx** out, int device, int64_t K, int64_t N_local) {
     if (!out) return fail(nullptr, MBAR_ERR_ARG, "out is NULL");
     *out = nullptr;
@@ -666,47 +676,31 @@ int mbar_ctx_create(mbar_ctx** out, int device, int64_t K, int64_t N_local) {
     // row pitch: whole 16-sample tiles; whole 64-sample tiles where the few-state evaluation kernel may run (K <= 32)
     c->ld = c->Kp <= 32 ? (N_local + 63) / 64 * 64 : (N_local + TS - 1) / TS * TS;
     if (c->ld == 0) c->ld = c->Kp <= 32 ? 64 : TS;
-#define CRT(expr)                                                                                   \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) {                                                                     \
-            int rc_ = fail(nullptr, MBAR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-            mbar_ctx_destroy(c);                                                                    \
-            return rc_;                                                                             \
-        }                                                                                           \
-    } while (0)
-    // (stream creation costs milliseconds: streams of destroyed contexts are kept for the next one)
-    {
-        std::lock_guard<std::mutex> lock(g_dev_mu);
-        auto& pool = g_stream_pool[device];
-        if (!pool.empty()) {
-            c->stream = pool.back();
-            pool.pop_back();
-        }
-    }
+    c->stream = take_pooled_stream(device);
     if (!c->stream) CRT(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const size_t ubytes = (size_t)c->Kp * c->ld * sizeof(double);
-    CRT(cache_malloc((void**)&c->u, ubytes));
+    CRT(c->u_alloc.grow((size_t)c->Kp * c->ld));
+    c->u = c->u_alloc;
     CRT(launch_zero(c->stream, c->u, ubytes));
     // three logden vectors in ONE allocation: the device-resident loop addresses them as base + slot * ld
-    CRT(cache_malloc((void**)&c->logden[0], (size_t)3 * c->ld * sizeof(double)));
-    CRT(launch_zero(c->stream, c->logden[0], (size_t)3 * c->ld * sizeof(double)));
-    c->logden[1] = c->logden[0] + c->ld;
-    c->logden[2] = c->logden[0] + 2 * c->ld;
-    CRT(cache_malloc((void**)&c->cw, (size_t)c->ld * sizeof(double)));
+    CRT(c->logden_alloc.grow((size_t)3 * c->ld));
+    CRT(launch_zero(c->stream, c->logden_alloc, (size_t)3 * c->ld * sizeof(double)));
+    for (int i = 0; i < 3; ++i) c->logden[i] = c->logden_alloc + i * c->ld;
+    CRT(c->cw.grow((size_t)c->ld));
     CRT(launch_zero(c->stream, c->cw, (size_t)c->ld * sizeof(double)));
     if (c->N > 0) CRT(launch_fill(c->stream, c->cw, 1.0, c->N));  // (unit multiplicities, 0 on the padding: filled on the device)
-    CRT(cache_malloc((void**)&c->small, small_doubles(c->Kp) * sizeof(double)));
-    CRT(cache_host_malloc((void**)&c->hstage, (size_t)4 * c->Kp * sizeof(double)));
+    CRT(c->small.grow(small_doubles(c->Kp)));
+    CRT(c->hstage.grow((size_t)4 * c->Kp));
     CRT(hipMemsetAsync(c->small, 0, small_doubles(c->Kp) * sizeof(double), c->stream));
     CRT(hipStreamSynchronize(c->stream));
-#undef CRT
     c->Nk.assign(K, 0.0);
     c->lnNk.assign(K, 0.0);
     *out = c;
     return MBAR_OK;
 }
 
+// What is not memory goes here; the buffers go back to the cache with their owning members in `delete c` -- after the stream has
+// been drained (the pool is shared: no block may return to it while a kernel still uses it) and before the cache is trimmed
 void mbar_ctx_destroy(mbar_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -714,34 +708,9 @@ void mbar_ctx_destroy(mbar_ctx* c) {
     flush_timers(c);
     for (auto e : c->pool) (void)hipEventDestroy(e);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
-    if (c->u_alloc) (void)cache_free(c->u_alloc);
-    else if (c->u) (void)cache_free(c->u);
-    if (c->logden[0]) (void)cache_free(c->logden[0]);
-    if (c->ad) (void)cache_free(c->ad);
-    if (c->P) (void)cache_free(c->P);
-    if (c->pm_vec) (void)cache_free(c->pm_vec);
-    if (c->pm_ld0) (void)cache_free(c->pm_ld0);
-    if (c->part_g) (void)cache_free(c->part_g);
-    if (c->cwsq) (void)cache_free(c->cwsq);
-    if (c->chol) (void)cache_free(c->chol);
-    if (c->ad_ints) (void)cache_free(c->ad_ints);
-    if (c->h_ctl) (void)cache_host_free(c->h_ctl);
     if (c->ad_graph) (void)hipGraphExecDestroy(c->ad_graph);
-    if (c->dn) (void)cache_free(c->dn);
-    if (c->cw) (void)cache_free(c->cw);
-    if (c->lden_eff) (void)cache_free(c->lden_eff);
-    if (c->small) (void)cache_free(c->small);
-    if (c->part) (void)cache_free(c->part);
-    if (c->scratch) (void)cache_free(c->scratch);
-    if (c->red) (void)cache_free(c->red);
-    if (c->hred) (void)cache_host_free(c->hred);
-    if (c->lognum_part) (void)cache_free(c->lognum_part);
-    if (c->f_hist) (void)cache_free(c->f_hist);
-    if (c->hstage) (void)cache_host_free(c->hstage);
-    if (c->vec_tmp) (void)cache_free(c->vec_tmp);
-    if (c->boot_idx) (void)cache_free(c->boot_idx);
-    if (c->stamps) (void)hipFree(c->stamps);
     if (c->sci_graph) (void)hipGraphExecDestroy(c->sci_graph);
+    if (c->stamps) (void)hipFree(c->stamps);
     if (c->stream) {  // (idle: synchronised above) kept for the next context on this device
         std::lock_guard<std::mutex> lock(g_dev_mu);
         auto& pool = g_stream_pool[c->device];
@@ -827,31 +796,29 @@ int mbar_ctx_upload_u(mbar_ctx* c, const double* u_host, int64_t ld_host, int64_
     HIPCHK(c, hipMemcpy2DAsync(c->u + col0_dev, (size_t)c->ld * sizeof(double), u_host + col0_host,
                                (size_t)ld_host * sizeof(double), (size_t)ncols * sizeof(double), (size_t)c->K,
                                hipMemcpyHostToDevice, c->stream));
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
+    matrix_touched(c);
     return sync_stream(c);
 }
 
+// rows [row0, row0 + nrows) are rows of the context
+static bool rows_in_range(const mbar_ctx* c, int64_t row0, int64_t nrows) { return row0 >= 0 && nrows >= 0 && row0 + nrows <= c->K; }
+
 int mbar_ctx_upload_rows(mbar_ctx* c, int64_t row0, int64_t nrows, const double* rows_host, int64_t ld_host) {
     if (!c || !rows_host) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (row0 < 0 || nrows < 0 || row0 + nrows > c->K || ld_host < c->N) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
+    if (!rows_in_range(c, row0, nrows) || ld_host < c->N) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
     if (nrows == 0) return MBAR_OK;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpy2DAsync(c->u + row0 * c->ld, (size_t)c->ld * sizeof(double), rows_host,
                                (size_t)ld_host * sizeof(double), (size_t)c->N * sizeof(double), (size_t)nrows,
                                hipMemcpyHostToDevice, c->stream));
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
+    matrix_touched(c);
     return sync_stream(c);
 }
 
 int mbar_ctx_copy_rows(mbar_ctx* dst, int64_t dst_row0, mbar_ctx* src, int64_t src_row0, int64_t nrows) {
     if (!dst || !src) return fail(dst, MBAR_ERR_ARG, "NULL argument");
     if (dst->device != src->device || dst->N != src->N) return fail(dst, MBAR_ERR_ARG, "contexts must share device and N_local");
-    if (nrows < 0 || dst_row0 < 0 || src_row0 < 0 || dst_row0 + nrows > dst->K || src_row0 + nrows > src->K)
-        return fail(dst, MBAR_ERR_ARG, "row range out of bounds");
+    if (!rows_in_range(dst, dst_row0, nrows) || !rows_in_range(src, src_row0, nrows)) return fail(dst, MBAR_ERR_ARG, "row range out of bounds");
     if (nrows == 0) return MBAR_OK;
     HIPCHK(dst, hipSetDevice(dst->device));
     HIPCHK(dst, hipStreamSynchronize(src->stream));  // whatever produced the source rows has finished
@@ -862,10 +829,20 @@ int mbar_ctx_copy_rows(mbar_ctx* dst, int64_t dst_row0, mbar_ctx* src, int64_t s
         HIPCHK(dst, hipMemcpy2DAsync(dst->u + dst_row0 * dst->ld, (size_t)dst->ld * sizeof(double), src->u + src_row0 * src->ld,
                                      (size_t)src->ld * sizeof(double), (size_t)dst->N * sizeof(double), (size_t)nrows,
                                      hipMemcpyDeviceToDevice, dst->stream));
-    dst->u_checked = false;
-    dst->P_valid = false;
-    dst->last_psum.clear();
+    matrix_touched(dst);
     return sync_stream(dst);
+}
+
+// The staging vector of the row operations (one N_local-vector, allocated at its first use) ...
+static hipError_t need_vec_tmp(mbar_ctx* c) { return c->vec_tmp.grow((size_t)c->ld); }
+// ... holding v_host, or (NULL) still what the previous call put there: one observable at many states
+static int stage_vec(mbar_ctx* c, const double* v_host) {
+    HIPCHK(c, need_vec_tmp(c));
+    if (v_host) {
+        c->vec_holds_logshift = false;
+        HIPCHK(c, hipMemcpyAsync(c->vec_tmp, v_host, (size_t)c->N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    return MBAR_OK;
 }
 
 int mbar_ctx_row_sub(mbar_ctx* c, int64_t row, const double* v_host) {
@@ -873,55 +850,63 @@ int mbar_ctx_row_sub(mbar_ctx* c, int64_t row, const double* v_host) {
     if (row < 0 || row >= c->K) return fail(c, MBAR_ERR_ARG, "row out of range");
     if (!v_host && !c->vec_tmp) return fail(c, MBAR_ERR_STATE, "mbar_ctx_row_sub: no vector has been uploaded yet");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->vec_tmp) HIPCHK(c, cache_malloc((void**)&c->vec_tmp, (size_t)c->ld * sizeof(double)));
-    double* tmp = c->vec_tmp;
-    if (v_host) c->vec_holds_logshift = false;
-    if (v_host)  // NULL: subtract the vector of the previous call again (one observable at many states)
-        HIPCHK(c, hipMemcpyAsync(tmp, v_host, (size_t)c->N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_row_sub(c->stream, c->u + row * c->ld, tmp, c->N));
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
+    int rc = stage_vec(c, v_host);
+    if (rc) return rc;
+    HIPCHK(c, launch_row_sub(c->stream, c->u + row * c->ld, c->vec_tmp, c->N));
+    matrix_touched(c);
     return sync_stream(c);
 }
 
+// dst rows = src rows - v (v_host, or NULL: the vector staged in dst by the previous call / mbar_ctx_vec_logshift); src is dst or its
+// base.  `who`: the entry point, for the error strings.
+static int rows_sub_from(const char* who, mbar_ctx* dst, int64_t dst_row0, mbar_ctx* src, int64_t src_row0, int64_t nrows,
+                         const double* v_host) {
+    if (!dst || !src) return fail(dst, MBAR_ERR_ARG, "NULL argument");
+    if (src != dst && dst->ext_base != src) return fail(dst, MBAR_ERR_ARG, std::string(who) + ": src must be dst or its base");
+    if (!rows_in_range(dst, dst_row0, nrows) || !rows_in_range(src, src_row0, nrows)) return fail(dst, MBAR_ERR_ARG, "row range out of bounds");
+    if (src == dst && dst_row0 != src_row0 && dst_row0 < src_row0 + nrows && src_row0 < dst_row0 + nrows)
+        return fail(dst, MBAR_ERR_ARG, std::string(who) + ": the row ranges overlap");
+    if (!v_host && !dst->vec_tmp) return fail(dst, MBAR_ERR_STATE, std::string(who) + ": no vector has been uploaded yet");
+    if (nrows == 0) return MBAR_OK;
+    HIPCHK(dst, hipSetDevice(dst->device));
+    if (src != dst) HIPCHK(dst, hipStreamSynchronize(src->stream));
+    int rc = stage_vec(dst, v_host);
+    if (rc) return rc;
+    HIPCHK(dst, launch_rows_sub(dst->stream, dst->u + dst_row0 * dst->ld, src->u + src_row0 * src->ld, dst->ld, nrows, dst->vec_tmp, dst->N));
+    matrix_touched(dst);
+    return sync_stream(dst);
+}
 int mbar_ctx_rows_sub(mbar_ctx* c, int64_t dst_row0, int64_t src_row0, int64_t nrows, const double* v_host) {
-    if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (nrows < 0 || dst_row0 < 0 || src_row0 < 0 || dst_row0 + nrows > c->K || src_row0 + nrows > c->K)
-        return fail(c, MBAR_ERR_ARG, "row range out of bounds");
-    if (dst_row0 != src_row0 && dst_row0 < src_row0 + nrows && src_row0 < dst_row0 + nrows)
-        return fail(c, MBAR_ERR_ARG, "mbar_ctx_rows_sub: the row ranges overlap");
-    if (!v_host && !c->vec_tmp) return fail(c, MBAR_ERR_STATE, "mbar_ctx_rows_sub: no vector has been uploaded yet");
-    if (nrows == 0) return MBAR_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->vec_tmp) HIPCHK(c, cache_malloc((void**)&c->vec_tmp, (size_t)c->ld * sizeof(double)));
-    if (v_host) c->vec_holds_logshift = false;
-    if (v_host)  // NULL: the vector of the previous call again (one observable at many states)
-        HIPCHK(c, hipMemcpyAsync(c->vec_tmp, v_host, (size_t)c->N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, launch_rows_sub(c->stream, c->u + dst_row0 * c->ld, c->u + src_row0 * c->ld, c->ld, nrows, c->vec_tmp, c->N));
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
-    return sync_stream(c);
+    return rows_sub_from("mbar_ctx_rows_sub", c, dst_row0, c, src_row0, nrows, v_host);
+}
+int mbar_ctx_rows_sub_from(mbar_ctx* dst, int64_t dst_row0, mbar_ctx* src, int64_t src_row0, int64_t nrows, const double* v_host) {
+    return rows_sub_from("mbar_ctx_rows_sub_from", dst, dst_row0, src, src_row0, nrows, v_host);
 }
 
-int mbar_ctx_rows_rsub(mbar_ctx* c, int64_t dst_row0, int64_t src_row0, int64_t nrows) {
-    if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (nrows < 0 || dst_row0 < 0 || src_row0 < 0 || dst_row0 + nrows > c->K || src_row0 + nrows > c->K)
-        return fail(c, MBAR_ERR_ARG, "row range out of bounds");
-    if (dst_row0 < src_row0 + nrows && src_row0 < dst_row0 + nrows) return fail(c, MBAR_ERR_ARG, "mbar_ctx_rows_rsub: the row ranges overlap");
+// dst rows = src rows - dst rows; src is dst or its base
+static int rows_rsub_from(const char* who, mbar_ctx* dst, int64_t dst_row0, mbar_ctx* src, int64_t src_row0, int64_t nrows) {
+    if (!dst || !src) return fail(dst, MBAR_ERR_ARG, "NULL argument");
+    if (src != dst && dst->ext_base != src) return fail(dst, MBAR_ERR_ARG, std::string(who) + ": src must be dst or its base");
+    if (!rows_in_range(dst, dst_row0, nrows) || !rows_in_range(src, src_row0, nrows)) return fail(dst, MBAR_ERR_ARG, "row range out of bounds");
+    if (src == dst && dst_row0 < src_row0 + nrows && src_row0 < dst_row0 + nrows)
+        return fail(dst, MBAR_ERR_ARG, std::string(who) + ": the row ranges overlap");
     if (nrows == 0) return MBAR_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, launch_rows_rsub(c->stream, c->u + dst_row0 * c->ld, c->u + src_row0 * c->ld, c->ld, nrows, c->N));
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
-    return sync_stream(c);
+    HIPCHK(dst, hipSetDevice(dst->device));
+    if (src != dst) HIPCHK(dst, hipStreamSynchronize(src->stream));
+    HIPCHK(dst, launch_rows_rsub(dst->stream, dst->u + dst_row0 * dst->ld, src->u + src_row0 * src->ld, dst->ld, nrows, dst->N));
+    matrix_touched(dst);
+    return sync_stream(dst);
+}
+int mbar_ctx_rows_rsub(mbar_ctx* c, int64_t dst_row0, int64_t src_row0, int64_t nrows) {
+    return rows_rsub_from("mbar_ctx_rows_rsub", c, dst_row0, c, src_row0, nrows);
+}
+int mbar_ctx_rows_rsub_from(mbar_ctx* dst, int64_t dst_row0, mbar_ctx* src, int64_t src_row0, int64_t nrows) {
+    return rows_rsub_from("mbar_ctx_rows_rsub_from", dst, dst_row0, src, src_row0, nrows);
 }
 
 // shared tail of the two log-shift entry points: `base` holds nrows rows of raw observable values
 static int logshift_rows(mbar_ctx* c, double* base, int64_t nrows, double* shift_host) {
-    int rc = ensure(c, &c->scratch, &c->scratch_doubles, (size_t)nrows * 257);
+    int rc = ensure(c, c->scratch, (size_t)nrows * 257);
     if (rc) return rc;
     double* shift_dev = c->scratch + (size_t)nrows * 256;
     HIPCHK(c, launch_rows_logshift(c->stream, base, c->ld, nrows, c->N, c->scratch, shift_dev));
@@ -931,13 +916,11 @@ static int logshift_rows(mbar_ctx* c, double* base, int64_t nrows, double* shift
 
 int mbar_ctx_rows_logshift(mbar_ctx* c, int64_t row0, int64_t nrows, double* shift_out) {
     if (!c || !shift_out) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (row0 < 0 || nrows < 0 || row0 + nrows > c->K) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
+    if (!rows_in_range(c, row0, nrows)) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
     if (nrows == 0) return MBAR_OK;
     if (c->nranks > 1) return fail(c, MBAR_ERR_STATE, "mbar_ctx_rows_logshift: the minimum is taken over this context's samples only");
     HIPCHK(c, hipSetDevice(c->device));
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
+    matrix_touched(c);
     return logshift_rows(c, c->u + row0 * c->ld, nrows, shift_out);
 }
 
@@ -945,32 +928,28 @@ int mbar_ctx_vec_logshift(mbar_ctx* c, const double* A_host, double* shift_out) 
     if (!c || !A_host || !shift_out) return fail(c, MBAR_ERR_ARG, "NULL argument");
     if (c->nranks > 1) return fail(c, MBAR_ERR_STATE, "mbar_ctx_vec_logshift: the minimum is taken over this context's samples only");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->vec_tmp) HIPCHK(c, cache_malloc((void**)&c->vec_tmp, (size_t)c->ld * sizeof(double)));
-    HIPCHK(c, hipMemcpyAsync(c->vec_tmp, A_host, (size_t)c->N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    c->vec_holds_logshift = false;
-    const int lrc = logshift_rows(c, c->vec_tmp, 1, shift_out);
+    int lrc = stage_vec(c, A_host);
+    if (lrc) return lrc;
+    lrc = logshift_rows(c, c->vec_tmp, 1, shift_out);
     c->vec_holds_logshift = lrc == MBAR_OK;
     return lrc;
 }
 
 int mbar_ctx_fill_masked_rows(mbar_ctx* c, int64_t row0, int64_t nrows, const double* v_host, const int32_t* label_host) {
     if (!c || !v_host || !label_host) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (row0 < 0 || nrows < 0 || row0 + nrows > c->K) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
+    if (!rows_in_range(c, row0, nrows)) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
     if (nrows == 0) return MBAR_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->vec_tmp) HIPCHK(c, cache_malloc((void**)&c->vec_tmp, (size_t)c->ld * sizeof(double)));
-    int* dlabel = nullptr;
-    HIPCHK(c, cache_malloc((void**)&dlabel, (size_t)c->N * sizeof(int)));
+    HIPCHK(c, need_vec_tmp(c));
+    DevBuf<int> dlabel;
+    HIPCHK(c, dlabel.grow((size_t)c->N));
     c->vec_holds_logshift = false;
     hipError_t e = hipMemcpyAsync(c->vec_tmp, v_host, (size_t)c->N * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dlabel, label_host, (size_t)c->N * sizeof(int), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = launch_fill_masked_rows(c->stream, c->u + row0 * c->ld, c->ld, c->N, nrows, c->vec_tmp, dlabel);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)cache_free(dlabel);
     if (e != hipSuccess) return fail(c, MBAR_ERR_HIP, std::string("mbar_ctx_fill_masked_rows: ") + hipGetErrorString(e));
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
+    matrix_touched(c);
     flush_timers(c);
     return MBAR_OK;
 }
@@ -1005,9 +984,7 @@ int mbar_ctx_generate_harmonic(mbar_ctx* c, uint64_t seed, const double* O_k, co
         ScopedTimer t(c, MBAR_TIMER_OTHER);
         HIPCHK(c, launch_generate_harmonic(c->stream, c->u, c->ld, c->N, c->K, seed, dO, dK, dC, n_global0));
     }
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
+    matrix_touched(c);
     return sync_stream(c);
 }
 
@@ -1053,20 +1030,16 @@ int mbar_ctx_set_sample_weights(mbar_ctx* c, const double* c_n) {
         }
         if (bad) return fail(c, MBAR_ERR_ARG, "sample weights must be finite and >= 0");
     }
-    if (weighted && !c->lden_eff) {
-        HIPCHK(c, cache_malloc((void**)&c->lden_eff, (size_t)c->ld * sizeof(double)));
-        HIPCHK(c, hipMemsetAsync(c->lden_eff, 0, (size_t)c->ld * sizeof(double), c->stream));
-    }
-    if (weighted)
+    if (weighted) {  // (an unweighted call allocates nothing)
+        int rc = need_zeroed_vec(c, c->lden_eff);
+        if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync(c->cw, c_n, (size_t)c->N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    else
-        HIPCHK(c, launch_fill(c->stream, c->cw, 1.0, c->N));  // (the padding behind N stays 0)
-    if (weighted) {  // sqrt(c_n) for the MFMA operands of the fused sweep (plain 0 / 1 weights are their own square roots)
-        if (!c->cwsq) {
-            HIPCHK(c, cache_malloc((void**)&c->cwsq, (size_t)c->ld * sizeof(double)));
-            HIPCHK(c, hipMemsetAsync(c->cwsq, 0, (size_t)c->ld * sizeof(double), c->stream));
-        }
+        rc = need_zeroed_vec(c, c->cwsq);
+        if (rc) return rc;
+        // sqrt(c_n) for the MFMA operands of the fused sweep (plain 0 / 1 weights are their own square roots)
         HIPCHK(c, launch_sqrt_vec(c->stream, c->cwsq, c->cw, c->N));
+    } else {
+        HIPCHK(c, launch_fill(c->stream, c->cw, 1.0, c->N));  // (the padding behind N stays 0)
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->weighted = weighted;
@@ -1082,11 +1055,7 @@ static int upload_bootstrap_layout(mbar_ctx* c, const int64_t* cumN, int64_t K_s
     if (order)
         for (int64_t p = 0; p < total; ++p)
             if (order[p] < 0 || order[p] >= total) return fail(c, MBAR_ERR_ARG, "bootstrap layout: order entry out of range");
-    if (c->boot_idx && c->boot_idx_words < words) {
-        (void)cache_free(c->boot_idx);
-        c->boot_idx = nullptr;
-    }
-    if (!c->boot_idx) HIPCHK(c, cache_malloc((void**)&c->boot_idx, words * sizeof(int64_t)));
+    HIPCHK(c, c->boot_idx.grow(words));
     HIPCHK(c, hipMemcpyAsync(c->boot_idx, cumN, (size_t)(K_states + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     if (order)
         HIPCHK(c, hipMemcpyAsync(c->boot_idx + K_states + 1, order, (size_t)total * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
@@ -1148,13 +1117,9 @@ int mbar_ctx_draw_bootstrap_weights(mbar_ctx* c, uint64_t seed, int64_t replicat
     const int64_t total = c->boot_total;
     const bool has_order = c->boot_has_order;
     if (total < n_global0 + c->N) return fail(c, MBAR_ERR_ARG, "mbar_ctx_draw_bootstrap_weights: the runs do not cover this shard");
-    if (!c->lden_eff) {
-        HIPCHK(c, cache_malloc((void**)&c->lden_eff, (size_t)c->ld * sizeof(double)));
-        HIPCHK(c, hipMemsetAsync(c->lden_eff, 0, (size_t)c->ld * sizeof(double), c->stream));
-    }
-    if (!c->cwsq) {
-        HIPCHK(c, cache_malloc((void**)&c->cwsq, (size_t)c->ld * sizeof(double)));
-        HIPCHK(c, hipMemsetAsync(c->cwsq, 0, (size_t)c->ld * sizeof(double), c->stream));
+    {
+        int rc = need_weight_vecs(c);
+        if (rc) return rc;
     }
     HIPCHK(c, launch_fill(c->stream, c->cw, 0.0, c->N));
     HIPCHK(c, launch_bootstrap_counts(c->stream, seed, replicate, c->boot_idx, K_states, total, has_order ? c->boot_idx + K_states + 1 : nullptr,
@@ -1174,13 +1139,9 @@ int mbar_ctx_weights_from_vec(mbar_ctx* c, double power) {
                                        "mbar_ctx_row_sub / rows_sub / fill_masked_rows re-use that vector)");
     if (!(std::fabs(power) <= 8.0)) return fail(c, MBAR_ERR_ARG, "mbar_ctx_weights_from_vec: |power| must be <= 8");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->lden_eff) {
-        HIPCHK(c, cache_malloc((void**)&c->lden_eff, (size_t)c->ld * sizeof(double)));
-        HIPCHK(c, hipMemsetAsync(c->lden_eff, 0, (size_t)c->ld * sizeof(double), c->stream));
-    }
-    if (!c->cwsq) {
-        HIPCHK(c, cache_malloc((void**)&c->cwsq, (size_t)c->ld * sizeof(double)));
-        HIPCHK(c, hipMemsetAsync(c->cwsq, 0, (size_t)c->ld * sizeof(double), c->stream));
+    {
+        int rc = need_weight_vecs(c);
+        if (rc) return rc;
     }
     int* flag = reinterpret_cast<int*>(d_misc(c));
     int overflow = 0;
@@ -1205,20 +1166,14 @@ int mbar_ctx_set_objective_offset(mbar_ctx* c, const double* f0) {
     if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
     HIPCHK(c, hipSetDevice(c->device));
     if (!f0) {
-        if (c->dn) HIPCHK(c, cache_free(c->dn));
-        c->dn = nullptr;
+        c->dn.reset();
         return MBAR_OK;
     }
-    double* tmp = nullptr;
-    if (!c->dn) {
-        HIPCHK(c, cache_malloc((void**)&tmp, (size_t)c->ld * sizeof(double)));
-        HIPCHK(c, hipMemsetAsync(tmp, 0, (size_t)c->ld * sizeof(double), c->stream));
-    } else {
-        tmp = c->dn;
-        c->dn = nullptr;
-    }
-    int rc = eval_core(c, f0, 1, 0, tmp, nullptr, nullptr, nullptr, nullptr);
-    c->dn = tmp;
+    DevBuf<double> tmp = std::move(c->dn);  // (the context has no offset while the sweep writes the new one)
+    int rc = need_zeroed_vec(c, tmp);
+    if (rc) return rc;
+    rc = eval_core(c, f0, 1, 0, tmp, nullptr, nullptr, nullptr, nullptr);
+    c->dn = std::move(tmp);
     return rc;
 }
 
@@ -1227,11 +1182,40 @@ int mbar_logden(mbar_ctx* c, const double* f, double* out_n) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    if (c->u_poison || !f_is_finite(c, f, 1)) {
-        std::fill(out_n, out_n + c->N, std::numeric_limits<double>::quiet_NaN());
+    if (unusable(c, f)) {
+        fill_nan(out_n, c->N);
         return MBAR_OK;
     }
     HIPCHK(c, hipMemcpyAsync(out_n, c->logden[0], (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+// One log-normaliser sweep: log sum_n c_n exp(-row_kn - logden_n) of the K rows of `c` (a context, or an extension) against the
+// log-denominators in slot 0 of `den` (c itself, or the extension's base) and den's multiplicities, as per-row maximum hm and
+// sum hs of this rank: the normaliser is hm + log(hs)
+static int lognum_sweep(mbar_ctx* c, mbar_ctx* den, std::vector<double>& hm, std::vector<double>& hs) {
+    const int64_t nch = lognum_chunks(c->N, c->K);
+    int rc = ensure(c, c->lognum_part, (size_t)2 * c->K * nch + 2 * c->K);
+    if (rc) return rc;
+    double* pmax = c->lognum_part;
+    double* psum = pmax + (size_t)c->K * nch;
+    double* omax = psum + (size_t)c->K * nch;
+    double* osum = omax + c->K;
+    HIPCHK(c, hipMemsetAsync(d_anum(c), 0, (size_t)c->Kp * sizeof(double), c->stream));  // anum = 0
+    const double* lden = den->logden[0];
+    if (den->weighted) {  // log sum_n c_n exp(...) = log sum_n exp(... + ln c_n)
+        HIPCHK(c, launch_shift_logden(c->stream, den->logden[0], den->cw, 1.0, den->N, den->lden_eff));
+        lden = den->lden_eff;
+    }
+    {
+        ScopedTimer t(c, MBAR_TIMER_OTHER);
+        HIPCHK(c, launch_lognum(c->stream, c->u, c->ld, c->N, c->K, d_anum(c), lden, pmax, psum, nch));
+        HIPCHK(c, launch_lognum_merge(c->stream, pmax, psum, c->K, nch, omax, osum));
+    }
+    hm.resize(c->K);
+    hs.resize(c->K);
+    HIPCHK(c, hipMemcpyAsync(hm.data(), omax, c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hs.data(), osum, c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     return sync_stream(c);
 }
 
@@ -1240,32 +1224,12 @@ int mbar_lognum(mbar_ctx* c, const double* f, double* lognum) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    if (c->u_poison || !f_is_finite(c, f, 1)) {
-        std::fill(lognum, lognum + c->K, std::numeric_limits<double>::quiet_NaN());
+    if (unusable(c, f)) {
+        fill_nan(lognum, c->K);
         return MBAR_OK;
     }
-    const int64_t nch = lognum_chunks(c->N, c->K);
-    rc = ensure(c, &c->lognum_part, &c->lognum_part_doubles, (size_t)2 * c->K * nch + 2 * c->K);
-    if (rc) return rc;
-    double* pmax = c->lognum_part;
-    double* psum = pmax + (size_t)c->K * nch;
-    double* omax = psum + (size_t)c->K * nch;
-    double* osum = omax + c->K;
-    HIPCHK(c, hipMemsetAsync(d_anum(c), 0, (size_t)c->Kp * sizeof(double), c->stream));  // anum = 0
-    const double* lden = c->logden[0];
-    if (c->weighted) {  // log sum_n c_n exp(...) = log sum_n exp(... + ln c_n)
-        HIPCHK(c, launch_shift_logden(c->stream, c->logden[0], c->cw, 1.0, c->N, c->lden_eff));
-        lden = c->lden_eff;
-    }
-    {
-        ScopedTimer t(c, MBAR_TIMER_OTHER);
-        HIPCHK(c, launch_lognum(c->stream, c->u, c->ld, c->N, c->K, d_anum(c), lden, pmax, psum, nch));
-        HIPCHK(c, launch_lognum_merge(c->stream, pmax, psum, c->K, nch, omax, osum));
-    }
-    std::vector<double> hm(c->K), hs(c->K);
-    HIPCHK(c, hipMemcpyAsync(hm.data(), omax, c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hs.data(), osum, c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    rc = sync_stream(c);
+    std::vector<double> hm, hs;
+    rc = lognum_sweep(c, c, hm, hs);
     if (rc) return rc;
     if (c->nranks > 1) {
         std::vector<double> gm = hm;
@@ -1294,30 +1258,29 @@ static int logw_impl(mbar_ctx* c, const double* f, double* out_kn, int64_t ld_ou
     HIPCHK(c, hipSetDevice(c->device));
     int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    if (c->u_poison || !f_is_finite(c, f, 1)) {
-        for (int64_t k = 0; k < c->K; ++k) std::fill(out_kn + k * ld_out, out_kn + k * ld_out + c->N, std::numeric_limits<double>::quiet_NaN());
+    if (unusable(c, f)) {
+        for (int64_t k = 0; k < c->K; ++k) fill_nan(out_kn + k * ld_out, c->N);
         return MBAR_OK;
     }
     // stream the result through a device staging buffer in row blocks to bound extra memory
     const int64_t rows_per = std::max<int64_t>(1, std::min<int64_t>(c->K, (int64_t)((256ull << 20) / ((size_t)c->ld * 8))));
-    double* stage = nullptr;
-    HIPCHK(c, cache_malloc((void**)&stage, (size_t)rows_per * c->ld * sizeof(double)));
+    DevBuf<double> stage;
+    HIPCHK(c, stage.grow((size_t)rows_per * c->ld));
     HIPCHK(c, hipMemcpyAsync(d_f(c), f, c->K * sizeof(double), hipMemcpyHostToDevice, c->stream));
     for (int64_t k0 = 0; k0 < c->K; k0 += rows_per) {
         const int64_t nr = std::min(rows_per, c->K - k0);
         {
             ScopedTimer t(c, MBAR_TIMER_OTHER);
             hipError_t e = launch_logw(c->stream, c->u + k0 * c->ld, c->ld, c->N, nr, d_f(c) + k0, c->logden[0], stage, c->ld, exponentiate);
-            if (e != hipSuccess) { (void)cache_free(stage); return fail(c, MBAR_ERR_HIP, hipGetErrorString(e)); }
+            if (e != hipSuccess) return fail(c, MBAR_ERR_HIP, hipGetErrorString(e));
         }
         hipError_t e = hipMemcpy2DAsync(out_kn + k0 * ld_out, (size_t)ld_out * sizeof(double), stage,
                                         (size_t)c->ld * sizeof(double), (size_t)c->N * sizeof(double), (size_t)nr,
                                         hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { (void)cache_free(stage); return fail(c, MBAR_ERR_HIP, hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(c, MBAR_ERR_HIP, hipGetErrorString(e));
     }
     flush_timers(c);
-    HIPCHK(c, cache_free(stage));
     return MBAR_OK;
 }
 
@@ -1326,9 +1289,9 @@ int mbar_gram_w(mbar_ctx* c, const double* f, double* gramW, double* wsum) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
-    if (c->u_poison || !f_is_finite(c, f, 1)) {
-        if (gramW) std::fill(gramW, gramW + (size_t)c->K * c->K, std::numeric_limits<double>::quiet_NaN());
-        if (wsum) std::fill(wsum, wsum + c->K, std::numeric_limits<double>::quiet_NaN());
+    if (unusable(c, f)) {
+        fill_nan(gramW, (size_t)c->K * c->K);
+        fill_nan(wsum, c->K);
         return MBAR_OK;
     }
     GramPlan plan = plan_for(c);
@@ -1381,30 +1344,13 @@ int mbar_ctx_create_ext(mbar_ctx** out, mbar_ctx* base, int64_t K_rows) {
     c->ld = base->ld;
     c->num_cu = base->num_cu;
     c->ext_base = base;
-#define CRT(expr)                                                                                   \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) {                                                                     \
-            int rc_ = fail(nullptr, MBAR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-            mbar_ctx_destroy(c);                                                                    \
-            return rc_;                                                                             \
-        }                                                                                           \
-    } while (0)
     CRT(hipSetDevice(c->device));
-    {
-        std::lock_guard<std::mutex> lock(g_dev_mu);
-        auto& pool = g_stream_pool[c->device];
-        if (!pool.empty()) {
-            c->stream = pool.back();
-            pool.pop_back();
-        }
-    }
+    c->stream = take_pooled_stream(c->device);
     if (!c->stream) CRT(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const size_t pitch = (size_t)c->ld * sizeof(double);
-    const size_t ubytes = (size_t)c->Kp * pitch;
-    CRT(cache_malloc((void**)&c->u_alloc, ubytes + pitch));
+    CRT(c->u_alloc.grow((size_t)(c->Kp + 1) * c->ld));
     {   // first address of the allocation that is congruent to base->u modulo the row pitch
-        const uintptr_t a = reinterpret_cast<uintptr_t>(c->u_alloc), b = reinterpret_cast<uintptr_t>(base->u);
+        const uintptr_t a = reinterpret_cast<uintptr_t>(c->u_alloc.p), b = reinterpret_cast<uintptr_t>(base->u);
         const uintptr_t r = a >= b ? (a - b) % pitch : (pitch - (b - a) % pitch) % pitch;
         c->u = reinterpret_cast<double*>(a + (r == 0 ? 0 : pitch - r));
     }
@@ -1414,66 +1360,23 @@ int mbar_ctx_create_ext(mbar_ctx** out, mbar_ctx* base, int64_t K_rows) {
     if (c->Kp > c->K) CRT(launch_zero(c->stream, c->u + (size_t)c->K * c->ld, (size_t)(c->Kp - c->K) * pitch));
     if (c->ld > c->N)
         CRT(hipMemset2DAsync(c->u + c->N, pitch, 0, (size_t)(c->ld - c->N) * sizeof(double), (size_t)c->K, c->stream));
-    CRT(cache_malloc((void**)&c->logden[0], (size_t)3 * 16 * sizeof(double)));  // (never swept on its own: the log-denominators are the base's)
-    c->logden[1] = c->logden[2] = c->logden[0];
-    CRT(cache_malloc((void**)&c->small, small_doubles(256) * sizeof(double)));
-    CRT(cache_host_malloc((void**)&c->hstage, (size_t)4 * 256 * sizeof(double)));
+    CRT(c->logden_alloc.grow((size_t)3 * 16));  // (never swept on its own: the log-denominators are the base's)
+    c->logden[0] = c->logden[1] = c->logden[2] = c->logden_alloc;
+    CRT(c->small.grow(small_doubles(256)));
+    CRT(c->hstage.grow((size_t)4 * 256));
     CRT(hipMemsetAsync(c->small, 0, small_doubles(256) * sizeof(double), c->stream));
     CRT(hipStreamSynchronize(c->stream));
-#undef CRT
     c->Nk.assign(K_rows, 0.0);
     c->lnNk.assign(K_rows, 0.0);
     *out = c;
     return MBAR_OK;
 }
+#undef CRT
 
 static int ext_pair_ok(mbar_ctx* ext, mbar_ctx* base, const char* who) {
     if (!ext || !base) return fail(ext, MBAR_ERR_ARG, std::string(who) + ": NULL context");
     if (ext->ext_base != base) return fail(ext, MBAR_ERR_ARG, std::string(who) + ": the first context is not an extension of the second");
     return MBAR_OK;
-}
-static void ext_touched(mbar_ctx* c) {
-    c->u_checked = false;
-    c->P_valid = false;
-    c->last_psum.clear();
-}
-
-// dst rows = src rows - v (v_host, or NULL: the vector staged in dst by the previous call / mbar_ctx_vec_logshift); src is dst or its base
-int mbar_ctx_rows_sub_from(mbar_ctx* dst, int64_t dst_row0, mbar_ctx* src, int64_t src_row0, int64_t nrows, const double* v_host) {
-    if (!dst || !src) return fail(dst, MBAR_ERR_ARG, "NULL argument");
-    if (src != dst && dst->ext_base != src) return fail(dst, MBAR_ERR_ARG, "mbar_ctx_rows_sub_from: src must be dst or its base");
-    if (nrows < 0 || dst_row0 < 0 || src_row0 < 0 || dst_row0 + nrows > dst->K || src_row0 + nrows > src->K)
-        return fail(dst, MBAR_ERR_ARG, "row range out of bounds");
-    if (src == dst && dst_row0 != src_row0 && dst_row0 < src_row0 + nrows && src_row0 < dst_row0 + nrows)
-        return fail(dst, MBAR_ERR_ARG, "mbar_ctx_rows_sub_from: the row ranges overlap");
-    if (!v_host && !dst->vec_tmp) return fail(dst, MBAR_ERR_STATE, "mbar_ctx_rows_sub_from: no vector has been uploaded yet");
-    if (nrows == 0) return MBAR_OK;
-    HIPCHK(dst, hipSetDevice(dst->device));
-    if (src != dst) HIPCHK(dst, hipStreamSynchronize(src->stream));
-    if (!dst->vec_tmp) HIPCHK(dst, cache_malloc((void**)&dst->vec_tmp, (size_t)dst->ld * sizeof(double)));
-    if (v_host) {
-        dst->vec_holds_logshift = false;
-        HIPCHK(dst, hipMemcpyAsync(dst->vec_tmp, v_host, (size_t)dst->N * sizeof(double), hipMemcpyHostToDevice, dst->stream));
-    }
-    HIPCHK(dst, launch_rows_sub(dst->stream, dst->u + dst_row0 * dst->ld, src->u + src_row0 * src->ld, dst->ld, nrows, dst->vec_tmp, dst->N));
-    ext_touched(dst);
-    return sync_stream(dst);
-}
-
-// dst rows = src rows - dst rows
-int mbar_ctx_rows_rsub_from(mbar_ctx* dst, int64_t dst_row0, mbar_ctx* src, int64_t src_row0, int64_t nrows) {
-    if (!dst || !src) return fail(dst, MBAR_ERR_ARG, "NULL argument");
-    if (src != dst && dst->ext_base != src) return fail(dst, MBAR_ERR_ARG, "mbar_ctx_rows_rsub_from: src must be dst or its base");
-    if (nrows < 0 || dst_row0 < 0 || src_row0 < 0 || dst_row0 + nrows > dst->K || src_row0 + nrows > src->K)
-        return fail(dst, MBAR_ERR_ARG, "row range out of bounds");
-    if (src == dst && dst_row0 < src_row0 + nrows && src_row0 < dst_row0 + nrows)
-        return fail(dst, MBAR_ERR_ARG, "mbar_ctx_rows_rsub_from: the row ranges overlap");
-    if (nrows == 0) return MBAR_OK;
-    HIPCHK(dst, hipSetDevice(dst->device));
-    if (src != dst) HIPCHK(dst, hipStreamSynchronize(src->stream));
-    HIPCHK(dst, launch_rows_rsub(dst->stream, dst->u + dst_row0 * dst->ld, src->u + src_row0 * src->ld, dst->ld, nrows, dst->N));
-    ext_touched(dst);
-    return sync_stream(dst);
 }
 
 // dst rows = base rows [state_row0 ..) - log(base rows [obs_row0 ..) - shift_r), shift_r = min_r - |4 eps min_r| (mbar.py:827-832)
@@ -1486,20 +1389,19 @@ int mbar_ctx_rows_obs_from(mbar_ctx* dst, int64_t dst_row0, mbar_ctx* base, int6
     int rc = ext_pair_ok(dst, base, "mbar_ctx_rows_obs_from");
     if (rc) return rc;
     if (!shift_out) return fail(dst, MBAR_ERR_ARG, "NULL argument");
-    if (nrows < 0 || dst_row0 < 0 || state_row0 < 0 || obs_row0 < 0 || dst_row0 + nrows > dst->K || state_row0 + nrows > base->K ||
-        obs_row0 + nrows > base->K)
+    if (!rows_in_range(dst, dst_row0, nrows) || !rows_in_range(base, state_row0, nrows) || !rows_in_range(base, obs_row0, nrows))
         return fail(dst, MBAR_ERR_ARG, "row range out of bounds");
     if (nrows == 0) return MBAR_OK;
     HIPCHK(dst, hipSetDevice(dst->device));
     HIPCHK(dst, hipStreamSynchronize(base->stream));
-    rc = ensure(dst, &dst->scratch, &dst->scratch_doubles, (size_t)nrows * 257);
+    rc = ensure(dst, dst->scratch, (size_t)nrows * 257);
     if (rc) return rc;
     double* shift_dev = dst->scratch + (size_t)nrows * 256;
     if (min_in) HIPCHK(dst, hipMemcpyAsync(dst->scratch, min_in, (size_t)nrows * sizeof(double), hipMemcpyHostToDevice, dst->stream));
     HIPCHK(dst, launch_rows_obs(dst->stream, dst->u + dst_row0 * dst->ld, base->u + obs_row0 * base->ld, base->u + state_row0 * base->ld,
                                 dst->ld, nrows, dst->N, dst->scratch, shift_dev, min_in != nullptr));
     HIPCHK(dst, hipMemcpyAsync(shift_out, shift_dev, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, dst->stream));
-    ext_touched(dst);
+    matrix_touched(dst);
     rc = sync_stream(dst);
     if (rc) return rc;
     if (min_out) {  // shift = m - |4 eps m|  <=>  m = shift / (1 -+ 4 eps): the minimum itself is what the kernel reduces, so hand back ITS bits
@@ -1532,32 +1434,12 @@ int mbar_lognum_ext(mbar_ctx* ext, mbar_ctx* base, const double* f_base, double*
     if (rc) return fail(ext, rc, std::string("mbar_lognum_ext: ") + mbar_last_error(base));
     rc = refresh_poison(ext);
     if (rc) return rc;
-    if (base->u_poison || ext->u_poison || !f_is_finite(base, f_base, 1)) {
-        std::fill(lognum_ext, lognum_ext + ext->K, std::numeric_limits<double>::quiet_NaN());
+    if (unusable(base, f_base) || ext->u_poison) {
+        fill_nan(lognum_ext, ext->K);
         return MBAR_OK;
     }
-    const int64_t nch = lognum_chunks(ext->N, ext->K);
-    rc = ensure(ext, &ext->lognum_part, &ext->lognum_part_doubles, (size_t)2 * ext->K * nch + 2 * ext->K);
-    if (rc) return rc;
-    double* pmax = ext->lognum_part;
-    double* psum = pmax + (size_t)ext->K * nch;
-    double* omax = psum + (size_t)ext->K * nch;
-    double* osum = omax + ext->K;
-    HIPCHK(ext, hipMemsetAsync(d_anum(ext), 0, (size_t)ext->Kp * sizeof(double), ext->stream));  // anum = 0
-    const double* lden = base->logden[0];
-    if (base->weighted) {  // log sum_n c_n exp(...) = log sum_n exp(... + ln c_n)
-        HIPCHK(ext, launch_shift_logden(ext->stream, base->logden[0], base->cw, 1.0, base->N, base->lden_eff));
-        lden = base->lden_eff;
-    }
-    {
-        ScopedTimer t(ext, MBAR_TIMER_OTHER);
-        HIPCHK(ext, launch_lognum(ext->stream, ext->u, ext->ld, ext->N, ext->K, d_anum(ext), lden, pmax, psum, nch));
-        HIPCHK(ext, launch_lognum_merge(ext->stream, pmax, psum, ext->K, nch, omax, osum));
-    }
-    std::vector<double> hm(ext->K), hs(ext->K);
-    HIPCHK(ext, hipMemcpyAsync(hm.data(), omax, ext->K * sizeof(double), hipMemcpyDeviceToHost, ext->stream));
-    HIPCHK(ext, hipMemcpyAsync(hs.data(), osum, ext->K * sizeof(double), hipMemcpyDeviceToHost, ext->stream));
-    rc = sync_stream(ext);
+    std::vector<double> hm, hs;
+    rc = lognum_sweep(ext, base, hm, hs);
     if (rc) return rc;
     for (int64_t k = 0; k < ext->K; ++k) lognum_ext[k] = hm[k] + std::log(hs[k]);
     return MBAR_OK;
@@ -1580,58 +1462,49 @@ int mbar_gram_w_ext(mbar_ctx* ext, mbar_ctx* base, const double* f_base, const d
     rc = refresh_poison(ext);
     if (rc) return rc;
     const int64_t Kb = base->K, Ke = ext->K, Kt = Kb + Ke, rows = base->Kp + ext->Kp;
-    bool finite = f_is_finite(base, f_base, 1);
+    bool finite = true;
     for (int64_t k = 0; k < Ke; ++k) finite = finite && std::isfinite(f_ext[k]);
-    if (base->u_poison || ext->u_poison || !finite) {
-        std::fill(gramW, gramW + (size_t)Kt * Kt, std::numeric_limits<double>::quiet_NaN());
-        if (wsum) std::fill(wsum, wsum + Kt, std::numeric_limits<double>::quiet_NaN());
+    if (unusable(base, f_base) || ext->u_poison || !finite) {
+        fill_nan(gramW, (size_t)Kt * Kt);
+        fill_nan(wsum, Kt);
         return MBAR_OK;
     }
-    const double* logden_thin = base->logden[0];
+    const double ninf = -std::numeric_limits<double>::infinity();
+    const int64_t ntiles = (ext->N + TS - 1) / TS;
+    // first row of the extension, counted in row pitches from the base's matrix
+    const int64_t row_e = (reinterpret_cast<intptr_t>(ext->u) - reinterpret_cast<intptr_t>(base->u)) / (intptr_t)((size_t)base->ld * sizeof(double));
+    double* an_dev = ext->small;  // (small_doubles(256) of them)
+    const double* logden = base->logden[0];
+    auto fold_weights = [&]() -> int {  // sum_n c_n p p^T: each operand carries sqrt(c_n), folded into the exponent
+        if (!base->weighted) return MBAR_OK;
+        HIPCHK(ext, launch_shift_logden(ext->stream, logden, base->cw, 0.5, base->N, base->lden_eff));
+        logden = base->lden_eff;
+        return MBAR_OK;
+    };
     if (gram_base && Ke <= 16 && base->Kp == 128) {
-        if (base->weighted) {
-            HIPCHK(ext, launch_shift_logden(ext->stream, logden_thin, base->cw, 0.5, base->N, base->lden_eff));
-            logden_thin = base->lden_eff;
-        }
-        const double ninf = -std::numeric_limits<double>::infinity();
+        rc = fold_weights();
+        if (rc) return rc;
         std::vector<double> an((size_t)128 + 16, ninf);  // [f_base padded to 128 | f_ext padded to 16]
         for (int64_t k = 0; k < Kb; ++k) an[k] = f_base[k];
         for (int64_t k = 0; k < Ke; ++k) an[(size_t)128 + k] = f_ext[k];
-        double* an_dev = ext->small;
         HIPCHK(ext, hipMemcpyAsync(an_dev, an.data(), an.size() * sizeof(double), hipMemcpyHostToDevice, ext->stream));
-        const int64_t ntiles = (ext->N + TS - 1) / TS;
-        const int64_t row_e = (reinterpret_cast<intptr_t>(ext->u) - reinterpret_cast<intptr_t>(base->u)) / (intptr_t)((size_t)base->ld * sizeof(double));
         rc = ensure_red(ext, (size_t)9 * 256);
         if (rc) return rc;
-        {   // rectangle: I = the appended block row, J = the resident panel
-            LaunchGeom g = gram_geometry(144, false, ext->num_cu, ntiles, ext->opt_grid);
-            const size_t rec = (size_t)8 * 256;
-            rc = ensure(ext, &ext->part, &ext->part_doubles, (size_t)g.nwaves * rec);
-            if (rc) return rc;
-            rc = ensure(ext, &ext->scratch, &ext->scratch_doubles, ((size_t)g.nwaves / 32 + 1) * rec);
-            if (rc) return rc;
-            {
-                ScopedTimer t(ext, MBAR_TIMER_GRAM);
-                HIPCHK(ext, launch_gram_thin(ext->stream, g, base->u, base->ld, base->N, an_dev + 128, an_dev, logden_thin, row_e, 0, ext->part));
-            }
-            ScopedTimer t(ext, MBAR_TIMER_REDUCE);
-            HIPCHK(ext, launch_reduce(ext->stream, ext->part, g.nwaves, (int64_t)rec, ext->scratch, ext->red));
-        }
-        {   // the appended rows among themselves
-            LaunchGeom g = gram_geometry(16, true, ext->num_cu, ntiles, ext->opt_grid);
-            const size_t rec = 256;
-            rc = ensure(ext, &ext->part, &ext->part_doubles, (size_t)g.nwaves * rec);
-            if (rc) return rc;
-            rc = ensure(ext, &ext->scratch, &ext->scratch_doubles, ((size_t)g.nwaves / 32 + 1) * rec);
-            if (rc) return rc;
-            {
-                ScopedTimer t(ext, MBAR_TIMER_GRAM);
-                LoopCtl lo;
-                HIPCHK(ext, launch_gram_diag(ext->stream, 1, g, ext->u, ext->ld, ext->N, an_dev + 128, logden_thin, 0, ext->part, nullptr, lo));
-            }
-            ScopedTimer t(ext, MBAR_TIMER_REDUCE);
-            HIPCHK(ext, launch_reduce(ext->stream, ext->part, g.nwaves, (int64_t)rec, ext->scratch, ext->red + 8 * 256));
-        }
+        // rectangle: I = the appended block row, J = the resident panel
+        LaunchGeom g = gram_geometry(144, false, ext->num_cu, ntiles, ext->opt_grid);
+        rc = launch_and_reduce(ext, g.nwaves, (size_t)8 * 256, ext->red, [&]() -> int {
+            HIPCHK(ext, launch_gram_thin(ext->stream, g, base->u, base->ld, base->N, an_dev + 128, an_dev, logden, row_e, 0, ext->part));
+            return MBAR_OK;
+        });
+        if (rc) return rc;
+        // the appended rows among themselves
+        g = gram_geometry(16, true, ext->num_cu, ntiles, ext->opt_grid);
+        rc = launch_and_reduce(ext, g.nwaves, 256, ext->red + 8 * 256, [&]() -> int {
+            LoopCtl lo;
+            HIPCHK(ext, launch_gram_diag(ext->stream, 1, g, ext->u, ext->ld, ext->N, an_dev + 128, logden, 0, ext->part, nullptr, lo));
+            return MBAR_OK;
+        });
+        if (rc) return rc;
         HIPCHK(ext, hipMemcpyAsync(ext->hred, ext->red, (size_t)9 * 256 * sizeof(double), hipMemcpyDeviceToHost, ext->stream));
         rc = sync_stream(ext);
         if (rc) return rc;
@@ -1645,56 +1518,37 @@ int mbar_gram_w_ext(mbar_ctx* ext, mbar_ctx* base, const double* f_base, const d
             }
             for (int64_t q = 0; q < Ke; ++q) gramW[(size_t)(Kb + r) * Kt + Kb + q] = ext->hred[(size_t)8 * 256 + r * 16 + q];
         }
-        if (wsum) {
-            std::vector<double> Nk((size_t)Kt, 0.0);
-            for (int64_t k = 0; k < Kb; ++k) Nk[k] = base->Nk[k];
-            gram_operand_sums(gramW, Kt, Nk.data(), wsum);
-        }
-        return MBAR_OK;
+    } else {
+        const int nbt = (int)(rows / 16);
+        GramPlan plan = gram_plan(rows, true);
+        const size_t total = plan.total_blocks * 256;
+        rc = ensure_red(ext, total);
+        if (rc) return rc;
+        // operand constants of the joint panel: f_base, padding, f_ext, padding (-inf: a zero operand)
+        std::vector<double> an((size_t)rows, ninf);
+        for (int64_t k = 0; k < Kb; ++k) an[k] = f_base[k];
+        for (int64_t k = 0; k < Ke; ++k) an[(size_t)base->Kp + k] = f_ext[k];
+        HIPCHK(ext, hipMemcpyAsync(an_dev, an.data(), an.size() * sizeof(double), hipMemcpyHostToDevice, ext->stream));
+        rc = fold_weights();
+        if (rc) return rc;
+        LaunchGeom g = gram_quad_geometry(nbt, ext->num_cu, ntiles, ext->opt_grid);
+        // (padding blocks at the END of the joint panel are left out of the sweep like quad_trim does for one matrix)
+        g.live_blocks = ext->opt_quad_trim ? (int)((base->Kp + Ke + 15) / 16) : 0;
+        rc = launch_and_reduce(ext, g.nwaves, total, ext->red, [&]() -> int {
+            HIPCHK(ext, launch_gram_quad_split(ext->stream, nbt, g, base->u, base->ld, base->N, an_dev, logden, ext->part, base->Kp, row_e));
+            return MBAR_OK;
+        });
+        if (rc) return rc;
+        HIPCHK(ext, hipMemcpyAsync(ext->hred, ext->red, total * sizeof(double), hipMemcpyDeviceToHost, ext->stream));
+        rc = sync_stream(ext);
+        if (rc) return rc;
+        std::vector<double> Gp((size_t)rows * rows, 0.0);
+        unpack_gram(plan, ext->hred, rows, Gp.data());
+        auto src = [&](int64_t k) { return k < Kb ? k : base->Kp + (k - Kb); };
+        for (int64_t i = 0; i < Kt; ++i)
+            for (int64_t j = 0; j < Kt; ++j) gramW[(size_t)i * Kt + j] = Gp[(size_t)src(i) * rows + src(j)];
     }
-    const int nbt = (int)(rows / 16);
-    GramPlan plan = gram_plan(rows, true);
-    const size_t total = plan.total_blocks * 256;
-    rc = ensure_red(ext, total);
-    if (rc) return rc;
-    // operand constants of the joint panel: f_base, padding, f_ext, padding (-inf: a zero operand)
-    std::vector<double> an((size_t)rows, -std::numeric_limits<double>::infinity());
-    for (int64_t k = 0; k < Kb; ++k) an[k] = f_base[k];
-    for (int64_t k = 0; k < Ke; ++k) an[(size_t)base->Kp + k] = f_ext[k];
-    double* an_dev = ext->small;  // (small_doubles(256) of them)
-    HIPCHK(ext, hipMemcpyAsync(an_dev, an.data(), an.size() * sizeof(double), hipMemcpyHostToDevice, ext->stream));
-    const double* logden = base->logden[0];
-    if (base->weighted) {  // sum_n c_n p p^T: each operand carries sqrt(c_n), folded into the exponent
-        HIPCHK(ext, launch_shift_logden(ext->stream, logden, base->cw, 0.5, base->N, base->lden_eff));
-        logden = base->lden_eff;
-    }
-    const int64_t ntiles = (ext->N + TS - 1) / TS;
-    LaunchGeom g = gram_quad_geometry(nbt, ext->num_cu, ntiles, ext->opt_grid);
-    // (padding blocks at the END of the joint panel are left out of the sweep like quad_trim does for one matrix)
-    g.live_blocks = ext->opt_quad_trim ? (int)((base->Kp + Ke + 15) / 16) : 0;
-    const size_t rec = (size_t)plan.items[0].nblk * 256;
-    rc = ensure(ext, &ext->part, &ext->part_doubles, (size_t)g.nwaves * rec);
-    if (rc) return rc;
-    rc = ensure(ext, &ext->scratch, &ext->scratch_doubles, ((size_t)g.nwaves / 32 + 1) * rec);
-    if (rc) return rc;
-    const int64_t row_j0 = (reinterpret_cast<intptr_t>(ext->u) - reinterpret_cast<intptr_t>(base->u)) / (intptr_t)((size_t)base->ld * sizeof(double));
-    {
-        ScopedTimer t(ext, MBAR_TIMER_GRAM);
-        HIPCHK(ext, launch_gram_quad_split(ext->stream, nbt, g, base->u, base->ld, base->N, an_dev, logden, ext->part, base->Kp, row_j0));
-    }
-    {
-        ScopedTimer t(ext, MBAR_TIMER_REDUCE);
-        HIPCHK(ext, launch_reduce(ext->stream, ext->part, g.nwaves, (int64_t)rec, ext->scratch, ext->red));
-    }
-    HIPCHK(ext, hipMemcpyAsync(ext->hred, ext->red, total * sizeof(double), hipMemcpyDeviceToHost, ext->stream));
-    rc = sync_stream(ext);
-    if (rc) return rc;
-    std::vector<double> Gp((size_t)rows * rows, 0.0);
-    unpack_gram(plan, ext->hred, rows, Gp.data());
-    auto src = [&](int64_t k) { return k < Kb ? k : base->Kp + (k - Kb); };
-    for (int64_t i = 0; i < Kt; ++i)
-        for (int64_t j = 0; j < Kt; ++j) gramW[(size_t)i * Kt + j] = Gp[(size_t)src(i) * rows + src(j)];
-    if (wsum) {
+    if (wsum) {  // sum_n W_nj with N_k = 0 for the appended rows
         std::vector<double> Nk((size_t)Kt, 0.0);
         for (int64_t k = 0; k < Kb; ++k) Nk[k] = base->Nk[k];
         gram_operand_sums(gramW, Kt, Nk.data(), wsum);

@@ -222,6 +222,51 @@ inline hipError_t cache_free(void* p) { return g_mem.release(p); }
 inline hipError_t cache_host_malloc(void** p, size_t bytes) { return g_mem.alloc(p, bytes, true); }
 inline hipError_t cache_host_free(void* p) { return g_mem.release(p); }
 
+// One block of the cache, owned: freed when the owner goes
+// (Pinned: page-locked host memory of the same cache, mapped into the device's address space)
+template <typename T, bool Pinned = false>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;  // capacity in elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) {
+        o.p = nullptr;
+        o.n = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    void reset() {
+        if (p) (void)cache_free(p);
+        p = nullptr;
+        n = 0;
+    }
+    // at least `want` elements (contents are not kept)
+    auto grow(size_t want) -> hipError_t {
+        if (n >= want) return hipSuccess;
+        if (p) {
+            hipError_t e = cache_free(p);
+            if (e != hipSuccess) return e;
+        }
+        p = nullptr;
+        n = 0;
+        hipError_t e = g_mem.alloc((void**)&p, want * sizeof(T), Pinned);
+        if (e == hipSuccess) n = want;
+        return e;
+    }
+    // grow(count), then the synchronous copy of `count` elements from the host to the buffer's start
+    auto upload(const T* src, size_t count) -> hipError_t {
+        hipError_t e = grow(count);
+        return e != hipSuccess ? e : hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+
 struct TimerPair {
     hipEvent_t a, b;
     int which;
@@ -231,6 +276,7 @@ struct TimerPair {
 }  // namespace host
 }  // namespace mbar
 using mbar::host::TimerPair;
+using mbar::host::DevBuf;
 
 // In-process transport: the contexts of several caller threads on ONE device meet in a stream-ordered all-reduce (events
 // across their streams, a rendezvous of the host threads per collective, no host-device synchronisation).  It drives exactly
@@ -267,30 +313,29 @@ struct mbar_ctx {
     bool u_posinf = true;                      // +inf entries (legal) may be present: keep the exponentials clamped
     std::vector<double> Nk, lnNk;   // K
     std::vector<int> sampled;       // indices with N_k > 0
-    // device
-    double* u = nullptr;
-    double* u_alloc = nullptr;  // extension contexts (mbar_ctx_create_ext): the allocation `u` points into
-    mbar_ctx* ext_base = nullptr;  // ... and the context whose rows theirs are appended to
-    double* logden[3] = {nullptr, nullptr, nullptr};
-    double* dn = nullptr;           // objective offsets (or null)
-    double* cw = nullptr;           // per-sample multiplicities (ld doubles; 1 on data, 0 on padding by default)
-    double* lden_eff = nullptr;     // logden - alpha ln c for the kernels that consume logden (only when weighted)
+    // device: every DevBuf member owns its block of the cache and gives it back when the context is deleted (mbar_ctx_destroy
+    // drains the stream first); the raw pointers next to them are views into those blocks
+    DevBuf<double> u_alloc;         // the matrix's allocation
+    double* u = nullptr;            // ... and the matrix: the allocation's start, or (extension contexts) the first address in it
+                                    // that lies a whole number of row pitches from the base's matrix
+    mbar_ctx* ext_base = nullptr;   // extension contexts (mbar_ctx_create_ext): the context whose rows theirs are appended to
+    DevBuf<double> logden_alloc;    // three logden vectors in ONE allocation ...
+    double* logden[3] = {nullptr, nullptr, nullptr};  // ... and the three slots in it
+    DevBuf<double> dn;              // objective offsets (or null)
+    DevBuf<double> cw;              // per-sample multiplicities (ld doubles; 1 on data, 0 on padding by default)
+    DevBuf<double> lden_eff;        // logden - alpha ln c for the kernels that consume logden (only when weighted)
     bool weighted = false;
-    double* small = nullptr;        // aden[2][Kp] | anum[Kp] | f[Kp] | Nk[Kp] | lnNk[Kp] | delta[...]
-    double* part = nullptr;         // per-wave partial records
-    size_t part_doubles = 0;
-    double* scratch = nullptr;      // level-1 reduction scratch
-    size_t scratch_doubles = 0;
-    double* red = nullptr;          // reduced outputs (contiguous: psum | obj | gram blocks)
-    size_t red_doubles = 0;
-    double* hred = nullptr;         // pinned host mirror of red
-    double* hstage = nullptr;       // pinned staging for the small per-sweep uploads (2 Kp doubles), no sync needed
-    double* lognum_part = nullptr;
-    size_t lognum_part_doubles = 0;
-    double* f_hist = nullptr;       // SCI f history [batch][Kp]
-    double* vec_tmp = nullptr;      // staging for one N_local-vector (mbar_ctx_row_sub)
-    int64_t* boot_idx = nullptr;    // bootstrap draws: cum[K + 1] | order[total] (mbar_ctx_draw_bootstrap_weights keeps the last layout)
-    size_t boot_idx_words = 0;
+    DevBuf<double> small;           // aden[2][Kp] | anum[Kp] | f[Kp] | Nk[Kp] | lnNk[Kp] | delta[...]
+    DevBuf<double> part;            // per-wave partial records
+    DevBuf<double> scratch;         // level-1 reduction scratch
+    DevBuf<double> red;             // reduced outputs (contiguous: psum | obj | gram blocks)
+    DevBuf<double, true> hred;      // pinned host mirror of red
+    DevBuf<double, true> hstage;    // pinned staging for the small per-sweep uploads (2 Kp doubles), no sync needed
+    DevBuf<double> lognum_part;
+    DevBuf<double> f_hist;          // SCI f history [batch][Kp]
+    DevBuf<double> vec_tmp;         // staging for one N_local-vector (mbar_ctx_row_sub)
+    DevBuf<int64_t> boot_idx;       // bootstrap draws: cum[K + 1] | order[total] (mbar_ctx_draw_bootstrap_weights keeps the last layout)
+    size_t boot_idx_words = 0;      // words of the layout it holds
     uint64_t boot_layout_digest[2] = {0, 0};
     int64_t boot_states = 0, boot_total = 0;  // the layout on the device: number of runs, positions in total
     bool boot_has_order = false;
@@ -301,22 +346,21 @@ struct mbar_ctx {
     double sci_graph_tol = 0.0;
     // device-resident adaptive loop: solver state (f, psum, candidates, ratio, parameters, history), control words and
     // the sampled-state list live on the device; a batch of whole iterations can be replayed from a hipGraph
-    double* ad = nullptr;
+    DevBuf<double> ad;
     int64_t ad_hist_cap = 0;
-    int* ad_ints = nullptr;         // ctl[CTL_WORDS] | sampled[Kp]
-    int* h_ctl = nullptr;           // pinned mirror of the control words
+    DevBuf<int> ad_ints;            // ctl[CTL_WORDS] | sampled[Kp]
+    DevBuf<int, true> h_ctl;        // pinned mirror of the control words
     hipGraphExec_t ad_graph = nullptr;
     int64_t ad_graph_batch = 0, ad_graph_sig = 0;
     // P mode of that loop: resident probability matrix exp(a0 - u - logden(a0)), Kp x ld doubles, built once per solve
-    double* P = nullptr;
+    DevBuf<double> P;
     bool P_failed = false;          // the allocation did not fit: stay in the classic mode for the life of the context
-    double* pm_vec = nullptr;       // a0[Kp] | ccur[Kp] | cgram[Kp]
-    double* pm_ld0 = nullptr;       // host-driven loop on P (257 .. 1024 states): log-denominators at the anchor, ld doubles
-    double* part_g = nullptr;       // Gram partial records of the fused-sweep loop (the psum records use `part`)
-    size_t part_g_doubles = 0;
-    double* cwsq = nullptr;         // sqrt of the per-sample multiplicities (only when weighted; else cw itself serves)
-    double* chol = nullptr;         // workspace of the blocked Cholesky Newton solve (129 .. 256 states)
-    long long* stamps = nullptr;    // MBAR_DEBUG_STAMPS: phase stamps of k_select_newton (64 launches x 16)
+    DevBuf<double> pm_vec;          // a0[Kp] | ccur[Kp] | cgram[Kp]
+    DevBuf<double> pm_ld0;          // host-driven loop on P (257 .. 1024 states): log-denominators at the anchor, ld doubles
+    DevBuf<double> part_g;          // Gram partial records of the fused-sweep loop (the psum records use `part`)
+    DevBuf<double> cwsq;            // sqrt of the per-sample multiplicities (only when weighted; else cw itself serves)
+    DevBuf<double> chol;            // workspace of the blocked Cholesky Newton solve (129 .. 256 states)
+    long long* stamps = nullptr;    // MBAR_DEBUG_STAMPS: phase stamps of k_select_newton (64 launches x 16); hipMalloc, debug only
     // P outlives the solve that built it: a later solve on the same matrix whose start lies within the window of the anchor
     // (bootstrap replicates, protocol stages, continuation) starts with ONE fused sweep instead of the build sweep
     std::vector<double> last_psum;  // per-state sums at the f the last adaptive solve returned (empty: none)
@@ -357,50 +401,6 @@ inline int bad_arg(const std::string& msg) { return fail(nullptr, MBAR_ERR_ARG, 
 // ---- the handles of the other backends (mbar_kde, mbar_acf, mbar_bar, mbar_bspline, mbar_batch) -----------------------------
 // A handle derives from Handle, holds its device memory in DevBuf members, is made by create_handle and released by
 // destroy_handle: no buffer list to keep in step with the struct.
-
-// One block of the cache, owned: freed when the owner goes
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;  // capacity in elements
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) {
-        o.p = nullptr;
-        o.n = 0;
-    }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        std::swap(p, o.p);
-        std::swap(n, o.n);
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    operator T*() const { return p; }
-    void reset() {
-        if (p) (void)cache_free(p);
-        p = nullptr;
-        n = 0;
-    }
-    // at least `want` elements (contents are not kept)
-    auto grow(size_t want) -> hipError_t {
-        if (n >= want) return hipSuccess;
-        if (p) {
-            hipError_t e = cache_free(p);
-            if (e != hipSuccess) return e;
-        }
-        p = nullptr;
-        n = 0;
-        hipError_t e = cache_malloc((void**)&p, want * sizeof(T));
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    // grow(count), then the synchronous copy of `count` elements from the host to the buffer's start
-    auto upload(const T* src, size_t count) -> hipError_t {
-        hipError_t e = grow(count);
-        return e != hipSuccess ? e : hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
 
 // Makes `device` current after checking that it exists and is a gfx950; its properties are looked up once per process
 int open_device(int device, DevInfo* out);
@@ -585,7 +585,8 @@ struct GramPlan {
 void flush_timers(mbar_ctx* c);
 int sync_stream(mbar_ctx* c);
 int drop_graphs(mbar_ctx* c);
-int ensure(mbar_ctx* c, double** p, size_t* have, size_t want);
+int ensure(mbar_ctx* c, DevBuf<double>& buf, size_t want);  // grow, after drop_graphs: captured graphs hold these pointers
+int need_zeroed_vec(mbar_ctx* c, DevBuf<double>& v);  // one ld-vector, allocated and zeroed at its first use
 int refresh_poison(mbar_ctx* c);
 bool f_is_finite(const mbar_ctx* c, const double* f, int nf);
 bool loop_barrier(mbar_loopback* g);

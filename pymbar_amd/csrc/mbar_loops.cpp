@@ -44,21 +44,20 @@ int adaptive_host_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t 
     const GramPlan plan_p = hp ? (c->opt_host_pmode >= 2 ? gram_plan_pmode(Kp) : plan) : GramPlan();
     std::vector<double> a0, an_host((size_t)Kp), cm((size_t)Kp, 1.0);
     auto anchor_here = [&]() -> int {  // P at the current f (whose log-denominators are in slot `cur`)
-        if (!c->P && cache_malloc((void**)&c->P, (size_t)Kp * c->ld * sizeof(double)) != hipSuccess) {
+        if (c->P.grow((size_t)Kp * c->ld) != hipSuccess) {
             (void)hipGetLastError();
-            c->P = nullptr;
             c->P_failed = true;
             hp = false;
             return MBAR_OK;
         }
-        if (!c->pm_ld0) HIPCHK(c, cache_malloc((void**)&c->pm_ld0, (size_t)c->ld * sizeof(double)));
-        if (!c->lden_eff) {
-            HIPCHK(c, cache_malloc((void**)&c->lden_eff, (size_t)c->ld * sizeof(double)));
-            HIPCHK(c, hipMemsetAsync(c->lden_eff, 0, (size_t)c->ld * sizeof(double), c->stream));
+        HIPCHK(c, c->pm_ld0.grow((size_t)c->ld));
+        {
+            int lrc = need_zeroed_vec(c, c->lden_eff);
+            if (lrc) return lrc;
         }
         a0.assign((size_t)Kp, 0.0);
         build_aden(c, f.data(), a0.data(), Kp);
-        std::copy(a0.begin(), a0.end(), c->hstage);
+        std::copy(a0.begin(), a0.end(), c->hstage.p);
         HIPCHK(c, hipMemcpyAsync(d_aden(c), c->hstage, (size_t)Kp * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, launch_make_p(c->stream, c->num_cu, c->u, c->ld, c->N, Kp, d_aden(c), c->logden[cur], c->P));
         HIPCHK(c, hipMemcpyAsync(c->pm_ld0, c->logden[cur], (size_t)c->N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -98,11 +97,11 @@ int adaptive_host_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t 
         const size_t n_ps = (size_t)2 * Kp, total = n_ps + 2;
         int r2 = ensure_red(c, total);
         if (r2) return r2;
-        r2 = ensure(c, &c->part, &c->part_doubles, (size_t)c->num_cu * 2 * (Kp + 1));
+        r2 = ensure(c, c->part, (size_t)c->num_cu * 2 * (Kp + 1));
         if (r2) return r2;
-        r2 = ensure(c, &c->scratch, &c->scratch_doubles, (size_t)(c->num_cu / 32 + 2) * 2 * (Kp + 1));
+        r2 = ensure(c, c->scratch, (size_t)(c->num_cu / 32 + 2) * 2 * (Kp + 1));
         if (r2) return r2;
-        std::copy(h.begin(), h.end(), c->hstage);
+        std::copy(h.begin(), h.end(), c->hstage.p);
         HIPCHK(c, hipMemcpyAsync(d_aden(c), c->hstage, h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         if (ldA == c->logden[0] || ldB == c->logden[0]) c->ld0_valid = false;
         int blocks = 0;
@@ -313,13 +312,11 @@ int ensure_ad(mbar_ctx* c, int64_t hist_rows) {
     if (!c->ad || c->ad_hist_cap < cap) {
         int rc = drop_graphs(c);
         if (rc) return rc;
-        if (c->ad) HIPCHK(c, cache_free(c->ad));
-        c->ad = nullptr;
-        HIPCHK(c, cache_malloc((void**)&c->ad, (ad_off_hist(c) + (size_t)4 * cap) * sizeof(double)));
+        HIPCHK(c, c->ad.grow(ad_off_hist(c) + (size_t)4 * cap));
         c->ad_hist_cap = cap;
     }
-    if (!c->ad_ints) HIPCHK(c, cache_malloc((void**)&c->ad_ints, (size_t)(CTL_WORDS + c->Kp) * sizeof(int)));
-    if (!c->h_ctl) HIPCHK(c, cache_host_malloc((void**)&c->h_ctl, (size_t)CTL_WORDS * sizeof(int)));
+    HIPCHK(c, c->ad_ints.grow((size_t)(CTL_WORDS + c->Kp)));
+    HIPCHK(c, c->h_ctl.grow((size_t)CTL_WORDS));
     return MBAR_OK;
 }
 
@@ -389,14 +386,13 @@ int plan_device_loop(mbar_ctx* c, const std::vector<double>& f, int check_conver
     // (129 .. 256 states: P mode exists in its fused form only)
     bool pmode = c->opt_pmode && !c->P_failed && (!wide || (c->opt_wide_pmode && c->opt_fused));
     int arc = ensure_ad(c, history ? history_rows : 0);
-    if (!arc && wide && !c->chol && cache_malloc((void**)&c->chol, NEWTON_CHOL_WORK * sizeof(double)) != hipSuccess)
+    if (!arc && wide && c->chol.grow(NEWTON_CHOL_WORK) != hipSuccess)
         arc = fail(c, MBAR_ERR_HIP, "allocation of the Newton workspace failed");
     if (!arc && pmode && !c->P) {
         arc = drop_graphs(c);
         if (!arc) {
-            if (cache_malloc((void**)&c->P, (size_t)Kp * c->ld * sizeof(double)) != hipSuccess) {
+            if (c->P.grow((size_t)Kp * c->ld) != hipSuccess) {
                 (void)hipGetLastError();
-                c->P = nullptr;
                 c->P_failed = true;
                 pmode = false;
             } else if (launch_zero(c->stream, c->P, (size_t)Kp * c->ld * sizeof(double)) != hipSuccess) {
@@ -414,7 +410,7 @@ int plan_device_loop(mbar_ctx* c, const std::vector<double>& f, int check_conver
         }
     }
     p.pmode = pmode;
-    if (!arc && pmode && !c->pm_vec && cache_malloc((void**)&c->pm_vec, (size_t)3 * Kp * sizeof(double)) != hipSuccess)
+    if (!arc && pmode && c->pm_vec.grow((size_t)3 * Kp) != hipSuccess)
         arc = fail(c, MBAR_ERR_HIP, "allocation of the P-mode vectors failed");
     const bool fused = p.fused = pmode && c->opt_fused;
     // (fused loop: the Newton solve of an iteration rides in the launch of the previous iteration's selection -- k_select_newton --
@@ -465,14 +461,14 @@ int plan_device_loop(mbar_ctx* c, const std::vector<double>& f, int check_conver
     const size_t off_gram = p.off_gram = rec_l + 2;
     if (!arc) arc = ensure_red(c, off_gram + rec_g);
     if (!arc)
-        arc = ensure(c, &c->part, &c->part_doubles,
+        arc = ensure(c, c->part,
                      std::max(std::max((size_t)gg.nwaves * rec_g, (size_t)gl.nwaves * (rec_l + 2)), (size_t)gb.nwaves * Kp));
     // (level-1 scratch of the widest reduction: the fused loop reduces the per-state sums and the Gram records in ONE pair of launches)
     if (!arc)
-        arc = ensure(c, &c->scratch, &c->scratch_doubles,
+        arc = ensure(c, c->scratch,
                      std::max(((size_t)std::max(gg.nwaves, gl.nwaves) / 32 + 1) * (rec_g + rec_l + 2), ((size_t)gb.nwaves / 32 + 1) * (Kp + rec_g)));
     if (!arc && c->weighted && !c->lden_eff) arc = fail(c, MBAR_ERR_STATE, "weighted context without its logden buffer");
-    if (!arc && fused) arc = ensure(c, &c->part_g, &c->part_g_doubles, (size_t)gl.nwaves * rec_g);
+    if (!arc && fused) arc = ensure(c, c->part_g, (size_t)gl.nwaves * rec_g);
     {
         bool ok = arc == MBAR_OK;
         const std::string local_err = c->error;
@@ -527,7 +523,7 @@ int start_warm(mbar_ctx* c, const DeviceLoopPlan& p, const std::vector<double>&,
     const int64_t K = c->K, Kp = c->Kp;
     std::vector<int> z((size_t)CTL_WORDS, 0);  // slot 0, running: the sweep leaves the reciprocals of its first row in slot 1
     HIPCHK(c, hipMemcpyAsync(c->ad_ints, z.data(), z.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    std::copy(p.cm0.begin(), p.cm0.end(), c->hstage);
+    std::copy(p.cm0.begin(), p.cm0.end(), c->hstage.p);
     std::copy(p.cm0.begin(), p.cm0.end(), c->hstage + Kp);
     HIPCHK(c, hipMemcpyAsync(d_aden(c), c->hstage, (size_t)2 * Kp * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->red, 0, p.off_gram * sizeof(double), c->stream));
@@ -1141,7 +1137,7 @@ int mbar_solve_sci(mbar_ctx* c, double* f_inout, double tol, int64_t maxiter, in
     }
     const int64_t rows = lse_rows(c);
     const int64_t batch = c->opt_sci_batch;
-    if (!c->f_hist) HIPCHK(c, cache_malloc((void**)&c->f_hist, (size_t)256 * Kp * sizeof(double)));
+    HIPCHK(c, c->f_hist.grow((size_t)256 * Kp));
     int rc = ensure_red(c, (size_t)rows + 8);
     if (rc) return rc;
     // initial f and aden on the device
@@ -1167,9 +1163,9 @@ int mbar_solve_sci(mbar_ctx* c, double* f_inout, double tol, int64_t maxiter, in
     const bool merged = fast && g.variant == 4 && c->opt_sci_merged && c->nranks <= 1 && !c->comm && !stream_transport(c) &&
                         rows == Kp && batch % 2 == 0;
     if (fast) {
-        rc = ensure(c, &c->part, &c->part_doubles, std::max((size_t)g.nwaves * (rows + 1), (size_t)2 * g.blocks * rows + g.blocks));
+        rc = ensure(c, c->part, std::max((size_t)g.nwaves * (rows + 1), (size_t)2 * g.blocks * rows + g.blocks));
         if (rc) return rc;
-        rc = ensure(c, &c->scratch, &c->scratch_doubles, ((size_t)g.nwaves / 32 + 16) * (rows + 1));
+        rc = ensure(c, c->scratch, ((size_t)g.nwaves / 32 + 16) * (rows + 1));
         if (rc) return rc;
     }
     // iteration 0 of the merged loop: the plain sweep at the start point leaves its records and f in the parity-0 buffers
