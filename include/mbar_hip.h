@@ -109,6 +109,8 @@ int mbar_device_synchronize(int device);
  *   "device_loop"    1 = adaptive iterations run device-resident where possible (default), 0 = host-driven loop (what the
  *                    host all-reduce transport and K > 256 run)
  *   "adapt_batch"    adaptive iterations enqueued between two looks at the control words (default 8)
+ *   "hist_part_bytes" byte budget of the partial records of one sweep of the binned passes (default 256 MiB); read by
+ *                    mbar_ctx_set_bins, which cuts the bins into tiles -- one sweep each -- until a sweep's records fit
  *   "pmode"          1 = the device-resident loop keeps P = exp(a0 - u - logden(a0)) resident (one more K x N array, built
  *                    once per solve) and sweeps that: no exponentials in the loop (default); 0 = sweeps recompute them from u
  *                    (what runs when P does not fit on some rank)
@@ -293,6 +295,32 @@ int mbar_w(mbar_ctx* ctx, const double* f, double* out_kn, int64_t ld_out);
 /* gramW[K][K] = sum_n W_ni W_nj and wsum[k] = sum_n W_nk for ALL states (W^T W of
  * mbar.py:1816,1849 and compute_overlap mbar.py:606); fp64 MFMA. */
 int mbar_gram_w(mbar_ctx* ctx, const double* f, double* gramW, double* wsum);
+
+/* ---- histogram bins by label ----------------------------------------------------------------
+ * The bins of a histogram free energy surface as LABELS of the samples of the resident matrix (pymbar/fes.py:575-595,
+ * 1383-1406) -- no row per bin, no second matrix.  Single-rank contexts with a normal row pitch only: a context with a
+ * transport attached, an extension context or a wide-pitch matrix gets MBAR_ERR_STATE naming the limit.
+ *   mbar_ctx_set_bins   label[n] in [-1, nbins) is the bin of sample n (-1: none), v[n] the target potential (finite or +inf);
+ *                       both are uploaded once, the label range is validated, and the chunk table of the labels is built on the
+ *                       host in O(N): contiguous chunks of at most 2048 samples touching at most 64 distinct bins.  The partial
+ *                       records of one sweep ((K + 2) doubles per (chunk, bin of the chunk)) are bounded by the option
+ *                       "hist_part_bytes" as it stands at this call: above it the bins are cut into tiles, one sweep per tile
+ *                       (labels outside the tile count as -1).  nbins = 0 releases everything.
+ *   mbar_ctx_bins_info  sweeps per pass, chunks in all, bytes of the largest sweep's partial records (any pointer may be NULL).
+ *   mbar_bin_lognum     lognum_bins[i] = log sum_{n in bin i} c_n exp(-v_n - logden_n(f)), in log space against the bin's OWN
+ *                       maximum; -inf for a bin none of whose samples has c_n > 0 (c_n: mbar_ctx_set_sample_weights /
+ *                       mbar_ctx_draw_bootstrap_weights).  The bin free energy is -lognum_bins[i].
+ *   mbar_bin_gram_w     with B_n = exp(f_bins[label_n] - v_n - logden_n(f)) and W_nk = exp(f_k - u_kn - logden_n(f)):
+ *                       cross[k][i] = sum_{n in i} c_n W_nk B_n (K x nbins, row-major; NULL: not computed),
+ *                       diag[i] = sum_{n in i} c_n B_n^2, wsum_bins[i] = sum_{n in i} c_n B_n (1 at f_bins = -lognum_bins):
+ *                       the border of W^T W that the covariance of the bins needs next to mbar_gram_w of the resident states.
+ *                       The matrix is read once, in its natural order.
+ * No floating-point atomics: every sum's order is a function of (labels, N, K, nbins, "hist_part_bytes"), two identical calls
+ * return identical bits.  Kernel time is booked under MBAR_TIMER_OTHER. */
+int mbar_ctx_set_bins(mbar_ctx* ctx, int64_t nbins, const int32_t* label_host, const double* v_host);
+int mbar_ctx_bins_info(mbar_ctx* ctx, int64_t* sweeps, int64_t* chunks, int64_t* record_bytes);
+int mbar_bin_lognum(mbar_ctx* ctx, const double* f, double* lognum_bins);
+int mbar_bin_gram_w(mbar_ctx* ctx, const double* f, const double* f_bins, double* cross, double* diag, double* wsum_bins);
 
 /* ---- extension contexts: rows appended to a resident matrix without a copy of it ------------
  * The general path of the expectation family (pymbar/mbar.py:886-903 builds an N x (K + NL + S) host array of log weights;

@@ -298,6 +298,13 @@ struct mbar_loopback {
     std::vector<int> attached;
 };
 
+// Histogram bins by label (mbar_ctx_set_bins): the chunk table of one tile of bins on the device (mbar_hist.cpp)
+struct HistTile {
+    int64_t b0 = 0, b1 = 0, nchunks = 0, nrec = 0;
+    DevBuf<int64_t> chunk_n, chunk_rec, bin_ptr, bin_rec;
+    DevBuf<uint8_t> slot;
+};
+
 struct mbar_ctx {
     int device = 0;
     int num_cu = 256;
@@ -360,6 +367,13 @@ struct mbar_ctx {
     DevBuf<double> part_g;          // Gram partial records of the fused-sweep loop (the psum records use `part`)
     DevBuf<double> cwsq;            // sqrt of the per-sample multiplicities (only when weighted; else cw itself serves)
     DevBuf<double> chol;            // workspace of the blocked Cholesky Newton solve (129 .. 256 states)
+    // histogram bins by label: labels and target potential (N each), one chunk table per tile of bins, the partial records of one
+    // sweep and the merged outputs (binmax | lognum or wsum | diag | cross[K][nbins] | f_bins)
+    int64_t hist_nbins = 0;
+    DevBuf<int32_t> hist_label;
+    DevBuf<double> hist_v;
+    std::vector<HistTile> hist_tiles;
+    DevBuf<double> hist_rec, hist_out;
     long long* stamps = nullptr;    // MBAR_DEBUG_STAMPS: phase stamps of k_select_newton (64 launches x 16); hipMalloc, debug only
     // P outlives the solve that built it: a later solve on the same matrix whose start lies within the window of the anchor
     // (bootstrap replicates, protocol stages, continuation) starts with ONE fused sweep instead of the build sweep
@@ -370,6 +384,7 @@ struct mbar_ctx {
     int64_t opt_grid = 0, opt_force_generic = 0, opt_check_finite = 1, opt_sci_batch = 16, opt_timing = 0, opt_graph = 1, opt_small = 1, opt_wide = 1;
     int64_t opt_device_loop = 1, opt_adapt_batch = 8, opt_pmode = 1, opt_fused = 1, opt_quad = 1, opt_device_loop_wide = 1, opt_pcache = 1, opt_merge_select = 1, opt_sci_merged = 1, opt_wide_pmode = 1, opt_quad_trim = 1, opt_light_last = 1, opt_direct_results = 1, opt_debug_download_p = 0, opt_fused_general = 0;
     int64_t opt_small_balanced = 1, opt_sci_pingpong = 1, opt_host_pmode = 2, opt_rect_waves = 8, opt_newton_ldlt = 1;
+    int64_t opt_hist_part_bytes = (int64_t)1 << 28;  // byte budget of the partial records of one sweep of the binned passes
 
     // comm
     ncclComm_t comm = nullptr;

@@ -174,6 +174,59 @@ class DeviceMatrix:
         self._check(self._lib.mbar_ctx_fill_masked_rows(self._ctx, int(row0), int(nrows), _dptr(v_n),
                                                         label_n.ctypes.data_as(C.POINTER(C.c_int32))))
 
+    # ---- histogram bins by label (the label path of pymbar_amd.fes) ----------------------------------------------------------
+    def set_bins(self, nbins, label_n=None, v_n=None):
+        """Bins of a histogram surface as labels of the resident samples: ``label_n`` in ``[-1, nbins)`` (-1: in no bin) and the
+        target potential ``v_n``, uploaded once (``mbar_ctx_set_bins``).  ``nbins=0`` releases them."""
+        self._nbins = 0
+        if int(nbins) == 0:
+            self._check(self._lib.mbar_ctx_set_bins(self._ctx, 0, None, None))
+            return
+        label_n = np.asarray(label_n)
+        v_n = np.ascontiguousarray(v_n, dtype=np.float64)
+        if v_n.shape != (self.N_local,) or label_n.shape != (self.N_local,):
+            raise ValueError("v_n and label_n must have N_local entries")
+        if label_n.dtype != np.int32:  # (values that do not fit an int32 would wrap into the valid range)
+            if label_n.size and (label_n.min() < -1 or label_n.max() >= int(nbins)):
+                raise ValueError("labels must lie in [-1, nbins)")
+            label_n = label_n.astype(np.int32)
+        label_n = np.ascontiguousarray(label_n)
+        rc = self._lib.mbar_ctx_set_bins(self._ctx, int(nbins), label_n.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(v_n))
+        if rc == -1:  # MBAR_ERR_ARG: a label outside [-1, nbins), or NaN / -inf in v_n
+            raise ValueError(_lib.last_error(self._ctx))
+        self._check(rc)
+        self._nbins = int(nbins)
+
+    def bins_info(self):
+        """``dict(sweeps, chunks, record_bytes)`` of the chunk table ``set_bins`` built."""
+        vals = [C.c_int64(0) for _ in range(3)]
+        self._check(self._lib.mbar_ctx_bins_info(self._ctx, *[C.byref(v) for v in vals]))
+        return dict(sweeps=vals[0].value, chunks=vals[1].value, record_bytes=vals[2].value)
+
+    def bin_lognum(self, f):
+        """``log sum_{n in bin i} c_n exp(-v_n - logden_n(f))`` for every bin (``-inf``: no sample with ``c_n > 0``)."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.shape != (self.K,):
+            raise ValueError(f"f must have shape ({self.K},)")
+        out = np.empty(getattr(self, "_nbins", 0), dtype=np.float64)
+        self._check(self._lib.mbar_bin_lognum(self._ctx, _dptr(f), _dptr(out)))
+        return out
+
+    def bin_gram_w(self, f, f_bins, cross=True):
+        """``(cross, diag, wsum)`` of the bins' normalised weights ``B_n = exp(f_bins[label_n] - v_n - logden_n(f))`` against the
+        resident states' ``W``: ``cross[k, i] = sum_{n in i} c_n W_nk B_n`` (``None`` with ``cross=False``), ``diag[i] = sum c_n
+        B_n^2``, ``wsum[i] = sum c_n B_n``."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        f_bins = np.ascontiguousarray(f_bins, dtype=np.float64)
+        nbins = getattr(self, "_nbins", 0)
+        if f.shape != (self.K,) or f_bins.shape != (nbins,):
+            raise ValueError("f must have K entries and f_bins one per bin")
+        X = np.empty((self.K, nbins), dtype=np.float64) if cross else None
+        d = np.empty(nbins, dtype=np.float64)
+        w = np.empty(nbins, dtype=np.float64)
+        self._check(self._lib.mbar_bin_gram_w(self._ctx, _dptr(f), _dptr(f_bins), _dptr(X), _dptr(d), _dptr(w)))
+        return X, d, w
+
     def set_option(self, key, value):
         self._check(self._lib.mbar_ctx_set_option(self._ctx, key.encode(), int(value)))
 

@@ -20,6 +20,13 @@ formula of ``FES._get_fes_histogram``).  :class:`FES` puts it behind the referen
 surfaces, whose sums run in ``pymbar_amd.kde`` (its own device path, not the K x N matrix), and spline surfaces with the
 reference's Monte Carlo sampler of the spline coefficients, whose sums over the samples are B-spline moments computed once per
 fit in ``pymbar_amd.bspline``.
+
+Above ``K + nbins = 256`` rows, and for every bootstrap replicate, a bin is not a row but a LABEL of the samples of the mbar's
+own resident matrix (:func:`histogram_fes_labels`): the bin free energies are a segmented log-sum-exp over N numbers
+(``mbar_bin_lognum``), and the covariance of the bins follows from the resident ``K x K`` Gram matrix, a ``K x nbins`` cross block
+and the diagonal of the bin block (``mbar_bin_gram_w``) through a ``K x K`` eigenproblem -- no second matrix, no ``Theta`` of
+order ``K + nbins``.  A bootstrap replicate is one re-solve on the resident matrix with draw counts as sample multiplicities plus
+one pass over N numbers.
 """
 import logging
 
@@ -151,6 +158,129 @@ def histogram_fes(mbar, u_n, sample_label, reference="from-lowest", reference_la
     return out
 
 
+ROW_PATH_MAX_ROWS = 256  # K + nbins up to which FES builds one matrix row per bin (the matrix-core Gram panels end at 256 rows)
+
+
+def _draw_bootstrap_indices(N_k, idx):
+    """One bootstrap replicate's indices into ``idx``, from the global NumPy stream exactly as the reference draws them
+    (pymbar/fes.py:395-405): per state the resampled indices, then the one int32 the per-state ``MBAR`` construction that is
+    skipped here would draw for its seed (mbar.py:273-274)."""
+    index = 0
+    for k in range(len(N_k)):
+        idx[index:index + N_k[k]] = index + np.random.randint(0, N_k[k], size=N_k[k])
+        index += N_k[k]
+        np.random.randint(np.iinfo(np.int32).max)
+    return idx
+
+
+def _bordered_theta_factors(G, C, N_k):
+    """``(Y, g)`` with ``Theta_bins = diag(d) + Y^T diag(g) Y`` for the bins' block of the asymptotic covariance
+    ``W^T (I - W N W^T)^+ W`` of the augmented weights ``[W | B]`` (bins: ``N = 0``, disjoint supports, ``B^T B = diag(d)``).
+    With ``A = W D^(1/2)``, ``D = diag(N_k)``, and ``A^T A = D^(1/2) G D^(1/2) = V diag(lam) V^T``: ``(I - A A^T)^+ = I + U
+    diag(g) U^T`` on the range of ``A`` (``U = A V lam^(-1/2)``), ``g = lam / (1 - lam)`` -- and ``g = -1`` on the direction
+    ``lam = 1``, the normalisation ``sum_k N_k W_nk = 1``, which the pseudo-inverse removes.  ``U^T B = lam^(-1/2) V^T D^(1/2) C``
+    with the cross block ``C = W^T B``.  Directions with ``lam <= 1e-10`` (states without samples) carry nothing."""
+    rt = np.sqrt(np.asarray(N_k, dtype=np.float64))
+    lam, V = np.linalg.eigh(rt[:, None] * G * rt[None, :])
+    keep = lam > 1e-10
+    lam, V = lam[keep], V[:, keep]
+    one = np.abs(1.0 - lam) <= 1e-10
+    g = np.where(one, -1.0, lam / np.where(one, 1.0, 1.0 - lam))
+    Y = (V.T @ (rt[:, None] * C)) / np.sqrt(lam)[:, None]
+    return Y, g
+
+
+def _check_labels(mbar, u_n, sample_label):
+    u_n = np.ascontiguousarray(u_n, dtype=np.float64)
+    sample_label = np.asarray(sample_label, dtype=np.int64)
+    N = mbar.N
+    if u_n.shape != (N,) or sample_label.shape != (N,):
+        raise ParameterError("u_n and sample_label must have one entry per sample")
+    nbins = int(sample_label.max()) + 1 if N > 0 else 0
+    if nbins < 1:
+        raise DataError("no sample falls into any bin")
+    if int(sample_label.min()) < -1:
+        raise ParameterError("sample_label must lie in [-1, nbins)")
+    return u_n, sample_label, nbins
+
+
+def _binned_matrix(mbar, what):
+    """The mbar's resident matrix, if its handle has the binned passes (``set_bins`` / ``bin_lognum`` / ``bin_gram_w``: the
+    single-rank :class:`pymbar_amd.device.DeviceMatrix`); any other handle cannot label its samples."""
+    dm = mbar._dm
+    if getattr(dm, "nranks", 1) != 1 or not all(hasattr(dm, name) for name in ("set_bins", "bin_lognum", "bin_gram_w")):
+        raise ParameterError(f"{what} need the binned passes of a single-rank device matrix and are {_NOT_HERE} for this handle")
+    return dm
+
+
+def _reference_bin(f_raw, reference, reference_label):
+    nbins = len(f_raw)
+    if reference == "from-lowest":
+        return int(np.argmin(f_raw))
+    if reference == "from-specified":
+        if reference_label is None or not (0 <= int(reference_label) < nbins):
+            raise ParameterError("Specified reference point for FES not given")
+        return int(reference_label)
+    raise ParameterError(f"reference point method {reference} is not supported for histogram surfaces here")
+
+
+def histogram_fes_labels(mbar, u_n, sample_label, reference="from-lowest", reference_label=None, uncertainty_method="analytical",
+                         theta_method=None, return_theta=False):
+    """:func:`histogram_fes` with the bins as LABELS of the samples of ``mbar``'s own resident matrix: the same arguments, checks
+    and result keys (``f_i, df_i, f_raw, reference``), no second device matrix and no ``Theta`` of order ``K + nbins``.
+
+    The bin free energies are ``-mbar_bin_lognum``; the analytical uncertainties come from the resident ``W^T W``, the ``K x
+    nbins`` cross block and the diagonal of the bin block (``mbar_bin_gram_w``) through :func:`_bordered_theta_factors`, and
+    ``df_i^2 = Theta_ii + Theta_jj - 2 Theta_ij`` needs column ``j`` only.  ``theta_method``: None / "svd-ew" (the bordered
+    form), "approximate" (``diag(d)``, the bin block of ``W^T W`` itself); "svd" is not offered on this path.
+    ``return_theta=True`` adds ``Theta_bins`` (``nbins x nbins``) to the result."""
+    from .utils import check_w_sums
+
+    u_n, sample_label, nbins = _check_labels(mbar, u_n, sample_label)
+    if uncertainty_method not in (None, "analytical"):
+        raise ParameterError(f"Uncertainty_method {uncertainty_method} is not a valid option")
+    if theta_method == "bootstrap":
+        theta_method = None
+    if theta_method == "svd":
+        raise ParameterError("theta_method 'svd' needs the weight matrix itself and is not offered on the label path")
+    if theta_method not in (None, "svd-ew", "approximate"):
+        raise ParameterError(f"Method {theta_method} unrecognized.")
+    dm = _binned_matrix(mbar, "histogram surfaces by bin label")
+    dm.set_Nk(mbar.N_k)
+    dm.set_bins(nbins, sample_label, u_n)
+    try:
+        f_raw = -dm.bin_lognum(mbar.f_k)  # = -logsumexp(log_w_n[bin])   (fes.py:585)
+        if not np.all(np.isfinite(f_raw)):  # (a bin without samples has lognum = -inf: looked for only then)
+            counts = np.bincount(sample_label[sample_label >= 0], minlength=nbins)
+            if np.any(counts == 0):
+                raise DataError(f"WARNING: bin {int(np.where(counts == 0)[0][0])} has no samples -- all bins must have at least one sample.")
+        j = _reference_bin(f_raw, reference, reference_label)
+        out = dict(f_i=f_raw - f_raw[j], f_raw=f_raw, reference=j)
+        if uncertainty_method == "analytical":
+            approximate = theta_method == "approximate"
+            C, d, wsum = dm.bin_gram_w(mbar.f_k, f_raw, cross=not approximate)
+            check_w_sums(wsum, 0.0)
+            if approximate:
+                var = d + d[j]
+                var[j] = 0.0
+                Y = g = None
+            else:
+                G, ws = mbar._gram_w()
+                check_w_sums(ws, 0.0)
+                Y, g = _bordered_theta_factors(G, C, mbar.N_k)
+                col = Y.T @ (g * Y[:, j])  # column j of Y^T diag(g) Y
+                border = np.einsum("ki,k,ki->i", Y, g, Y)
+                diag_theta = d + border
+                col[j] += d[j]
+                var = diag_theta + diag_theta[j] - 2.0 * col
+            out["df_i"] = np.sqrt(np.maximum(var, 0.0))
+            if return_theta:
+                out["Theta_bins"] = np.diag(d) if approximate else np.diag(d) + Y.T @ (g[:, None] * Y)
+    finally:
+        dm.set_bins(0)
+    return out
+
+
 _NOT_HERE = "not supported on this backend"
 SPLINE_WEIGHTS = ("unbiasedstate", "biasedstates", "simplesum")
 SPLINE_SCIPY_METHODS = ("Newton-CG", "CG", "BFGS", "L-BFGS-B", "TNC", "SLSQP")
@@ -162,11 +292,13 @@ class FES:
     """``pymbar.FES`` on the MI355X path (pymbar/fes.py:74-1609): the MBAR solve on the device, histogram surfaces through
     :func:`label_samples` / :func:`histogram_fes`, kernel-density surfaces through :class:`pymbar_amd.kde.KernelDensity`.
 
-    Supported: ``fes_type="histogram"`` (``get_fes`` from-lowest / from-specified, uncertainties None or "analytical"),
+    Supported: ``fes_type="histogram"`` (``get_fes`` from-lowest / from-specified, uncertainties None, "analytical" or
+    "bootstrap"; one matrix row per bin up to ``K + nbins = 256``, bins as labels of the resident samples above that and for every
+    bootstrap replicate: :func:`histogram_fes_labels`),
     ``fes_type="kde"`` (from-lowest / from-specified / from-normalization, uncertainties None or "bootstrap") and
     ``fes_type="spline"`` (from-lowest / from-specified, uncertainties None or "bootstrap", information criteria, and the Monte
     Carlo sampler of the coefficients: ``sample_parameter_distribution``, ``get_confidence_intervals``, ``get_mc_data``).
-    Histogram bootstraps and the histogram from-normalization / all-differences modes raise ``ParameterError``.  The deliberate
+    The histogram from-normalization / all-differences modes raise ``ParameterError``, as they do in the reference.  The deliberate
     differences from the reference are listed in INTEGRATION.md ("FES")."""
 
     def __init__(self, u_kn, N_k, verbose=False, mbar_options=None, timings=True, **kwargs):
@@ -221,7 +353,9 @@ class FES:
     # ---- generate ---------------------------------------------------------------------------------------------------------
     def generate_fes(self, u_n, x_n, fes_type="histogram", histogram_parameters=None, kde_parameters=None,
                      spline_parameters=None, n_bootstraps=0, seed=-1):
-        """Build the surface (pymbar/fes.py:221-438).  kde: the replicates of ``n_bootstraps > 0`` draw from the global NumPy
+        """Build the surface (pymbar/fes.py:221-438).  histogram: replicate b re-solves MBAR on the resident matrix with its draw
+        counts as sample multiplicities and takes the bin free energies in one pass over N numbers (``_histogram_replicates``).
+        kde: the replicates of ``n_bootstraps > 0`` draw from the global NumPy
         stream exactly as the reference does and become weight columns over the ORIGINAL positions (see ``_generate_kde``)."""
         from timeit import default_timer as timer
 
@@ -242,9 +376,7 @@ class FES:
         if x_n.ndim == 1:
             x_n = x_n.reshape(-1, 1)
         if fes_type == "histogram":
-            if n_bootstraps > 0:
-                raise ParameterError(f"histogram surfaces with n_bootstraps > 0 are {_NOT_HERE}")
-            self._generate_histogram(x_n, histogram_parameters)
+            self._generate_histogram(x_n, histogram_parameters, n_bootstraps)
         elif fes_type == "kde":
             self._generate_kde(x_n, kde_parameters, n_bootstraps)
         elif fes_type == "spline":
@@ -287,11 +419,7 @@ class FES:
         cols[:, 0] = self.w_n
         idx = np.arange(0, self.N)
         for b in range(1, n_bootstraps + 1):
-            index = 0
-            for k in range(self.mbar.K):
-                idx[index:index + N_k[k]] = index + np.random.randint(0, N_k[k], size=N_k[k])
-                index += N_k[k]
-                np.random.randint(np.iinfo(np.int32).max)  # (the rseed draw of the skipped MBAR construction)
+            _draw_bootstrap_indices(N_k, idx)
             cols[:, b] = np.bincount(idx, weights=self.w_n, minlength=self.N)
         self.bootstrap_weights = cols
         self.kdes = None  # (the replicates are the columns 1..B of bootstrap_weights, evaluated in one device pass)
@@ -303,7 +431,40 @@ class FES:
             self._w_kn = np.exp(self.mbar.Log_W_nk)
         return self._w_kn
 
-    def _generate_histogram(self, x_n, histogram_parameters):
+    def _histogram_rows(self, nbins):
+        """Whether the surface builds one matrix row per bin (:func:`histogram_fes`) or labels the samples."""
+        return self.K + nbins <= ROW_PATH_MAX_ROWS
+
+    def _histogram_replicates(self, labels, nbins, n_bootstraps):
+        """The bootstrap replicates of a histogram surface (pymbar/fes.py:388-424): the draws of the reference from the global
+        stream, MBAR re-solved from ``mbar.f_k`` with the draw counts as sample multiplicities on the resident matrix (the
+        reference's MBAR on the resampled matrix), and the bin free energies of the resampled data -- ``-mbar_bin_lognum`` with the
+        same multiplicities -- in the b = 0 bin order.  A bin that drew no sample has ``f = +inf`` in that replicate.  No N-vector
+        returns to the host per replicate."""
+        from .mbar_solvers import solve_mbar_for_all_states
+
+        mbar, N = self.mbar, self.N
+        N_k = mbar.N_k
+        dm = _binned_matrix(mbar, "histogram surfaces with n_bootstraps > 0")
+        self.histogram_datas = []
+        self._hist_f_boots = []
+        idx = np.arange(0, N)
+        dm.set_Nk(N_k)
+        dm.set_bins(nbins, labels, self.u_n)
+        try:
+            for _ in range(n_bootstraps):
+                _draw_bootstrap_indices(N_k, idx)
+                counts = np.bincount(idx, minlength=N).astype(np.float64)
+                dm.set_sample_weights(counts)
+                f_b = solve_mbar_for_all_states(dm, N_k, mbar.f_k, mbar.states_with_samples, None)
+                self.histogram_datas.append(dict(f=-dm.bin_lognum(f_b)))
+                self._hist_f_boots.append(f_b)
+        finally:
+            dm.set_sample_weights(None)
+            dm.set_Nk(N_k)
+            dm.set_bins(0)
+
+    def _generate_histogram(self, x_n, histogram_parameters, n_bootstraps=0):
         if histogram_parameters is None or "bin_edges" not in histogram_parameters:
             raise ParameterError("histogram_parameters['bin_edges'] cannot be undefined with fes_type = histogram")
         bins = histogram_parameters["bin_edges"]
@@ -313,14 +474,20 @@ class FES:
         self.histogram_parameters = dict(histogram_parameters, bin_edges=bins)
         if x_n.shape != (self.N, len(bins)):
             raise DataError("x_n and bin_edges have inconsistent dimension")
+        if n_bootstraps > 0:
+            _binned_matrix(self.mbar, "histogram surfaces with n_bootstraps > 0")
         self.w_n = self._normalized_weights()
         self._w_kn = None
         labels, grid = label_samples(x_n, bins)
-        raw = histogram_fes(self.mbar, self.u_n, labels, uncertainty_method=None)
+        surface = histogram_fes if self._histogram_rows(len(grid)) else histogram_fes_labels
+        raw = surface(self.mbar, self.u_n, labels, uncertainty_method=None)
         # bins are numbered in order of first appearance like the reference's bin_order (fes.py:552-560); grid_of_label[i] is
         # the tuple of grid indices of bin i (None: the bin of the samples left of the grid)
         self.histogram_data = dict(bins=bins, dims=len(bins), f=raw["f_raw"], sample_label=labels, grid_of_label=grid,
                                    label_of_grid={g: i for i, g in enumerate(grid) if g is not None})
+        self.histogram_datas = None
+        if n_bootstraps > 0:
+            self._histogram_replicates(labels, len(grid), n_bootstraps)
 
     # ---- evaluate ---------------------------------------------------------------------------------------------------------
     def get_fes(self, x, reference_point="from-lowest", fes_reference=None, uncertainty_method=None):
@@ -374,11 +541,11 @@ class FES:
         bins, dims = hd["bins"], hd["dims"]
         if x.shape[1] != dims:
             raise DataError("query coordinates have inconsistent dimension with the data the FES is fit to.")
-        if uncertainty_method == "bootstrap":
-            raise ParameterError(f"bootstrap uncertainties of histogram surfaces are {_NOT_HERE}")
-        if uncertainty_method not in (None, "analytical"):
+        if uncertainty_method not in (None, "analytical", "bootstrap"):
             raise ParameterError(f"Uncertainty_method {uncertainty_method} is not a valid option")
-        if reference_point in ("from-normalization", "all-differences"):
+        if uncertainty_method == "bootstrap" and not self.histogram_datas:
+            raise ParameterError(f"bootstrap uncertainties of a histogram surface generated without replicates (n_bootstraps = 0) are {_NOT_HERE}")
+        if reference_point in ("from-normalization", "all-differences"):  # (the reference raises for both too, fes.py:1369-1448)
             raise ParameterError(f"reference point {reference_point!r} for histogram surfaces is {_NOT_HERE}")
         ref_label = None
         if reference_point == "from-specified":
@@ -391,8 +558,25 @@ class FES:
             ref_label = hd["label_of_grid"][g]
         elif reference_point != "from-lowest":
             raise ParameterError(f"reference point {reference_point!r} is not a valid option")
-        res = histogram_fes(self.mbar, self.u_n, hd["sample_label"], reference=reference_point, reference_label=ref_label,
-                            uncertainty_method=uncertainty_method)
+        if uncertainty_method == "bootstrap":
+            # pymbar/fes.py:1417-1422: the spread over the replicates of f^b_i - f^b_j, j from the b = 0 surface.  A replicate in
+            # which bin i or the reference bin drew no sample (f = +inf) is left out of bin i's spread; fewer than two usable
+            # replicates: NaN.  (The reference cannot broadcast such a replicate into its table and raises.)
+            f_raw = hd["f"]
+            j = _reference_bin(f_raw, reference_point, ref_label)
+            fall = np.stack([h["f"] - h["f"][j] if np.isfinite(h["f"][j]) else np.full(len(f_raw), np.nan)
+                             for h in self.histogram_datas], axis=1)
+            fall[~np.isfinite(fall)] = np.nan
+            usable = np.sum(~np.isnan(fall), axis=1)
+            df = np.full(len(f_raw), np.nan)
+            ok = usable >= 2
+            if np.any(ok):
+                df[ok] = np.nanstd(fall[ok], axis=1)
+            res = dict(f_i=f_raw - f_raw[j], df_i=df)
+        else:
+            surface = histogram_fes if self._histogram_rows(len(hd["f"])) else histogram_fes_labels
+            res = surface(self.mbar, self.u_n, hd["sample_label"], reference=reference_point, reference_label=ref_label,
+                          uncertainty_method=uncertainty_method)
         # each query point to its bin (fes.py:1419-1440): NaN outside the grid and in bins without samples
         loc = np.stack([np.digitize(x[:, d], bins[d]) - 1 for d in range(dims)], axis=1)
         f_x = np.full(len(x), np.nan)
@@ -527,11 +711,7 @@ class FES:
         idx = np.arange(0, N)
         N_k = mbar.N_k
         for b in range(1, n_bootstraps + 1):
-            index = 0
-            for k in range(mbar.K):
-                idx[index:index + N_k[k]] = index + np.random.randint(0, N_k[k], size=N_k[k])
-                index += N_k[k]
-                np.random.randint(np.iinfo(np.int32).max)  # (the rseed draw of the skipped MBAR construction)
+            _draw_bootstrap_indices(N_k, idx)
             counts = np.bincount(idx, minlength=N).astype(np.float64)
             if not unbiased:
                 cols[:, b] = counts
