@@ -20,6 +20,7 @@ import ctypes as C
 import logging
 import os
 import time
+from typing import NamedTuple
 
 import numpy as np
 
@@ -798,30 +799,35 @@ class MBARBatch:
         return out
 
     # ---- the one pass underneath ----
-    # ---- the one pass underneath ----
     def compute_expectations_inner(self, A_list, u_ln_list, state_maps, uncertainty_method=None, warning_cutoff=1.0e-10,
                                    return_theta=False):
         """``expectations.compute_expectations_inner`` of every problem: ``A_list[p]`` the observables (n_obs, N_p) (None: no
         observables), ``u_ln_list[p]`` the states (L_p, N_p) (None: the resident states), ``state_maps[p]`` as there.  Returns
         per problem the dict of ``observables``, ``f``, ``Theta``, ``Amin``.
 
-        The augmented matrix of problem p is its resident block plus extension rows, built as ``_augmented_matrix`` builds them:
-        resident states are not duplicated (their copies of the reference's layout are columns scaled by exp(f_l - f_k[l]): the
-        ``dedup`` algebra), new states are rows with N = 0, observable s is the row u_{l(s),n} - log(A_sn - shift_s) with the shift
-        of ``rows_logshift`` taken on the host.  A problem that needs no rows at all (resident states, no observables) is answered
-        from the kept covariance pass at ``f_k``.  ``self.timing`` holds the wall-clock split (s) of the last call: the rows built on
-        the host, upload and device passes, covariances and results."""
+        The augmented matrix of problem p is its resident block plus extension rows, built as ``expectations._augmented_matrix``
+        builds them: resident states are not duplicated (their copies of the reference's layout are columns scaled by
+        exp(f_l - f_k[l]): the ``distinct`` case of ``expectations.assemble_inner``, which writes every result dict), new states
+        are rows with N = 0, observable s is the row u_{l(s),n} - log(A_sn - shift_s) with the shift of ``rows_logshift`` taken
+        on the host.  A problem that needs no rows at all (resident states, no observables) is answered from the kept covariance
+        pass at ``f_k``.  ``self.timing`` holds the wall-clock split (s) of the last call: the rows built on the host, upload and
+        device passes, covariances and results."""
+        from .expectations import assemble_inner
+
         method = _check_method("MBARBatch", uncertainty_method)
         h = self._handle()
         plans = self._plan_inner(A_list, u_ln_list, state_maps)   # (every input rule, before any device work)
         device = ~self.host_fallback
         t0 = time.perf_counter()
-        rows = [_extension_rows(pl) if device[p] and pl["R"] > 0 else None for p, pl in enumerate(plans)]
+        rows, shifts = [None] * self.P, [None] * self.P
+        for p, pl in enumerate(plans):
+            if device[p] and pl.R > 0:
+                rows[p], shifts[p] = _extension_rows(pl)
         t1 = time.perf_counter()
         R = np.array([0 if r is None else r.shape[0] for r in rows], dtype=np.int64)
         mask = R > 0
         # the kept pass at f_k: the normalisers of resident states, and the Gram matrix of a problem without rows
-        kept = any(device[p] and (pl["resident"] or (return_theta and pl["R"] == 0)) for p, pl in enumerate(plans))
+        kept = any(device[p] and (pl.resident or (return_theta and pl.R == 0)) for p, pl in enumerate(plans))
         Gs, Ws = self._gram_w() if kept else (None, None)
         lognum_ext, gram, wsum = np.zeros(0), None, None
         if mask.any():
@@ -859,108 +865,88 @@ class MBARBatch:
             thetas = {sel[i]: t for idx, stack in _theta_stacks(Gaug, Naug, method) for i, t in zip(idx, stack)}
         out = [None] * self.P
         for p in sel:
-            ln_resident = None
-            if plans[p]["resident"]:
+            # the K + R columns of problem p are distinct: resident states are not duplicated (expectations.assemble_inner puts
+            # their copies back), new states are the first NL extension rows; the observable rows follow
+            plan, ln_ext = plans[p].plan, lognum_ext[roff[p]:roff[p + 1]]
+            if plans[p].resident:
                 with np.errstate(divide="ignore"):
-                    ln_resident = np.log(Ws[p]) - self.f_k[p]   # (from sum_n W_nk = exp(f_k + lognum_k))
-            out[p] = _assemble_inner(plans[p], int(self.K[p]), self.f_k[p], ln_resident, lognum_ext[roff[p]:roff[p + 1]],
-                                     thetas.get(p))
+                    ln_L = (np.log(Ws[p]) - self.f_k[p])[plan.L_list]   # (from sum_n W_nk = exp(f_k + lognum_k))
+                ln_obs = ln_ext
+            else:
+                ln_L, ln_obs = ln_ext[:plan.NL], ln_ext[plan.NL:]
+            out[p] = assemble_inner(plan, int(self.K[p]), self.f_k[p], ln_L, ln_obs, shifts[p], thetas.get(p),
+                                    distinct=plans[p].resident)
         for p in np.where(self.host_fallback)[0]:
             pl, m = plans[p], self._mbar(p)
-            A = np.array([0]) if pl["A"] is None else (m.u_kn if pl["A"] is self._blocks[p] else pl["A"])
-            out[p] = m.compute_expectations_inner(A, m.u_kn if pl["resident"] else pl["u_ln"], state_maps[p],
+            A = np.array([0]) if pl.A is None else (m.u_kn if pl.A is self._blocks[p] else pl.A)
+            out[p] = m.compute_expectations_inner(A, m.u_kn if pl.resident else pl.u_ln, state_maps[p],
                                                   uncertainty_method=uncertainty_method, warning_cutoff=warning_cutoff,
                                                   return_theta=return_theta)
         self.timing = dict(rows=t1 - t0, device=t2 - t1, covariance=time.perf_counter() - t2)
         return out
 
     def _plan_inner(self, A_list, u_ln_list, state_maps):
-        """Per problem what ``compute_expectations_inner`` is asked for, checked: the states and observables of the state map, the
-        distinct states ``L_list``, the extension rows ``R`` it takes (the observables at resident states; the distinct new
-        states and the observables otherwise)."""
+        """Per problem what ``compute_expectations_inner`` is asked for, checked: the plan of its state map
+        (``expectations.plan_inner``), its states and observables, and the extension rows ``R`` it takes (the observables at
+        resident states; the distinct new states and the observables otherwise)."""
+        from .expectations import plan_inner
+
         self._check_list("A_list", A_list)
         self._check_list("u_ln_list", u_ln_list)
         self._check_list("state_maps", state_maps)
         plans = []
         for p in range(self.P):
             K, N = int(self.K[p]), int(self.N[p])
-            sm = np.asarray(state_maps[p])
-            if sm.ndim < 2:
-                state_list, obs_list = np.array(sm, dtype=int), np.zeros(0, dtype=int)
-            else:
-                state_list, obs_list = np.array(sm[0, :], dtype=int), np.array(sm[1, :], dtype=int)
             resident = u_ln_list[p] is None
             u_ln = self._blocks[p] if resident else u_ln_list[p]
             A = A_list[p]
-            S = len(obs_list)
+            n_states = u_ln.shape[0] if u_ln.ndim == 2 else 0   # (what is not an array of rows is refused below)
+            n_obs = A.shape[0] if A is not None and A.ndim == 2 else 0
+            plan = plan_inner(state_maps[p], n_states, n_obs)
+            state_list, obs_list, S = plan.state_list, plan.obs_list, plan.S
             if u_ln.ndim != 2 or u_ln.shape[1] != N or (S > 0 and (A is None or A.ndim != 2 or A.shape[1] != N)):
                 raise ParameterError(f"problem {p}: states and observables must be arrays of {N} columns")
-            if np.any(state_list < 0) or np.any(state_list >= u_ln.shape[0]) or (
-                    S > 0 and (np.any(obs_list < 0) or np.any(obs_list >= A.shape[0]))):
+            if np.any(state_list < 0) or np.any(state_list >= plan.n_states) or (
+                    S > 0 and (np.any(obs_list < 0) or np.any(obs_list >= plan.n_obs))):
                 raise ParameterError(f"problem {p}: the state map names a state or an observable that is not there")
             if not self.host_fallback[p]:   # (a problem that fell back is MBAR's, with MBAR's answer to such input)
                 for i in np.unique(obs_list):
                     if not np.all(np.isfinite(A[i])):
                         raise ParameterError(f"problem {p}: observable {int(i)} is not finite")
-            L_list = np.unique(state_list)
-            NL = len(L_list)
-            R = S if resident else NL + S
+            R = S if resident else plan.NL + S
             if K + R > MAX_AUG:
                 raise ParameterError(f"problem {p}: K + extra rows = {K + R} > {MAX_AUG}: use MBAR")
-            plans.append(dict(state_list=state_list, obs_list=obs_list, L_list=L_list, NL=NL, S=S, R=R, resident=resident, u_ln=u_ln,
-                              A=A))
+            plans.append(_BatchPlan(plan, R, resident, u_ln, A))
         return plans
 
 
-def _extension_rows(pl):
-    """The extension rows of one planned problem, and its observables' shifts (``pl["shift"]``): the distinct new states (none
-    where the states are resident), then per observable s the row u_{l(s),n} - log(A_sn - shift), shift = amin - |4 eps amin|."""
-    A, u_ln, S = pl["A"], pl["u_ln"], pl["S"]
+class _BatchPlan(NamedTuple):
+    """One problem of ``MBARBatch.compute_expectations_inner``: the plan of its state map and what is the batch's own."""
+    plan: "InnerPlan"   # (expectations.InnerPlan)
+    R: int              # extension rows
+    resident: bool      # the states are the resident ones
+    u_ln: np.ndarray    # the states (L, N)
+    A: np.ndarray       # the observables (n_obs, N), or None
+
+
+def _extension_rows(bp):
+    """``(rows, shift)`` of one planned problem: its extension rows -- the distinct new states (none where the states are
+    resident), then per observable s the row u_{l(s),n} - log(A_sn - shift) -- and its observables' shifts, shift = amin -
+    |4 eps amin|."""
+    plan, A, u_ln = bp.plan, bp.A, bp.u_ln
     eps4 = 4.0 * np.finfo(np.float64).eps
-    shift = np.zeros(len(A) if S > 0 else 0, dtype=np.float64)
+    shift = np.zeros(plan.n_obs if plan.S > 0 else 0, dtype=np.float64)
     logA = {}
-    for i in np.unique(pl["obs_list"]):
+    for i in np.unique(plan.obs_list):
         amin = A[i].min()
         shift[i] = amin - np.abs(eps4 * amin)
         with np.errstate(divide="ignore"):
             logA[int(i)] = np.log(A[i] - shift[i])
-    block = np.empty((pl["R"], u_ln.shape[1]), dtype=np.float64)
+    block = np.empty((bp.R, u_ln.shape[1]), dtype=np.float64)
     r0 = 0
-    if not pl["resident"]:
-        block[:pl["NL"]] = u_ln[pl["L_list"]]
-        r0 = pl["NL"]
-    for s in range(S):
-        block[r0 + s] = u_ln[pl["state_list"][s]] - logA[int(pl["obs_list"][s])]
-    pl["shift"] = shift
-    return block
-
-
-def _assemble_inner(pl, K, f_k, ln_resident, ln_ext, theta):
-    """The result dict of one planned problem from the normalisers of its rows ``ln_ext``, those of the resident rows as states
-    ``ln_resident`` (where its states are resident) and Theta of its K + R distinct columns (None: not asked for)."""
-    S, NL, L_list, state_list, obs_list = pl["S"], pl["NL"], pl["L_list"], pl["state_list"], pl["obs_list"]
-    if pl["resident"]:
-        ln_state, obs0 = ln_resident, 0
-    else:
-        ln_state = np.full(pl["u_ln"].shape[0], np.nan)
-        ln_state[L_list] = ln_ext[:NL]
-        obs0 = NL
-    res = dict()
-    if S > 0:
-        res["observables"] = np.exp(ln_ext[obs0:obs0 + S] - ln_state[state_list[:S]]) + pl["shift"][obs_list]
-    res["f"] = -ln_state[state_list]
-    if theta is not None:
-        if pl["resident"]:
-            # (the layout [K | NL state copies | S observables] from the K + S distinct columns: copy l is column l scaled by
-            # c_l = exp(f_l - f_k[l]), and Theta is bilinear in the columns)
-            src = np.concatenate((np.arange(K), L_list, K + np.arange(S))).astype(int)
-            scale = np.concatenate((np.ones(K), np.exp(-ln_state[L_list] - f_k[L_list]), np.ones(S)))
-            theta = (scale[:, None] * theta[np.ix_(src, src)]) * scale[None, :]
-        col_of_state = {int(l): j for j, l in enumerate(L_list)}
-        si = K + NL + np.arange(S)
-        li = K + np.array([col_of_state[int(l)] for l in state_list], dtype=int)
-        idx = np.concatenate((si, li)).astype(int)
-        res["Theta"] = theta[np.ix_(idx, idx)]
-        if S > 0:
-            res["Amin"] = pl["shift"][obs_list]
-    return res
+    if not bp.resident:
+        block[:plan.NL] = u_ln[plan.L_list]
+        r0 = plan.NL
+    for s in range(plan.S):
+        block[r0 + s] = u_ln[plan.state_list[s]] - logA[int(plan.obs_list[s])]
+    return block, shift

@@ -16,7 +16,102 @@ from . import _lib
 _dptr = _lib.ptr
 
 
-class DeviceMatrix:
+class _ContextMatrix:
+    """What :class:`DeviceMatrix` and :class:`ExtendedMatrix` share: they own one ``mbar_ctx`` (``_ctx``) and write whole rows of
+    it (the row-level assembly of the expectation family).  The two differ in three hooks: where a destination row lives
+    (``_dst_row``), where a source run lives (``_src``) and what a write invalidates (``_touched``)."""
+
+    def _check(self, rc):
+        if rc != _lib.MBAR_OK:
+            raise _lib.MbarHipError(rc, _lib.last_error(self._ctx))
+
+    def close(self):
+        if getattr(self, "_ctx", None) is not None and self._ctx:
+            self._lib.mbar_ctx_destroy(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- the hooks (these are DeviceMatrix's: every row is the context's own) --------------------------------
+    def _dst_row(self, row, n=1):
+        """Row of the context that holds row ``row`` of the matrix, the first of ``n`` to be written."""
+        return int(row)
+
+    def _src(self, row0, n):
+        """(context, row) of a source run of ``n`` rows."""
+        return self._ctx, int(row0)
+
+    def _touched(self):
+        """The rows are about to change."""
+
+    # ---- row-level assembly of an augmented matrix on the device (expectation family) ----------------------
+    def _vec(self, v_n, name):
+        """A host vector of N_local entries for the staging vector, contiguous; None stays None (the vector staged before)."""
+        if v_n is None:
+            return None
+        v_n = np.ascontiguousarray(v_n, dtype=np.float64)
+        if v_n.shape != (self.N_local,):
+            raise ValueError(f"{name} must have N_local entries")
+        return v_n
+
+    def upload_rows(self, row0, rows):
+        """Whole rows ``[row0, row0 + len(rows))`` from a host array ``rows`` (R, N_local)."""
+        self._touched()
+        rows = np.ascontiguousarray(np.atleast_2d(rows), dtype=np.float64)
+        if rows.shape[1] != self.N_local:
+            raise ValueError("rows must have N_local columns")
+        self._check(self._lib.mbar_ctx_upload_rows(self._ctx, self._dst_row(row0, rows.shape[0]), rows.shape[0], _dptr(rows),
+                                                   rows.shape[1]))
+
+    def copy_rows_from(self, src, dst_row0=0, src_row0=0, nrows=None):
+        """Device-to-device copy of rows of another resident matrix (same device, same N_local)."""
+        self._touched()
+        nrows = src.K - src_row0 if nrows is None else nrows
+        self._check(self._lib.mbar_ctx_copy_rows(self._ctx, self._dst_row(dst_row0, nrows), src._ctx, int(src_row0), int(nrows)))
+
+    def rows_sub(self, dst_row0, src_row0, nrows, v_n=None):
+        """``u[dst_row0 + r, :] = u[src_row0 + r, :] - v_n`` for ``r < nrows`` in one launch (``v_n=None``: the vector of the
+        previous call): an observable evaluated at a run of states, the state rows copied and shifted in the same pass."""
+        self._touched()
+        sctx, srow = self._src(src_row0, nrows)
+        v_n = self._vec(v_n, "v_n")
+        self._check(self._lib.mbar_ctx_rows_sub_from(self._ctx, self._dst_row(dst_row0, nrows), sctx, srow, int(nrows), _dptr(v_n)))
+
+    def rows_rsub(self, dst_row0, src_row0, nrows):
+        """``u[dst_row0 + r, :] = u[src_row0 + r, :] - u[dst_row0 + r, :]`` for ``r < nrows`` in one launch: rows uploaded as
+        ``log A`` become observable rows ``u - log A``."""
+        self._touched()
+        sctx, srow = self._src(src_row0, nrows)
+        self._check(self._lib.mbar_ctx_rows_rsub_from(self._ctx, self._dst_row(dst_row0, nrows), sctx, srow, int(nrows)))
+
+    def rows_logshift(self, row0, nrows):
+        """Rows ``[row0, row0 + nrows)`` hold raw observable values and become ``log(A - shift)`` in place, ``shift = min A -
+        |4 eps min A|`` per row (returned): the reference's shift-to-positive + log (mbar.py:858-867, :886-903) on the device."""
+        self._touched()
+        shift = np.empty(int(nrows), dtype=np.float64)
+        self._check(self._lib.mbar_ctx_rows_logshift(self._ctx, self._dst_row(row0, nrows), int(nrows), _dptr(shift)))
+        return shift
+
+    def vec_logshift(self, A_n):
+        """One observable ``A_n`` (N_local,) into the staging vector as ``log(A - shift)``; returns ``shift``.  ``rows_sub`` /
+        ``row_sub`` with ``v_n=None`` subtract it."""
+        A_n = self._vec(A_n, "A_n")
+        shift = np.empty(1, dtype=np.float64)
+        self._check(self._lib.mbar_ctx_vec_logshift(self._ctx, _dptr(A_n), _dptr(shift)))
+        return float(shift[0])
+
+
+class DeviceMatrix(_ContextMatrix):
     """(K x N_local) fp64 matrix on one MI355X plus the solver state attached to it."""
 
     def __init__(self, K, N_local, device=None):
@@ -74,94 +169,19 @@ class DeviceMatrix:
             N_k_global.ctypes.data_as(C.POINTER(C.c_int64)), n_global0))
         return dm
 
-    # ---- plumbing ---------------------------------------------------------------------------------
-    def _check(self, rc):
-        if rc != _lib.MBAR_OK:
-            raise _lib.MbarHipError(rc, _lib.last_error(self._ctx))
-
-    def close(self):
-        if getattr(self, "_ctx", None) is not None and self._ctx:
-            self._lib.mbar_ctx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+    def _touched(self):
+        self._version += 1  # (the caches of lognum_cached / gram_w_cached and the row minima are keyed by it)
 
     @property
     def shape(self):
         return (self.K, self.N_local)
 
-    # ---- row-level assembly of an augmented matrix on the device (expectation family) ----------------------
-    def upload_rows(self, row0, rows):
-        """Whole rows ``[row0, row0 + len(rows))`` from a host array ``rows`` (R, N_local)."""
-        self._version += 1
-        rows = np.ascontiguousarray(np.atleast_2d(rows), dtype=np.float64)
-        if rows.shape[1] != self.N_local:
-            raise ValueError("rows must have N_local columns")
-        self._check(self._lib.mbar_ctx_upload_rows(self._ctx, int(row0), rows.shape[0], _dptr(rows), rows.shape[1]))
-
-    def copy_rows_from(self, src, dst_row0=0, src_row0=0, nrows=None):
-        """Device-to-device copy of rows of another resident matrix (same device, same N_local)."""
-        self._version += 1
-        nrows = src.K - src_row0 if nrows is None else nrows
-        self._check(self._lib.mbar_ctx_copy_rows(self._ctx, int(dst_row0), src._ctx, int(src_row0), int(nrows)))
-
     def row_sub(self, row, v_n=None):
         """``u[row, :] -= v_n`` on the device (v = log A_n turns a state row into an observable row).
         ``v_n=None`` subtracts the vector of the previous call again (no upload)."""
-        self._version += 1
-        if v_n is None:
-            self._check(self._lib.mbar_ctx_row_sub(self._ctx, int(row), None))
-            return
-        v_n = np.ascontiguousarray(v_n, dtype=np.float64)
-        if v_n.shape != (self.N_local,):
-            raise ValueError("v_n must have N_local entries")
+        self._touched()
+        v_n = self._vec(v_n, "v_n")
         self._check(self._lib.mbar_ctx_row_sub(self._ctx, int(row), _dptr(v_n)))
-
-    def rows_sub(self, dst_row0, src_row0, nrows, v_n=None):
-        """``u[dst_row0 + r, :] = u[src_row0 + r, :] - v_n`` for ``r < nrows`` in one launch (``v_n=None``: the vector of the
-        previous call): an observable evaluated at a run of states, the state rows copied and shifted in the same pass."""
-        self._version += 1
-        if v_n is None:
-            self._check(self._lib.mbar_ctx_rows_sub(self._ctx, int(dst_row0), int(src_row0), int(nrows), None))
-            return
-        v_n = np.ascontiguousarray(v_n, dtype=np.float64)
-        if v_n.shape != (self.N_local,):
-            raise ValueError("v_n must have N_local entries")
-        self._check(self._lib.mbar_ctx_rows_sub(self._ctx, int(dst_row0), int(src_row0), int(nrows), _dptr(v_n)))
-
-    def rows_rsub(self, dst_row0, src_row0, nrows):
-        """``u[dst_row0 + r, :] = u[src_row0 + r, :] - u[dst_row0 + r, :]`` for ``r < nrows`` in one launch: rows uploaded as
-        ``log A`` become observable rows ``u - log A``."""
-        self._version += 1
-        self._check(self._lib.mbar_ctx_rows_rsub(self._ctx, int(dst_row0), int(src_row0), int(nrows)))
-
-    def rows_logshift(self, row0, nrows):
-        """Rows ``[row0, row0 + nrows)`` hold raw observable values and become ``log(A - shift)`` in place, ``shift = min A -
-        |4 eps min A|`` per row (returned): the reference's shift-to-positive + log (mbar.py:858-867, :886-903) on the device."""
-        self._version += 1
-        shift = np.empty(int(nrows), dtype=np.float64)
-        self._check(self._lib.mbar_ctx_rows_logshift(self._ctx, int(row0), int(nrows), _dptr(shift)))
-        return shift
-
-    def vec_logshift(self, A_n):
-        """One observable ``A_n`` (N_local,) into the staging vector as ``log(A - shift)``; returns ``shift``.  ``rows_sub`` /
-        ``row_sub`` with ``v_n=None`` subtract it."""
-        A_n = np.ascontiguousarray(A_n, dtype=np.float64)
-        if A_n.shape != (self.N_local,):
-            raise ValueError("A_n must have N_local entries")
-        shift = np.empty(1, dtype=np.float64)
-        self._check(self._lib.mbar_ctx_vec_logshift(self._ctx, _dptr(A_n), _dptr(shift)))
-        return float(shift[0])
 
     def fill_masked_rows(self, row0, nrows, v_n, label_n):
         """Rows ``row0 + i`` (``i < nrows``) become ``v_n`` on the samples with ``label_n == i`` and ``+inf`` (weight zero)
@@ -485,7 +505,7 @@ class DeviceMatrix:
         return t.value
 
 
-class ExtendedMatrix:
+class ExtendedMatrix(_ContextMatrix):
     """``[rows of a resident DeviceMatrix | rows appended to it]`` without a copy of the resident rows: the appended rows live in
     an extension context of the library (``mbar_ctx_create_ext``) and the sweeps read both matrices (``mbar_lognum_ext``,
     ``mbar_gram_w_ext``).  Row indices are those of the augmented matrix of pymbar/mbar.py:886-903 -- ``[0, K)`` the resident
@@ -501,31 +521,12 @@ class ExtendedMatrix:
         self.N_local = base.N_local
         self.nranks = 1
 
-    def _check(self, rc):
-        if rc != _lib.MBAR_OK:
-            raise _lib.MbarHipError(rc, _lib.last_error(self._ctx))
-
-    def close(self):
-        if self._ctx:
-            self._lib.mbar_ctx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _ext_row(self, row, n=1):
         if row < self.Kb or row + n > self.K:
             raise ValueError("only the appended rows can be written")
         return int(row - self.Kb)
+
+    _dst_row = _ext_row
 
     def _src(self, row0, n):
         """(context, row) of a source run: the resident matrix below K, the extension from K on (a run does not straddle)."""
@@ -535,31 +536,11 @@ class ExtendedMatrix:
             return self._ctx, int(row0 - self.Kb)
         raise ValueError("a source run straddles the resident and the appended rows")
 
-    def upload_rows(self, row0, rows):
-        rows = np.ascontiguousarray(np.atleast_2d(rows), dtype=np.float64)
-        if rows.shape[1] != self.N_local:
-            raise ValueError("rows must have N_local columns")
-        self._check(self._lib.mbar_ctx_upload_rows(self._ctx, self._ext_row(row0, rows.shape[0]), rows.shape[0], _dptr(rows), rows.shape[1]))
-
     def copy_rows_from(self, src, dst_row0=0, src_row0=0, nrows=None):
         nrows = src.K - src_row0 if nrows is None else nrows
         if src is self.base and dst_row0 == 0 and src_row0 == 0 and nrows == self.Kb:
             return  # (the resident rows ARE the first K rows)
-        self._check(self._lib.mbar_ctx_copy_rows(self._ctx, self._ext_row(dst_row0, nrows), src._ctx, int(src_row0), int(nrows)))
-
-    def rows_sub(self, dst_row0, src_row0, nrows, v_n=None):
-        sctx, srow = self._src(src_row0, nrows)
-        vp = None
-        if v_n is not None:
-            v_n = np.ascontiguousarray(v_n, dtype=np.float64)
-            if v_n.shape != (self.N_local,):
-                raise ValueError("v_n must have N_local entries")
-            vp = _dptr(v_n)
-        self._check(self._lib.mbar_ctx_rows_sub_from(self._ctx, self._ext_row(dst_row0, nrows), sctx, srow, int(nrows), vp))
-
-    def rows_rsub(self, dst_row0, src_row0, nrows):
-        sctx, srow = self._src(src_row0, nrows)
-        self._check(self._lib.mbar_ctx_rows_rsub_from(self._ctx, self._ext_row(dst_row0, nrows), sctx, srow, int(nrows)))
+        super().copy_rows_from(src, dst_row0, src_row0, nrows)
 
     def rows_obs_from_base(self, dst_row0, state_row0, obs_row0, nrows):
         """Appended rows ``dst`` = resident rows ``state`` - log(resident rows ``obs`` - shift); ``shift`` per row is returned."""
@@ -575,19 +556,6 @@ class ExtendedMatrix:
         if mins is None:
             self.base._rowmin_cache = (key, out)
         return shift
-
-    def rows_logshift(self, row0, nrows):
-        shift = np.empty(int(nrows), dtype=np.float64)
-        self._check(self._lib.mbar_ctx_rows_logshift(self._ctx, self._ext_row(row0, nrows), int(nrows), _dptr(shift)))
-        return shift
-
-    def vec_logshift(self, A_n):
-        A_n = np.ascontiguousarray(A_n, dtype=np.float64)
-        if A_n.shape != (self.N_local,):
-            raise ValueError("A_n must have N_local entries")
-        shift = np.empty(1, dtype=np.float64)
-        self._check(self._lib.mbar_ctx_vec_logshift(self._ctx, _dptr(A_n), _dptr(shift)))
-        return float(shift[0])
 
     def set_Nk(self, N_k):
         N_k = np.asarray(N_k, dtype=np.float64)

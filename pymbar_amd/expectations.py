@@ -22,6 +22,7 @@ so that, with ``N_k = 0`` for the extra rows,
 No N x K array is formed on the host; only (K + NL + S)-sized linear algebra runs there.
 """
 import logging
+from typing import NamedTuple
 
 import numpy as np
 
@@ -30,97 +31,161 @@ from .utils import DataError, ParameterError, kln_to_kn, kn_to_n
 logger = logging.getLogger(__name__)
 
 
+class InnerPlan(NamedTuple):
+    """What a state map asks of ``compute_expectations_inner`` (see :func:`plan_inner`)."""
+    state_list: np.ndarray   # the state of every entry of the map
+    obs_list: np.ndarray     # the observable of every entry (empty for a 1-D map: free energies only)
+    S: int                   # observable columns of the reference's augmented matrix (mbar.py:886-903)
+    L_list: np.ndarray       # the distinct states, sorted
+    NL: int                  # ... and how many: its state columns
+    col_of_state: np.ndarray  # per entry i of the map: its state is L_list[col_of_state[i]], column K + col_of_state[i] there
+    n_states: int            # states in u_ln
+    n_obs: int               # observables in A_n: one shift each
 
-def _augmented_matrix(mbar, u_ln, L_list, state_rows, A_n, obs_rows, device, dedup=False, extend=False):
-    """Assemble ``[u_kn; u_ln[L_list]; u_ln[state_rows[s]] - log(A[obs_rows[s]] - shift)]`` ON THE DEVICE, the extra rows as
+
+def plan_inner(state_map, n_states, n_obs):
+    """The bookkeeping of one ``compute_expectations_inner`` call from its state map (``[[states...],[observables...]]``, or a 1-D
+    list of states for free energies only), for ``n_states`` states in ``u_ln`` and ``n_obs`` observables.  The only parse of a
+    state map: the single-problem paths below and ``MBARBatch`` all start here."""
+    state_map = np.asarray(state_map)
+    if state_map.ndim < 2:
+        state_list = np.array(state_map, dtype=int)
+        obs_list = np.zeros(0, dtype=int)
+    else:
+        state_list = np.array(state_map[0, :], dtype=int)
+        obs_list = np.array(state_map[1, :], dtype=int)
+    L_list, col_of_state = np.unique(state_list, return_inverse=True)
+    return InnerPlan(state_list, obs_list, len(obs_list), L_list, len(L_list), col_of_state, int(n_states), int(n_obs))
+
+
+def assemble_inner(plan, K, f_k, ln_L, ln_obs, shift, theta=None, distinct=False):
+    """The result dict of ``compute_expectations_inner`` -- ``observables``, ``f`` and, with ``theta``, ``Theta`` and ``Amin`` --
+    from what the device returned, however it got there (augmented copy, extension, no extra rows at all, a batch):
+
+    * ``ln_L[j]``: log-normaliser of state ``plan.L_list[j]`` as an unsampled state (``f_l = -ln_L``), ``ln_obs[s]``: that of
+      observable row ``s``, ``shift[i]``: what made observable ``i`` positive (mbar.py:858-867), ``f_k``: the K free energies;
+    * ``theta``: Theta of the weight columns that were on the device -- the reference's layout ``[K sampled | NL state copies |
+      S observables]`` (mbar.py:886-903), or with ``distinct`` only its ``K + S`` distinct columns ``[K | S]``: the states are
+      resident rows then, their copies were never made, and they are put back here.  Copy ``l`` is column ``l`` scaled by
+      ``c_l = exp(f_l - f_k[l])``, and Theta = W^T (I - W N W^T)^+ W (Eq. D6; what the eigen-form of mbar.py:1838-1858
+      evaluates) is bilinear in the weight columns: the copies' rows / columns are those of column ``l`` times ``c_l`` -- an
+      eigendecomposition of order K + S instead of K + NL + S (256 instead of 384 at 128 states: 7 ms instead of 23)."""
+    state_list, obs_list, S, L_list, NL = plan.state_list, plan.obs_list, plan.S, plan.L_list, plan.NL
+    ln_state = ln_L[plan.col_of_state]
+    res = dict()
+    if S > 0:
+        res["observables"] = np.exp(ln_obs - ln_state[:S]) + shift[obs_list]
+    res["f"] = -ln_state
+    if theta is not None:
+        if distinct:
+            src = np.concatenate((np.arange(K), L_list, K + np.arange(S))).astype(int)
+            scale = np.concatenate((np.ones(K), np.exp(-ln_L - f_k[L_list]), np.ones(S)))
+            theta = (scale[:, None] * theta[np.ix_(src, src)]) * scale[None, :]
+        si = K + NL + np.arange(S)
+        li = K + plan.col_of_state
+        idx = np.concatenate((si, li)).astype(int)
+        res["Theta"] = theta[np.ix_(idx, idx)]
+        if S > 0:
+            res["Amin"] = shift[obs_list]
+    return res
+
+
+def _runs(rows):
+    """Tuples of row indices -> maximal ``[i0, j0, ..., n]`` runs along which every index is consecutive: one device call per
+    run."""
+    out = []
+    for t in rows:
+        if out and all(i0 + out[-1][-1] == i for i0, i in zip(out[-1], t)):
+            out[-1][-1] += 1
+        else:
+            out.append([*map(int, t), 1])
+    return out
+
+
+def _resident_plus_rows(mbar, R, device, extend=False):
+    """``(dm, N_aug)``: the K resident rows and room for R more, unsampled states (N_aug = [N_k | 0]: they do not enter the
+    denominator) -- with ``extend`` an extension of the resident matrix where the library can sweep the two as one panel, else an
+    empty matrix with the resident rows copied in device to device.  The caller writes the R rows, then ``dm.set_Nk(N_aug)``."""
+    from .device import DeviceMatrix
+
+    dm = None
+    if extend and hasattr(mbar._dm, "extend") and R > 0:
+        dm = mbar._dm.extend(R)
+    if dm is None:
+        dm = DeviceMatrix.empty(mbar.K + R, mbar.N, device=device)
+        try:
+            dm.copy_rows_from(mbar._dm, 0, 0, mbar.K)
+        except Exception:
+            dm.close()
+            raise
+    N_aug = np.zeros(mbar.K + R, dtype=np.float64)
+    N_aug[:mbar.K] = mbar.N_k
+    return dm, N_aug
+
+
+def _augmented_matrix(mbar, plan, u_ln, A_n, device, dedup=False, extend=False):
+    """Assemble ``[u_kn; u_ln[L_list]; u_ln[state_list[s]] - log(A[obs_list[s]] - shift)]`` ON THE DEVICE, the extra rows as
     unsampled states (N_k = 0: they do not enter the denominator).  The resident ``u_kn`` is copied device to device; a
     new-state row that IS a resident row (``u_ln is mbar.u_kn``, the default of compute_expectations) likewise, and so are
     observables that are resident rows (entropy / enthalpy: the reduced potentials themselves); only genuinely new rows and
     the RAW observables cross PCIe -- never the N x (K + NL + S) host array of mbar.py:886-903.  The shift that makes an
     observable positive (mbar.py:858-867: ``A - (min A - |4 eps min A|)``) and the logarithm are taken on the device
-    (``rows_logshift`` / ``vec_logshift``); returns ``(dm, N_aug, shift, col)`` with ``shift[i]`` of observable ``i`` and
-    ``col[l]`` the row that holds state ``l``.
+    (``rows_logshift`` / ``vec_logshift``); returns ``(dm, N_aug, shift, row_of_L)`` with ``shift[i]`` of observable ``i`` and
+    ``row_of_L[j]`` the row that holds state ``L_list[j]``.
 
     ``dedup`` (only when the new states ARE resident rows): the copies are not made at all -- state ``l`` is row ``l`` -- and the
     matrix has K + S rows instead of K + NL + S (compute_expectations and the entropy / enthalpy decomposition at 128 states:
-    256 rows instead of 384, which keeps the sweeps on the one-read kernels); the caller expands the Gram matrix.
+    256 rows instead of 384, which keeps the sweeps on the one-read kernels); ``assemble_inner`` expands Theta.
 
     ``extend`` (round 6): the resident rows are not copied either -- the extra rows go into an extension of the resident matrix
     (``DeviceMatrix.extend``: the library sweeps ``[resident rows | appended rows]`` as one panel) when it can hold them (up to
     128 resident states, 129 .. 256 rows in total, one rank); observables that are resident rows at resident states (entropy /
     enthalpy) are then written in one pass, ``u_l - log(u_i - shift)`` straight from the resident rows."""
-    from .device import DeviceMatrix
-
-    K, N = mbar.K, mbar.N
-    NL, S = len(L_list), len(state_rows)
+    K, S, L_list = mbar.K, plan.S, plan.L_list
     resident = u_ln is mbar.u_kn
     dedup = dedup and resident
+    NL = 0 if dedup else plan.NL
+    dm, N_aug = _resident_plus_rows(mbar, NL + S, device, extend)
+    shift = np.zeros(plan.n_obs if S > 0 else 0, dtype=np.float64)
     if dedup:
-        NL = 0
-    dm = None
-    if extend and hasattr(mbar._dm, "extend") and NL + S > 0:
-        dm = mbar._dm.extend(NL + S)
-    if dm is None:
-        dm = DeviceMatrix.empty(K + NL + S, N, device=device)
-        dm.copy_rows_from(mbar._dm, 0, 0, K)
-    shift = np.zeros(len(A_n) if S > 0 else 0, dtype=np.float64)
-
-    def runs(pairs):
-        """(dst, src) row pairs -> maximal (dst0, src0, n) runs with both indices consecutive: one device call per run."""
-        out = []
-        for d, s_ in pairs:
-            if out and out[-1][0] + out[-1][2] == d and out[-1][1] + out[-1][2] == s_:
-                out[-1][2] += 1
-            else:
-                out.append([d, s_, 1])
-        return out
-
-    if dedup:
-        col = {int(l): int(l) for l in L_list}
+        row_of_L = L_list.astype(int)
     else:
+        row_of_L = K + np.arange(NL)
         if resident:
-            for d0, s0, n in runs([(K + j, int(l)) for j, l in enumerate(L_list)]):
+            for d0, s0, n in _runs(zip(row_of_L, L_list)):
                 dm.copy_rows_from(mbar._dm, d0, s0, n)
         else:
             for j, l in enumerate(L_list):
                 dm.upload_rows(K + j, u_ln[int(l)][np.newaxis, :])
-        col = {int(l): K + j for j, l in enumerate(L_list)}
-    uniq = np.unique(obs_rows) if S > 0 else []
+    # per observable row s: the row itself, its observable, the row of the state it is evaluated at
+    rows = [(K + NL + s, int(plan.obs_list[s]), int(row_of_L[plan.col_of_state[s]])) for s in range(S)]
+    uniq = np.unique(plan.obs_list) if S > 0 else []
     if len(uniq) > 2 and len(uniq) * 2 > S:
         # mostly DIFFERENT observables (entropy / enthalpy: the K reduced potentials, each at its own state): the raw rows go
         # into the observable rows (device to device when they are rows of the resident matrix, one transfer per run of
         # consecutive observables otherwise), become log(A - shift) there and then u - log(A - shift), one launch per run
-        if A_n is mbar.u_kn and hasattr(dm, "rows_obs_from_base") and all(col[int(l)] < K for l in state_rows):
+        if A_n is mbar.u_kn and hasattr(dm, "rows_obs_from_base") and all(st < K for _, _, st in rows):
             # (resident observables at resident states into appended rows: one pass per run, no copy of the observable rows)
-            trip = []
-            for s in range(S):
-                d, o_, st = K + NL + s, int(obs_rows[s]), col[int(state_rows[s])]
-                if trip and trip[-1][0] + trip[-1][3] == d and trip[-1][1] + trip[-1][3] == o_ and trip[-1][2] + trip[-1][3] == st:
-                    trip[-1][3] += 1
-                else:
-                    trip.append([d, o_, st, 1])
-            for d0, o0, s0, n in trip:
+            for d0, o0, s0, n in _runs(rows):
                 shift[o0:o0 + n] = dm.rows_obs_from_base(d0, s0, o0, n)
         else:
-            for d0, o0, n in runs([(K + NL + s, int(obs_rows[s])) for s in range(S)]):
+            for d0, o0, n in _runs((d, o) for d, o, _ in rows):
                 if A_n is mbar.u_kn:
                     dm.copy_rows_from(mbar._dm, d0, o0, n)
                 else:
                     dm.upload_rows(d0, A_n[o0:o0 + n])
             shift_rows = dm.rows_logshift(K + NL, S)
-            shift[np.asarray(obs_rows, dtype=int)] = shift_rows
-            for d0, s0, n in runs([(K + NL + s, col[int(state_rows[s])]) for s in range(S)]):
+            shift[plan.obs_list] = shift_rows
+            for d0, s0, n in _runs((d, st) for d, _, st in rows):
                 dm.rows_rsub(d0, s0, n)
         uniq = []
     for i in uniq:  # one upload of A_i; its log, shifted, is subtracted at every state it is evaluated at
         shift[int(i)] = dm.vec_logshift(A_n[int(i)])
         # observable rows = state rows - log(A_i - shift), written in one pass per run of consecutive rows
-        for d0, s0, n in runs([(K + NL + s, col[int(state_rows[s])]) for s in range(S) if int(obs_rows[s]) == int(i)]):
+        for d0, s0, n in _runs((d, st) for d, o, st in rows if o == int(i)):
             dm.rows_sub(d0, s0, n, None)
-    N_aug = np.zeros(K + NL + S, dtype=np.float64)
-    N_aug[:K] = mbar.N_k
     dm.set_Nk(N_aug)
-    return dm, N_aug, shift, col
+    return dm, N_aug, shift, row_of_L
 
 
 def _augmented_solve(dm, K, R, f_k):
@@ -138,43 +203,31 @@ def compute_expectations_inner(mbar, A_n, u_ln, state_map, uncertainty_method=No
     (``[[states...],[observables...]]``, or a 1-D list of states for free energies only), with the covariance
     ``Theta`` of the log normalisers.  Same inputs and result keys as pymbar/mbar.py:732-1001:
     ``observables``, ``f``, ``Theta``, ``Amin`` (+ ``bootstrapped_observables`` / ``bootstrapped_f``)."""
-    state_map = np.asarray(state_map)
-    if state_map.ndim < 2:
-        state_list = np.array(state_map, dtype=int)
-        obs_list = np.zeros(0, dtype=int)
-    else:
-        state_list = np.array(state_map[0, :], dtype=int)
-        obs_list = np.array(state_map[1, :], dtype=int)
-    S = len(obs_list)
     u_ln = np.asarray(u_ln, dtype=np.float64)
     if u_ln.ndim == 1:
         u_ln = u_ln.reshape(1, -1)
     A_n = np.asarray(A_n, dtype=np.float64)  # (never modified: the shift to positive values and the log are taken on the device)
     if A_n.ndim == 1:
         A_n = A_n.reshape(1, -1)
+    plan = plan_inner(state_map, len(u_ln), len(A_n))
+    state_list, obs_list, S = plan.state_list, plan.obs_list, plan.S
     K, N = mbar.K, mbar.N
-    L_list = np.unique(state_list)
-    NL = len(L_list)
-    col_of_state = {int(l): j for j, l in enumerate(L_list)}  # column K + j of the reference's augmented matrix (:886-903)
     # New states that ARE resident rows (the default of compute_expectations, the entropy / enthalpy decomposition) are not
     # duplicated on the device: W_l = W_k exp(f_l - f_k) column for column, so the Gram matrix of the reference's
     # (K + NL + S)-column layout is the (K + S)-row one with rows / columns repeated and scaled.  ("svd" needs W itself.)
     dedup = u_ln is mbar.u_kn and uncertainty_method != "svd"
 
-    result_vals = dict()
     bootstrap = uncertainty_method == "bootstrap"
     n_total = mbar.n_bootstraps + 1 if bootstrap else 1
     if bootstrap:
         A_i_bootstrap = np.zeros([mbar.n_bootstraps, S])
         f_bootstrap = np.zeros([mbar.n_bootstraps, len(state_list)])
-    Theta_ij = None
     # ONE observable at resident states, no bootstrap replicates: no augmented matrix at all (see _single_observable_moments)
     if (dedup and not bootstrap and S > 0 and np.all(obs_list == obs_list[0]) and len(state_list) == S
-            and len(np.unique(state_list)) == S and getattr(mbar, "_dm", None) is not None
+            and plan.NL == S and getattr(mbar, "_dm", None) is not None
             and hasattr(mbar._dm, "weights_from_vec") and getattr(mbar._dm, "nranks", 1) == 1):
         try:
-            return _single_observable_moments(mbar, A_n[int(obs_list[0])], state_list, int(obs_list[0]), len(A_n), col_of_state,
-                                              L_list, uncertainty_method, return_theta)
+            return _single_observable_moments(mbar, A_n[int(obs_list[0])], plan, uncertainty_method, return_theta)
         except _LinearWeightsOverflow:
             pass  # an observable spanning more than ~1e154: its square has no linear-space weights; the log-space path below has no such limit
     # The augmented matrix goes to the device once.  A bootstrap replicate (mbar.py:905-912 gathers
@@ -183,9 +236,8 @@ def compute_expectations_inner(mbar, A_n, u_ln, state_map, uncertainty_method=No
     # A_min[i] - logfactors[i], found on the device)
     # (an extension of the resident matrix instead of an augmented copy where the library can sweep the two as one panel; bootstrap
     # replicates put multiplicities on the augmented matrix and "svd" downloads its weights: those keep the copy)
-    dm, N_dm, shift, row_of_state = _augmented_matrix(mbar, u_ln, L_list, state_list[:S] if S > 0 else [], A_n, obs_list,
-                                                      getattr(mbar, "_device", None), dedup=dedup,
-                                                      extend=not bootstrap and uncertainty_method != "svd")
+    dm, N_dm, shift, row_of_L = _augmented_matrix(mbar, plan, u_ln, A_n, getattr(mbar, "_device", None), dedup=dedup,
+                                                  extend=not bootstrap and uncertainty_method != "svd")
     R_dm = len(N_dm) - K      # extra rows on the device: S when the state rows are not duplicated, NL + S otherwise
     obs_row0 = len(N_dm) - S  # first observable row
     try:
@@ -199,44 +251,26 @@ def compute_expectations_inner(mbar, A_n, u_ln, state_map, uncertainty_method=No
                 else:
                     dm.set_sample_weights(np.bincount(mbar.bootstrap_rints[n - 1], minlength=N))
             f_full, lognum = _augmented_solve(dm, K, R_dm, f_k)
-            f_states = np.array([-lognum[row_of_state[int(l)]] for l in state_list])
-            A_i = np.array([np.exp(lognum[obs_row0 + s] - lognum[row_of_state[int(state_list[s])]]) for s in range(S)])
+            Theta = None
+            if n == 0 and return_theta:
+                # (the column sums go along: like the reference's check_w_normalized on the augmented W, weights that
+                # do not sum to one raise instead of silently producing a Theta)
+                G, wsum = dm.gram_w(f_full)
+                if dedup:   # (Theta of the K + S distinct columns that are on the device)
+                    Theta = mbar._theta_from_gram(G, N_dm.astype(np.int64), uncertainty_method, wsum=wsum)
+                else:
+                    Theta = mbar._theta_from_gram(G, N_dm.astype(np.int64), uncertainty_method, wsum=wsum, dm=dm, f_full=f_full)
+            res = assemble_inner(plan, K, f_k, lognum[row_of_L], lognum[obs_row0:], shift, Theta, distinct=dedup)
             if n == 0:
-                if S > 0:
-                    result_vals["observables"] = A_i + shift[obs_list]
-                if return_theta:
-                    # (the column sums go along: like the reference's check_w_normalized on the augmented W, weights that
-                    # do not sum to one raise instead of silently producing a Theta)
-                    G, wsum = dm.gram_w(f_full)
-                    if dedup:
-                        # the reference's layout [K sampled | NL state copies | S observables] from the rows on the device:
-                        # copy l is row l scaled by c_l = exp(f_l - f_k[l]), f_l = -lognum[l] its normaliser as an unsampled state
-                        # (N = 0).  Theta = W^T (I - W N W^T)^+ W (Eq. D6) is bilinear in the weight columns, so Theta of the
-                        # (K + S) DISTINCT columns is computed (an eigendecomposition of that order) and the copies' rows /
-                        # columns are those of column l times c_l.
-                        src = np.concatenate((np.arange(K), L_list.astype(int), K + np.arange(S))).astype(int)
-                        scale = np.concatenate((np.ones(K), np.exp(-lognum[L_list.astype(int)] - f_k[L_list.astype(int)]), np.ones(S)))
-                        Theta_red = mbar._theta_from_gram(G, N_dm.astype(np.int64), uncertainty_method, wsum=wsum)
-                        Theta_ij = (scale[:, None] * Theta_red[np.ix_(src, src)]) * scale[None, :]
-                    else:
-                        Theta_ij = mbar._theta_from_gram(G, N_dm.astype(np.int64), uncertainty_method, wsum=wsum, dm=dm,
-                                                         f_full=f_full)
-                result_vals["f"] = f_states
+                result_vals = res
             else:
-                A_i_bootstrap[n - 1, :] = A_i + shift[obs_list] if S > 0 else 0.0
-                f_bootstrap[n - 1, :] = f_states
+                A_i_bootstrap[n - 1, :] = res["observables"] if S > 0 else 0.0
+                f_bootstrap[n - 1, :] = res["f"]
     finally:
         dm.close()
     if bootstrap:
         result_vals["bootstrapped_observables"] = A_i_bootstrap
         result_vals["bootstrapped_f"] = f_bootstrap
-    if return_theta:
-        si = K + NL + np.arange(S)
-        li = K + np.array([col_of_state[int(l)] for l in state_list], dtype=int)
-        idx = np.concatenate((si, li)).astype(int)
-        result_vals["Theta"] = Theta_ij[np.ix_(idx, idx)]
-        if S > 0:
-            result_vals["Amin"] = shift[obs_list]
     return result_vals
 
 
@@ -255,7 +289,7 @@ def _weights_from_vec(dm, power):
         raise
 
 
-def _single_observable_moments(mbar, A_row, state_list, obs_index, n_obs, col_of_state, L_list, uncertainty_method, return_theta):
+def _single_observable_moments(mbar, A_row, plan, uncertainty_method, return_theta):
     """``compute_expectations_inner`` for ONE observable evaluated at S distinct RESIDENT states (``compute_expectations(A_n)``,
     mbar.py:1039-1312, the common call) WITHOUT an augmented matrix.  The weight column of "A at state l" is
     ``W_s = A'_n W_nl exp(f_s - f_l)`` with ``A' = A - shift > 0`` (mbar.py:858-867), so
@@ -269,14 +303,13 @@ def _single_observable_moments(mbar, A_row, state_list, obs_index, n_obs, col_of
       blocks of three 128-row sweeps; config 3: 20 GB less device memory and half the sweep time).
 
     Same result keys as the general path."""
-    K, N = mbar.K, mbar.N
+    K = mbar.K
     dm = mbar._dm
-    S = len(state_list)
-    NL = len(L_list)
-    states = np.asarray(state_list, dtype=int)
+    S = plan.S
+    states = plan.state_list
+    obs_index = int(plan.obs_list[0])
     f_k = mbar.f_k
-    result_vals = dict()
-    shift = np.zeros(n_obs, dtype=np.float64)
+    shift = np.zeros(plan.n_obs, dtype=np.float64)
     try:
         dm.set_sample_weights(None)
         cached = hasattr(dm, "lognum_cached")
@@ -284,10 +317,7 @@ def _single_observable_moments(mbar, A_row, state_list, obs_index, n_obs, col_of
         shift[obs_index] = dm.vec_logshift(A_row)       # log(A - shift) stays on the device
         _weights_from_vec(dm, 1.0)
         lognum1 = dm.lognum(f_k)                       # log sum_n A'_n exp(-u_ln - logden_n)
-        f_states = -lognum0[states]
-        A_i = np.exp(lognum1[states] - lognum0[states])
-        result_vals["observables"] = A_i + shift[obs_index]
-        result_vals["f"] = f_states
+        Theta_red = None
         if return_theta:
             G1, ws1 = dm.gram_w(f_k)
             _weights_from_vec(dm, 2.0)
@@ -295,13 +325,8 @@ def _single_observable_moments(mbar, A_row, state_list, obs_index, n_obs, col_of
             dm.set_sample_weights(None)
             G0, ws0 = dm.gram_w_cached(f_k) if cached else dm.gram_w(f_k)
             # Theta on the (K + S) DISTINCT weight columns [K resident | S observables], observable s = A' W_l(s) scaled by
-            # d_s = exp(f_s - f_k[l(s)]), f_s = -lognum1[l(s)].  The reference's layout [K sampled | NL state copies | S observables]
-            # (mbar.py:886-903) holds, besides these, NL columns that are exact multiples c_l W_l of resident ones, c_l =
-            # exp(f_l - f_k[l]), with N = 0: Theta = W^T (I - W N W^T)^+ W (Eq. D6; what the eigen-form of mbar.py:1838-1858
-            # evaluates) is bilinear in the columns, so their rows / columns of Theta are those of column l times c_l -- an
-            # eigendecomposition of order K + S instead of K + NL + S (256 instead of 384 at 128 states: 7 ms instead of 23).
-            Ls = L_list.astype(int)
-            c_l = np.exp(-lognum0[Ls] - f_k[Ls])
+            # d_s = exp(f_s - f_k[l(s)]), f_s = -lognum1[l(s)]; assemble_inner puts the NL state copies of the reference's layout
+            # back
             d_s = np.exp(-lognum1[states] - f_k[states])
             n_red = K + S
             G = np.empty((n_red, n_red), dtype=np.float64)
@@ -314,17 +339,9 @@ def _single_observable_moments(mbar, A_row, state_list, obs_index, n_obs, col_of
             N_red = np.zeros(n_red, dtype=np.int64)
             N_red[:K] = mbar.N_k
             Theta_red = mbar._theta_from_gram(G, N_red, uncertainty_method, wsum=wsum)
-            src = np.concatenate((np.arange(K), Ls, K + np.arange(S))).astype(int)
-            scale = np.concatenate((np.ones(K), c_l, np.ones(S)))
-            Theta_ij = (scale[:, None] * Theta_red[np.ix_(src, src)]) * scale[None, :]
-            si = K + NL + np.arange(S)
-            li = K + np.array([col_of_state[int(l)] for l in state_list], dtype=int)
-            idx = np.concatenate((si, li)).astype(int)
-            result_vals["Theta"] = Theta_ij[np.ix_(idx, idx)]
-            result_vals["Amin"] = shift[np.full(S, obs_index, dtype=int)]
     finally:
         dm.set_sample_weights(None)
-    return result_vals
+    return assemble_inner(plan, K, f_k, lognum0[plan.L_list], lognum1[states], shift, Theta_red, distinct=True)
 
 
 def compute_covariance_of_sums(mbar, d_ij, K, a):

@@ -111,8 +111,7 @@ def histogram_fes(mbar, u_n, sample_label, reference="from-lowest", reference_la
 
     Returns ``dict(f_i, df_i, f_raw, reference, Theta)``; ``f_raw`` are the bin free energies before the reference
     is subtracted (``histogram_data["f"]`` of the reference)."""
-    from .device import DeviceMatrix
-    from .expectations import _augmented_solve
+    from .expectations import _augmented_solve, _resident_plus_rows
 
     u_n = np.ascontiguousarray(u_n, dtype=np.float64)
     sample_label = np.asarray(sample_label, dtype=np.int64)
@@ -128,23 +127,13 @@ def histogram_fes(mbar, u_n, sample_label, reference="from-lowest", reference_la
     if uncertainty_method not in (None, "analytical"):
         raise ParameterError(f"Uncertainty_method {uncertainty_method} is not a valid option")
 
-    dm = DeviceMatrix.empty(K + nbins, N, device=getattr(mbar, "_device", None))
+    dm, N_aug = _resident_plus_rows(mbar, nbins, getattr(mbar, "_device", None))
     try:
-        dm.copy_rows_from(mbar._dm, 0, 0, K)
         dm.fill_masked_rows(K, nbins, u_n, sample_label)  # one "state" per bin: u_n on its samples, +inf elsewhere
-        N_aug = np.zeros(K + nbins, dtype=np.float64)
-        N_aug[:K] = mbar.N_k
         dm.set_Nk(N_aug)
         f_full, _ = _augmented_solve(dm, K, nbins, mbar.f_k)
         f_raw = f_full[K:].copy()  # = -logsumexp(log_w_n[bin])   (fes.py:585)
-        if reference == "from-lowest":
-            j = int(np.argmin(f_raw))
-        elif reference == "from-specified":
-            if reference_label is None or not (0 <= int(reference_label) < nbins):
-                raise ParameterError("Specified reference point for FES not given")
-            j = int(reference_label)
-        else:
-            raise ParameterError(f"reference point method {reference} is not supported for histogram surfaces here")
+        j = _reference_bin(f_raw, reference, reference_label)
         out = dict(f_i=f_raw - f_raw[j], f_raw=f_raw, reference=j)
         if uncertainty_method == "analytical":
             G, wsum = dm.gram_w(f_full)
