@@ -322,6 +322,31 @@ int mbar_ctx_bins_info(mbar_ctx* ctx, int64_t* sweeps, int64_t* chunks, int64_t*
 int mbar_bin_lognum(mbar_ctx* ctx, const double* f, double* lognum_bins);
 int mbar_bin_gram_w(mbar_ctx* ctx, const double* f, const double* f_bins, double* cross, double* diag, double* wsum_bins);
 
+/* ---- reweighting scans over a linear family of unsampled states ------------------------------
+ * Solve once, then reweight to L states that were never sampled (a temperature, pressure or lambda grid, a sweep of a restraint
+ * centre): member l is u_l(n) = sum_b coeff[l][b] basis[b][n] + offset[l], B <= MBAR_SCAN_MAX_B coefficients instead of a matrix
+ * row of N doubles.  Nothing of size L x N is allocated.  Single-rank contexts with a normal row pitch and at most 128 states
+ * only: any other context gets MBAR_ERR_STATE naming the limit.  With x_ln = -u_l(n) - logden_n(f) (u_l as one fma chain over
+ * ascending b), t_0n = 1, t_jn = t[j - 1][n] (j = 1 .. Q: the observables, shifted positive by the caller), J = 1 + Q and c_n the
+ * sample multiplicities:
+ *   mbar_ctx_set_scan   uploads the B + Q N-vectors (row-major, B x N and Q x N) once; B = 0 releases them.
+ *   mbar_scan_lognum    pass A.  M_l = max_{c_n > 0} x_ln, S_lj = sum_n c_n exp(x_ln - M_l) t_jn, lognum[l] = M_l + log S_l0
+ *                       (f_l = -lognum[l]), mean[l][j] = S_lj / S_l0 (L x J; NULL: not returned).  Every member is referred to its
+ *                       OWN maximum.  Reads B + Q + 2 N-vectors twice, never the matrix.  offset NULL: zeros.
+ *   mbar_scan_gram_w    pass B.  b_ln = exp(f_scan[l] + x_ln), W_nk = exp(f_k - u_kn - logden_n), r the reference member:
+ *                       cross[k][l][j] = sum_n c_n W_nk b_ln t_jn (K x L x J; NULL: not computed) on the fp64 matrix cores, the
+ *                       b t operand generated in registers; within[l][i <= j] = sum_n c_n b_ln^2 t_in t_jn (L x J (J + 1) / 2,
+ *                       row-major upper triangle), refcol[l][j] = sum_n c_n b_rn b_ln t_jn (L x J), wsum[l] = sum_n c_n b_ln (1 at
+ *                       f_scan = -lognum).  The matrix is read once per panel of 64 .. 256 members.
+ * No floating-point atomics; the samples are cut into chunks by N alone and merged in chunk order: two identical calls return
+ * identical bits, and member l's outputs do not depend on the other members of the call.  Kernel time: MBAR_TIMER_OTHER. */
+#define MBAR_SCAN_MAX_B 8
+#define MBAR_SCAN_MAX_Q 3
+int mbar_ctx_set_scan(mbar_ctx* ctx, int64_t B, const double* basis, int64_t Q, const double* t);
+int mbar_scan_lognum(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, double* lognum, double* mean);
+int mbar_scan_gram_w(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan,
+                     int64_t r, double* cross, double* within, double* refcol, double* wsum);
+
 /* ---- extension contexts: rows appended to a resident matrix without a copy of it ------------
  * The general path of the expectation family (pymbar/mbar.py:886-903 builds an N x (K + NL + S) host array of log weights;
  * rounds 3-5 of this library copied the resident matrix device to device into a (K + NL + S)-row one per call).  An extension

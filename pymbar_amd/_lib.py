@@ -125,6 +125,9 @@ SIGNATURES = {
     "mbar_ctx_bins_info": (C.c_int, [_ctx, _ip, _ip, _ip]),
     "mbar_bin_lognum": (C.c_int, [_ctx, _dp, _dp]),
     "mbar_bin_gram_w": (C.c_int, [_ctx, _dp, _dp, _dp, _dp, _dp]),
+    "mbar_ctx_set_scan": (C.c_int, [_ctx, C.c_int64, _dp, C.c_int64, _dp]),
+    "mbar_scan_lognum": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
+    "mbar_scan_gram_w": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
     "mbar_ctx_create_ext": (C.c_int, [C.POINTER(_ctx), _ctx, C.c_int64]),
     "mbar_ctx_rows_sub_from": (C.c_int, [_ctx, C.c_int64, _ctx, C.c_int64, C.c_int64, _dp]),
     "mbar_ctx_rows_rsub_from": (C.c_int, [_ctx, C.c_int64, _ctx, C.c_int64, C.c_int64]),

@@ -374,6 +374,10 @@ struct mbar_ctx {
     DevBuf<double> hist_v;
     std::vector<HistTile> hist_tiles;
     DevBuf<double> hist_rec, hist_out;
+    // scans over a linear family (mbar_ctx_set_scan): basis[B][ld] | t[Q][ld], the members of one call (coeff | offset | f_scan),
+    // the partial records of one panel and the merged outputs
+    int64_t scan_B = 0, scan_Q = 0;
+    DevBuf<double> scan_vec, scan_in, scan_part, scan_out;
     long long* stamps = nullptr;    // MBAR_DEBUG_STAMPS: phase stamps of k_select_newton (64 launches x 16); hipMalloc, debug only
     // P outlives the solve that built it: a later solve on the same matrix whose start lies within the window of the anchor
     // (bootstrap replicates, protocol stages, continuation) starts with ONE fused sweep instead of the build sweep

@@ -397,6 +397,37 @@ hipError_t launch_hist_cross(hipStream_t s, const HistSweep& h, const double* u,
                              const double* f_bins, double* part);
 hipError_t launch_hist_cross_combine(hipStream_t s, const HistSweep& h, int64_t K, const double* part, double* cross);
 
+// ---- reweighting scans over a linear family of unsampled states (mbar_k_scan.hip; panels and C ABI in mbar_scan.cpp) --------
+constexpr int SCAN_MAX_B = MBAR_SCAN_MAX_B;  // basis vectors
+constexpr int SCAN_MAX_Q = MBAR_SCAN_MAX_Q;  // observables
+constexpr int SCAN_VCHUNK = 2048;            // samples of one wave of pass A
+constexpr int SCAN_CHUNK = 8192;             // samples of one workgroup of pass B: the cut of N depends on N alone
+// blocks of 16 members per wave of pass B for J = 1 + Q operand columns per member, and per-member sums of its vec record
+constexpr int scan_mb(int J) { return J == 1 ? 4 : J == 2 ? 2 : 1; }
+constexpr int scan_nv(int J) { return 1 + J + J * (J + 1) / 2; }
+struct ScanData {
+    int64_t N, ldv;
+    int B, Q;
+    const double* basis;   // [B][ldv]
+    const double* t;       // [Q][ldv] shifted observables (> 0)
+    const double* logden;  // [N]
+    const double* cw;      // [N] multiplicities (NULL: 1)
+};
+// pass A: per-chunk records of the maxima (sum = false: rec[chunk][L]) or of the J scaled sums (rec[chunk][L][J]) of the members
+// [0, L) of coeff / offset, and their merge in chunk order into M, or into lognum and mean[L][J]
+hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, bool sum, int64_t L, const double* coeff, const double* offset,
+                           const double* M, double* rec);
+hipError_t launch_scan_vec_merge(hipStream_t s, const ScanData& d, bool sum, int64_t L, const double* rec, double* M, double* lognum,
+                                 double* mean);
+// pass B for the panel of members [p0, p0 + 64 scan_mb(J)) of L: part[chunk][scan_record_doubles(nb, J)], then cross[K][L][J] and
+// vec[L][scan_nv(J)] = wsum | refcol[J] | within[i <= j].  nb = scan_nb_for(K) blocks of 16 states, or 0: no cross block.
+int scan_nb_for(int64_t K);
+int64_t scan_record_doubles(int nb, int J);
+hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, int nb, const double* u, int64_t ld, int64_t K, const double* f, int64_t L,
+                             int64_t p0, const double* coeff, const double* offset, const double* f_scan, int64_t ref, double* part);
+hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, int nb, int64_t K, int64_t L, int64_t p0, const double* part,
+                                   double* cross, double* vec);
+
 // ---- lagged fluctuation sums of a timeseries (mbar_k_acf.hip; C ABI in mbar_acf.cpp) ----------------------------------------
 constexpr int ACF_WG = 256;                 // threads per workgroup
 constexpr int ACF_R = 8;                     // consecutive positions per thread

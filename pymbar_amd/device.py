@@ -247,6 +247,71 @@ class DeviceMatrix(_ContextMatrix):
         self._check(self._lib.mbar_bin_gram_w(self._ctx, _dptr(f), _dptr(f_bins), _dptr(X), _dptr(d), _dptr(w)))
         return X, d, w
 
+    # ---- reweighting scans over a linear family of unsampled states (pymbar_amd.scan) -----------------------------------------
+    def set_scan(self, basis_bn=None, t_qn=None):
+        """The ``B`` basis vectors (``B x N``, ``1 <= B <= 8``) and the ``Q`` shifted observables (``Q x N``, ``Q <= 3``, or
+        None) of a scan, uploaded once (``mbar_ctx_set_scan``).  ``basis_bn=None`` releases them."""
+        self._scan = None
+        if basis_bn is None:
+            self._check(self._lib.mbar_ctx_set_scan(self._ctx, 0, None, 0, None))
+            return
+        basis_bn = np.ascontiguousarray(basis_bn, dtype=np.float64)
+        t_qn = np.zeros((0, self.N_local)) if t_qn is None else np.ascontiguousarray(t_qn, dtype=np.float64)
+        if basis_bn.ndim != 2 or t_qn.ndim != 2 or basis_bn.shape[1] != self.N_local or t_qn.shape[1] != self.N_local:
+            raise ValueError("basis_bn and t_qn must have N_local columns")
+        B, Q = basis_bn.shape[0], t_qn.shape[0]
+        rc = self._lib.mbar_ctx_set_scan(self._ctx, B, _dptr(basis_bn), Q, _dptr(t_qn) if Q else None)
+        if rc == -1:  # MBAR_ERR_ARG: B or Q outside the limits
+            raise ValueError(_lib.last_error(self._ctx))
+        self._check(rc)
+        self._scan = (B, Q)
+
+    def _scan_members(self, coeff_lb, offset_l):
+        if getattr(self, "_scan", None) is None:
+            raise ValueError("no basis on this matrix (set_scan first)")
+        coeff_lb = np.ascontiguousarray(coeff_lb, dtype=np.float64)
+        if coeff_lb.ndim != 2 or coeff_lb.shape[1] != self._scan[0] or coeff_lb.shape[0] < 1:
+            raise ValueError("coeff_lb must have one row per member and one column per basis vector")
+        L = coeff_lb.shape[0]
+        offset_l = np.zeros(L) if offset_l is None else np.ascontiguousarray(offset_l, dtype=np.float64)
+        if offset_l.shape != (L,):
+            raise ValueError("offset_l must have one entry per member")
+        return coeff_lb, offset_l, L, 1 + self._scan[1]
+
+    def scan_lognum(self, f, coeff_lb, offset_l=None):
+        """Pass A of a scan: ``(lognum, mean)`` with ``lognum[l] = log sum_n c_n exp(-u_l(n) - logden_n(f))`` and ``mean[l, j]``
+        the average of ``t_j`` (``t_0 = 1``) in member ``l`` (``L x (1 + Q)``)."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.shape != (self.K,):
+            raise ValueError(f"f must have shape ({self.K},)")
+        coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
+        lognum = np.empty(L, dtype=np.float64)
+        mean = np.empty((L, J), dtype=np.float64)
+        self._check(self._lib.mbar_scan_lognum(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(lognum), _dptr(mean)))
+        return lognum, mean
+
+    def scan_gram_w(self, f, coeff_lb, offset_l, f_scan, reference=0, cross=True):
+        """Pass B of a scan: ``(cross, within, refcol, wsum)`` of the members' normalised weights ``b_ln = exp(f_scan[l] - u_l(n) -
+        logden_n(f))`` -- ``cross[k, l, j] = sum_n c_n W_nk b_ln t_jn`` (``None`` with ``cross=False``), ``within[l, i, j] = sum_n
+        c_n b_ln^2 t_in t_jn`` (symmetric ``J x J``), ``refcol[l, j] = sum_n c_n b_rn b_ln t_jn`` for the reference member ``r``,
+        ``wsum[l] = sum_n c_n b_ln``."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
+        f_scan = np.ascontiguousarray(f_scan, dtype=np.float64)
+        if f.shape != (self.K,) or f_scan.shape != (L,) or not 0 <= int(reference) < L:
+            raise ValueError("f must have K entries, f_scan one per member, and the reference must be a member")
+        X = np.empty((self.K, L, J), dtype=np.float64) if cross else None
+        tri = np.empty((L, J * (J + 1) // 2), dtype=np.float64)
+        refcol = np.empty((L, J), dtype=np.float64)
+        w = np.empty(L, dtype=np.float64)
+        self._check(self._lib.mbar_scan_gram_w(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(f_scan), int(reference),
+                                               _dptr(X), _dptr(tri), _dptr(refcol), _dptr(w)))
+        within = np.empty((L, J, J), dtype=np.float64)
+        iu = np.triu_indices(J)
+        within[:, iu[0], iu[1]] = tri
+        within[:, iu[1], iu[0]] = tri
+        return X, within, refcol, w
+
     def set_option(self, key, value):
         self._check(self._lib.mbar_ctx_set_option(self._ctx, key.encode(), int(value)))
 

@@ -32,7 +32,7 @@ import logging
 
 import numpy as np
 
-from .utils import ConvergenceError, DataError, ParameterError
+from .utils import ConvergenceError, DataError, ParameterError, bordered_theta_factors
 
 logger = logging.getLogger(__name__)
 
@@ -162,21 +162,8 @@ def _draw_bootstrap_indices(N_k, idx):
     return idx
 
 
-def _bordered_theta_factors(G, C, N_k):
-    """``(Y, g)`` with ``Theta_bins = diag(d) + Y^T diag(g) Y`` for the bins' block of the asymptotic covariance
-    ``W^T (I - W N W^T)^+ W`` of the augmented weights ``[W | B]`` (bins: ``N = 0``, disjoint supports, ``B^T B = diag(d)``).
-    With ``A = W D^(1/2)``, ``D = diag(N_k)``, and ``A^T A = D^(1/2) G D^(1/2) = V diag(lam) V^T``: ``(I - A A^T)^+ = I + U
-    diag(g) U^T`` on the range of ``A`` (``U = A V lam^(-1/2)``), ``g = lam / (1 - lam)`` -- and ``g = -1`` on the direction
-    ``lam = 1``, the normalisation ``sum_k N_k W_nk = 1``, which the pseudo-inverse removes.  ``U^T B = lam^(-1/2) V^T D^(1/2) C``
-    with the cross block ``C = W^T B``.  Directions with ``lam <= 1e-10`` (states without samples) carry nothing."""
-    rt = np.sqrt(np.asarray(N_k, dtype=np.float64))
-    lam, V = np.linalg.eigh(rt[:, None] * G * rt[None, :])
-    keep = lam > 1e-10
-    lam, V = lam[keep], V[:, keep]
-    one = np.abs(1.0 - lam) <= 1e-10
-    g = np.where(one, -1.0, lam / np.where(one, 1.0, 1.0 - lam))
-    Y = (V.T @ (rt[:, None] * C)) / np.sqrt(lam)[:, None]
-    return Y, g
+# (shared with the scans over a linear family, pymbar_amd/scan.py: the same border, dense instead of diagonal)
+_bordered_theta_factors = bordered_theta_factors
 
 
 def _check_labels(mbar, u_n, sample_label):

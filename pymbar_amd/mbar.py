@@ -21,6 +21,7 @@ import numpy as np
 
 from . import expectations as _expectations
 from . import mbar_solvers
+from . import scan as _scan
 from .mbar_solvers import (BOOTSTRAP_SOLVER_PROTOCOL, DEFAULT_SOLVER_PROTOCOL, JAX_SOLVER_PROTOCOL,
                            ROBUST_SOLVER_PROTOCOL)
 from .utils import ParameterError, check_w_sums, kln_to_kn
@@ -530,6 +531,8 @@ class MBAR:
     compute_multiple_expectations = _expectations.compute_multiple_expectations
     compute_perturbed_free_energies = _expectations.compute_perturbed_free_energies
     compute_entropy_and_enthalpy = _expectations.compute_entropy_and_enthalpy
+    # ---- scans over a linear family of unsampled states (pymbar_amd/scan.py) --------------------------
+    compute_scan = _scan.compute_scan
 
     def _computeUnnormalizedLogWeights(self, u_n):
         """``-ln sum_k N_k exp(f_k - (u_k(x_n) - u(x_n)))`` for one target potential ``u_n`` (mbar.py:1919-1934):

@@ -1,0 +1,196 @@
+"""Reweighting scans over a linear family of unsampled states (``MBAR.compute_scan``): solve once, then reweight to hundreds or
+thousands of states that were never sampled -- a temperature, pressure or lambda grid, a sweep of a restraint centre -- and read
+free energies, averages and their uncertainties along the scan.
+
+Member ``l`` of the family is ``u_l(n) = sum_b coeff_lb[l, b] basis_bn[b, n] + offset_l[l]``: ``B`` coefficients, not a matrix
+row of ``N`` doubles.  The free energies and averages come from pass A of the device (``mbar_scan_lognum``), which never reads the
+resident matrix.  The analytical uncertainties follow DESIGN.md section 17: the members are weight columns with ``N = 0`` appended
+to the resident ``W``, so ``Theta(z, z') = z . z' + y(z)^T diag(g) y(z')`` with the border ``(y, g)`` of
+:func:`pymbar_amd.utils.bordered_theta_basis` -- the resident ``K x K`` Gram matrix, the ``K x L x J`` cross block and the members'
+own products (``mbar_scan_gram_w``, pass B, the cross block on the fp64 matrix cores) replace the ``Theta`` of order ``K + 2 L``
+that ``compute_perturbed_free_energies(u_ln)`` / ``compute_expectations(A_n, u_kn=u_ln)`` decompose.
+
+Every member's numbers are computed by operations whose order does not depend on the other members of the call (the host sums
+below run over states and eigen-directions in explicit loops, not through BLAS): member ``l`` scanned alone returns the bits it
+returns inside a scan of thousands.
+"""
+import logging
+
+import numpy as np
+
+from .utils import DataError, ParameterError, bordered_theta_basis, check_w_sums
+
+logger = logging.getLogger(__name__)
+
+MAX_BASIS = 8
+MAX_OBSERVABLES = 3
+MAX_STATES = 128
+_NOT_HERE = "not supported on this backend"
+
+
+def _scan_matrix(mbar):
+    """The mbar's resident matrix, if its handle has the scan passes (the single-rank :class:`pymbar_amd.device.DeviceMatrix`)."""
+    dm = mbar._dm
+    if getattr(dm, "nranks", 1) != 1 or not all(hasattr(dm, name) for name in ("set_scan", "scan_lognum", "scan_gram_w")):
+        raise ParameterError(f"scans over a linear family need the scan passes of a single-rank device matrix and are {_NOT_HERE} for this handle")
+    if mbar.K > MAX_STATES:
+        raise ParameterError(f"scans over a linear family serve at most {MAX_STATES} states (this object has {mbar.K})")
+    return dm
+
+
+def _check_inputs(mbar, basis_bn, coeff_lb, offset_l, A_qn, reference):
+    N = mbar.N
+    basis_bn = np.ascontiguousarray(basis_bn, dtype=np.float64)
+    coeff_lb = np.ascontiguousarray(coeff_lb, dtype=np.float64)
+    if basis_bn.ndim != 2 or basis_bn.shape[1] != N or not 1 <= basis_bn.shape[0] <= MAX_BASIS:
+        raise ParameterError(f"basis_bn must have shape (B, N) with 1 <= B <= {MAX_BASIS}")
+    B = basis_bn.shape[0]
+    if coeff_lb.ndim != 2 or coeff_lb.shape[1] != B or coeff_lb.shape[0] < 1:
+        raise ParameterError("coeff_lb must have shape (L, B) with L >= 1")
+    L = coeff_lb.shape[0]
+    offset_l = np.zeros(L) if offset_l is None else np.ascontiguousarray(offset_l, dtype=np.float64)
+    if offset_l.shape != (L,):
+        raise ParameterError("offset_l must have shape (L,)")
+    if A_qn is None:
+        A_qn = np.zeros((0, N))
+    A_qn = np.asarray(A_qn, dtype=np.float64)
+    if A_qn.ndim == 1:
+        A_qn = A_qn.reshape(1, -1)
+    if A_qn.ndim != 2 or A_qn.shape[1] != N or A_qn.shape[0] > MAX_OBSERVABLES:
+        raise ParameterError(f"A_qn must have shape (Q, N) with 0 <= Q <= {MAX_OBSERVABLES}, or (N,)")
+    if not (isinstance(reference, (int, np.integer)) and 0 <= int(reference) < L):
+        raise ParameterError("reference must be the index of a member of the family")
+    if not (np.all(np.isfinite(basis_bn)) and np.all(np.isfinite(coeff_lb)) and np.all(np.isfinite(offset_l)) and np.all(np.isfinite(A_qn))):
+        raise DataError("basis_bn, coeff_lb, offset_l and A_qn must be finite")
+    return basis_bn, coeff_lb, offset_l, A_qn, L
+
+
+def _shifted(A_qn):
+    """``(t_qn, shift)``: the observables made positive as the reference does (mbar.py:858-878)."""
+    if len(A_qn) == 0:
+        return np.zeros_like(A_qn), np.zeros(0)
+    amin = A_qn.min(axis=1)
+    shift = amin - np.abs(4.0 * np.finfo(np.float64).eps * amin)
+    return A_qn - shift[:, None], shift
+
+
+def _sqrt_small_negative_zeroed(d2, warning_cutoff):
+    """``sqrt`` of squared uncertainties; small negative ones are zeroed (mbar.py:1687-1715, elementwise)."""
+    d2 = np.array(d2)
+    cutoff = -abs(warning_cutoff)
+    if np.any(d2 < 0.0):
+        if np.any(d2 < cutoff):
+            logger.warning("A squared uncertainty is negative. Largest Magnitude = {0:f}".format(abs(np.min(d2[d2 < cutoff]))))
+        d2[np.logical_and(0 > d2, d2 > cutoff)] = 0.0
+    with np.errstate(invalid="ignore"):
+        return np.sqrt(d2)
+
+
+def _border(mbar, cross):
+    """``y[i, l, j]`` of the members' columns ``b_l t_j`` and ``g``: ``y = lam^(-1/2) V^T D^(1/2) C``, summed over the states in
+    ascending order, element by element."""
+    G, ws = mbar._gram_w()
+    check_w_sums(ws, 0.0)
+    rt, lam, V, g = bordered_theta_basis(G, mbar.N_k)
+    y = np.zeros((len(lam),) + cross.shape[1:])
+    for k in range(cross.shape[0]):
+        y += (V[k] * rt[k])[:, None, None] * cross[k][None, :, :]
+    y /= np.sqrt(lam)[:, None, None]
+    return y, g
+
+
+def _qform(g, a, b):
+    """``sum_i g_i a_i b_i`` over the eigen-directions in ascending order, element by element (``a``, ``b``: ``(m, ...)``)."""
+    out = np.zeros(np.broadcast(a[0], b[0]).shape)
+    for i in range(len(g)):
+        out += g[i] * a[i] * b[i]
+    return out
+
+
+def _analytical(mbar, dm, coeff_lb, offset_l, f, mean, reference, approximate, warning_cutoff):
+    """``(dDelta_f, sigma)`` from pass B.  Member ``l`` contributes the columns ``z_l0 = b_l`` and ``z_lj = b_l t_j / mean_lj``;
+    the cross block is bilinear, so the ``1 / mean`` scaling happens here."""
+    L, J = mean.shape
+    r = int(reference)
+    cross, within, refcol, wsum = dm.scan_gram_w(mbar.f_k, coeff_lb, offset_l, f, reference=r, cross=not approximate)
+    check_w_sums(wsum, 0.0)
+    # z . z' of the columns that meet: b_l b_l, b_l b_r, (b_l t_j)(b_l t_j), (b_l t_j) b_l
+    bb, br, rr = within[:, 0, 0], refcol[:, 0], within[r, 0, 0]
+    if approximate:
+        qbb = qbr = qrr = 0.0
+    else:
+        y, g = _border(mbar, cross)
+        yb = y[:, :, 0]
+        qbb, qbr, qrr = _qform(g, yb, yb), _qform(g, yb, yb[:, r:r + 1]), _qform(g, yb[:, r], yb[:, r])
+    d2 = (bb + qbb) + (rr + qrr) - 2.0 * (br + qbr)
+    d2[r] = 0.0
+    dDelta_f = _sqrt_small_negative_zeroed(d2, warning_cutoff)
+    sigma = np.zeros((J - 1, L))
+    for j in range(1, J):
+        m = mean[:, j]
+        zz, zb = within[:, j, j] / (m * m), within[:, 0, j] / m
+        if not approximate:
+            yz = y[:, :, j] / m[None, :]
+            zz, zb = zz + _qform(g, yz, yz), zb + _qform(g, yz, yb)
+        var = (m * m) * (zz + (bb + qbb) - 2.0 * zb)
+        with np.errstate(invalid="ignore"):
+            sigma[j - 1] = np.sqrt(var)  # (as the reference: sqrt of the covariance's diagonal, mbar.py:1287)
+    return dDelta_f, sigma
+
+
+def compute_scan(mbar, basis_bn, coeff_lb, offset_l=None, A_qn=None, reference=0, compute_uncertainty=True, uncertainty_method=None,
+                 warning_cutoff=1.0e-10):
+    """Free energies, averages and their uncertainties along a linear family of unsampled states.
+
+    Member ``l`` is the state ``u_l(n) = sum_b coeff_lb[l, b] basis_bn[b, n] + offset_l[l]``; ``basis_bn`` is ``(B, N)`` with ``1 <=
+    B <= 8``, ``coeff_lb`` ``(L, B)`` with any ``L >= 1``, ``A_qn`` optional, ``(Q, N)`` with ``Q <= 3`` or ``(N,)``.  Returns a
+    dict: ``f`` ``(L,)`` in the gauge of ``mbar.f_k``; ``Delta_f = f - f[reference]`` and its uncertainty ``dDelta_f`` -- row
+    ``reference`` of what ``compute_perturbed_free_energies(u_ln)`` returns for the dense ``u_ln``; with observables ``mu`` and
+    ``sigma`` ``(Q, L)`` -- entry ``l`` of ``compute_expectations(A_qn[q], u_kn=u_ln, state_dependent=False)``.
+    ``uncertainty_method``: None / "svd-ew" (the bordered form), "approximate", "bootstrap" (adds ``bootstrapped_f`` ``(n_bootstraps,
+    L)`` and ``bootstrapped_observables`` ``(n_bootstraps, Q, L)``; the uncertainties are the ``std`` over replicates as
+    ``compute_perturbed_free_energies`` and ``compute_expectations`` take it); "svd" needs the weight matrix itself and is not
+    offered."""
+    if uncertainty_method == "svd":
+        raise ParameterError("uncertainty_method 'svd' needs the weight matrix itself and is not offered for scans")
+    if uncertainty_method not in (None, "svd-ew", "approximate", "bootstrap"):
+        raise ParameterError(f"Method {uncertainty_method} unrecognized.")
+    bootstrap = uncertainty_method == "bootstrap"
+    if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
+        raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
+    basis_bn, coeff_lb, offset_l, A_qn, L = _check_inputs(mbar, basis_bn, coeff_lb, offset_l, A_qn, reference)
+    dm = _scan_matrix(mbar)
+    Q = len(A_qn)
+    t_qn, shift = _shifted(A_qn)
+    dm.set_Nk(mbar.N_k)
+    dm.set_scan(basis_bn, t_qn)
+    try:
+        lognum, mean = dm.scan_lognum(mbar.f_k, coeff_lb, offset_l)
+        f = -lognum
+        out = dict(f=f, Delta_f=f - f[int(reference)])
+        if Q:
+            out["mu"] = mean[:, 1:].T + shift[:, None]
+        if bootstrap:
+            fb = np.zeros((mbar.n_bootstraps, L))
+            Ab = np.zeros((mbar.n_bootstraps, Q, L))
+            try:
+                for b in range(mbar.n_bootstraps):
+                    mbar._set_bootstrap_weights(dm, b)
+                    ln_b, mean_b = dm.scan_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l)
+                    fb[b] = -ln_b
+                    Ab[b] = mean_b[:, 1:].T + shift[:, None]
+            finally:
+                dm.set_sample_weights(None)
+            out["bootstrapped_f"], out["bootstrapped_observables"] = fb, Ab
+            if compute_uncertainty:
+                out["dDelta_f"] = np.std(fb, axis=0)  # (the per-state spread, as the reference returns it: mbar.py:1514)
+                if Q:
+                    out["sigma"] = np.std(Ab, axis=0)
+        elif compute_uncertainty:
+            out["dDelta_f"], sigma = _analytical(mbar, dm, coeff_lb, offset_l, f, mean, reference, uncertainty_method == "approximate",
+                                                 warning_cutoff)
+            if Q:
+                out["sigma"] = sigma
+    finally:
+        dm.set_scan(None)
+    return out

@@ -14,6 +14,7 @@ import numpy as np
 __all__ = [
     "harmonic_u_kn",
     "harmonic_free_energies",
+    "harmonic_scan_family",
     "exponential_u_kn",
     "exponential_free_energies",
     "config1",
@@ -56,6 +57,21 @@ def harmonic_free_energies(K_k, beta=1.0, subtract_component=0):
     if subtract_component is not None:
         fe = fe - fe[subtract_component]
     return fe
+
+
+def harmonic_scan_family(x_n, O_l, K_l, beta=1.0):
+    """The harmonic oscillators ``(O_l, K_l)`` as a linear family over the samples ``x_n`` for ``MBAR.compute_scan``:
+    ``(basis_bn, coeff_lb, offset_l)`` with basis ``{x^2, x}``, so that ``coeff_lb @ basis_bn + offset_l[:, None]`` is
+    ``u_ln[l, n] = beta/2 * K_l * (x_n - O_l)**2``."""
+    x_n = np.asarray(x_n, dtype=np.float64)
+    O_l = np.atleast_1d(np.asarray(O_l, dtype=np.float64))
+    K_l = np.atleast_1d(np.asarray(K_l, dtype=np.float64))
+    if O_l.shape != K_l.shape or O_l.ndim != 1:
+        raise ValueError("O_l and K_l must have one entry per member")
+    basis_bn = np.stack([x_n * x_n, x_n])
+    coeff_lb = np.stack([0.5 * beta * K_l, -beta * K_l * O_l], axis=1)
+    offset_l = 0.5 * beta * K_l * O_l * O_l
+    return basis_bn, coeff_lb, offset_l
 
 
 def exponential_u_kn(rates, N_k, seed=None, beta=1.0):

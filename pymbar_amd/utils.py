@@ -97,6 +97,33 @@ def check_w_sums(column_sums, row_sum_dev, tolerance=1.0e-4):
         raise ParameterError("Warning: Should have \\sum__k N_k W_nk = 1.")
 
 
+
+def bordered_theta_basis(G, N_k):
+    """``(rt, lam, V, g)`` of the border of the asymptotic covariance ``W^T (I - W N W^T)^+ W`` for weight columns with ``N = 0``
+    appended to the resident ``W``.  With ``A = W D^(1/2)``, ``D = diag(N_k)``, ``rt = sqrt(N_k)`` and ``A^T A = D^(1/2) G D^(1/2) =
+    V diag(lam) V^T``: ``(I - A A^T)^+ = I + U diag(g) U^T`` on the range of ``A`` (``U = A V lam^(-1/2)``), ``g = lam / (1 -
+    lam)`` -- and ``g = -1`` on the direction ``lam = 1``, the normalisation ``sum_k N_k W_nk = 1``, which the pseudo-inverse
+    removes.  Directions with ``lam <= 1e-10`` (states without samples) carry nothing."""
+    rt = np.sqrt(np.asarray(N_k, dtype=np.float64))
+    lam, V = np.linalg.eigh(rt[:, None] * G * rt[None, :])
+    keep = lam > 1e-10
+    lam, V = lam[keep], V[:, keep]
+    one = np.abs(1.0 - lam) <= 1e-10
+    g = np.where(one, -1.0, lam / np.where(one, 1.0, 1.0 - lam))
+    return rt, lam, V, g
+
+
+def bordered_theta_factors(G, C, N_k):
+    """``(Y, g)`` with ``Theta(z, z') = z . z' + y(z)^T diag(g) y(z')`` for appended weight columns ``z`` with ``N = 0`` whose
+    cross block with the resident weights is ``C = W^T Z`` (``K x columns``): ``Y = U^T Z = lam^(-1/2) V^T D^(1/2) C`` in the
+    notation of :func:`bordered_theta_basis`.  Histogram bins by label have disjoint supports, ``Z^T Z = diag(d)``, and
+    ``Theta_bins = diag(d) + Y^T diag(g) Y``; the members of a scan need ``z . z'`` on the diagonal and against one reference
+    column only."""
+    rt, lam, V, g = bordered_theta_basis(G, N_k)
+    Y = (V.T @ (rt[:, None] * C)) / np.sqrt(lam)[:, None]
+    return Y, g
+
+
 def kn_to_n(kn, N_k=None, cleanup=False):
     """(K, N_max) -> (N_total,) concatenation of the first N_k[k] entries of each row (pymbar/utils.py:78-114)."""
     kn = np.asarray(kn)
