@@ -111,6 +111,8 @@ int mbar_device_synchronize(int device);
  *   "adapt_batch"    adaptive iterations enqueued between two looks at the control words (default 8)
  *   "hist_part_bytes" byte budget of the partial records of one sweep of the binned passes (default 256 MiB); read by
  *                    mbar_ctx_set_bins, which cuts the bins into tiles -- one sweep each -- until a sweep's records fit
+ *   "scan_part_bytes" byte budget of the partial records of one launch of pass A of the scans (default 256 MiB); read by
+ *                    mbar_scan_lognum, which cuts the members into panels of a multiple of 64 (at least 64) whose records fit
  *   "pmode"          1 = the device-resident loop keeps P = exp(a0 - u - logden(a0)) resident (one more K x N array, built
  *                    once per solve) and sweeps that: no exponentials in the loop (default); 0 = sweeps recompute them from u
  *                    (what runs when P does not fit on some rank)
@@ -339,7 +341,8 @@ int mbar_bin_gram_w(mbar_ctx* ctx, const double* f, const double* f_bins, double
  *                       row-major upper triangle), refcol[l][j] = sum_n c_n b_rn b_ln t_jn (L x J), wsum[l] = sum_n c_n b_ln (1 at
  *                       f_scan = -lognum).  The matrix is read once per panel of 64 .. 256 members.
  * No floating-point atomics; the samples are cut into chunks by N alone and merged in chunk order: two identical calls return
- * identical bits, and member l's outputs do not depend on the other members of the call.  Kernel time: MBAR_TIMER_OTHER. */
+ * identical bits, and member l's outputs do not depend on the other members of the call, nor on where the member panels of
+ * pass A are cut: they are the same bits for any value of "scan_part_bytes".  Kernel time: MBAR_TIMER_OTHER. */
 #define MBAR_SCAN_MAX_B 8
 #define MBAR_SCAN_MAX_Q 3
 int mbar_ctx_set_scan(mbar_ctx* ctx, int64_t B, const double* basis, int64_t Q, const double* t);

@@ -21,7 +21,12 @@
 // Order.  The cut of N into chunks depends on N alone; a member's sums are the same sequence of operations wherever it sits in
 // the call (which wave, which block, which lane column); the merge kernels add a member's chunk records in chunk order
 // (compensated).  No atomics: two identical calls return identical bits, and member l's outputs do not depend on the others.
+// Every fused multiply-add below is written as one (fma, MFMA) and nothing else is contracted: left to the compiler, "wsum += c_n
+// b_ln" became one fma at every unrolled site of k_scan_cross<0, J> but only at some of the sites of <NB > 0, J> (a rounded product
+// and an addition at the others), so that cross = NULL changed wsum by an ulp wherever a multiplicity c_n makes c_n b_ln inexact.
 #include "mbar_device.h"
+
+#pragma clang fp contract(off)
 
 namespace mbar {
 

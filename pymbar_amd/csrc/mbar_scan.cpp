@@ -8,8 +8,7 @@ using namespace mbar::host;
 
 namespace {
 
-constexpr int64_t SCAN_MAX_K = 128;                     // one W tile of the cross kernel
-constexpr int64_t SCAN_PART_BYTES = (int64_t)1 << 28;   // partial records of one launch of pass A
+constexpr int64_t SCAN_MAX_K = 128;  // one W tile of the cross kernel
 
 int scan_ready(mbar_ctx* c, const char* who) {
     if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
@@ -106,9 +105,10 @@ int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coef
     rc = upload_members(c, L, coeff, offset, nullptr);
     if (rc) return rc;
     const ScanData d = data_of(c);
-    // members in panels of a multiple of 64 whose records ([chunk][member][J]) fit the budget: a member's sums do not depend on the cut
+    // members in panels of a multiple of 64 whose records ([chunk][member][J]) fit the budget ("scan_part_bytes"): a member's sums
+    // do not depend on the cut
     const int64_t nchunks = (c->N + SCAN_VCHUNK - 1) / SCAN_VCHUNK;
-    int64_t pw = SCAN_PART_BYTES / (std::max<int64_t>(nchunks, 1) * J * (int64_t)sizeof(double)) / 64 * 64;
+    int64_t pw = c->opt_scan_part_bytes / (std::max<int64_t>(nchunks, 1) * J * (int64_t)sizeof(double)) / 64 * 64;
     pw = std::min<int64_t>(std::max<int64_t>(pw, 64), (L + 63) / 64 * 64);
     HIPCHK(c, c->scan_part.grow((size_t)std::max<int64_t>(nchunks, 1) * (size_t)pw * (size_t)J));
     HIPCHK(c, c->scan_out.grow((size_t)L * (size_t)(2 + J)));

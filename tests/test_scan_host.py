@@ -8,7 +8,7 @@ import pymbar_amd
 from pymbar_amd import testsystems
 from pymbar_amd.utils import DataError, ParameterError
 from tests.conftest import load_golden
-from tests.scan_standin import ScanOracleMatrix
+from tests.scan_standin import ScanFloat64Matrix, ScanOracleMatrix, build_case, case_id, instantiation_cases, run_passes
 
 
 @pytest.fixture
@@ -221,3 +221,30 @@ def test_handles_without_the_scan_passes_are_refused(monkeypatch, config1):
     mbar = pymbar_amd.MBAR(u_kn, N_k)
     with pytest.raises(ParameterError, match="not supported on this backend"):
         mbar.compute_scan(np.stack([x_n * x_n, x_n]), np.ones((2, 2)))
+
+
+@pytest.mark.parametrize("shape", instantiation_cases(), ids=case_id)
+def test_instantiation_cases_suit_the_standin(shape):
+    """The cases tests/test_gpu_scan.py holds the device to (rtol 1e-10 with atol 0 on the products, 1e-11 absolute on lognum and
+    wsum) are cases at which the long-double stand-in is a reference: everything is finite, the weights are normalised, no entry of
+    a product is zero or negative (the shifted observables leave nothing to cancel, so a relative bound alone means something), and
+    the same formulas in plain float64 give the same numbers to 1e-12 relative -- a factor 100 under the device's bound.  lognum is
+    held to 1e-12 absolute (a factor 10 under the device's): the far member's is about -900, where one ulp is 1.1e-13."""
+    case = build_case(shape, True)
+    ref = shape[2] - 1
+    out = []
+    for cls in (ScanOracleMatrix, ScanFloat64Matrix):
+        m = cls(case["u"])
+        m.set_Nk(case["N_k"])
+        m.set_sample_weights(case["c"])
+        m.set_scan(case["basis"], case["t"])
+        out.append(run_passes(m, case, ref=ref))
+    want, plain = out
+    for name, v in want.items():
+        assert np.all(np.isfinite(v)), name
+    np.testing.assert_allclose(want["wsum"], 1.0, rtol=0, atol=1e-13)
+    for name in ("cross", "within", "refcol", "mean"):
+        assert np.all(want[name] > 0.0), name
+    np.testing.assert_allclose(plain["lognum"], want["lognum"], rtol=0, atol=1e-12)
+    for name in ("mean", "cross", "within", "refcol", "wsum"):
+        np.testing.assert_allclose(plain[name], want[name], rtol=1e-12, atol=0)
