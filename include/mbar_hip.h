@@ -457,6 +457,11 @@ void mbar_kde_destroy(mbar_kde* kde);
 int mbar_kde_set_weights(mbar_kde* kde, int64_t C, const double* v);
 /* q: M x d row-major host array (finite); out: M x C row-major host array of log densities. */
 int mbar_kde_eval(mbar_kde* kde, int64_t M, const double* q, double* out);
+/* Options of a handle.  "max_chunks": the largest number of sample chunks (workgroups along the samples) of the next
+ * mbar_kde_eval calls; 0 (default): ceil(4 num_cu / query blocks), any value >= 1 caps that number (it stays at most the number
+ * of 64-sample tiles).  Results for different cuts agree to rounding; for one cut they are the same bits from call to call.
+ * An unknown key or a negative value is MBAR_ERR_ARG. */
+int mbar_kde_set_option(mbar_kde* kde, const char* key, int64_t value);
 /* The log-normaliser log(1 / integral of k_h over R^d) the library adds (host only; tests / documentation). */
 int mbar_kde_log_norm(int kernel, int d, double bandwidth, double* out);
 

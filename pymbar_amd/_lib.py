@@ -145,7 +145,8 @@ SIGNATURES = {
     "mbar_kde_destroy": (None, [C.c_void_p]),
     "mbar_kde_set_weights": (C.c_int, [C.c_void_p, C.c_int64, _dp]),
     "mbar_kde_eval": (C.c_int, [C.c_void_p, C.c_int64, _dp, _dp]),
-    "mbar_kde_log_norm": (C.c_int, [C.c_int, C.c_int, C.c_double, _dp]),
+    "mbar_kde_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "mbar_kde_log_norm":(C.c_int, [C.c_int, C.c_int, C.c_double, _dp]),
     "mbar_acf_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, _dp, _dp, C.c_int64, _ip, C.c_double, C.c_double]),
     "mbar_acf_destroy": (None, [C.c_void_p]),
     "mbar_acf_suffix_g": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _dp, _ip, C.POINTER(C.c_int32)]),

@@ -23,6 +23,12 @@
 // than ~900 doublings below the shift would lose its terms to underflow.  k_kde_combine flags such (query, column) pairs
 // (sum < 2^-900 with a positive column total) and k_kde_exact recomputes them with their own maximum over the samples of
 // positive weight, in plain log space: the result is the exact, finite log density wherever one exists.
+//
+// A pair so far apart that r^2, or r coef, overflows (|q - x| beyond ~1e154 for the gaussian kernel) makes the exp2s argument
+// -inf, and exp2s(-inf) is inf - inf = NaN in every column sum of that query (and of no other: a query is a lane).  The common
+// path does not test for it: k_kde_combine flags a NaN sum like a small one, and k_kde_exact -- which measures an overflowing
+// distance in units of its largest coordinate difference -- returns the value the exact log density rounds to: finite where
+// -r / h or -r^2 / 2h^2 is inside the fp64 range, -inf below it, never NaN.
 #include "mbar_device.h"
 
 namespace mbar {
@@ -164,7 +170,9 @@ k_kde_combine(const double* __restrict__ part, int64_t nchunks, int CB, int64_t 
         L = NAN;  // a column of zero total weight has no density
     } else {
         L = (unbounded ? mx * LN2_OVER_S : 0.0) + log(s) - lw + lognorm;
-        fl = s < KDE_FLAG_BELOW && (unbounded || s > 0.0);
+        // (unbounded kernels: also a NaN sum -- a pair whose r coef overflowed to -inf put inf - inf into every column of its
+        // query; k_kde_exact works in log space and gives such a query its finite value, or -inf below the fp64 range)
+        fl = unbounded ? !(s >= KDE_FLAG_BELOW) : (s < KDE_FLAG_BELOW && s > 0.0);
     }
     out[q * cv + c] = L;
     flag[q * cv + c] = fl;
@@ -197,9 +205,26 @@ k_kde_exact(const double* __restrict__ X, int64_t ldx, int dg, int64_t N, const 
             }
         }
         double lk;
-        if constexpr (KER == KDE_GAUSSIAN) lk = -0.5 * r2 * inv_h2;
-        else if constexpr (KER == KDE_EXPONENTIAL) lk = -sqrt(r2) * inv_h;
-        else {
+        if constexpr (kde_unbounded<KER>()) {
+            if (r2 < INFINITY) {
+                lk = KER == KDE_GAUSSIAN ? -0.5 * r2 * inv_h2 : -sqrt(r2) * inv_h;
+            } else {
+                // r^2 is beyond the fp64 range, r / h need not be: the distance in units of the largest |dx| (halved
+                // coordinates, exact at this size: q - x itself may overflow).  Rolled loops on the coordinates in memory:
+                // this path is rare and must not cost the common one registers.
+                double amax = 0.0;
+#pragma unroll 1
+                for (int k = 0; k < dg; ++k) amax = fmax(amax, fabs(0.5 * Q[k * ldq + q] - 0.5 * X[k * ldx + n]));
+                double u2 = 0.0;
+#pragma unroll 1
+                for (int k = 0; k < dg; ++k) {
+                    const double u = (0.5 * Q[k * ldq + q] - 0.5 * X[k * ldx + n]) / amax;
+                    u2 = fma(u, u, u2);
+                }
+                const double rh = 2.0 * (amax * inv_h * sqrt(u2));  // r / h (inf when that is out of range too)
+                lk = KER == KDE_GAUSSIAN ? -0.5 * rh * rh : -rh;
+            }
+        } else {
             const double kv = kde_compact<KER>(sqrt(r2), h, inv_h, inv_h2);
             if (!(kv > 0.0)) return -INFINITY;
             lk = log(kv);

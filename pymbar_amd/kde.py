@@ -60,6 +60,10 @@ class DeviceKDE(_lib.Handle):
         _lib.check(self._lib.mbar_kde_set_weights(self._h, V.shape[1], _lib.ptr(V)))
         self.n_columns = V.shape[1]
 
+    def set_option(self, key, value):
+        """``mbar_kde_set_option``: ``"max_chunks"`` caps the number of sample chunks of the next calls (0: the default cut)."""
+        _lib.check(self._lib.mbar_kde_set_option(self._h, key.encode(), int(value)))
+
     def log_density(self, Q):
         Q = np.ascontiguousarray(Q, dtype=np.float64)
         out = np.empty((Q.shape[0], self.n_columns), dtype=np.float64)

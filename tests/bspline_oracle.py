@@ -20,13 +20,14 @@ def intervals(t, k, x):
     return np.clip(ub - 1, k, n - 1)
 
 
-def basis_values(t, k, x):
-    """(N, k + 1) values of B_{l-k .. l} at x (long double) and the intervals l."""
+def basis_values(t, k, x, dtype=LD):
+    """(N, k + 1) values of B_{l-k .. l} at x (long double) and the intervals l.  ``dtype=np.float64``: the same recursion, every
+    operation rounded to float64 and none fused -- the operation order of scipy's own evaluation."""
     x = np.asarray(x, dtype=np.float64).reshape(-1)
     l = intervals(t, k, x)
-    tl = np.asarray(t, dtype=LD)
-    xl = x.astype(LD)
-    h = np.zeros((len(x), k + 1), dtype=LD)
+    tl = np.asarray(t, dtype=dtype)
+    xl = x.astype(dtype)
+    h = np.zeros((len(x), k + 1), dtype=dtype)
     h[:, 0] = 1
     for j in range(1, k + 1):
         hh = h[:, :j].copy()
@@ -35,8 +36,8 @@ def basis_values(t, k, x):
             xb = tl[l + m]
             xa = tl[l + m - j]
             same = xb == xa
-            d = np.where(same, LD(1), xb - xa)
-            w = np.where(same, LD(0), hh[:, m - 1] / d)
+            d = np.where(same, dtype(1), xb - xa)
+            w = np.where(same, dtype(0), hh[:, m - 1] / d)
             h[:, m - 1] += w * (xb - xl)
             h[:, m] = w * (xl - xa)
     return h, l
@@ -120,6 +121,65 @@ class OracleBSplineMoments:
 
     def __exit__(self, *exc):
         self.close()
+
+
+# ---- the cases of the instantiation tests of k_bspline<K, CB> (tests/test_gpu_spline_fes.py) ------------------------------------
+# k_bspline<K, CB> has 8 x 6 bodies: K = 0 .. 7 is the degree, CB the smallest of 1, 2, 4, 8, 16, 32 that holds the C columns.
+C_TO_CB = {1: 1, 2: 2, 3: 4, 7: 8, 13: 16, 29: 32}
+SLAB_ENTRIES = 768  # (cell, column) entries of one output tile: tile_cells = 768 / CB
+
+
+def knots(k, nbasis, lo=-1.0, hi=1.0, rng=None):
+    inner = np.linspace(lo, hi, nbasis - k + 1)
+    if rng is not None:  # non-uniform, with a repeated interior knot
+        inner = np.sort(np.r_[lo, hi, rng.uniform(lo, hi, nbasis - k - 1)])
+        if len(inner) > 4:
+            inner[2] = inner[3]
+    return np.r_[[lo] * k, inner, [hi] * k]
+
+
+def tile_seams(k, nbasis, G, C):
+    """The flattened cells g nbasis + i at which an output tile starts (all but the first)."""
+    tile = SLAB_ENTRIES // C_TO_CB[C]
+    return list(range(tile, G * nbasis, tile))
+
+
+def cell_keys(x, groups, t, k):
+    """The first flattened cell g nbasis + l - k of every sample (its k + 1 entries follow it in row g)."""
+    return np.asarray(groups, dtype=np.int64) * (len(t) - k - 1) + intervals(t, k, x) - k
+
+
+def matrix_case(k, C, N=700):
+    """x, V, t, groups, G for one body: about 2.5 output tiles (G nbasis = 2.5 x 768 / CB cells), non-uniform knots with a repeated
+    interior knot, x at every knot, at xrange[1], outside the range, and -- for k >= 1 -- on both sides of and across every tile
+    seam that lies inside a row.  N = 700 is one sample chunk: three batches for wave 0 and a ragged last batch."""
+    rng = np.random.default_rng(1000 * k + C)
+    nbasis = 11 + k
+    tile = SLAB_ENTRIES // C_TO_CB[C]
+    G = -(-5 * tile // (2 * nbasis))
+    t = knots(k, nbasis, rng=rng)
+    xs, gs = [], []
+    for f0 in tile_seams(k, nbasis, G, C):
+        g, i = divmod(f0, nbasis)
+        # intervals l whose entries l - k .. l end left of the seam, straddle it, start at it
+        for l in [i - 1] + list(range(i, i + k)) + [i + k]:
+            if k <= l <= nbasis - 1 and t[l] < t[l + 1]:
+                xs.append(0.5 * (t[l] + t[l + 1]))
+                gs.append(g)
+    fixed = np.r_[xs, t, 1.0]
+    x = np.r_[fixed, rng.uniform(-1.4, 1.4, N - len(fixed))]
+    groups = np.r_[gs, rng.integers(0, G, N - len(gs))].astype(np.int64)
+    perm = rng.permutation(N)
+    return x[perm], rng.normal(size=(N, C))[perm], t, groups[perm], G
+
+
+def scipy_case(k, N=300):
+    """x, t for the comparison with scipy's design matrix bit for bit: non-uniform knots with a repeated interior knot, x at the
+    knots, inside and outside the range; one sample per group (G = N)."""
+    rng = np.random.default_rng(50 + k)
+    t = knots(k, 11 + k, -1.0, 2.0, rng=rng)
+    x = np.r_[t, 2.0, -1.0, rng.uniform(-1.5, 2.5, N - len(t) - 2)]
+    return x, t
 
 
 # ---- the cases of tests/golden/fes_spline.npz (tests/golden/make_golden_fes_spline.py) ------------------------------------------

@@ -106,6 +106,122 @@ def log_density(X, V, Q, kernel, h, block=None):
     return L
 
 
+# ---- the same sum in long double --------------------------------------------------------------------------------------------
+LD = np.longdouble
+LD_PI = 4 * np.arctan(LD(1))
+
+
+def _ld_log_unit_ball_volume(d):
+    """log(pi^(d/2) / Gamma(d/2 + 1)) with Gamma(d/2 + 1) as a finite product (d <= 8 here, any d works)."""
+    g = LD(1) if d % 2 == 0 else np.sqrt(LD_PI)
+    a = LD(d) / 2
+    while a > 0:
+        g = g * a
+        a = a - 1
+    return LD(d) / 2 * np.log(LD_PI) - np.log(g)
+
+
+def log_normaliser_ld(kernel, d, h):
+    """:func:`log_normaliser` in long double, from the closed forms of the radial integrals int_0^1 r^(d-1) k(r) dr (the float64
+    one integrates by quadrature: tests/test_kde_host.py holds the two against each other)."""
+    h = LD(h)
+    dlogh = d * np.log(h)
+    if kernel == "gaussian":
+        return -LD(d) / 2 * np.log(2 * LD_PI) - dlogh
+    logS = np.log(LD(d)) + _ld_log_unit_ball_volume(d)  # surface of the unit sphere
+    if kernel == "exponential":
+        fact = LD(1)
+        for i in range(2, d):
+            fact = fact * i
+        return -(logS + np.log(fact)) - dlogh
+    if kernel == "tophat":
+        radial = LD(1) / d
+    elif kernel == "epanechnikov":
+        radial = LD(1) / d - LD(1) / (d + 2)
+    elif kernel == "linear":
+        radial = LD(1) / d - LD(1) / (d + 1)
+    else:  # I_n = int r^n cos(pi r / 2), J_n = int r^n sin(pi r / 2): I_n = 2/pi - (2n/pi) J_(n-1), J_n = (2n/pi) I_(n-1)
+        I = J = 2 / LD_PI
+        for n in range(1, d):
+            I, J = 2 / LD_PI - (2 * n / LD_PI) * J, (2 * n / LD_PI) * I
+        radial = I
+    return -(logS + np.log(radial)) - dlogh
+
+
+def log_kernel_ld(kernel, X, Q, h):
+    """(M, N) log k_h in long double.  gaussian / exponential: from the float64 coordinates, every step in long double.  Compact
+    kernels: the library specifies the support test in float64 -- ``r2 = r2 + dx*dx`` in coordinate order without fma, the float64
+    square root, ``dist < h`` -- and sklearn's formulas are functions of that float64 ``dist``; both are reproduced here, and the
+    kernel value of a pair inside the support is evaluated on that ``dist`` in long double."""
+    X = np.asarray(X, dtype=np.float64)
+    Q = np.asarray(Q, dtype=np.float64)
+    hl = LD(h)
+    if kernel in ("gaussian", "exponential"):
+        r2 = np.zeros((Q.shape[0], X.shape[0]), dtype=LD)
+        for j in range(X.shape[1]):
+            dx = Q[:, None, j].astype(LD) - X[None, :, j].astype(LD)
+            r2 = r2 + dx * dx
+        return -r2 / (2 * hl * hl) if kernel == "gaussian" else -np.sqrt(r2) / hl
+    r2 = np.zeros((Q.shape[0], X.shape[0]))
+    with np.errstate(over="ignore"):
+        for j in range(X.shape[1]):
+            dx = Q[:, None, j] - X[None, :, j]
+            r2 = r2 + dx * dx
+        dist = np.sqrt(r2)
+    inside = dist < float(h)
+    u = np.where(inside, dist, 0.0).astype(LD) / hl
+    if kernel == "tophat":
+        k = np.ones_like(u)
+    elif kernel == "epanechnikov":
+        k = 1 - u * u
+    elif kernel == "linear":
+        k = 1 - u
+    else:
+        k = np.cos(LD_PI / 2 * u)
+    with np.errstate(divide="ignore"):
+        return np.where(inside & (k > 0), np.log(np.where(k > 0, k, LD(1))), -LD(np.inf))
+
+
+def log_density_ld(X, V, Q, kernel, h):
+    """``(L, cond)``: the (M, C) log densities of :func:`log_density` with every step in long double (per pair log k, per (query,
+    column) the maximum over the samples of positive weight and the log-sum-exp, the column totals, the normaliser), rounded to
+    float64 at the end -- a value below the float64 range becomes -inf; a column of zero total weight gives NaN.  ``cond[m, c]``
+    is the number of samples of positive weight with a positive kernel value, the terms an entry is made of."""
+    X = np.asarray(X, dtype=np.float64)
+    Q = np.asarray(Q, dtype=np.float64)
+    V = np.asarray(V, dtype=np.float64)
+    if V.ndim == 1:
+        V = V[:, None]
+    M, C = Q.shape[0], V.shape[1]
+    lk = log_kernel_ld(kernel, X, Q, h)
+    lognorm = log_normaliser_ld(kernel, X.shape[1], h)
+    L = np.full((M, C), np.nan, dtype=LD)
+    cond = np.zeros((M, C), dtype=np.int64)
+    for c in range(C):
+        pos = V[:, c] > 0
+        if not pos.any():
+            continue
+        t = lk[:, pos] + np.log(V[pos, c].astype(LD))[None, :]
+        tm = t.max(axis=1)
+        fin = np.isfinite(tm)
+        cond[:, c] = np.sum(np.isfinite(t), axis=1)
+        s = np.sum(np.exp(t[fin] - tm[fin, None]), axis=1)
+        Lc = np.full(M, -LD(np.inf))
+        Lc[fin] = tm[fin] + np.log(s)
+        L[:, c] = Lc - np.log(np.sum(V[pos, c].astype(LD))) + lognorm
+    with np.errstate(over="ignore"):
+        return L.astype(np.float64), cond
+
+
+def chunk_ranges(N, max_chunks, tile=64):
+    """The sample ranges [n0, n1) of the chunks of an evaluation under the handle option ``"max_chunks"`` >= 1 (the host's cut:
+    whole tiles of 64 samples, ceil(tiles / chunks) tiles per chunk; the padding of the last tile repeats the last sample)."""
+    ntiles = (N + tile - 1) // tile
+    want = max(1, min(max_chunks, ntiles))
+    per = (ntiles + want - 1) // want * tile
+    return [(n0, min(n0 + per, N)) for n0 in range(0, ntiles * tile, per)]
+
+
 class OracleKDE:
     """Stand-in for ``pymbar_amd.kde.DeviceKDE`` on the CPU."""
 

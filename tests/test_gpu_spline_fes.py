@@ -1,4 +1,5 @@
-"""Weighted B-spline moments on the MI355X (``mbar_bspline_*``) against the long-double oracle of tests/bspline_oracle.py, and
+"""Weighted B-spline moments on the MI355X (``mbar_bspline_*``) against the long-double oracle of tests/bspline_oracle.py (every
+body of ``k_bspline<K, CB>`` among them, and the bases against scipy's design matrix bit for bit), and
 the spline surfaces of ``pymbar_amd.FES`` through the device against the unmodified reference (tests/golden/fes_spline.npz)."""
 import numpy as np
 import pytest
@@ -13,13 +14,7 @@ from tests.conftest import load_golden
 pytestmark = pytest.mark.gpu
 
 
-def knots(k, nbasis, lo=-1.0, hi=1.0, rng=None):
-    inner = np.linspace(lo, hi, nbasis - k + 1)
-    if rng is not None:  # non-uniform, with a repeated interior knot
-        inner = np.sort(np.r_[lo, hi, rng.uniform(lo, hi, nbasis - k - 1)])
-        if len(inner) > 4:
-            inner[2] = inner[3]
-    return np.r_[[lo] * k, inner, [hi] * k]
+knots = bo.knots
 
 
 def check(x, V, t, k, groups=None, G=1):
@@ -79,6 +74,41 @@ def test_moments_state_sorted_7e6():
     g = np.repeat(np.arange(7), n)
     t = knots(3, 10, -0.7, 0.7)
     check(x, np.ones(len(x)), t, 3, g, G=7)
+
+
+# ---- every body of k_bspline<K, CB>: K = 0 .. 7 x CB = 1, 2, 4, 8, 16, 32 (C = 1, 2, 3, 7, 13, 29) -------------------------------------
+@pytest.mark.parametrize("C", list(bo.C_TO_CB))
+@pytest.mark.parametrize("k", range(8))
+def test_moments_every_body(k, C):
+    """One sample chunk (N = 700: three batches for wave 0, a ragged last batch), about 2.5 output tiles with samples on both sides
+    of and across every tile seam (tests/bspline_oracle.py: matrix_case; tests/test_spline_fes_host.py checks the coverage)."""
+    x, V, t, g, G = bo.matrix_case(k, C)
+    check(x, V, t, k, g, G)
+
+
+@pytest.mark.parametrize("k,C", list(zip((2, 5, 3, 7, 1, 4), bo.C_TO_CB)))
+def test_moments_every_width_two_chunks(k, C):
+    x, V, t, g, G = bo.matrix_case(k, C, N=4096 + 300)
+    check(x, V, t, k, g, G)
+
+
+@pytest.mark.parametrize("k", range(8))
+def test_bases_are_scipys_bits(k):
+    """One sample per group and unit weights: row g of the moments is a single product through exact sums, so it must be row g of
+    scipy's design matrix bit for bit (the claim of csrc/mbar_k_bspline.hip; scipy's matrix is the unfused float64 recursion,
+    tests/test_spline_fes_host.py).  The device adds a product to zeros, so a zero comes out positive: values are compared, the
+    sign of a zero is not.  With 13 columns (CB = 16), one of ones and the others powers of two, the scaling is exact too."""
+    x, t = bo.scipy_case(k)
+    N = len(x)
+    D = BSpline.design_matrix(x, t, k, extrapolate=True).toarray()
+    scale = 2.0 ** np.array([0, -3, 5, 1, -1, 10, -20, 2, 3, -2, 7, -7, 4])
+    with DeviceBSplineMoments(x, groups=np.arange(N), n_groups=N) as dev:
+        got = dev.moments(t, k)
+        assert got.shape == (N, 1, D.shape[1])
+        np.testing.assert_array_equal(got[:, 0, :], D)
+        dev.set_weights(np.tile(scale, (N, 1)))
+        got = dev.moments(t, k)
+        np.testing.assert_array_equal(got, D[:, None, :] * scale[None, :, None])
 
 
 def test_nonfinite_input_raises():

@@ -8,7 +8,7 @@ import pytest
 import pymbar_amd
 from pymbar_amd import kde as amd_kde
 from pymbar_amd.utils import DataError, ParameterError
-from tests import kde_oracle
+from tests import kde_cases, kde_oracle
 from tests.conftest import load_golden
 
 KERNELS = kde_oracle.KERNELS
@@ -249,3 +249,131 @@ def test_fes_input_rules(standins):
         off += n
     fes.generate_fes(u_kn_layout, u["x_n"], fes_type="kde", kde_parameters={"bandwidth": 0.05})
     np.testing.assert_array_equal(fes.u_n, u["u_n"])
+
+
+# ---- the long-double oracle and the cases of the instantiation tests (tests/kde_cases.py) ------------------------------------
+def _same_pattern(a, b):
+    np.testing.assert_array_equal(np.isnan(a), np.isnan(b))
+    np.testing.assert_array_equal(np.isneginf(a), np.isneginf(b))
+    assert not np.any(np.isposinf(a)) and not np.any(np.isposinf(b))
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_long_double_normaliser_matches_quadrature(kernel):
+    assert np.finfo(np.longdouble).eps < 1.1e-19  # (the oracle needs the 64-bit mantissa of x87 long double)
+    for d in range(1, 9):
+        for h in (0.3, 1.0, 2.5):
+            assert abs(float(kde_oracle.log_normaliser_ld(kernel, d, h)) - kde_oracle.log_normaliser(kernel, d, h)) < 1e-13
+            # the library's own: a few ulps of a value of at most 20 (the cosine recursion in fp64 left 2.3e-13 at d = 8)
+            assert abs(float(kde_oracle.log_normaliser_ld(kernel, d, h)) - amd_kde.log_normaliser(kernel, d, h)) < 1e-14
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_matrix_cases_suit_both_oracles(kernel, capsys):
+    """Every case of the device's instantiation matrix: finite input, finite answers where they are meant to be, the float64 and
+    the long-double oracle with the same NaN / -inf pattern, and the float64 oracle's scaled error against the long-double one
+    (printed: the baseline of profiles/kde_instantiation_matrix.txt) far below the 1e-11 the float64 oracle has been trusted to."""
+    worst = 0.0
+    for k, d, C in kde_cases.matrix_cases():
+        if k != kernel:
+            continue
+        X, V, Q, h = kde_cases.matrix_case(k, d, C)
+        assert X.shape == (197, d) and Q.shape == (259, d) and V.shape == (197, C)
+        assert all(np.all(np.isfinite(a)) for a in (X, V, Q)) and np.all(V >= 0)
+        assert 0.1 < np.mean(V.max(axis=1) == 0) < 0.3
+        L, cond = kde_cases.matrix_oracle(k, d, C)
+        L64 = kde_oracle.log_density(X, V, Q, k, h)
+        _same_pattern(L64, L)
+        live = np.ones(C, dtype=bool)
+        if C >= 3:
+            live[1] = False
+            assert np.all(np.isnan(L[:, 1]))
+        assert not np.any(np.isnan(L[:, live]))
+        np.testing.assert_array_equal(np.isfinite(L[:, live]), cond[:, live] > 0)
+        if k in kde_cases.UNBOUNDED:
+            assert np.all(np.isfinite(L[:, live]))  # the far queries too
+        else:  # queries with and without a weighted sample inside the support, the far ones without
+            assert np.any(np.isfinite(L[:-2, live])) and np.all(np.isneginf(L[-2:, live]))
+        err = kde_cases.scaled_error(L64, L)
+        with capsys.disabled():
+            print(f"\nfloat64-oracle {k:13s} d={d} C={C:2d} scaled error vs long double {err:.3e}", end="")
+        worst = max(worst, err)
+    assert worst < 1e-12
+
+
+def test_chunk_ranges_follow_the_host_cut():
+    assert kde_oracle.chunk_ranges(197, 1) == [(0, 197)]
+    assert kde_oracle.chunk_ranges(197, 2) == [(0, 128), (128, 197)]
+    assert kde_oracle.chunk_ranges(197, 3) == [(0, 128), (128, 197)]  # ceil(4 / 3) = 2 tiles per chunk
+    assert kde_oracle.chunk_ranges(192, 3) == [(0, 64), (64, 128), (128, 192)]
+    assert kde_oracle.chunk_ranges(197, 7) == [(0, 64), (64, 128), (128, 192), (192, 197)]
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_exact_cases_hold_the_pairs_they_are_built_for(kernel):
+    for d in kde_cases.EXACT_DIMS:
+        X, V, Q, h = kde_cases.exact_case(kernel, d)
+        L, cond = kde_oracle.log_density_ld(X, V, Q, kernel, h)
+        _same_pattern(kde_oracle.log_density(X, V, Q, kernel, h), L)
+        assert not np.any(np.isnan(L))
+        if kernel in kde_cases.UNBOUNDED:
+            assert np.all(np.isfinite(L))
+            assert np.all(L[:10, 2] < L[:10, 1] - 900 * np.log(2))  # flagged: far below the shared shift
+        else:
+            assert np.all(np.isneginf(L[:10, 2])) and np.all(np.isneginf(L[20:]))  # zero-weight inside / nothing inside
+            assert np.all(np.isfinite(L[:10, 3])) and np.all(cond[:10, 3] >= 1)  # positive sum below 2^-900
+            assert np.all(L[:10, 3] < L[:10, 1] + np.log(1e-280))
+
+
+@pytest.mark.parametrize("kernel", kde_cases.UNBOUNDED)
+def test_combine_cases_order_the_chunk_shifts(kernel):
+    for order, want in ((("far", "mid", "near"), (0, 1, 2)), (("near", "far", "mid"), (1, 2, 0))):
+        X, V, Q, h = kde_cases.combine_case(kernel, order)
+        mx = kde_cases.chunk_maxima_doublings(X, Q, kernel, h, 3)
+        assert mx.shape == (len(Q), 3)
+        lo, mid, hi = (mx[:, i] for i in want)
+        assert np.all(hi - lo > 960 + 2 * 256) and np.all(hi - mid > 256) and np.all(hi - mid < 960 - 256) and np.all(mid - lo > 256)
+        assert np.all(np.isfinite(kde_oracle.log_density_ld(X, V, Q, kernel, h)[0]))
+
+
+@pytest.mark.parametrize("kernel", kde_cases.COMPACT)
+def test_boundary_cases_sit_on_the_boundary(kernel):
+    for name, (X, Q, h) in kde_cases.boundary_cases().items():
+        L = kde_oracle.log_density_ld(X, np.ones(1), Q, kernel, h)[0][:, 0]
+        _same_pattern(kde_oracle.log_density(X, np.ones(1), Q, kernel, h)[:, 0], L)
+        r2 = np.zeros(len(Q))
+        for j in range(Q.shape[1]):
+            r2 = r2 + Q[:, j] * Q[:, j]
+        dist = np.sqrt(r2)
+        assert dist[0] == dist[1] and np.isfinite(L[-1])
+        if name.endswith("/h"):
+            assert dist[0] == h and np.isneginf(L[0]) and np.isneginf(L[1])  # dist == h is outside
+            assert np.any(np.isfinite(L[2:-1])) and np.any(np.isneginf(L[2:-1]))  # the neighbours fall on both sides
+        elif name.endswith("/h_up"):
+            assert dist[0] == np.nextafter(h, 0.0) and np.isfinite(L[0]) and np.isfinite(L[1])  # one ulp inside
+        else:
+            assert np.isneginf(L[0])
+
+
+def test_overflow_cases_have_finite_long_double_answers():
+    for name, (kernel, X, V, Q, h, far) in kde_cases.overflow_cases().items():
+        L = kde_oracle.log_density_ld(X, V, Q, kernel, h)[0]
+        assert not np.any(np.isnan(L)) and not np.any(np.isposinf(L))
+        near = np.setdiff1d(np.arange(len(Q)), far)
+        assert np.all(np.isfinite(L[near]))
+        if name == "gaussian-d1":
+            assert np.all(np.isneginf(L[far[:2]])) and np.all(np.isfinite(L[far[2]])) and np.all(L[far[2]] < -1e307)
+        elif kernel == "gaussian":
+            assert np.all(np.isneginf(L[far]))
+        else:  # -r / h is inside the float64 range although r^2, or r times the coefficient, is not
+            assert np.all(np.isfinite(L[far])) and np.all(L[far] < -1e150)
+
+
+def test_kde_option_error_paths_without_device():
+    from pymbar_amd import _lib
+
+    lib = _lib.load_library()
+    assert lib.mbar_kde_set_option(None, b"max_chunks", 2) == -1 and "NULL" in _lib.last_error(None)
+    assert lib.mbar_kde_set_option(None, b"max_chunk", 2) == -1 and "unknown kde option" in _lib.last_error(None)
+    assert lib.mbar_kde_set_option(None, None, 2) == -1 and "unknown kde option" in _lib.last_error(None)
+    assert lib.mbar_kde_set_option(None, b"max_chunks", -1) == -1 and ">= 0" in _lib.last_error(None)

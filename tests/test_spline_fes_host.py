@@ -65,6 +65,38 @@ def test_oracle_matches_scipy_design_matrix(k):
     np.testing.assert_array_equal(bo.intervals(t, k, [2.0, 2.5, -1.5])[[0, 1]], [len(t) - k - 2] * 2)
 
 
+@pytest.mark.parametrize("k", range(8))
+def test_scipy_design_matrix_is_the_unfused_float64_recursion(k):
+    """What the device's bases are held to bit for bit (tests/test_gpu_spline_fes.py): scipy's design matrix equals the Cox-de Boor
+    recursion with every operation rounded to float64 and none fused, on the very case the device test uses."""
+    x, t = bo.scipy_case(k)
+    assert len(x) == 300 and x.min() < t[0] and x.max() > t[-1] and np.all(np.isin(t, x)) and np.any(np.diff(t[k:-k or None]) == 0)
+    D = BSpline.design_matrix(x, t, k, extrapolate=True).toarray()
+    h, l = bo.basis_values(t, k, x, dtype=np.float64)
+    want = np.zeros_like(D)
+    for j in range(k + 1):
+        want[np.arange(len(x)), l - k + j] = h[:, j]
+    np.testing.assert_array_equal(D, want)  # (equal values: the sign of a zero is not compared)
+
+
+@pytest.mark.parametrize("C", list(bo.C_TO_CB))
+def test_matrix_cases_cover_the_tile_seams(C):
+    for k in range(8):
+        for N in (700, 4096 + 300):
+            x, V, t, g, G = bo.matrix_case(k, C, N)
+            nbasis = len(t) - k - 1
+            assert len(x) == N and V.shape == (N, C) and 1 <= G <= 1024 and g.min() >= 0 and g.max() < G
+            assert np.all(np.isin(t, x)) and x.min() < t[0] and x.max() > t[-1] and np.any(np.diff(t[k:-k or None]) == 0)
+            seams = bo.tile_seams(k, nbasis, G, C)
+            assert 2 <= len(seams) + 1 <= 4  # several tiles, G nbasis a small multiple of the tile
+            key = bo.cell_keys(x, g, t, k)
+            for f0 in seams:
+                i = f0 % nbasis
+                assert np.any(key + k < f0) and np.any(key >= f0)
+                if k >= 1 and 1 <= i <= nbasis - k:  # the seam lies inside a row: a sample's entries lie across it
+                    assert np.any((key < f0) & (key + k >= f0)), (k, C, f0)
+
+
 def test_oracle_groups_and_columns():
     rng = np.random.default_rng(3)
     x = rng.uniform(0, 1, 300)
