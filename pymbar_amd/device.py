@@ -198,9 +198,9 @@ class DeviceMatrix(_ContextMatrix):
     def set_bins(self, nbins, label_n=None, v_n=None):
         """Bins of a histogram surface as labels of the resident samples: ``label_n`` in ``[-1, nbins)`` (-1: in no bin) and the
         target potential ``v_n``, uploaded once (``mbar_ctx_set_bins``).  ``nbins=0`` releases them."""
-        self._nbins = 0
         if int(nbins) == 0:
             self._check(self._lib.mbar_ctx_set_bins(self._ctx, 0, None, None))
+            self._nbins = 0
             return
         label_n = np.asarray(label_n)
         v_n = np.ascontiguousarray(v_n, dtype=np.float64)

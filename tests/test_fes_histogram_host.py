@@ -7,6 +7,7 @@ import pytest
 import pymbar_amd
 from pymbar_amd import fes as amd_fes
 from pymbar_amd.utils import ParameterError
+from tests import hist_cases as hc
 from tests.conftest import load_golden
 from tests.hist_standin import HistOracleMatrix
 
@@ -216,3 +217,78 @@ def test_parameter_errors(standin, umb):
     fes.generate_fes(g["u_n"], g["x_n"], histogram_parameters={"bin_edges": g["bin_edges"]})
     with pytest.raises(ParameterError):
         fes.get_fes([0.0], uncertainty_method="bootstrap")  # no replicates
+
+
+# ---- the branch model of the binned passes (tests/hist_cases.py): what the GPU cases reach, asserted from the model ----------------
+@pytest.fixture(scope="module")
+def branch_cases():
+    return [hc.make_case(*key) for key in hc.case_keys()]
+
+
+def test_model_constants_are_the_kernels():
+    """the census describes the kernels only while the model's constants are theirs (HIST_ROUNDS = 7 would still sum correctly,
+    with other steps handed over: no numeric check can see it)"""
+    import os
+    import re
+
+    csrc = os.path.join(os.path.dirname(amd_fes.__file__), "csrc")
+    text = open(os.path.join(csrc, "mbar_k_hist.hip")).read() + open(os.path.join(csrc, "mbar_internal.h")).read()
+    for name, value in (("HIST_ROUNDS", hc.HIST_ROUNDS), ("HIST_SLOTS", hc.HIST_SLOTS), ("HIST_NO_SLOT", hc.NO_SLOT),
+                        ("HIST_CHUNK_SAMPLES", hc.HIST_CHUNK_SAMPLES), ("HIST_ROWS", hc.HIST_ROWS)):
+        found = re.findall(r"constexpr int %s = (\d+);" % name, text)
+        assert found == [str(value)], (name, found)
+
+
+def test_model_chunk_counts():
+    counts = [hc.model_chunks(hc.pattern_labels(p, 4500, nb), nb, 1) for p, nb in hc.PATTERNS[:6]]
+    assert tuple(counts) == hc.CHUNKS_AT_4500
+    chunks, slot = hc.chunk_table(hc.pattern_labels("late65", 4500, 65), 0, 65)
+    assert chunks == [(0, 2047, 64), (2047, 2048, 1), (2048, 4096, 64), (4096, 4500, 64)] and slot[2047] == 0
+    # a tile of the bins sees the other labels as "no slot": 64-sample chunks of 300 distinct bins become 2048-sample ones
+    lab = hc.pattern_labels("distinct", 4500, 300)
+    assert hc.model_chunks(lab, 300, 300) == 300 * 3 and hc.model_chunks(lab, 300, 1) == 71
+
+
+def test_case_set_reaches_every_branch(branch_cases):
+    steps, lens, nbs, max_slot, max_lane = set(), set(), set(), -1, -1
+    for case in branch_cases:
+        for w in ("none", "mult"):
+            cs = hc.step_census(case["labels"], hc.weights_of(case, w)[1], case["nbins"])
+            steps |= set(cs["steps"])
+            lens |= set(cs["chunk_len"])
+            nbs |= set(cs["chunk_nb"])
+            max_slot, max_lane = max(max_slot, cs["max_slot"]), max(max_lane, cs["max_lane"])
+    distinct = {d for d, _ in steps}
+    assert {0, 1, hc.HIST_ROUNDS, hc.HIST_ROUNDS + 1, 64} <= distinct
+    assert (hc.HIST_ROUNDS, 0) in steps  # eight slots: the last butterfly leaves nothing
+    assert any(d == hc.HIST_ROUNDS + 1 and left > 1 for d, left in steps)  # nine: one slot's several samples handed over
+    assert (64, 56) in steps
+    assert max_slot == 63 and max_lane == 63
+    assert 1 in lens and 0 in nbs and hc.HIST_SLOTS in nbs
+    # the patterns on their own terms, unit multiplicities, N = 4500
+    def own(pattern, nbins):
+        return set(hc.step_census(hc.pattern_labels(pattern, 4500, nbins), np.ones(4500), nbins)["steps"])
+
+    assert own("sorted", 128) == {(1, 0), (2, 0), (3, 0)}
+    assert own("eight", 300) == {(8, 0)}
+    assert own("nine", 300) == {(1, 0), (9, 2), (9, 7), (10, 8)}  # (a chunk's short last step; 9 or 10 slots, 2, 7 or 8 handed over)
+    assert own("distinct", 300) == own("distinct", 64) == {(20, 12), (64, 56)}
+    assert (0, 0) in own("gaps", 300)  # a whole step of -1 inside a chunk with bins
+
+
+def test_every_case_runs_on_the_standin(branch_cases):
+    """every case and weighting through the CPU stand-in, whose sums the vectorised oracle of the GPU tests must reproduce"""
+    for case in branch_cases:
+        with np.errstate(divide="ignore"):  # (log N_k of a state without samples)
+            dm = HistOracleMatrix(case["u"])
+            dm.set_Nk(case["N_k"])
+            for w in hc.WEIGHTINGS:
+                weights, c = hc.weights_of(case, w)
+                r = hc.passes_on(dm, case, weights)
+                dm.set_sample_weights(None)
+                o = hc.oracle(case["u"], dm.logden(case["f"]), case["v"], case["f"], case["labels"], c, case["nbins"])
+                live = o["n_i"] > 0
+                assert np.all(np.isneginf(r["lognum"][~live])) and np.all(r["wsum"][~live] == 0)
+                np.testing.assert_allclose(r["lognum"][live], o["lognum"][live].astype(np.float64), rtol=0, atol=1e-13)
+                for name in ("cross", "diag", "wsum"):
+                    np.testing.assert_allclose(r[name], o[name].astype(np.float64), rtol=1e-13, atol=0)

@@ -2,14 +2,10 @@
 MI355X against a numpy long-double oracle, against the row path on the device, and through ``pymbar_amd.FES`` against the
 unmodified reference (tests/golden/fes_histogram.npz).
 
-Error bound of a binned sum (``bin_bound``).  Every term is positive, so a bin's sum of ``n_i`` terms carries at most
-``(n_i - 1) u`` relative (``u = 2^-53``; each term passes through at most ``n_i - 1`` additions however the chunks group them; the
-compensated merges add less) plus the largest relative error of a term.  A term is a product of ``E`` device exponentials (``E = 1``
-for lognum and wsum, 2 for cross and diag); each carries the pinned ``3.1 u`` of ``exp2s_fast``
-(tests/test_device_math_tables.py, profiles/device_math_accuracy.txt) plus ``2^-52 max|argument|`` for its rounded argument,
-the products and the multiplicity add one ``u`` per multiplication (``E + 1`` of them at most).  ``lognum = max + log(sum)`` gets the
-same figure as an absolute error.  The oracle works on the device's own downloaded ``u``, ``logden(f)`` and ``v``, so only the binned
-passes are under test."""
+The cases, the oracle, the bound (``bin_bound``) and the model of the chunk table and of the step loop are in tests/hist_cases.py.
+The branch cases run every label pattern of that file (1, 8, 9 and 64 distinct slots per 64-sample step, slot 63, a one-sample
+chunk, a chunk without bins), N around 64 and 2048, K around ``HIST_ROWS`` = 16, without multiplicities, with all ones and with
+0 .. 3, against the oracle within the unchanged bound; the model's chunk count must be the device's."""
 import numpy as np
 import pytest
 
@@ -19,82 +15,10 @@ from pymbar_amd.device import DeviceMatrix
 from tests.conftest import load_golden
 from tests.test_fes_histogram_host import check_bootstraps, record_draws, system_b
 
+from tests import hist_cases as hc
+from tests.hist_cases import assert_within, awkward_case, bin_bound, oracle, run_passes
+
 pytestmark = pytest.mark.gpu
-
-LD = np.longdouble
-U = 2.0 ** -53
-E_EXP = 3.1  # (u) pinned relative error of the device exp
-
-
-def awkward_case(seed=3):
-    """K = 130 (two row blocks past 128, nine groups of 16 rows), N = 3001 (no multiple of 64), 300 bins with random labels so
-    that chunks close on the 64-bin cap, 5 % of the labels -1, multiplicities 0 .. 3 with 30 % zeros, bin 298 with a single
-    sample, bin 299 with three samples that all have multiplicity 0."""
-    rng = np.random.default_rng(seed)
-    K, N, nbins = 130, 3001, 300
-    x = rng.normal(0.0, 1.0, N)
-    centers = np.linspace(-2.0, 2.0, K)
-    u = 0.5 * (x[None, :] - centers[:, None]) ** 2 * 4.0 + rng.normal(0.0, 0.05, (K, N))
-    N_k = np.full(K, N // K)
-    N_k[: N - N_k.sum()] += 1
-    f = rng.normal(0.0, 0.5, K)
-    v = rng.uniform(0.0, 5.0, N)
-    labels = rng.integers(0, 298, N)
-    labels[rng.random(N) < 0.05] = -1
-    c = rng.integers(1, 4, N).astype(np.float64)
-    c[rng.random(N) < 0.30] = 0.0
-    labels[1234], c[1234] = 298, 2.0
-    labels[[17, 1500, 2999]], c[[17, 1500, 2999]] = 299, 0.0
-    return dict(K=K, N=N, nbins=nbins, u=u, N_k=N_k, f=f, v=v, labels=labels, c=c)
-
-
-def oracle(u, logden, v, f, labels, c, nbins):
-    """Long-double lognum, cross, diag, wsum with f_bins = -lognum, their bounds, from the device's own u / logden."""
-    K = u.shape[0]
-    x = -(v.astype(LD) + logden.astype(LD))
-    logW = f.astype(LD)[:, None] - u.astype(LD) - logden.astype(LD)[None, :]
-    lognum = np.full(nbins, -np.inf, dtype=LD)
-    cross, diag, wsum = np.zeros((K, nbins), dtype=LD), np.zeros(nbins, dtype=LD), np.zeros(nbins, dtype=LD)
-    n_i, arg = np.zeros(nbins), np.zeros(nbins)
-    for i in range(nbins):
-        m = (labels == i) & (c > 0)
-        n_i[i] = m.sum()
-        if not m.any():
-            continue
-        mx = x[m].max()
-        lognum[i] = mx + np.log(np.sum(c[m] * np.exp(x[m] - mx)))
-        b = x[m] - lognum[i]  # log B_n at f_bins = -lognum
-        B = np.exp(b)
-        wsum[i], diag[i] = np.sum(c[m] * B), np.sum(c[m] * B * B)
-        cross[:, i] = np.exp(logW[:, m]) @ (c[m] * B)
-        arg[i] = float(max(np.abs(x[m]).max(), np.abs(x[m] - mx).max(), np.abs(b).max(), np.abs(logW[:, m]).max(),
-                           np.abs(f).max() + np.abs(u[:, m]).max()))
-    return dict(lognum=lognum, cross=cross, diag=diag, wsum=wsum, n_i=n_i, arg=arg)
-
-
-def bin_bound(o, n_exp):
-    """Relative bound of a bin's sum whose terms hold n_exp exponentials (module docstring)."""
-    return (np.maximum(o["n_i"] - 1, 0) + n_exp * (E_EXP + 2.0 * o["arg"]) + (n_exp + 1)) * U
-
-
-def run_passes(case, part_bytes=None, perm=None):
-    p = slice(None) if perm is None else perm
-    with DeviceMatrix.from_host(case["u"][:, p]) as dm:
-        dm.set_Nk(case["N_k"])
-        if part_bytes is not None:
-            dm.set_option("hist_part_bytes", part_bytes)
-        labels, v, c = case["labels"][p], case["v"][p], case["c"][p]
-        dm.set_sample_weights(c)
-        dm.set_bins(case["nbins"], labels, v)
-        info = dm.bins_info()
-        lognum = dm.bin_lognum(case["f"])
-        X, d, w = dm.bin_gram_w(case["f"], -lognum)
-        again = (dm.bin_lognum(case["f"]), dm.bin_gram_w(case["f"], -lognum))
-        dm.set_bins(case["nbins"], labels, v)
-        third = (dm.bin_lognum(case["f"]), dm.bin_gram_w(case["f"], -lognum))
-        dm.set_sample_weights(None)
-        logden, u_dev = dm.logden(case["f"]), dm.to_host()
-    return dict(lognum=lognum, cross=X, diag=d, wsum=w, info=info, again=again, third=third, logden=logden, u=u_dev, labels=labels, v=v, c=c)
 
 
 @pytest.fixture(scope="module")
@@ -107,22 +31,6 @@ def single_sweep(case):
     r = run_passes(case)
     r["oracle"] = oracle(r["u"], r["logden"], r["v"], case["f"], r["labels"], r["c"], case["nbins"])
     return r
-
-
-def assert_within(r, o, factor=1.0):
-    live = o["n_i"] > 0
-    err = np.abs(r["lognum"][live].astype(LD) - o["lognum"][live])
-    print("lognum: worst error / bound", float(np.max(err / (factor * bin_bound(o, 1)[live]))))
-    assert np.all(err <= factor * bin_bound(o, 1)[live])
-    assert np.all(np.isneginf(r["lognum"][~live]))
-    for name, n_exp in (("wsum", 1), ("diag", 2)):
-        err = np.abs(r[name].astype(LD) - o[name])
-        print(name, "worst error / bound", float(np.max(err[live] / (factor * bin_bound(o, n_exp) * np.abs(o[name]))[live])))
-        assert np.all(err <= factor * bin_bound(o, n_exp) * np.abs(o[name]))
-    err = np.abs(r["cross"].astype(LD) - o["cross"])
-    bound = factor * bin_bound(o, 2)[None, :] * np.abs(o["cross"])
-    print("cross worst error / bound", float(np.max(err[:, live] / bound[:, live])))
-    assert np.all(err <= bound)
 
 
 def test_binned_passes_against_long_double_oracle(case, single_sweep):
@@ -241,3 +149,175 @@ def test_fes_label_path_reproduces_reference_2d(monkeypatch):
         np.testing.assert_allclose(sp["df_i"], gold["b_df_specified"], rtol=1e-7, atol=1e-9)
     finally:
         fes.mbar.close()
+
+
+# ---- every branch, seam and form of the binned passes (cases and model: tests/hist_cases.py) --------------------------------------
+OUT = ("lognum", "cross", "diag", "wsum")
+
+
+def bits(r):
+    return tuple(r[k].tobytes() for k in OUT)
+
+
+def check_run(case, r, label):
+    """chunk count against the model, the four outputs against the oracle within ``bin_bound``, wsum = 1 at f_bins = -lognum,
+    and cross=False against cross=True"""
+    o = r["oracle"]
+    assert r["info"]["chunks"] == hc.model_chunks(case["labels"], case["nbins"], r["info"]["sweeps"]), label
+    assert_within(r, o, label=label)
+    np.testing.assert_allclose(r["wsum"][o["n_i"] > 0], 1.0, rtol=0, atol=1e-12)
+    assert r["diag_only"].tobytes() == r["diag"].tobytes() and r["wsum_only"].tobytes() == r["wsum"].tobytes(), label
+
+
+@pytest.mark.parametrize("key", hc.case_keys(), ids=lambda k: f"{k[0]}{k[1]}-N{k[2]}-K{k[3]}")
+def test_branch_cases_three_weightings(key):
+    case = hc.make_case(*key)
+    with hc.open_matrix(case) as dm:
+        runs = {w: hc.run_weighting(dm, case, w) for w in hc.WEIGHTINGS}
+    for w, r in runs.items():
+        assert r["info"]["sweeps"] == 1
+        check_run(case, r, f"{case['name']} {w}")
+    # without multiplicities and with all ones: the same table, and a product with 1.0 is exact
+    assert runs["none"]["logden"].tobytes() == runs["ones"]["logden"].tobytes(), "logden differs: a finding about the sweep"
+    assert bits(runs["none"]) == bits(runs["ones"])
+    if key[2] > 1:
+        empty = np.unique(case["labels"][case["labels"] >= 0])[-1]  # the bin whose samples all have multiplicity 0
+        assert runs["mult"]["oracle"]["n_i"][empty] == 0 and runs["none"]["oracle"]["n_i"][empty] > 0
+
+
+@pytest.fixture(scope="module")
+def nine():
+    return hc.make_case("nine", 300, 2049, 16)
+
+
+def run_mult(case, part_bytes=None, **changed):
+    case = dict(case, **changed)
+    with hc.open_matrix(case, part_bytes) as dm:
+        return case, hc.run_weighting(dm, case, "mult")
+
+
+def test_magnitudes_per_bin_maxima(nine):
+    """v per bin from {0, 800, 1600} + uniform(0, 5): against one global maximum every term of two thirds of the bins underflows"""
+    rng = np.random.default_rng(21)
+    v = rng.choice([0.0, 800.0, 1600.0], nine["nbins"])[nine["labels"]] + rng.uniform(0.0, 5.0, nine["N"])
+    case, r = run_mult(nine, v=v)
+    live = r["oracle"]["n_i"] > 0
+    assert np.all(np.isfinite(r["lognum"][live])) and r["lognum"][live].min() < -1500 and r["lognum"][live].max() > -100
+    assert r["oracle"]["arg"].max() > 1500  # (the bound's argument term covers the rounding of 1600)
+    check_run(case, r, "magnitudes")
+
+
+def test_infinite_target_potential(nine):
+    """v = +inf on every counted sample of one bin (lognum -inf; zeros in pass B at f_bins = +inf) and on some samples of another
+    (those are ignored); no NaN anywhere"""
+    lab, c = nine["labels"], nine["c"]
+    whole, part = int(lab[5]), int(lab[7])
+    v = nine["v"].copy()
+    v[(lab == whole) & (c > 0)] = np.inf
+    some = np.flatnonzero((lab == part) & (c > 0))
+    assert some.size >= 2 and whole != part
+    v[some[::2]] = np.inf
+    case, r = run_mult(nine, v=v)
+    o = r["oracle"]
+    assert o["n_i"][whole] == 0 and o["n_i"][part] == some.size - some[::2].size
+    assert np.isneginf(r["lognum"][whole]) and np.isposinf(r["f_bins"][whole])
+    assert np.all(r["cross"][:, whole] == 0) and r["diag"][whole] == 0 and r["wsum"][whole] == 0
+    check_run(case, r, "v = +inf")  # (asserts that no output holds a NaN)
+
+
+def test_infinite_entries_of_the_matrix(nine):
+    rng = np.random.default_rng(22)
+    u = nine["u"].copy()
+    hit = rng.random(u.shape) < 0.02
+    hit[np.argmin(u, axis=0), np.arange(nine["N"])] = False  # never a whole column
+    u[hit] = np.inf
+    case, r = run_mult(nine, u=u)
+    assert np.all(np.isfinite(r["logden"]))
+    check_run(case, r, "u = +inf")
+
+
+@pytest.mark.parametrize("pattern", ["nine", "gaps"])
+def test_sweeps_two_four_and_one_bin_each(pattern):
+    case = hc.make_case(pattern, 300, 4500, 17)
+    _, single = run_mult(case)
+    assert single["info"]["sweeps"] == 1
+    check_run(case, single, f"{pattern} 1 sweep")
+    o = single["oracle"]
+    live = o["n_i"] > 0
+    for sweeps in (2, 4, case["nbins"]):
+        _, r = run_mult(case, hc.part_bytes_for(case, sweeps))
+        assert r["info"]["sweeps"] == sweeps
+        check_run(case, r, f"{pattern} {sweeps} sweeps")
+        for name, n_exp in (("lognum", 1), ("wsum", 1), ("diag", 2)):
+            scale = 1.0 if name == "lognum" else np.abs(o[name]).astype(np.float64)[live]
+            assert np.all(np.abs(r[name][live] - single[name][live]) <= 2.0 * bin_bound(o, n_exp)[live] * scale)
+        assert np.all(np.abs(r["cross"] - single["cross"]) <= 2.0 * bin_bound(o, 2)[None, :] * np.abs(o["cross"]).astype(np.float64))
+
+
+def test_threaded_chunk_table():
+    """129 blocks of 2048 samples: two or more builder threads; the table is the single-threaded model's"""
+    case = hc.make_case("random", 300, 262221, 2)
+    assert (case["N"] + 2047) // 2048 // 64 >= 2
+    case, r = run_mult(case)
+    assert r["info"]["sweeps"] == 1 and r["info"]["chunks"] > 3000
+    check_run(case, r, "threaded table")
+
+
+def test_state_between_and_around_the_passes(nine):
+    case = nine
+    rng = np.random.default_rng(23)
+    other_f = case["f"] + rng.normal(0.0, 1.0, case["K"])
+    other_Nk = case["N_k"][::-1] + np.arange(case["K"])
+    with hc.open_matrix(case) as dm:
+        first = hc.passes_on(dm, case, case["c"])
+        fb = first["f_bins"]
+        again = hc.passes_on(dm, case, case["c"])  # (set_bins with the same arrays, both passes again)
+        assert bits(again) == bits(first)
+        # logden(other_f) and gram_w write the log-denominators the passes read: each pass takes its own
+        lognum = dm.bin_lognum(case["f"])
+        dm.logden(other_f)
+        after_logden = dm.bin_gram_w(case["f"], fb)
+        dm.gram_w(other_f)
+        after_gram = dm.bin_gram_w(case["f"], fb)
+        for got in (after_logden, after_gram):
+            assert (lognum.tobytes(),) + tuple(a.tobytes() for a in got) == bits(first)
+        dm.set_Nk(other_Nk)
+        moved = dm.bin_lognum(case["f"])
+        assert moved.tobytes() != first["lognum"].tobytes()
+        dm.set_Nk(case["N_k"])
+        assert dm.bin_lognum(case["f"]).tobytes() == first["lognum"].tobytes()
+        assert tuple(a.tobytes() for a in dm.bin_gram_w(case["f"], fb)) == bits(first)[1:]
+        # other labels: their results, the ones of a fresh matrix
+        relabelled = dict(case, labels=hc.pattern_labels("distinct", case["N"], case["nbins"]))
+        second = hc.passes_on(dm, relabelled, case["c"])
+        assert second["lognum"].tobytes() != first["lognum"].tobytes()
+        with hc.open_matrix(relabelled) as fresh:
+            assert bits(hc.passes_on(fresh, relabelled, case["c"])) == bits(second)
+        # NaN in f or in f_bins: every output NaN
+        bad_f = case["f"].copy()
+        bad_f[3] = np.nan
+        assert np.all(np.isnan(dm.bin_lognum(bad_f)))
+        assert all(np.all(np.isnan(a)) for a in dm.bin_gram_w(bad_f, second["f_bins"]))
+        bad_fb = second["f_bins"].copy()
+        bad_fb[7] = np.nan
+        assert all(np.all(np.isnan(a)) for a in dm.bin_gram_w(case["f"], bad_fb))
+        assert all(np.all(np.isnan(a)) for a in dm.bin_gram_w(case["f"], bad_fb, cross=False)[1:])
+        # refused arrays leave the earlier bins in place and usable
+        for bad in (case["nbins"], -2):
+            lab = relabelled["labels"].astype(np.int32)
+            lab[100] = bad
+            with pytest.raises(ValueError, match="labels must lie"):
+                dm.set_bins(case["nbins"], lab, case["v"])
+        for bad in (np.nan, -np.inf):
+            v = case["v"].copy()
+            v[100] = bad
+            with pytest.raises(ValueError, match="must not hold NaN or -inf"):
+                dm.set_bins(case["nbins"], relabelled["labels"], v)
+        assert dm.bins_info() == second["info"]
+        assert dm.bin_lognum(case["f"]).tobytes() == second["lognum"].tobytes()
+        assert tuple(a.tobytes() for a in dm.bin_gram_w(case["f"], second["f_bins"])) == bits(second)[1:]
+        dm.set_bins(0)
+        with pytest.raises(Exception, match="no bins on this context"):
+            dm.bin_lognum(case["f"])
+        with pytest.raises(Exception, match="no bins on this context"):
+            dm.bin_gram_w(case["f"], np.zeros(0))
