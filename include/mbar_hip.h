@@ -350,6 +350,37 @@ int mbar_scan_lognum(mbar_ctx* ctx, const double* f, int64_t L, const double* co
 int mbar_scan_gram_w(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan,
                      int64_t r, double* cross, double* within, double* refcol, double* wsum);
 
+/* ---- histogram surfaces along a scan ---------------------------------------------------------
+ * The histogram free energy surface of EVERY member of a scan: the bins are labels of the resident samples as in "histogram bins
+ * by label", the target states are the members of the family uploaded by mbar_ctx_set_scan (with Q = 0).  Nothing of size L x N is
+ * built or uploaded.  Same limits as the scan passes (single rank, normal row pitch, at most 128 states; else MBAR_ERR_STATE naming
+ * the limit), and N < 2^31.  With x_ln and c_n as above and label_n in [-1, nbins) (-1: in no bin):
+ *   mbar_ctx_set_scan_bins  validates the labels and sorts the samples by bin on the host, O(N), stable: perm (sorted position ->
+ *                           sample, ascending n inside a bin, label -1 dropped) and bin_start[nbins + 1], both uploaded.  A chunk
+ *                           is a run of sorted positions of ONE bin, cut from the start of the bin: at most 2048 positions in
+ *                           pass A, 8192 in pass B; the chunk tables are a function of (label, N) alone.  nbins = 0 releases.
+ *   mbar_scan_bins_table    the same perm (N entries of room, bin_start[nbins] of them written) and bin_start on the host: host
+ *                           only, no context.
+ *   mbar_scan_bin_lognum    pass A.  lognum[l][i] = log sum_{n in i} c_n exp(x_ln) (L x nbins), every (member, bin) pair referred
+ *                           to its OWN maximum; -inf where no sample of the bin has c_n > 0.  The bin free energy of member l is
+ *                           -lognum[l][i].  Never reads the matrix.  offset NULL: zeros.
+ *   mbar_scan_bin_gram_w    pass B.  Bv = exp(f_bins[l][i] + x_ln) for n in i, W_nk = exp(f_k - u_kn - logden_n):
+ *                           cross[k][l][i] = sum_{n in i} c_n W_nk Bv (K x L x nbins; NULL: not computed) on the fp64 matrix cores,
+ *                           the W tile gathered through perm and the Bv operand generated in registers; diag[l][i] = sum c_n Bv^2,
+ *                           wsum[l][i] = sum c_n Bv (1 at f_bins = -lognum).  f_bins[l][i] = +inf (an empty bin) gives exact zeros.
+ *                           The samples in bins are read once per panel of 256 members.  The partial records of one sweep are
+ *                           bounded by "scan_part_bytes": above it the bins are processed in groups of whole bins, one sweep per
+ *                           group (a single bin is never split).
+ * No floating-point atomics.  A (member, bin) output depends on that member and on the bin's own samples in ascending n only: not
+ * on the other members, the other bins, the bin's number, the panel cut or "scan_part_bytes".  With nbins = 1 and every label 0
+ * pass A returns the bits of mbar_scan_lognum's lognum and pass B those of mbar_scan_gram_w's cross[:, :, 0], within[:, 0] and
+ * wsum: the same chunk cut, the same operations.  Kernel time: MBAR_TIMER_OTHER. */
+int mbar_ctx_set_scan_bins(mbar_ctx* ctx, int64_t nbins, const int32_t* label_host);
+int mbar_scan_bins_table(int64_t N, int64_t nbins, const int32_t* label, int32_t* perm_out, int64_t* bin_start_out);
+int mbar_scan_bin_lognum(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, double* lognum);
+int mbar_scan_bin_gram_w(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_bins,
+                         double* cross, double* diag, double* wsum);
+
 /* ---- extension contexts: rows appended to a resident matrix without a copy of it ------------
  * The general path of the expectation family (pymbar/mbar.py:886-903 builds an N x (K + NL + S) host array of log weights;
  * rounds 3-5 of this library copied the resident matrix device to device into a (K + NL + S)-row one per call).  An extension

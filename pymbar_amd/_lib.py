@@ -128,6 +128,10 @@ SIGNATURES = {
     "mbar_ctx_set_scan": (C.c_int, [_ctx, C.c_int64, _dp, C.c_int64, _dp]),
     "mbar_scan_lognum": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
     "mbar_scan_gram_w": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
+    "mbar_ctx_set_scan_bins": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int32)]),
+    "mbar_scan_bins_table": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _ip]),
+    "mbar_scan_bin_lognum": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp]),
+    "mbar_scan_bin_gram_w": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbar_ctx_create_ext": (C.c_int, [C.POINTER(_ctx), _ctx, C.c_int64]),
     "mbar_ctx_rows_sub_from": (C.c_int, [_ctx, C.c_int64, _ctx, C.c_int64, C.c_int64, _dp]),
     "mbar_ctx_rows_rsub_from": (C.c_int, [_ctx, C.c_int64, _ctx, C.c_int64, C.c_int64]),

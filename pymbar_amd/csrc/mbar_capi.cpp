@@ -782,7 +782,7 @@ int mbar_ctx_set_option(mbar_ctx* c, const char* key, int64_t value) {
         c->P_valid = false;  // (the trimmed build never writes the padding rows of P, the untrimmed sweeps read them)
     }
     else if (k == "hist_part_bytes") c->opt_hist_part_bytes = value < 1 ? 1 : value;  // (read by the next mbar_ctx_set_bins)
-    else if (k == "scan_part_bytes") c->opt_scan_part_bytes = value < 1 ? 1 : value;  // (read by the next mbar_scan_lognum)
+    else if (k == "scan_part_bytes") c->opt_scan_part_bytes = value < 1 ? 1 : value;  // (read by the next mbar_scan_lognum / mbar_scan_bin_lognum / mbar_scan_bin_gram_w)
     else if (k == "adapt_batch") c->opt_adapt_batch = value < 1 ? 1 : (value > 64 ? 64 : value);
     else return fail(c, MBAR_ERR_ARG, "unknown option: " + k);
     return MBAR_OK;

@@ -378,6 +378,14 @@ struct mbar_ctx {
     // the partial records of one panel and the merged outputs
     int64_t scan_B = 0, scan_Q = 0;
     DevBuf<double> scan_vec, scan_in, scan_part, scan_out;
+    // histogram surfaces along a scan (mbar_ctx_set_scan_bins): the samples sorted by bin and the chunk tables of the two passes
+    // (chunks of SCAN_VCHUNK / SCAN_CHUNK sorted positions, cut from the start of every bin); the host keeps pass B's chunk
+    // offsets to group the bins under the record budget
+    int64_t scanbin_nbins = 0, scanbin_chunks_a = 0, scanbin_chunks_b = 0;
+    DevBuf<int32_t> scanbin_perm, scanbin_cbin_a, scanbin_cbin_b;
+    DevBuf<int64_t> scanbin_start, scanbin_c0_a, scanbin_c0_b;
+    std::vector<int64_t> scanbin_c0_b_host;
+    DevBuf<double> scanbin_fbins;
     long long* stamps = nullptr;    // MBAR_DEBUG_STAMPS: phase stamps of k_select_newton (64 launches x 16); hipMalloc, debug only
     // P outlives the solve that built it: a later solve on the same matrix whose start lies within the window of the anchor
     // (bootstrap replicates, protocol stages, continuation) starts with ONE fused sweep instead of the build sweep
@@ -389,7 +397,7 @@ struct mbar_ctx {
     int64_t opt_device_loop = 1, opt_adapt_batch = 8, opt_pmode = 1, opt_fused = 1, opt_quad = 1, opt_device_loop_wide = 1, opt_pcache = 1, opt_merge_select = 1, opt_sci_merged = 1, opt_wide_pmode = 1, opt_quad_trim = 1, opt_light_last = 1, opt_direct_results = 1, opt_debug_download_p = 0, opt_fused_general = 0;
     int64_t opt_small_balanced = 1, opt_sci_pingpong = 1, opt_host_pmode = 2, opt_rect_waves = 8, opt_newton_ldlt = 1;
     int64_t opt_hist_part_bytes = (int64_t)1 << 28;  // byte budget of the partial records of one sweep of the binned passes
-    int64_t opt_scan_part_bytes = (int64_t)1 << 28;  // byte budget of the partial records of one member panel of pass A of the scans
+    int64_t opt_scan_part_bytes = (int64_t)1 << 28;  // byte budget of the partial records of one member panel of pass A of the scans, and of one sweep of the binned scan passes
 
     // comm
     ncclComm_t comm = nullptr;
@@ -655,6 +663,12 @@ int agree_all_ok(mbar_ctx* c, bool& ok);
 int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t maxiter, int64_t min_sc_iter, double gamma,
                          int check_convergence, double* history, int64_t history_rows, mbar_solve_result& res,
                          std::vector<double>& psum, double& max_delta, bool& handed_back);
+// the scan passes (mbar_scan.cpp), shared with the histogram surfaces along a scan (mbar_scanbin.cpp): the limits of the context,
+// the family as the kernels see it, the log-denominators of f in slot 0 (*nan_out: every output is NaN), the members' upload
+int scan_ready(mbar_ctx* c, const char* who);
+ScanData scan_data_of(const mbar_ctx* c);
+int scan_logden(mbar_ctx* c, const double* f, bool* nan_out);
+int scan_upload_members(mbar_ctx* c, int64_t L, const double* coeff, const double* offset, const double* f_scan);
 
 }  // namespace host
 }  // namespace mbar

@@ -428,6 +428,36 @@ hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, int nb, const dou
 hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, int nb, int64_t K, int64_t L, int64_t p0, const double* part,
                                    double* cross, double* vec);
 
+// ---- histogram surfaces along a scan (mbar_k_scanbin.hip; tables and C ABI in mbar_scanbin.cpp) ------------------------------
+// The samples sorted by bin (perm: sorted position -> sample, ascending n inside a bin) and cut into chunks that never straddle a
+// bin: chunk c of a table belongs to bin chunk_bin[c] and is that bin's chunk number c - bin_chunk0[bin], positions bin_start[bin]
+// + chunk number x chunk length onward.  With one bin holding every sample the cut is the cut of the scan passes.
+struct ScanBinTable {
+    int64_t nchunks = 0;
+    const int32_t* chunk_bin = nullptr;   // [nchunks]
+    const int64_t* bin_chunk0 = nullptr;  // [nbins + 1]
+};
+struct ScanBins {
+    int64_t nbins;
+    const int32_t* perm;       // [bin_start[nbins]]
+    const int64_t* bin_start;  // [nbins + 1]
+};
+constexpr int SCANBIN_NV = 2;  // per (member, bin) sums of a pass-B record: wsum | diag
+// pass A over the members [0, L) of coeff / offset: rec[chunk][L], M[bin][L] (bin-major, of this member panel), lognum[l][bin]
+// with row pitch nbins
+hipError_t launch_scanbin_vec(hipStream_t s, const ScanData& d, const ScanBins& sb, const ScanBinTable& t, bool sum, int64_t L,
+                              const double* coeff, const double* offset, const double* M, double* rec);
+hipError_t launch_scanbin_vec_merge(hipStream_t s, const ScanBins& sb, const ScanBinTable& t, bool sum, int64_t L, const double* rec,
+                                    double* M, double* lognum);
+// pass B for the panel of members [p0, p0 + 256) of L and the chunks [c0, c1) of the table, which are those of the bins [b0, b1):
+// part[chunk - c0][scanbin_record_doubles(nb)], then cross[k][l][bin] (K x L x nbins) and vec[l][bin][SCANBIN_NV]
+int64_t scanbin_record_doubles(int nb);
+hipError_t launch_scanbin_cross(hipStream_t s, const ScanData& d, const ScanBins& sb, const ScanBinTable& t, int64_t c0, int64_t c1, int nb,
+                                const double* u, int64_t ld, int64_t K, const double* f, int64_t L, int64_t p0, const double* coeff,
+                                const double* offset, const double* f_bins, double* part);
+hipError_t launch_scanbin_cross_merge(hipStream_t s, const ScanBins& sb, const ScanBinTable& t, int64_t c0, int64_t b0, int64_t b1, int nb,
+                                      int64_t K, int64_t L, int64_t p0, const double* part, double* cross, double* vec);
+
 // ---- lagged fluctuation sums of a timeseries (mbar_k_acf.hip; C ABI in mbar_acf.cpp) ----------------------------------------
 constexpr int ACF_WG = 256;                 // threads per workgroup
 constexpr int ACF_R = 8;                     // consecutive positions per thread

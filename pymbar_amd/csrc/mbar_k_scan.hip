@@ -30,27 +30,7 @@
 
 namespace mbar {
 
-namespace {
-constexpr int SV_THREADS = 256;
-constexpr int SCAN_PITCH = 17;  // doubles per state row of the W tile in LDS (16 samples + 1: the column read spreads over the banks)
-
-__device__ __forceinline__ double scan_exp(double x) { return exp2s_fast(x * LOG2E_S); }
-
-__device__ __forceinline__ void scan_neumaier(double& s, double& e, double v) {
-    const double t = s + v;
-    e += fabs(s) >= fabs(v) ? (s - t) + v : (v - t) + s;
-    s = t;
-}
-
-// -u_l(n) - logden_n with the fixed fma chain over ascending b
-__device__ __forceinline__ double scan_x(const ScanData& d, const double (&cf)[SCAN_MAX_B], double off, int64_t n) {
-    double u = off;
-#pragma unroll
-    for (int b = 0; b < SCAN_MAX_B; ++b)
-        if (b < d.B) u = fma(cf[b], d.basis[(int64_t)b * d.ldv + n], u);
-    return -u - d.logden[n];
-}
-}  // namespace
+// (SV_THREADS, SCAN_PITCH, scan_exp, scan_neumaier and scan_x are in mbar_device.h: the binned scan kernels share them)
 
 // One wave per (chunk of SCAN_VCHUNK samples, 64 members).  SUM = false: rec[chunk][l] = max of x_ln over the chunk's samples with
 // c_n > 0; SUM = true: rec[(chunk L + l) J + j] = sum c_n exp(x_ln - M_l) t_jn.

@@ -7,8 +7,11 @@ using namespace mbar;
 using namespace mbar::host;
 
 namespace {
-
 constexpr int64_t SCAN_MAX_K = 128;  // one W tile of the cross kernel
+}  // namespace
+
+namespace mbar {
+namespace host {
 
 int scan_ready(mbar_ctx* c, const char* who) {
     if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
@@ -20,7 +23,7 @@ int scan_ready(mbar_ctx* c, const char* who) {
     return MBAR_OK;
 }
 
-ScanData data_of(const mbar_ctx* c) {
+ScanData scan_data_of(const mbar_ctx* c) {
     ScanData d;
     d.N = c->N;
     d.ldv = c->ld;
@@ -42,7 +45,7 @@ int scan_logden(mbar_ctx* c, const double* f, bool* nan_out) {
 }
 
 // coeff | offset | f_scan of the call's members on the device (offset NULL: zeros; f_scan NULL: not uploaded)
-int upload_members(mbar_ctx* c, int64_t L, const double* coeff, const double* offset, const double* f_scan) {
+int scan_upload_members(mbar_ctx* c, int64_t L, const double* coeff, const double* offset, const double* f_scan) {
     const int64_t B = c->scan_B;
     HIPCHK(c, c->scan_in.grow((size_t)L * (size_t)(B + 2)));
     double* d_coeff = c->scan_in;
@@ -54,7 +57,8 @@ int upload_members(mbar_ctx* c, int64_t L, const double* coeff, const double* of
     return MBAR_OK;
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace mbar
 
 extern "C" {
 
@@ -102,9 +106,9 @@ int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coef
         if (mean) std::fill(mean, mean + L * J, q);
         return MBAR_OK;
     }
-    rc = upload_members(c, L, coeff, offset, nullptr);
+    rc = scan_upload_members(c, L, coeff, offset, nullptr);
     if (rc) return rc;
-    const ScanData d = data_of(c);
+    const ScanData d = scan_data_of(c);
     // members in panels of a multiple of 64 whose records ([chunk][member][J]) fit the budget ("scan_part_bytes"): a member's sums
     // do not depend on the cut
     const int64_t nchunks = (c->N + SCAN_VCHUNK - 1) / SCAN_VCHUNK;
@@ -154,9 +158,9 @@ int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coef
         std::fill(wsum, wsum + L, q);
         return MBAR_OK;
     }
-    rc = upload_members(c, L, coeff, offset, f_scan);
+    rc = scan_upload_members(c, L, coeff, offset, f_scan);
     if (rc) return rc;
-    const ScanData d = data_of(c);
+    const ScanData d = scan_data_of(c);
     const int nb = cross ? scan_nb_for(K) : 0;
     const int64_t nchunks = (c->N + SCAN_CHUNK - 1) / SCAN_CHUNK;
     const int64_t pw = 64 * scan_mb(J);

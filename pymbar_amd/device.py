@@ -312,6 +312,68 @@ class DeviceMatrix(_ContextMatrix):
         within[:, iu[1], iu[0]] = tri
         return X, within, refcol, w
 
+    # ---- histogram surfaces along a scan (pymbar_amd.scan.compute_scan_fes) ---------------------------------------------------
+    SCAN_BIN_CROSS_BYTES = 1 << 28  # the host cross block of one slab of members of scan_bin_gram_w stays under this
+
+    def set_scan_bins(self, nbins, label_n=None):
+        """Histogram bins as labels of the resident samples for the binned scan passes: ``label_n`` in ``[-1, nbins)`` (-1: in no
+        bin), sorted by bin on the host and uploaded once (``mbar_ctx_set_scan_bins``).  ``nbins=0`` releases them."""
+        self._scan_nbins = 0
+        if int(nbins) == 0:
+            self._check(self._lib.mbar_ctx_set_scan_bins(self._ctx, 0, None))
+            return
+        label_n = np.asarray(label_n)
+        if label_n.shape != (self.N_local,):
+            raise ValueError("label_n must have N_local entries")
+        if label_n.dtype != np.int32:  # (values that do not fit an int32 would wrap into the valid range)
+            if label_n.size and (label_n.min() < -1 or label_n.max() >= int(nbins)):
+                raise ValueError("labels must lie in [-1, nbins)")
+            label_n = label_n.astype(np.int32)
+        label_n = np.ascontiguousarray(label_n)
+        rc = self._lib.mbar_ctx_set_scan_bins(self._ctx, int(nbins), label_n.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc == -1:  # MBAR_ERR_ARG: a label outside [-1, nbins)
+            raise ValueError(_lib.last_error(self._ctx))
+        self._check(rc)
+        self._scan_nbins = int(nbins)
+
+    def scan_bin_lognum(self, f, coeff_lb, offset_l=None):
+        """Pass A of a binned scan: ``lognum[l, i] = log sum_{n in bin i} c_n exp(-u_l(n) - logden_n(f))`` (``L x nbins``; ``-inf``
+        where no sample of the bin has ``c_n > 0``)."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.shape != (self.K,):
+            raise ValueError(f"f must have shape ({self.K},)")
+        coeff_lb, offset_l, L, _ = self._scan_members(coeff_lb, offset_l)
+        lognum = np.empty((L, getattr(self, "_scan_nbins", 0)), dtype=np.float64)
+        self._check(self._lib.mbar_scan_bin_lognum(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(lognum)))
+        return lognum
+
+    def scan_bin_gram_w(self, f, coeff_lb, offset_l, f_bins, cross=True, slab=None):
+        """Pass B of a binned scan: ``(cross, diag, wsum)`` of the normalised weights ``Bv = exp(f_bins[l, i] - u_l(n) -
+        logden_n(f))`` of member ``l`` on the samples of bin ``i`` -- ``cross[k, l, i] = sum_{n in i} c_n W_nk Bv`` (``None`` with
+        ``cross=False``), ``diag[l, i] = sum c_n Bv^2``, ``wsum[l, i] = sum c_n Bv``.  The members go to the device in slabs (of
+        ``slab`` members; by default as many as keep a slab's ``cross`` block under 256 MiB): a (member, bin)'s bits do not depend
+        on the cut."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        coeff_lb, offset_l, L, _ = self._scan_members(coeff_lb, offset_l)
+        nbins = getattr(self, "_scan_nbins", 0)
+        f_bins = np.ascontiguousarray(f_bins, dtype=np.float64)
+        if f.shape != (self.K,) or f_bins.shape != (L, nbins):
+            raise ValueError("f must have K entries and f_bins one row per member and one column per bin")
+        if slab is None:
+            slab = self.SCAN_BIN_CROSS_BYTES // (8 * self.K * max(nbins, 1)) if cross else L
+        slab = max(1, min(int(slab), L))
+        X = np.empty((self.K, L, nbins), dtype=np.float64) if cross else None
+        d = np.empty((L, nbins), dtype=np.float64)
+        w = np.empty((L, nbins), dtype=np.float64)
+        for l0 in range(0, L, slab):
+            l1 = min(L, l0 + slab)
+            Xs = np.empty((self.K, l1 - l0, nbins), dtype=np.float64) if cross and (l0, l1) != (0, L) else X
+            self._check(self._lib.mbar_scan_bin_gram_w(self._ctx, _dptr(f), l1 - l0, _dptr(coeff_lb[l0:l1]), _dptr(offset_l[l0:l1]),
+                                                       _dptr(f_bins[l0:l1]), _dptr(Xs), _dptr(d[l0:l1]), _dptr(w[l0:l1])))
+            if cross and Xs is not X:
+                X[:, l0:l1, :] = Xs
+        return X, d, w
+
     def set_option(self, key, value):
         self._check(self._lib.mbar_ctx_set_option(self._ctx, key.encode(), int(value)))
 

@@ -533,6 +533,7 @@ class MBAR:
     compute_entropy_and_enthalpy = _expectations.compute_entropy_and_enthalpy
     # ---- scans over a linear family of unsampled states (pymbar_amd/scan.py) --------------------------
     compute_scan = _scan.compute_scan
+    compute_scan_fes = _scan.compute_scan_fes
 
     def _computeUnnormalizedLogWeights(self, u_n):
         """``-ln sum_k N_k exp(f_k - (u_k(x_n) - u(x_n)))`` for one target potential ``u_n`` (mbar.py:1919-1934):

@@ -194,3 +194,120 @@ def compute_scan(mbar, basis_bn, coeff_lb, offset_l=None, A_qn=None, reference=0
     finally:
         dm.set_scan(None)
     return out
+
+
+# ---- histogram free energy surfaces along a scan ----------------------------------------------------------------------------------
+def _scan_fes_matrix(mbar):
+    dm = _scan_matrix(mbar)
+    if not all(hasattr(dm, name) for name in ("set_scan_bins", "scan_bin_lognum", "scan_bin_gram_w")):
+        raise ParameterError(f"histogram surfaces along a scan need the binned scan passes of a single-rank device matrix and are {_NOT_HERE} for this handle")
+    return dm
+
+
+def _reference_bins(f_raw, reference, reference_label):
+    """``j_l``: the reference bin of every member (``fes._reference_bin`` per row)."""
+    if reference == "from-lowest":
+        return np.argmin(f_raw, axis=1).astype(np.int64)
+    return np.full(len(f_raw), int(reference_label), dtype=np.int64)
+
+
+def _neg_logsumexp_neg(f_raw):
+    """``-logsumexp_i(-f_raw[l, i])``, summed over the bins in ascending order, row by row."""
+    m = np.max(-f_raw, axis=1)
+    s = np.zeros(len(f_raw))
+    for i in range(f_raw.shape[1]):
+        s += np.exp(-f_raw[:, i] - m)
+    return -(m + np.log(s))
+
+
+def _fes_analytical(mbar, dm, coeff_lb, offset_l, f_raw, j_l, approximate):
+    """``df_i`` of every member from pass B: ``Theta_ij = delta_ij d_li + y_li^T diag(g) y_lj`` (DESIGN.md section 16's border,
+    per member), ``df^2 = Theta_ii + Theta_jj - 2 Theta_ij``."""
+    L = len(f_raw)
+    rows = np.arange(L)
+    cross, d, wsum = dm.scan_bin_gram_w(mbar.f_k, coeff_lb, offset_l, f_raw, cross=not approximate)
+    check_w_sums(wsum.ravel(), 0.0)
+    dj = d[rows, j_l][:, None]
+    if approximate:
+        var = d + dj
+    else:
+        y, g = _border(mbar, cross)  # (m, L, nbins)
+        yj = y[:, rows, j_l][:, :, None]
+        var = (d + _qform(g, y, y)) + (dj + _qform(g, yj, yj)) - 2.0 * _qform(g, y, yj)
+    var[rows, j_l] = 0.0
+    return np.sqrt(np.maximum(var, 0.0))
+
+
+def compute_scan_fes(mbar, basis_bn, coeff_lb, offset_l=None, sample_label=None, reference="from-lowest", reference_label=None,
+                     uncertainty_method=None, theta_method=None, warning_cutoff=1.0e-10):
+    """Histogram free energy surfaces of every member of a linear family of unsampled states: row ``l`` of every returned array
+    is what ``fes.histogram_fes_labels(mbar, coeff_lb[l] @ basis_bn + offset_l[l], sample_label, reference, reference_label, ...)``
+    returns, without a dense ``u_l``, an upload or a read of the resident matrix per member.
+
+    ``basis_bn``, ``coeff_lb``, ``offset_l`` as in :func:`compute_scan`; ``sample_label`` as :func:`pymbar_amd.fes.label_samples`
+    returns it (``[-1, nbins)``, every label below ``nbins = max + 1`` occurring).  Returns a dict: ``f_raw`` ``(L, nbins)``, the
+    bin free energies in the gauge of ``mbar.f_k``; ``reference`` ``(L,)``, the reference bin ``j_l`` of every member (its lowest
+    bin for "from-lowest", ``reference_label`` for "from-specified"); ``f_i = f_raw - f_raw[l, j_l]``; ``f`` ``(L,)``, ``-logsumexp_i(
+    -f_raw[l])``, the free energy of the member restricted to the binned samples.  ``uncertainty_method``: None, "analytical"
+    (``df_i``; ``theta_method`` None / "svd-ew": the bordered form, "approximate": the bin block alone, "svd": not offered) or
+    "bootstrap" (``bootstrapped_f_raw`` ``(n_bootstraps, L, nbins)`` and ``df_i``, the ``std`` over the replicates of ``f^b_li -
+    f^b_lj`` with ``j`` from the main estimate; a replicate that emptied the bin or the reference bin is left out, fewer than two
+    usable replicates give NaN)."""
+    from .fes import _check_labels
+
+    if uncertainty_method not in (None, "analytical", "bootstrap"):
+        raise ParameterError(f"Uncertainty_method {uncertainty_method} is not a valid option")
+    if theta_method == "bootstrap":
+        theta_method = None
+    if theta_method == "svd":
+        raise ParameterError("theta_method 'svd' needs the weight matrix itself and is not offered on the label path")
+    if theta_method not in (None, "svd-ew", "approximate"):
+        raise ParameterError(f"Method {theta_method} unrecognized.")
+    bootstrap = uncertainty_method == "bootstrap"
+    if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
+        raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
+    basis_bn, coeff_lb, offset_l, _, L = _check_inputs(mbar, basis_bn, coeff_lb, offset_l, None, 0)
+    if sample_label is None:
+        raise ParameterError("sample_label must have one entry per sample")
+    _, sample_label, nbins = _check_labels(mbar, np.zeros(mbar.N), sample_label)
+    counts = np.bincount(sample_label[sample_label >= 0], minlength=nbins)
+    if np.any(counts == 0):
+        raise DataError(f"WARNING: bin {int(np.where(counts == 0)[0][0])} has no samples -- all bins must have at least one sample.")
+    if reference == "from-specified":
+        if reference_label is None or not (0 <= int(reference_label) < nbins):
+            raise ParameterError("Specified reference point for FES not given")
+    elif reference != "from-lowest":
+        raise ParameterError(f"reference point method {reference} is not supported for histogram surfaces here")
+    dm = _scan_fes_matrix(mbar)
+    dm.set_Nk(mbar.N_k)
+    dm.set_scan(basis_bn, None)
+    try:
+        dm.set_scan_bins(nbins, sample_label)
+        f_raw = -dm.scan_bin_lognum(mbar.f_k, coeff_lb, offset_l)
+        j_l = _reference_bins(f_raw, reference, reference_label)
+        rows = np.arange(L)
+        out = dict(f_raw=f_raw, f_i=f_raw - f_raw[rows, j_l][:, None], reference=j_l, f=_neg_logsumexp_neg(f_raw))
+        if bootstrap:
+            fb = np.zeros((mbar.n_bootstraps, L, nbins))
+            try:
+                for b in range(mbar.n_bootstraps):
+                    mbar._set_bootstrap_weights(dm, b)
+                    fb[b] = -dm.scan_bin_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l)
+            finally:
+                dm.set_sample_weights(None)
+            out["bootstrapped_f_raw"] = fb
+            with np.errstate(invalid="ignore"):
+                fall = fb - fb[:, rows, j_l][:, :, None]  # (inf - inf = NaN: the reference bin was emptied)
+            fall[~np.isfinite(fall)] = np.nan
+            usable = np.sum(~np.isnan(fall), axis=0)
+            df = np.full((L, nbins), np.nan)
+            ok = usable >= 2
+            if np.any(ok):
+                df[ok] = np.nanstd(fall[:, ok], axis=0)
+            out["df_i"] = df
+        elif uncertainty_method == "analytical":
+            out["df_i"] = _fes_analytical(mbar, dm, coeff_lb, offset_l, f_raw, j_l, theta_method == "approximate")
+    finally:
+        dm.set_scan_bins(0)
+        dm.set_scan(None)
+    return out
