@@ -256,11 +256,10 @@ __global__ void __launch_bounds__(BAR_WG) k_bar_mom_merge(BarData d, int stage, 
         for (int64_t c = beg + threadIdx.x; c < end; c += BAR_WG) m = fmin(m, d.wmin[c]);
         const double wmin = -block_max(-m, lds);
         double s[2] = {0.0, 0.0};
-        if (wmin != INFINITY)
-            for (int64_t c = beg + threadIdx.x; c < end; c += BAR_WG) {
-                if (d.wmin[c] != INFINITY) s[0] += part[c] * exp(wmin - d.wmin[c]);
-                s[1] += part[d.nchunks + c];
-            }
+        for (int64_t c = beg + threadIdx.x; c < end; c += BAR_WG) {
+            if (d.wmin[c] != INFINITY) s[0] += part[c] * exp(wmin - d.wmin[c]);
+            s[1] += part[d.nchunks + c];  // (a side of +inf values: sum w = +inf, as the reference's)
+        }
         block_sum<2>(s, lds2);
         if (threadIdx.x == 0) {
             o[0] = wmin == INFINITY ? -INFINITY : -wmin + log(s[0]);

@@ -1,7 +1,9 @@
 """pymbar_amd.other_estimators on the CPU: the root find's state machine (the library's host entry point mbar_bar_step_host, the
 code the device runs) against a fresh restatement of the reference's loop, and the whole public module with the device handle
 replaced by the long-double stand-in (``OracleBAR`` for ``DeviceBAR``) against the reference's answers
-(tests/golden/other_estimators.npz, tests/golden/make_golden_other_estimators.py)."""
+(tests/golden/other_estimators.npz, tests/golden/make_golden_other_estimators.py); and the branch model of the device sums
+(tests/bar_cases.py): its census over the case set, the model against the long-double oracle, its seeded errors, and the dyadic
+root-find construction on the host."""
 import json
 import math
 
@@ -261,3 +263,116 @@ def test_package_exports_without_touching_a_device():
 
     for name in ("bar", "bar_overlap", "bar_zero", "exp", "exp_gauss", "other_estimators"):
         assert name in pymbar_amd.__all__ and hasattr(pymbar_amd, name)
+
+
+# ---- the branch model of the BAR / EXP sums (tests/bar_cases.py) --------------------------------------------------------------------
+from tests import bar_cases as bc  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def model_runs():
+    """the unmutated model on every case and DeltaF, once: [(case, k, values, census)]"""
+    return [(c, k) + bc.model_zero(c["w_F"], c["w_R"], d) for c in bc.cases() for k, d in enumerate(c["dfs"])]
+
+
+def test_case_set_census(model_runs):
+    """Over the whole case set every chunk kind, every form of ``lin``, x == 0, a shift difference above 745, padded slots of 1
+    and of 4095 and a second trip of the strided merge loop occur, and every side length occurs on both sides."""
+    sides = [cs[s] for _, _, _, cs in model_runs for s in "FR"]
+    for key in ("all_inf", "xmin_pos", "nonpos_only", "straddling", "n_pp", "n_straddle", "n_nonpos", "n_zero"):
+        assert any(s[key] > 0 for s in sides), key
+    assert any(s["shift_diff"] > 745.0 for s in sides)
+    assert any(s["pad"] == 1 for s in sides) and any(s["pad"] == bc.CHUNK - 1 for s in sides)
+    assert any(s["trips"] == 2 for s in sides) and all(s["trips"] in (1, 2) for s in sides)
+    for side in ("w_F", "w_R"):
+        assert {len(c[side]) for c in bc.cases()} >= set(bc.LENGTHS) | {bc.BIG}
+    assert any(len(c["w_F"]) == len(c["w_R"]) for c in bc.cases()) and any(len(c["w_F"]) != len(c["w_R"]) for c in bc.cases())
+    assert sum(len(c["w_F"]) + len(c["w_R"]) for c in bc.cases()) < 2_600_000
+    # the patterns force what they are named for
+    for c, k, _, cs in model_runs:
+        for s in "FR":
+            if c["pattern"] == "positive":
+                assert cs[s]["n_straddle"] == cs[s]["n_nonpos"] == 0
+            if c["pattern"] == "negative":
+                assert cs[s]["n_pp"] == cs[s]["n_straddle"] == 0
+            if c["pattern"] in ("zero", "straddle") and len(c["w_" + s]) > 1:
+                assert cs[s]["n_zero" if c["pattern"] == "zero" else "n_straddle"] > 0
+    # the moments' stages: a second merge trip, chunks of +inf, +inf inside a finite chunk
+    mom = [bc.model_moments(c[side])[1] for c in bc.cases() for side in ("w_F", "w_R")]
+    assert any(m["trips"] == 2 for m in mom) and any(m["all_inf"] > 0 for m in mom)
+    assert any(m["n_inf"] > 0 and m["all_inf"] == 0 for m in mom) and any(m["all_inf"] == m["chunks"] for m in mom)
+    # the depth of the moments' bound covers the device's tree at every length of the set
+    for n in bc.LENGTHS + (bc.BIG,):
+        assert bc.device_additions(n) + 1 <= 2 * bc.depth(n), n
+
+
+def test_model_within_the_bounds_of_the_oracle(model_runs):
+    worst = 0.0
+    for c, k, got, _ in model_runs:
+        q = bc.zero_ratios(c, k, got)
+        worst = max(worst, q.max())
+        assert np.all(q <= 1.0), (c["name"], c["dfs"][k], q)
+    print("model_zero: worst error / bound", worst)
+    worst = 0.0
+    for c in bc.cases():
+        for side, want in zip(("w_F", "w_R"), bc.oracle_moments(c)):
+            q = bc.moment_ratios(c[side], bc.model_moments(c[side])[0], want)
+            worst = max(worst, q.max())
+            assert np.all(q <= 1.0), (c["name"], side, q)
+    print("model_moments: worst error / bound", worst)
+
+
+def test_every_mutation_of_the_model_is_detected():
+    """Each deliberate error puts at least one case above its bound (the big pairs are left out: the others suffice)."""
+    small = [c for c in bc.cases() if max(len(c["w_F"]), len(c["w_R"])) < bc.BIG]
+    for mutate in bc.MUTATIONS:
+        worst, where = 0.0, None
+        for c in small:
+            if mutate == "mom_chunkmin":
+                q = max(bc.moment_ratios(c[s], bc.model_moments(c[s], mutate)[0], w).max()
+                        for s, w in zip(("w_F", "w_R"), bc.oracle_moments(c)))
+            else:
+                q = max(bc.zero_ratios(c, k, bc.model_zero(c["w_F"], c["w_R"], d, mutate)[0]).max() for k, d in enumerate(c["dfs"]))
+            if q > worst:
+                worst, where = q, c["name"]
+            if worst > 100.0:
+                break
+        print(f"mutation {mutate}: error / bound {worst:.3g} at {where}")
+        assert worst > 1.0, mutate
+
+
+def test_dropping_the_lo_word_of_the_shift_is_not_detectable(model_runs):
+    """NOT covered, on record: without the ``lo`` word of the chunks' shifts (``mutate="nolo"``, not one of MUTATIONS) every case
+    stays inside its bound, so neither this model nor the device tests can see that word."""
+    worst = max(bc.zero_ratios(c, k, bc.model_zero(c["w_F"], c["w_R"], c["dfs"][k], "nolo")[0]).max() for c, k, _, _ in model_runs)
+    print("without lo: worst error / bound", worst)
+    assert worst <= 1.0
+
+
+def test_step_host_reaches_every_exit_on_the_dyadic_construction():
+    """The hand-set brackets on the dyadic pairs, F from the model: every exit the device test asserts is reached on the host."""
+    problems = bc.dyadic_problems()
+
+    def zero(d):
+        with np.errstate(invalid="ignore"):
+            return np.array([bc.model_zero(pr[1], pr[2], d[p])[0] for p, pr in enumerate(problems)])
+
+    for p, (name, w_F, w_R, _, _) in enumerate(problems):
+        if name.startswith("dyadic"):
+            s = (w_F[0] - w_R[0]) / 2
+            assert bc.model_zero(w_F, w_R, s)[0][0] == 0.0, name
+            assert bc.model_zero(w_F, w_R, s + 1.0)[0][0] == -bc.model_zero(w_F, w_R, s - 1.0)[0][0], name
+    seen = set()
+    by_name = {}
+    # (the moments pass is the device's; 0, 1 and 500 iterations reach every exit)
+    for config in [c for c in bc.rootfind_configs() if c[3] == 0 and c[2] != 3]:
+        st = bc.make_states(problems, config)
+        _, widened = bc.drive_lockstep(zero, st)
+        for p, pr in enumerate(problems):
+            ex = bc.exits_of(st[p], widened[p])
+            seen |= ex
+            by_name.setdefault((pr[0], config[0]), set()).update(ex)
+    assert seen >= set(bc.EXITS), set(bc.EXITS) - seen
+    assert "BOUNDS" in by_name[("dyadic300-root", 1)] and "FNew==0" in by_name[("dyadic300-root", 0)]
+    assert "FNew==0" in by_name[("dyadic4097-sym", 0)] and "widened" in by_name[("dyadic300-widen", 1)]
+    assert "no-evaluation" in by_name[("dyadic64-zero", 0)] and "NAN_BRACKET" in by_name[("inf-both", 0)]
