@@ -210,6 +210,19 @@ int mbar_ctx_vec_logshift(mbar_ctx* ctx, const double* A, double* shift_out);
  * built on the device from ONE vector and ONE label array -- the N x (K + nbins) host matrix of the reference is never
  * formed.  A +inf entry is a sample of weight zero in that state. */
 int mbar_ctx_fill_masked_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, const double* v_host, const int32_t* label_host);
+/* Rows of the resident matrix from a LINEAR FAMILY instead of an upload: rows [row0, row0 + nrows) become
+ *   u[row0 + r][n] = fma(coeff[r][B-1], basis[B-1][n], ... fma(coeff[r][0], basis[0][n], offset[r]))        0 <= n < N_local
+ * -- a temperature ladder beta_k E, pressures beta (E + p_k V), harmonic umbrellas (linear in E, x^2, x, 1), linear alchemical
+ * coupling: every sampled state of such a simulation is B <= MBAR_SCAN_MAX_B coefficients over B shared per-sample vectors, and
+ * 8 B N bytes cross the bus instead of 8 K N.  basis_host[B][ld_host] is C-contiguous and its columns [col0_host, col0_host +
+ * N_local) are this context's samples (a rank passes the whole basis and its shard origin, as with mbar_ctx_upload_u; no
+ * communication); coeff[nrows][B]; offset[nrows] or NULL (zeros).  The chain is the one the scan passes evaluate (mbar_scan_lognum):
+ * a scan member with a sampled state's coefficients has that state's u to the bit.  The basis shard is staged in a temporary
+ * device block that is released before return; the call returns with the stream idle.  Any K the context supports; nothing is
+ * written outside the row range or behind column N_local.  MBAR_ERR_ARG: NULL basis_host / coeff, B outside [1, 8], a row range
+ * outside [0, K], a column range outside ld_host; MBAR_ERR_STATE: an extension context (mbar_ctx_create_ext).  nrows = 0: MBAR_OK. */
+int mbar_ctx_fill_linear_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
+                              int64_t col0_host, const double* coeff, const double* offset);
 /* Fill the shard on the device with the synthetic harmonic ladder of SURVEY.md 8(d):
  * global sample n (n_global0 <= n < n_global0+N_local) belongs to the state given by the
  * cumulative N_k_global, x_n ~ Normal(O_s, K_s^-1/2) from a counter-based RNG keyed by

@@ -428,6 +428,15 @@ hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, int nb, const dou
 hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, int nb, int64_t K, int64_t L, int64_t p0, const double* part,
                                    double* cross, double* vec);
 
+// ---- rows of the resident matrix from a linear family (mbar_k_linear.hip; C ABI: mbar_ctx_fill_linear_rows in mbar_capi.cpp) --
+constexpr int FILL_THREADS = 256;      // a lane owns two adjacent columns: 512 columns per workgroup and pass
+constexpr int FILL_ROWS = 128;         // rows a lane writes from one read of its basis values (grid.y = row groups)
+constexpr int FILL_MAX_BLOCKS = 2048;  // grid.x; the column pairs go round it
+// rows[r][n] = fma(coeff[r][B-1], basis[B-1][n], ... fma(coeff[r][0], basis[0][n], offset[r])) for r < nrows, n < N: the chain of
+// scan_x.  rows (pitch ld) and basis (pitch ldb) 16-byte aligned with even pitches; coeff[nrows][B], offset[nrows] on the device
+hipError_t launch_fill_linear_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis,
+                                   int64_t ldb, const double* coeff, const double* offset);
+
 // ---- histogram surfaces along a scan (mbar_k_scanbin.hip; tables and C ABI in mbar_scanbin.cpp) ------------------------------
 // The samples sorted by bin (perm: sorted position -> sample, ascending n inside a bin) and cut into chunks that never straddle a
 // bin: chunk c of a table belongs to bin chunk_bin[c] and is that bin's chunk number c - bin_chunk0[bin], positions bin_start[bin]

@@ -15,6 +15,31 @@ from . import _lib
 
 _dptr = _lib.ptr
 
+MAX_BASIS = 8  # MBAR_SCAN_MAX_B: basis vectors of a linear family (scans, fill_linear_rows)
+
+
+def linear_family_inputs(basis_bn, coeff_rb, offset_r=None, error=ValueError):
+    """``(basis_bn, coeff_rb, offset_r)`` of a linear family ``u_r(n) = sum_b coeff_rb[r, b] basis_bn[b, n] + offset_r[r]`` as
+    float64 C-contiguous arrays, under the rules of :func:`pymbar_amd.scan._check_inputs`: ``basis_bn`` ``(B, N)`` with ``1 <= B <=
+    8``, ``coeff_rb`` ``(R, B)`` with ``R >= 1``, ``offset_r`` ``(R,)`` or None (zeros).  A wrong shape raises ``error``, a
+    non-finite value :class:`pymbar_amd.utils.DataError`."""
+    from .utils import DataError
+
+    basis_bn = np.ascontiguousarray(basis_bn, dtype=np.float64)
+    coeff_rb = np.ascontiguousarray(coeff_rb, dtype=np.float64)
+    if basis_bn.ndim != 2 or not 1 <= basis_bn.shape[0] <= MAX_BASIS:
+        raise error(f"basis_bn must have shape (B, N) with 1 <= B <= {MAX_BASIS}")
+    B = basis_bn.shape[0]
+    if coeff_rb.ndim != 2 or coeff_rb.shape[1] != B or coeff_rb.shape[0] < 1:
+        raise error("the coefficients must have one row per state and one column per basis vector")
+    R = coeff_rb.shape[0]
+    offset_r = np.zeros(R) if offset_r is None else np.ascontiguousarray(offset_r, dtype=np.float64)
+    if offset_r.shape != (R,):
+        raise error("the offsets must have one entry per state")
+    if not (np.all(np.isfinite(basis_bn)) and np.all(np.isfinite(coeff_rb)) and np.all(np.isfinite(offset_r))):
+        raise DataError("basis_bn, the coefficients and the offsets must be finite")
+    return basis_bn, coeff_rb, offset_r
+
 
 class _ContextMatrix:
     """What :class:`DeviceMatrix` and :class:`ExtendedMatrix` share: they own one ``mbar_ctx`` (``_ctx``) and write whole rows of
@@ -153,6 +178,37 @@ class DeviceMatrix(_ContextMatrix):
         dm = cls(K, n1 - n0, device=device)
         dm._check(dm._lib.mbar_ctx_upload_u(dm._ctx, _dptr(u_kn), N, n0, n1 - n0, 0))
         return dm
+
+    @classmethod
+    def from_linear(cls, basis_bn, coeff_kb, offset_k=None, device=None, columns=None, validate=True):
+        """The matrix ``u[k, n] = sum_b coeff_kb[k, b] basis_bn[b, n] + offset_k[k]`` of a linear family, built ON THE DEVICE from
+        the ``B <= 8`` basis vectors (``mbar_ctx_fill_linear_rows``): ``8 B N`` bytes cross the bus instead of ``8 K N``.
+        ``columns=(n0, n1)`` as in :meth:`from_host`: only that slice of the samples (this rank's shard).  ``validate=False``: the
+        three arrays are what :func:`linear_family_inputs` returned (no second pass over the basis)."""
+        if validate:
+            basis_bn, coeff_kb, offset_k = linear_family_inputs(basis_bn, coeff_kb, offset_k)
+        n0, n1 = (0, basis_bn.shape[1]) if columns is None else columns
+        dm = cls(coeff_kb.shape[0], n1 - n0, device=device)
+        try:
+            dm.fill_linear_rows(0, basis_bn, coeff_kb, offset_k, col0=n0, validate=False)
+        except BaseException:
+            dm.close()
+            raise
+        return dm
+
+    def fill_linear_rows(self, row0, basis_bn, coeff_rb, offset_r=None, col0=0, validate=True):
+        """Rows ``[row0, row0 + R)`` become ``fma(coeff_rb[r, B-1], basis_bn[B-1, n], ... fma(coeff_rb[r, 0], basis_bn[0, n],
+        offset_r[r]))`` -- the chain of the scan passes -- on the device.  ``basis_bn`` is ``(B, >= col0 + N_local)``: its columns
+        ``[col0, col0 + N_local)`` are this matrix's samples.  ``validate=False`` as in :meth:`from_linear`."""
+        if validate:
+            basis_bn, coeff_rb, offset_r = linear_family_inputs(basis_bn, coeff_rb, offset_r)
+        col0 = int(col0)
+        if col0 < 0 or col0 + self.N_local > basis_bn.shape[1]:
+            raise ValueError("basis_bn must cover the columns [col0, col0 + N_local)")
+        self._touched()
+        B, R = basis_bn.shape[0], coeff_rb.shape[0]
+        self._check(self._lib.mbar_ctx_fill_linear_rows(self._ctx, int(row0), R, B, _dptr(basis_bn), basis_bn.shape[1], col0,
+                                                        _dptr(coeff_rb), _dptr(offset_r)))
 
     @classmethod
     def harmonic(cls, O_k, K_k, N_k_global, seed=0, n_global0=0, N_local=None, device=None):

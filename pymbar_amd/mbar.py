@@ -85,7 +85,7 @@ def _small_blas(K):
 _BLAS_CONTROLLER = None
 
 
-from .utils import private_copy as _private_copy  # noqa: E402
+from .utils import private_copy as _private_copy, private_copy_flat as _private_copy_flat  # noqa: E402
 
 
 _EARLY_UPLOAD_BYTES = 8 << 20  # from this size on the private host copy of u_kn and its upload run side by side (a thread start is ~0.1 ms)
@@ -127,12 +127,64 @@ class MBAR:
     def __init__(self, u_kn, N_k, maximum_iterations=10000, relative_tolerance=1.0e-7, verbose=False,
                  initial_f_k=None, solver_protocol=None, initialize="zeros", x_kindices=None, n_bootstraps=0,
                  bootstrap_solver_protocol=None, rseed=None, device=None, copy=True, bootstrap_rng="reference"):
+        self._construct(u_kn, N_k, maximum_iterations, relative_tolerance, verbose, initial_f_k, solver_protocol, initialize,
+                        x_kindices, n_bootstraps, bootstrap_solver_protocol, rseed, device, copy, bootstrap_rng)
+
+    @classmethod
+    def from_linear(cls, basis_bn, coeff_kb, N_k, offset_k=None, **kwargs):
+        """An ``MBAR`` whose sampled states are a LINEAR FAMILY over a few per-sample vectors: ``u_kn[k, n] = sum_b coeff_kb[k, b]
+        basis_bn[b, n] + offset_k[k]`` -- a temperature ladder ``beta_k E``, pressures ``beta (E + p_k V)``, harmonic umbrellas
+        (linear in ``E, x^2, x, 1``), linear alchemical coupling.  ``basis_bn`` is ``(B, N)`` with ``1 <= B <= 8``, ``coeff_kb``
+        ``(K, B)``, ``offset_k`` ``(K,)`` or None (zeros) -- what :meth:`compute_scan` takes for unsampled states.  The resident
+        matrix is built on the device from the basis (``8 B N`` bytes cross the bus instead of ``8 K N``) and no ``K x N`` host
+        array exists: ``u_kn`` is downloaded from the device on first access and then kept.  With the default
+        ``initialize="zeros"`` neither the constructor nor ``compute_free_energy_differences`` / ``compute_overlap`` touch it;
+        ``initialize="BAR"`` (also for every bootstrap replicate) and ``"mean-reduced-potential"`` read ``u_kn`` and therefore
+        trigger the download, as do the expectation methods whose default ``u_kn`` / ``A_n`` is the matrix.
+
+        ``kwargs`` are the constructor's keywords with the constructor's meaning, except ``copy`` (refused: there is no host
+        matrix to copy).  The object keeps private read-only copies ``basis_bn``, ``coeff_kb``, ``offset_k`` (``None`` on an object
+        made by the constructor); ``compute_scan`` / ``compute_scan_fes`` default to that basis.  ``upload_stats``: ``upload_s`` is the
+        basis upload plus the fill, ``upload_GBps`` counts the ``8 B N`` bytes that crossed the bus."""
+        from .device import linear_family_inputs
+
+        if "copy" in kwargs:
+            raise ParameterError("MBAR.from_linear has no host matrix to copy: the copy keyword is not accepted")
+        if kwargs.get("bootstrap_rng", "reference") not in ("reference", "device"):
+            raise ParameterError("bootstrap_rng must be 'reference' or 'device'")
+        basis_bn, coeff_kb, offset_k = linear_family_inputs(basis_bn, coeff_kb, offset_k, error=ParameterError)
+        if np.sum(np.asarray(N_k, dtype=np.int64)) != basis_bn.shape[1] or np.shape(N_k) != (coeff_kb.shape[0],):
+            raise ParameterError("N_k must have one entry per row of coeff_kb, and the sum of all N_k must equal the total number "
+                                 "of samples (length of second dimension of basis_bn).")
+        linear = (_private_copy_flat(basis_bn), np.array(coeff_kb), np.array(offset_k))  # (private copies: the caller's arrays stay theirs)
+        for a in linear:
+            a.setflags(write=False)
+        self = cls.__new__(cls)
+        self._construct(None, N_k, linear=linear, **kwargs)
+        return self
+
+    # ---- the host matrix -------------------------------------------------------------------------------------------
+    @property
+    def u_kn(self):
+        """(K, N) reduced potentials on the host: the constructor's private copy (or reference); on an object made by
+        :meth:`from_linear` downloaded from the device on first access, then kept (the same array on every access)."""
+        if self._u_kn is None and self.basis_bn is not None:
+            if getattr(self, "_dm", None) is None:
+                raise ParameterError("the device matrix of this object has been released: u_kn can no longer be downloaded")
+            u = self._dm.to_host()
+            u.setflags(write=False)
+            self._u_kn = u
+        return self._u_kn
+
+    @u_kn.setter
+    def u_kn(self, value):
+        self._u_kn = value
+
+    def _keep_host_matrix(self, u_kn, copy, device):
+        """The constructor's host copy of (or reference to) ``u_kn``; returns the record of the upload started beside a large
+        copy, or None."""
         from .device import DeviceMatrix
 
-        if bootstrap_rng not in ("reference", "device"):  # (before the upload and the main solve: a typo must not cost either)
-            raise ParameterError("bootstrap_rng must be 'reference' or 'device'")
-        self.N_k = np.array(N_k, dtype=np.int64)
-        self.N = int(np.sum(self.N_k))
         if len(np.shape(u_kn)) == 3:
             u_kn = kln_to_kn(u_kn, N_k=self.N_k)
         # Like the reference (mbar.py:243) the object keeps its OWN host copy of the matrix by default: the device copy is
@@ -177,10 +229,40 @@ class MBAR:
             self.u_kn.setflags(write=False)
         else:
             self.u_kn = src
+        return early_upload
+
+    def _linear_matrix(self, device):
+        """The device matrix of an object made by :meth:`from_linear` (made once; the time goes to ``_linear_upload_s``)."""
+        from .device import DeviceMatrix
+        import time as _time
+
+        if getattr(self, "_dm", None) is None:
+            t0 = _time.perf_counter()
+            self._dm = DeviceMatrix.from_linear(self.basis_bn, self.coeff_kb, self.offset_k, device=device, validate=False)  # (checked by from_linear)
+            self._linear_upload_s = _time.perf_counter() - t0
+        return self._dm
+
+    def _construct(self, u_kn, N_k, maximum_iterations=10000, relative_tolerance=1.0e-7, verbose=False, initial_f_k=None,
+                   solver_protocol=None, initialize="zeros", x_kindices=None, n_bootstraps=0, bootstrap_solver_protocol=None, rseed=None,
+                   device=None, copy=True, bootstrap_rng="reference", linear=None):
+        """The constructor: of a host matrix ``u_kn``, or (``linear = (basis_bn, coeff_kb, offset_k)``, checked) of a linear family."""
+        from .device import DeviceMatrix
+
+        if bootstrap_rng not in ("reference", "device"):  # (before the upload and the main solve: a typo must not cost either)
+            raise ParameterError("bootstrap_rng must be 'reference' or 'device'")
+        self.N_k = np.array(N_k, dtype=np.int64)
+        self.N = int(np.sum(self.N_k))
+        self.basis_bn, self.coeff_kb, self.offset_k = (None, None, None) if linear is None else linear
+        self._u_kn = None
+        self._dm = None
+        early_upload = None if linear is not None else self._keep_host_matrix(u_kn, copy, device)
         try:
-            if self.u_kn.ndim != 2:
-                raise ParameterError("u_kn must be a K x N (or K x L x N_max) array.")
-            K, N = self.u_kn.shape
+            if linear is not None:
+                K, N = self.coeff_kb.shape[0], self.basis_bn.shape[1]
+            else:
+                if self.u_kn.ndim != 2:
+                    raise ParameterError("u_kn must be a K x N (or K x L x N_max) array.")
+                K, N = self.u_kn.shape
             if verbose:
                 logger.info("K (total states) = {:d}, total samples = {:d}".format(K, N))
             if np.sum(self.N_k) != N:
@@ -202,7 +284,10 @@ class MBAR:
             maxpoint = min(50, self.N)
             indices = self.rng.choice(np.arange(self.N), maxpoint)
             if self.verbose:
-                sub = self.u_kn[:, indices]
+                if linear is not None:  # (the <= 50 columns from the basis, on the host: no download for a log line)
+                    sub = self.coeff_kb @ self.basis_bn[:, indices] + self.offset_k[:, None]
+                else:
+                    sub = self.u_kn[:, indices]
                 for k in range(K):
                     for l in range(k):
                         d = sub[k] - sub[l]
@@ -225,6 +310,8 @@ class MBAR:
                     raise ParameterError("initial_f_k must be a {:d}-dimensional np array.".format(K))
                 self.f_k = initial_f_k - initial_f_k[0]
             else:
+                if linear is not None and initialize in ("mean-reduced-potential", "BAR"):
+                    self._linear_matrix(device)  # (these two read u_kn: the matrix is built now and downloaded)
                 self._initializeFreeEnergies(verbose, method=initialize)
 
             solver_protocol = _resolve_protocol(solver_protocol, DEFAULT_SOLVER_PROTOCOL, ROBUST_SOLVER_PROTOCOL,
@@ -238,6 +325,7 @@ class MBAR:
                 early_upload["thread"].join()
                 if early_upload["dm"] is not None:
                     early_upload["dm"].close()
+            self.close()  # (a linear family's matrix, built early for the initial guess)
             raise
         # the matrix goes to HBM once and stays there for the lifetime of the object
         self._device = device
@@ -251,10 +339,14 @@ class MBAR:
                 raise early_upload["err"]
             self._dm = early_upload["dm"]
             _dt = early_upload["dt"]
+        elif linear is not None:
+            self._linear_matrix(device)
+            _dt = self._linear_upload_s
         else:
             self._dm = DeviceMatrix.from_host(self.u_kn, device=device)
             _dt = _time.perf_counter() - _t0
-        self.upload_stats = dict(upload_s=_dt, upload_GBps=8.0 * K * N / _dt * 1e-9 if _dt > 0 else float("inf"))
+        _bus_rows = K if linear is None else self.basis_bn.shape[0]  # (a linear family: only the basis crossed the bus)
+        self.upload_stats = dict(upload_s=_dt, upload_GBps=8.0 * _bus_rows * N / _dt * 1e-9 if _dt > 0 else float("inf"))
         self.f_k = mbar_solvers.solve_mbar_for_all_states(self._dm, self.N_k, self.f_k, self.states_with_samples,
                                                           solver_protocol)
 

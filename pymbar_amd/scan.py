@@ -138,12 +138,24 @@ def _analytical(mbar, dm, coeff_lb, offset_l, f, mean, reference, approximate, w
     return dDelta_f, sigma
 
 
-def compute_scan(mbar, basis_bn, coeff_lb, offset_l=None, A_qn=None, reference=0, compute_uncertainty=True, uncertainty_method=None,
+def _family_basis(mbar, basis_bn, coeff_lb):
+    """``basis_bn`` of a scan call: None stands for the basis an object made by ``MBAR.from_linear`` was built from."""
+    if coeff_lb is None:
+        raise ParameterError("coeff_lb must have shape (L, B) with L >= 1")
+    if basis_bn is not None:
+        return basis_bn
+    if getattr(mbar, "basis_bn", None) is None:
+        raise ParameterError("basis_bn=None stands for the basis of an object made by MBAR.from_linear; this object was built from "
+                             "a dense u_kn and has none: pass basis_bn")
+    return mbar.basis_bn
+
+
+def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, reference=0, compute_uncertainty=True, uncertainty_method=None,
                  warning_cutoff=1.0e-10):
     """Free energies, averages and their uncertainties along a linear family of unsampled states.
 
     Member ``l`` is the state ``u_l(n) = sum_b coeff_lb[l, b] basis_bn[b, n] + offset_l[l]``; ``basis_bn`` is ``(B, N)`` with ``1 <=
-    B <= 8``, ``coeff_lb`` ``(L, B)`` with any ``L >= 1``, ``A_qn`` optional, ``(Q, N)`` with ``Q <= 3`` or ``(N,)``.  Returns a
+    B <= 8`` (None: the basis of an object made by ``MBAR.from_linear``; on any other object None is a ``ParameterError``), ``coeff_lb`` ``(L, B)`` with any ``L >= 1``, ``A_qn`` optional, ``(Q, N)`` with ``Q <= 3`` or ``(N,)``.  Returns a
     dict: ``f`` ``(L,)`` in the gauge of ``mbar.f_k``; ``Delta_f = f - f[reference]`` and its uncertainty ``dDelta_f`` -- row
     ``reference`` of what ``compute_perturbed_free_energies(u_ln)`` returns for the dense ``u_ln``; with observables ``mu`` and
     ``sigma`` ``(Q, L)`` -- entry ``l`` of ``compute_expectations(A_qn[q], u_kn=u_ln, state_dependent=False)``.
@@ -158,7 +170,7 @@ def compute_scan(mbar, basis_bn, coeff_lb, offset_l=None, A_qn=None, reference=0
     bootstrap = uncertainty_method == "bootstrap"
     if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
         raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
-    basis_bn, coeff_lb, offset_l, A_qn, L = _check_inputs(mbar, basis_bn, coeff_lb, offset_l, A_qn, reference)
+    basis_bn, coeff_lb, offset_l, A_qn, L = _check_inputs(mbar, _family_basis(mbar, basis_bn, coeff_lb), coeff_lb, offset_l, A_qn, reference)
     dm = _scan_matrix(mbar)
     Q = len(A_qn)
     t_qn, shift = _shifted(A_qn)
@@ -238,13 +250,13 @@ def _fes_analytical(mbar, dm, coeff_lb, offset_l, f_raw, j_l, approximate):
     return np.sqrt(np.maximum(var, 0.0))
 
 
-def compute_scan_fes(mbar, basis_bn, coeff_lb, offset_l=None, sample_label=None, reference="from-lowest", reference_label=None,
+def compute_scan_fes(mbar, basis_bn=None, coeff_lb=None, offset_l=None, sample_label=None, reference="from-lowest", reference_label=None,
                      uncertainty_method=None, theta_method=None, warning_cutoff=1.0e-10):
     """Histogram free energy surfaces of every member of a linear family of unsampled states: row ``l`` of every returned array
     is what ``fes.histogram_fes_labels(mbar, coeff_lb[l] @ basis_bn + offset_l[l], sample_label, reference, reference_label, ...)``
     returns, without a dense ``u_l``, an upload or a read of the resident matrix per member.
 
-    ``basis_bn``, ``coeff_lb``, ``offset_l`` as in :func:`compute_scan`; ``sample_label`` as :func:`pymbar_amd.fes.label_samples`
+    ``basis_bn`` (None: the constructor's basis of ``MBAR.from_linear``), ``coeff_lb``, ``offset_l`` as in :func:`compute_scan`; ``sample_label`` as :func:`pymbar_amd.fes.label_samples`
     returns it (``[-1, nbins)``, every label below ``nbins = max + 1`` occurring).  Returns a dict: ``f_raw`` ``(L, nbins)``, the
     bin free energies in the gauge of ``mbar.f_k``; ``reference`` ``(L,)``, the reference bin ``j_l`` of every member (its lowest
     bin for "from-lowest", ``reference_label`` for "from-specified"); ``f_i = f_raw - f_raw[l, j_l]``; ``f`` ``(L,)``, ``-logsumexp_i(
@@ -266,7 +278,7 @@ def compute_scan_fes(mbar, basis_bn, coeff_lb, offset_l=None, sample_label=None,
     bootstrap = uncertainty_method == "bootstrap"
     if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
         raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
-    basis_bn, coeff_lb, offset_l, _, L = _check_inputs(mbar, basis_bn, coeff_lb, offset_l, None, 0)
+    basis_bn, coeff_lb, offset_l, _, L = _check_inputs(mbar, _family_basis(mbar, basis_bn, coeff_lb), coeff_lb, offset_l, None, 0)
     if sample_label is None:
         raise ParameterError("sample_label must have one entry per sample")
     _, sample_label, nbins = _check_labels(mbar, np.zeros(mbar.N), sample_label)

@@ -15,6 +15,7 @@ __all__ = [
     "harmonic_u_kn",
     "harmonic_free_energies",
     "harmonic_scan_family",
+    "harmonic_linear_family",
     "exponential_u_kn",
     "exponential_free_energies",
     "config1",
@@ -72,6 +73,24 @@ def harmonic_scan_family(x_n, O_l, K_l, beta=1.0):
     coeff_lb = np.stack([0.5 * beta * K_l, -beta * K_l * O_l], axis=1)
     offset_l = 0.5 * beta * K_l * O_l * O_l
     return basis_bn, coeff_lb, offset_l
+
+
+def harmonic_linear_family(O_k, K_k, N_k, seed=None, beta=1.0):
+    """The harmonic-oscillator system of :func:`harmonic_u_kn` (same draws for the same ``seed``) as a linear family for
+    ``MBAR.from_linear``, without the dense matrix: ``(basis_bn, coeff_kb, offset_k)`` with the basis ``[x^2, x]`` (``x_n`` is
+    ``basis_bn[1]``), since ``u_k = beta (K_k / 2 x^2 - K_k O_k x + K_k O_k^2 / 2)``."""
+    O_k = np.asarray(O_k, dtype=np.float64)
+    K_k = np.asarray(K_k, dtype=np.float64)
+    N_k = np.array(N_k, dtype=int)
+    if not (len(O_k) == len(K_k) == len(N_k)):
+        raise ValueError("O_k, K_k and N_k must have one entry per state")
+    np.random.seed(seed)
+    x_n = np.empty(int(N_k.sum()), dtype=np.float64)
+    start = 0
+    for k, n in enumerate(N_k):
+        x_n[start : start + n] = np.random.normal(loc=O_k[k], scale=(beta * K_k[k]) ** -0.5, size=n)
+        start += n
+    return harmonic_scan_family(x_n, O_k, K_k, beta=beta)
 
 
 def exponential_u_kn(rates, N_k, seed=None, beta=1.0):

@@ -221,6 +221,23 @@ def private_copy(src):
     return out
 
 
+def private_copy_flat(src):
+    """:func:`private_copy` for a C-contiguous array of FEW long rows (the ``B x N`` basis of a linear family): the threads split
+    the flattened array instead of the rows."""
+    import numpy as _np
+
+    if src.nbytes < _THREADED_COPY_BYTES or not src.flags.c_contiguous:
+        return _np.array(src, dtype=_np.float64)
+    from concurrent.futures import ThreadPoolExecutor
+
+    out = _np.empty_like(src)
+    fo, fs = out.reshape(-1), src.reshape(-1)
+    chunks = _row_chunks(fs.size, min(_host_threads(fs.size), max(2, src.nbytes >> 22)))
+    with ThreadPoolExecutor(len(chunks)) as ex:
+        list(ex.map(lambda c: _np.copyto(fo[c[0]:c[1]], fs[c[0]:c[1]]), chunks))
+    return out
+
+
 def prefault(out):
     """Touch the pages of a freshly allocated 2-D array from several threads (from 64 MB on): a device-to-host copy into
     untouched pageable memory runs at the page-fault rate of the ONE driver thread that performs it (17 GB/s measured for the
