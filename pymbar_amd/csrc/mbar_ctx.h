@@ -266,6 +266,11 @@ struct DevBuf {
         return e != hipSuccess ? e : hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
     }
 };
+// a host table on the device (an empty one still gets a block: the kernels are handed its pointer)
+template <class T>
+hipError_t put(DevBuf<T>& d, const std::vector<T>& h) {
+    return h.empty() ? d.grow(1) : d.upload(h.data(), h.size());
+}
 
 struct TimerPair {
     hipEvent_t a, b;
@@ -663,12 +668,11 @@ int agree_all_ok(mbar_ctx* c, bool& ok);
 int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t maxiter, int64_t min_sc_iter, double gamma,
                          int check_convergence, double* history, int64_t history_rows, mbar_solve_result& res,
                          std::vector<double>& psum, double& max_delta, bool& handed_back);
-// the scan passes (mbar_scan.cpp), shared with the histogram surfaces along a scan (mbar_scanbin.cpp): the limits of the context,
-// the family as the kernels see it, the log-denominators of f in slot 0 (*nan_out: every output is NaN), the members' upload
-int scan_ready(mbar_ctx* c, const char* who);
-ScanData scan_data_of(const mbar_ctx* c);
-int scan_logden(mbar_ctx* c, const double* f, bool* nan_out);
-int scan_upload_members(mbar_ctx* c, int64_t L, const double* coeff, const double* offset, const double* f_scan);
+// What the binned passes (mbar_hist.cpp) and the scan passes (mbar_scan.cpp) ask of a context before anything else (mbar_host.cpp).
+// family: "the binned passes" / "the scan passes", as the messages word it; max_K: the most states the family serves, 0: no limit.
+int passes_ready(mbar_ctx* c, const char* who, const char* family, int64_t max_K);
+// the log-denominators of f into slot 0; *nan_out: the matrix or f is unusable and every output is NaN
+int pass_logden(mbar_ctx* c, const double* f, bool* nan_out);
 
 }  // namespace host
 }  // namespace mbar

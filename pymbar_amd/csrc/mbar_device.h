@@ -683,18 +683,7 @@ static inline bool stage_offsets_wide(int64_t ld) { return (uint64_t)ld * 56u + 
 hipError_t launch_fused_quad(hipStream_t s, int nbt, const LaunchGeom& g, const double* P, int64_t ld, int64_t N, const double* cmul,
                              const double* cw, const double* wsq, double* rinv0, double* gp, double* pp, const LoopCtl& lc);
 
-// ---- shared by the scan kernels (mbar_k_scan.hip) and the binned scan kernels (mbar_k_scanbin.hip) ----------------------------
-constexpr int SV_THREADS = 256;
-constexpr int SCAN_PITCH = 17;  // doubles per state row of the W tile in LDS (16 samples + 1: the column read spreads over the banks)
-
-__device__ __forceinline__ double scan_exp(double x) { return exp2s_fast(x * LOG2E_S); }
-
-__device__ __forceinline__ void scan_neumaier(double& s, double& e, double v) {
-    const double t = s + v;
-    e += fabs(s) >= fabs(v) ? (s - t) + v : (v - t) + s;
-    s = t;
-}
-
+// ---- the scan kernels (mbar_k_scan.hip); mbar_k_linear.hip follows the same chain ---------------------------------------------
 // -u_l(n) - logden_n with the fixed fma chain over ascending b
 __device__ __forceinline__ double scan_x(const ScanData& d, const double (&cf)[SCAN_MAX_B], double off, int64_t n) {
     double u = off;

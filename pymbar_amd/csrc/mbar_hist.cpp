@@ -89,19 +89,8 @@ HostTile build_tile(const int32_t* label, int64_t N, int64_t nbins, int64_t b0, 
     return t;
 }
 
-template <class T>
-hipError_t put(DevBuf<T>& d, const std::vector<T>& h) {
-    return h.empty() ? d.grow(1) : d.upload(h.data(), h.size());
-}
-
-int hist_ready(mbar_ctx* c, const char* who) {
-    if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (c->ext_base) return fail(c, MBAR_ERR_STATE, std::string(who) + ": an extension context holds rows only");
-    if (c->nranks > 1 || stream_transport(c) || c->host_reduce)
-        return fail(c, MBAR_ERR_STATE, std::string(who) + ": the binned passes serve single-rank contexts only (a transport is attached)");
-    if (wide_pitch(c)) return fail(c, MBAR_ERR_STATE, std::string(who) + ": the binned passes do not serve wide-pitch matrices (row pitch x 56 bytes >= 4 GiB)");
-    return MBAR_OK;
-}
+// (the label path serves any number of states)
+int hist_ready(mbar_ctx* c, const char* who) { return passes_ready(c, who, "the binned passes", 0); }
 
 HistSweep sweep_of(const mbar_ctx* c, const HistTile& t) {
     HistSweep h;
@@ -121,14 +110,6 @@ HistSweep sweep_of(const mbar_ctx* c, const HistTile& t) {
     h.logden = c->logden[0];
     h.cw = c->weighted ? c->cw.p : nullptr;
     return h;
-}
-
-// the log-denominators of f into slot 0; *nan_out: the matrix or f is unusable and every output is NaN
-int hist_logden(mbar_ctx* c, const double* f, bool* nan_out) {
-    int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    *nan_out = c->u_poison || !f_is_finite(c, f, 1);
-    return MBAR_OK;
 }
 
 }  // namespace
@@ -215,7 +196,7 @@ int mbar_bin_lognum(mbar_ctx* c, const double* f, double* lognum_bins) {
     if (c->hist_nbins < 1) return fail(c, MBAR_ERR_STATE, "mbar_bin_lognum: no bins on this context (mbar_ctx_set_bins first)");
     HIPCHK(c, hipSetDevice(c->device));
     bool nan = false;
-    rc = hist_logden(c, f, &nan);
+    rc = pass_logden(c, f, &nan);
     if (rc) return rc;
     const int64_t nbins = c->hist_nbins;
     if (nan) {
@@ -246,7 +227,7 @@ int mbar_bin_gram_w(mbar_ctx* c, const double* f, const double* f_bins, double* 
     if (c->hist_nbins < 1) return fail(c, MBAR_ERR_STATE, "mbar_bin_gram_w: no bins on this context (mbar_ctx_set_bins first)");
     HIPCHK(c, hipSetDevice(c->device));
     bool nan = false;
-    rc = hist_logden(c, f, &nan);
+    rc = pass_logden(c, f, &nan);
     if (rc) return rc;
     const int64_t nbins = c->hist_nbins, K = c->K;
     for (int64_t i = 0; i < nbins; ++i) nan = nan || std::isnan(f_bins[i]);

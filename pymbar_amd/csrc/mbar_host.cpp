@@ -621,6 +621,23 @@ void newton_direction(const std::vector<double>& H, const std::vector<double>& g
     for (int k = 0; k < m; ++k) x[k] = y[k] - y[0];
 }
 
+int passes_ready(mbar_ctx* c, const char* who, const char* family, int64_t max_K) {
+    if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
+    const std::string head = std::string(who) + ": ", fam = family;
+    if (c->ext_base) return fail(c, MBAR_ERR_STATE, head + "an extension context holds rows only");
+    if (c->nranks > 1 || stream_transport(c) || c->host_reduce)
+        return fail(c, MBAR_ERR_STATE, head + fam + " serve single-rank contexts only (a transport is attached)");
+    if (wide_pitch(c)) return fail(c, MBAR_ERR_STATE, head + fam + " do not serve wide-pitch matrices (row pitch x 56 bytes >= 4 GiB)");
+    if (max_K > 0 && c->K > max_K) return fail(c, MBAR_ERR_STATE, head + fam + " serve at most " + std::to_string(max_K) + " states");
+    return MBAR_OK;
+}
+
+int pass_logden(mbar_ctx* c, const double* f, bool* nan_out) {
+    int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    *nan_out = c->u_poison || !f_is_finite(c, f, 1);
+    return MBAR_OK;
+}
 
 
 }  // namespace host

@@ -397,7 +397,8 @@ hipError_t launch_hist_cross(hipStream_t s, const HistSweep& h, const double* u,
                              const double* f_bins, double* part);
 hipError_t launch_hist_cross_combine(hipStream_t s, const HistSweep& h, int64_t K, const double* part, double* cross);
 
-// ---- reweighting scans over a linear family of unsampled states (mbar_k_scan.hip; panels and C ABI in mbar_scan.cpp) --------
+// ---- reweighting scans over a linear family of unsampled states, and the histogram surfaces along a scan (mbar_k_scan.hip;
+// panels, tables, bin groups and C ABI in mbar_scan.cpp) ------------------------------------------------------------------------
 constexpr int SCAN_MAX_B = MBAR_SCAN_MAX_B;  // basis vectors
 constexpr int SCAN_MAX_Q = MBAR_SCAN_MAX_Q;  // observables
 constexpr int SCAN_VCHUNK = 2048;            // samples of one wave of pass A
@@ -405,6 +406,7 @@ constexpr int SCAN_CHUNK = 8192;             // samples of one workgroup of pass
 // blocks of 16 members per wave of pass B for J = 1 + Q operand columns per member, and per-member sums of its vec record
 constexpr int scan_mb(int J) { return J == 1 ? 4 : J == 2 ? 2 : 1; }
 constexpr int scan_nv(int J) { return 1 + J + J * (J + 1) / 2; }
+constexpr int SCANBIN_NV = 2;  // per (member, bin) sums of a binned pass-B record: wsum | diag
 struct ScanData {
     int64_t N, ldv;
     int B, Q;
@@ -413,31 +415,6 @@ struct ScanData {
     const double* logden;  // [N]
     const double* cw;      // [N] multiplicities (NULL: 1)
 };
-// pass A: per-chunk records of the maxima (sum = false: rec[chunk][L]) or of the J scaled sums (rec[chunk][L][J]) of the members
-// [0, L) of coeff / offset, and their merge in chunk order into M, or into lognum and mean[L][J]
-hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, bool sum, int64_t L, const double* coeff, const double* offset,
-                           const double* M, double* rec);
-hipError_t launch_scan_vec_merge(hipStream_t s, const ScanData& d, bool sum, int64_t L, const double* rec, double* M, double* lognum,
-                                 double* mean);
-// pass B for the panel of members [p0, p0 + 64 scan_mb(J)) of L: part[chunk][scan_record_doubles(nb, J)], then cross[K][L][J] and
-// vec[L][scan_nv(J)] = wsum | refcol[J] | within[i <= j].  nb = scan_nb_for(K) blocks of 16 states, or 0: no cross block.
-int scan_nb_for(int64_t K);
-int64_t scan_record_doubles(int nb, int J);
-hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, int nb, const double* u, int64_t ld, int64_t K, const double* f, int64_t L,
-                             int64_t p0, const double* coeff, const double* offset, const double* f_scan, int64_t ref, double* part);
-hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, int nb, int64_t K, int64_t L, int64_t p0, const double* part,
-                                   double* cross, double* vec);
-
-// ---- rows of the resident matrix from a linear family (mbar_k_linear.hip; C ABI: mbar_ctx_fill_linear_rows in mbar_capi.cpp) --
-constexpr int FILL_THREADS = 256;      // a lane owns two adjacent columns: 512 columns per workgroup and pass
-constexpr int FILL_ROWS = 128;         // rows a lane writes from one read of its basis values (grid.y = row groups)
-constexpr int FILL_MAX_BLOCKS = 2048;  // grid.x; the column pairs go round it
-// rows[r][n] = fma(coeff[r][B-1], basis[B-1][n], ... fma(coeff[r][0], basis[0][n], offset[r])) for r < nrows, n < N: the chain of
-// scan_x.  rows (pitch ld) and basis (pitch ldb) 16-byte aligned with even pitches; coeff[nrows][B], offset[nrows] on the device
-hipError_t launch_fill_linear_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis,
-                                   int64_t ldb, const double* coeff, const double* offset);
-
-// ---- histogram surfaces along a scan (mbar_k_scanbin.hip; tables and C ABI in mbar_scanbin.cpp) ------------------------------
 // The samples sorted by bin (perm: sorted position -> sample, ascending n inside a bin) and cut into chunks that never straddle a
 // bin: chunk c of a table belongs to bin chunk_bin[c] and is that bin's chunk number c - bin_chunk0[bin], positions bin_start[bin]
 // + chunk number x chunk length onward.  With one bin holding every sample the cut is the cut of the scan passes.
@@ -451,21 +428,75 @@ struct ScanBins {
     const int32_t* perm;       // [bin_start[nbins]]
     const int64_t* bin_start;  // [nbins + 1]
 };
-constexpr int SCANBIN_NV = 2;  // per (member, bin) sums of a pass-B record: wsum | diag
-// pass A over the members [0, L) of coeff / offset: rec[chunk][L], M[bin][L] (bin-major, of this member panel), lognum[l][bin]
-// with row pitch nbins
-hipError_t launch_scanbin_vec(hipStream_t s, const ScanData& d, const ScanBins& sb, const ScanBinTable& t, bool sum, int64_t L,
-                              const double* coeff, const double* offset, const double* M, double* rec);
-hipError_t launch_scanbin_vec_merge(hipStream_t s, const ScanBins& sb, const ScanBinTable& t, bool sum, int64_t L, const double* rec,
-                                    double* M, double* lognum);
-// pass B for the panel of members [p0, p0 + 256) of L and the chunks [c0, c1) of the table, which are those of the bins [b0, b1):
-// part[chunk - c0][scanbin_record_doubles(nb)], then cross[k][l][bin] (K x L x nbins) and vec[l][bin][SCANBIN_NV]
-int64_t scanbin_record_doubles(int nb);
-hipError_t launch_scanbin_cross(hipStream_t s, const ScanData& d, const ScanBins& sb, const ScanBinTable& t, int64_t c0, int64_t c1, int nb,
-                                const double* u, int64_t ld, int64_t K, const double* f, int64_t L, int64_t p0, const double* coeff,
-                                const double* offset, const double* f_bins, double* part);
-hipError_t launch_scanbin_cross_merge(hipStream_t s, const ScanBins& sb, const ScanBinTable& t, int64_t c0, int64_t b0, int64_t b1, int nb,
-                                      int64_t K, int64_t L, int64_t p0, const double* part, double* cross, double* vec);
+// The cut of the samples a launch sums over, the compile-time policy of the kernels: the bins [b0(), b1()) and their chunks
+// [c0(), c1()) of at most len positions (chunk c0() writes record 0), the positions [p0, p1) of chunk c and its bin, the sample at
+// position p.  The whole cut also carries what only it has, the reference member of pass B.
+struct ScanWhole {  // every sample in its own order, as one bin: chunk c is [c len, min(N, (c + 1) len))
+    static constexpr bool binned = false;
+    int64_t ref = 0;
+    MBAR_HD int64_t nbins() const { return 1; }
+    MBAR_HD int64_t b0() const { return 0; }
+    MBAR_HD int64_t b1() const { return 1; }
+    MBAR_HD int64_t c0() const { return 0; }
+    MBAR_HD int64_t c1(int64_t N, int64_t len) const { return (N + len - 1) / len; }
+    MBAR_HD void bin_chunks(int64_t, int64_t N, int64_t len, int64_t& ca, int64_t& cb) const { ca = 0, cb = c1(N, len); }
+    MBAR_HD void range(int64_t c, int64_t N, int64_t len, int64_t& bin, int64_t& p0, int64_t& p1) const {
+        bin = 0;
+        p0 = c * len;
+        p1 = p0 + len < N ? p0 + len : N;
+    }
+    MBAR_HD int64_t sample(int64_t p) const { return p; }
+};
+struct ScanBinned {  // the sorted positions of the bins [b0_, b1_), whose chunks in table t are [c0_, c1_)
+    static constexpr bool binned = true;
+    ScanBins sb;
+    ScanBinTable t;
+    int64_t b0_, b1_, c0_, c1_;
+    MBAR_HD int64_t nbins() const { return sb.nbins; }
+    MBAR_HD int64_t b0() const { return b0_; }
+    MBAR_HD int64_t b1() const { return b1_; }
+    MBAR_HD int64_t c0() const { return c0_; }
+    MBAR_HD int64_t c1(int64_t, int64_t) const { return c1_; }
+    MBAR_HD void bin_chunks(int64_t bin, int64_t, int64_t, int64_t& ca, int64_t& cb) const { ca = t.bin_chunk0[bin], cb = t.bin_chunk0[bin + 1]; }
+    MBAR_HD void range(int64_t c, int64_t, int64_t len, int64_t& bin, int64_t& p0, int64_t& p1) const {
+        bin = t.chunk_bin[c];
+        const int64_t end = sb.bin_start[bin + 1];
+        p0 = sb.bin_start[bin] + (c - t.bin_chunk0[bin]) * len;
+        p1 = p0 + len < end ? p0 + len : end;
+    }
+    MBAR_HD int64_t sample(int64_t p) const { return sb.perm[p]; }
+};
+// Cut = ScanWhole or ScanBinned (Q = 0) in all four.
+// pass A over the members [0, L) of coeff / offset: per-chunk records of the maxima (sum = false: rec[chunk][L]) or of the J scaled
+// sums (rec[chunk][L][J]), and their merge in chunk order into M[bin][L] (bin-major, of this member panel), or into
+// lognum[l][bin] (row pitch nbins) and, on the whole cut, mean[L][J]
+template <class Cut>
+hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, bool sum, int64_t L, const double* coeff, const double* offset,
+                           const double* M, double* rec);
+template <class Cut>
+hipError_t launch_scan_vec_merge(hipStream_t s, const ScanData& d, const Cut& cut, bool sum, int64_t L, const double* rec, double* M,
+                                 double* lognum, double* mean);
+// pass B for the panel of members [p0, p0 + 64 scan_mb(J)) of L: part[chunk - c0][scan_record_doubles(nb, J, nv)], then
+// cross[k][l][bin][j] (K x L x nbins x J) and vec[l][bin][nv].  Whole cut: nv = scan_nv(J), vec = wsum | refcol[J] | within[i <= j],
+// fnorm = f_scan[L]; binned cut: J = 1, nv = SCANBIN_NV, vec = wsum | diag, fnorm = f_bins[L][nbins] (+inf: an empty bin of that
+// member, exact zeros).  nb = scan_nb_for(K) blocks of 16 states, or 0: no cross block.
+int scan_nb_for(int64_t K);
+int64_t scan_record_doubles(int nb, int J, int nv);
+template <class Cut>
+hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, int nb, const double* u, int64_t ld, int64_t K, const double* f,
+                             int64_t L, int64_t p0, const double* coeff, const double* offset, const double* fnorm, double* part);
+template <class Cut>
+hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int64_t K, int64_t L, int64_t p0,
+                                   const double* part, double* cross, double* vec);
+
+// ---- rows of the resident matrix from a linear family (mbar_k_linear.hip; C ABI: mbar_ctx_fill_linear_rows in mbar_capi.cpp) --
+constexpr int FILL_THREADS = 256;      // a lane owns two adjacent columns: 512 columns per workgroup and pass
+constexpr int FILL_ROWS = 128;         // rows a lane writes from one read of its basis values (grid.y = row groups)
+constexpr int FILL_MAX_BLOCKS = 2048;  // grid.x; the column pairs go round it
+// rows[r][n] = fma(coeff[r][B-1], basis[B-1][n], ... fma(coeff[r][0], basis[0][n], offset[r])) for r < nrows, n < N: the chain of
+// scan_x.  rows (pitch ld) and basis (pitch ldb) 16-byte aligned with even pitches; coeff[nrows][B], offset[nrows] on the device
+hipError_t launch_fill_linear_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis,
+                                   int64_t ldb, const double* coeff, const double* offset);
 
 // ---- lagged fluctuation sums of a timeseries (mbar_k_acf.hip; C ABI in mbar_acf.cpp) ----------------------------------------
 constexpr int ACF_WG = 256;                 // threads per workgroup

@@ -1,27 +1,19 @@
-// Host side of the reweighting scans over a linear family of unsampled states (include/mbar_hip.h, "reweighting scans"): the
-// upload of the basis and observable vectors, the member panels of the two passes under the record budget, and the C ABI.
-// Kernels: mbar_k_scan.hip.
+// Host side of the reweighting scans over a linear family of unsampled states (include/mbar_hip.h, "reweighting scans") and of the
+// histogram free energy surfaces along such a scan ("histogram surfaces along a scan"): the upload of the basis and observable
+// vectors, the stable counting sort of the samples by bin and the chunk tables of the two passes, the member panels and the bin
+// groups under the record budget, and the C ABI.  Kernels: mbar_k_scan.hip, one source for both cuts of the samples.
 #include "mbar_ctx.h"
+
+#include <initializer_list>
 
 using namespace mbar;
 using namespace mbar::host;
 
 namespace {
+
 constexpr int64_t SCAN_MAX_K = 128;  // one W tile of the cross kernel
-}  // namespace
 
-namespace mbar {
-namespace host {
-
-int scan_ready(mbar_ctx* c, const char* who) {
-    if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (c->ext_base) return fail(c, MBAR_ERR_STATE, std::string(who) + ": an extension context holds rows only");
-    if (c->nranks > 1 || stream_transport(c) || c->host_reduce)
-        return fail(c, MBAR_ERR_STATE, std::string(who) + ": the scan passes serve single-rank contexts only (a transport is attached)");
-    if (wide_pitch(c)) return fail(c, MBAR_ERR_STATE, std::string(who) + ": the scan passes do not serve wide-pitch matrices (row pitch x 56 bytes >= 4 GiB)");
-    if (c->K > SCAN_MAX_K) return fail(c, MBAR_ERR_STATE, std::string(who) + ": the scan passes serve at most 128 states");
-    return MBAR_OK;
-}
+int scan_ready(mbar_ctx* c, const char* who) { return passes_ready(c, who, "the scan passes", SCAN_MAX_K); }
 
 ScanData scan_data_of(const mbar_ctx* c) {
     ScanData d;
@@ -36,16 +28,38 @@ ScanData scan_data_of(const mbar_ctx* c) {
     return d;
 }
 
-// the log-denominators of f into slot 0; *nan_out: the matrix or f is unusable and every output is NaN
-int scan_logden(mbar_ctx* c, const double* f, bool* nan_out) {
-    int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
+// How the four passes open.  scan_open: the limits of the context, the caller's own argument check (args_ok), what the family
+// needs on the context, the device.
+int scan_open(mbar_ctx* c, const std::string& who, bool args_ok, bool binned) {
+    int rc = scan_ready(c, who.c_str());
     if (rc) return rc;
-    *nan_out = c->u_poison || !f_is_finite(c, f, 1);
+    if (!args_ok) return fail(c, MBAR_ERR_ARG, who + ": bad argument");
+    if (c->scan_B < 1) return fail(c, MBAR_ERR_STATE, who + ": no basis on this context (mbar_ctx_set_scan first)");
+    if (binned && c->scan_Q != 0) return fail(c, MBAR_ERR_STATE, who + ": the binned scan passes take a family without observables (Q = 0)");
+    if (binned && c->scanbin_nbins < 1) return fail(c, MBAR_ERR_STATE, who + ": no bins on this context (mbar_ctx_set_scan_bins first)");
+    HIPCHK(c, hipSetDevice(c->device));
     return MBAR_OK;
 }
 
-// coeff | offset | f_scan of the call's members on the device (offset NULL: zeros; f_scan NULL: not uploaded)
-int scan_upload_members(mbar_ctx* c, int64_t L, const double* coeff, const double* offset, const double* f_scan) {
+// scan_begin, once the sizes are known: the log-denominators of f; with an unusable matrix or f, or a NaN among the members'
+// normalisers fnorm[nnorm] (NULL: none), every output is filled with NaN and *done is set (the call returns MBAR_OK); otherwise
+// coeff | offset (NULL: zeros) | room for L normalisers go to the device and *d is the family as the kernels see it.
+struct ScanOut {
+    double* p;  // (NULL: not asked for)
+    size_t n;
+};
+int scan_begin(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* fnorm, size_t nnorm,
+               std::initializer_list<ScanOut> outs, bool* done, ScanData* d) {
+    bool nan = false;
+    int rc = pass_logden(c, f, &nan);
+    if (rc) return rc;
+    for (size_t x = 0; x < nnorm; ++x) nan = nan || std::isnan(fnorm[x]);
+    *done = nan;
+    if (nan) {
+        for (const ScanOut& o : outs)
+            if (o.p) std::fill(o.p, o.p + o.n, std::numeric_limits<double>::quiet_NaN());
+        return MBAR_OK;
+    }
     const int64_t B = c->scan_B;
     HIPCHK(c, c->scan_in.grow((size_t)L * (size_t)(B + 2)));
     double* d_coeff = c->scan_in;
@@ -53,12 +67,74 @@ int scan_upload_members(mbar_ctx* c, int64_t L, const double* coeff, const doubl
     HIPCHK(c, hipMemcpyAsync(d_coeff, coeff, (size_t)L * B * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (offset) HIPCHK(c, hipMemcpyAsync(d_off, offset, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
     else HIPCHK(c, hipMemsetAsync(d_off, 0, (size_t)L * sizeof(double), c->stream));
-    if (f_scan) HIPCHK(c, hipMemcpyAsync(d_off + L, f_scan, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    *d = scan_data_of(c);
     return MBAR_OK;
 }
 
-}  // namespace host
-}  // namespace mbar
+// member panels of pass A: a multiple of 64 members whose records ([chunk][member][J]) fit the budget ("scan_part_bytes"); a
+// member's sums, and a (member, bin)'s, do not depend on the cut
+int64_t vec_panel(const mbar_ctx* c, int64_t nchunks, int64_t J, int64_t L) {
+    const int64_t pw = c->opt_scan_part_bytes / (nchunks * J * (int64_t)sizeof(double)) / 64 * 64;
+    return std::min<int64_t>(std::max<int64_t>(pw, 64), (L + 63) / 64 * 64);
+}
+
+// ---- the binned cut: the samples sorted by bin, and the chunk tables ----
+// perm (sorted position -> sample, ascending n inside a bin, label -1 dropped) and bin_start[nbins + 1]; false: a label outside
+// [-1, nbins)
+bool bins_table(int64_t N, int64_t nbins, const int32_t* label, int32_t* perm, int64_t* bin_start) {
+    std::fill(bin_start, bin_start + nbins + 1, (int64_t)0);
+    for (int64_t n = 0; n < N; ++n) {
+        const int64_t lab = label[n];
+        if (lab < -1 || lab >= nbins) return false;
+        if (lab >= 0) ++bin_start[lab + 1];
+    }
+    for (int64_t i = 0; i < nbins; ++i) bin_start[i + 1] += bin_start[i];
+    std::vector<int64_t> fill(bin_start, bin_start + nbins);
+    for (int64_t n = 0; n < N; ++n)
+        if (label[n] >= 0) perm[fill[(size_t)label[n]]++] = (int32_t)n;
+    return true;
+}
+
+// chunks of at most `len` sorted positions, cut from the start of every bin: the bin of each chunk and the first chunk of each bin
+void chunk_table(const std::vector<int64_t>& bin_start, int64_t len, std::vector<int32_t>& chunk_bin, std::vector<int64_t>& bin_chunk0) {
+    const int64_t nbins = (int64_t)bin_start.size() - 1;
+    bin_chunk0.assign((size_t)nbins + 1, 0);
+    chunk_bin.clear();
+    for (int64_t i = 0; i < nbins; ++i) {
+        const int64_t nch = (bin_start[(size_t)i + 1] - bin_start[(size_t)i] + len - 1) / len;
+        bin_chunk0[(size_t)i + 1] = bin_chunk0[(size_t)i] + nch;
+        chunk_bin.insert(chunk_bin.end(), (size_t)nch, (int32_t)i);
+    }
+}
+
+void release(mbar_ctx* c) {
+    c->scanbin_nbins = c->scanbin_chunks_a = c->scanbin_chunks_b = 0;
+    c->scanbin_perm.reset();
+    c->scanbin_start.reset();
+    c->scanbin_cbin_a.reset();
+    c->scanbin_cbin_b.reset();
+    c->scanbin_c0_a.reset();
+    c->scanbin_c0_b.reset();
+    c->scanbin_fbins.reset();
+    c->scanbin_c0_b_host.clear();
+}
+
+// every bin of the context and every chunk of pass A's table (pass_b = false) or of pass B's
+ScanBinned binned_of(const mbar_ctx* c, bool pass_b) {
+    ScanBinned s;
+    s.sb.nbins = c->scanbin_nbins;
+    s.sb.perm = c->scanbin_perm;
+    s.sb.bin_start = c->scanbin_start;
+    s.t.nchunks = pass_b ? c->scanbin_chunks_b : c->scanbin_chunks_a;
+    s.t.chunk_bin = pass_b ? c->scanbin_cbin_b : c->scanbin_cbin_a;
+    s.t.bin_chunk0 = pass_b ? c->scanbin_c0_b : c->scanbin_c0_a;
+    s.b0_ = s.c0_ = 0;
+    s.b1_ = s.sb.nbins;
+    s.c1_ = s.t.nchunks;
+    return s;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -91,44 +167,31 @@ int mbar_ctx_set_scan(mbar_ctx* c, int64_t B, const double* basis, int64_t Q, co
 }
 
 int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, double* lognum, double* mean) {
-    int rc = scan_ready(c, "mbar_scan_lognum");
-    if (rc) return rc;
-    if (!f || !coeff || !lognum || L < 1) return fail(c, MBAR_ERR_ARG, "mbar_scan_lognum: bad argument");
-    if (c->scan_B < 1) return fail(c, MBAR_ERR_STATE, "mbar_scan_lognum: no basis on this context (mbar_ctx_set_scan first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    bool nan = false;
-    rc = scan_logden(c, f, &nan);
+    int rc = scan_open(c, "mbar_scan_lognum", f && coeff && lognum && L >= 1, false);
     if (rc) return rc;
     const int64_t B = c->scan_B, J = 1 + c->scan_Q;
-    if (nan) {
-        const double q = std::numeric_limits<double>::quiet_NaN();
-        std::fill(lognum, lognum + L, q);
-        if (mean) std::fill(mean, mean + L * J, q);
-        return MBAR_OK;
-    }
-    rc = scan_upload_members(c, L, coeff, offset, nullptr);
-    if (rc) return rc;
-    const ScanData d = scan_data_of(c);
-    // members in panels of a multiple of 64 whose records ([chunk][member][J]) fit the budget ("scan_part_bytes"): a member's sums
-    // do not depend on the cut
-    const int64_t nchunks = (c->N + SCAN_VCHUNK - 1) / SCAN_VCHUNK;
-    int64_t pw = c->opt_scan_part_bytes / (std::max<int64_t>(nchunks, 1) * J * (int64_t)sizeof(double)) / 64 * 64;
-    pw = std::min<int64_t>(std::max<int64_t>(pw, 64), (L + 63) / 64 * 64);
-    HIPCHK(c, c->scan_part.grow((size_t)std::max<int64_t>(nchunks, 1) * (size_t)pw * (size_t)J));
+    bool done = false;
+    ScanData d;
+    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{lognum, (size_t)L}, {mean, (size_t)(L * J)}}, &done, &d);
+    if (rc || done) return rc;
+    const int64_t nchunks = std::max<int64_t>((c->N + SCAN_VCHUNK - 1) / SCAN_VCHUNK, 1);
+    const int64_t pw = vec_panel(c, nchunks, J, L);
+    HIPCHK(c, c->scan_part.grow((size_t)nchunks * (size_t)pw * (size_t)J));
     HIPCHK(c, c->scan_out.grow((size_t)L * (size_t)(2 + J)));
     double* d_M = c->scan_out;
     double* d_lognum = d_M + L;
     double* d_mean = d_lognum + L;
     const double* d_coeff = c->scan_in;
     const double* d_off = d_coeff + L * B;
+    const ScanWhole cut{};
     {
         ScopedTimer timer(c, MBAR_TIMER_OTHER);
         for (int64_t p0 = 0; p0 < L; p0 += pw) {
             const int64_t pl = std::min(pw, L - p0);
-            HIPCHK(c, launch_scan_vec(c->stream, d, false, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
-            HIPCHK(c, launch_scan_vec_merge(c->stream, d, false, pl, c->scan_part, d_M + p0, nullptr, nullptr));
-            HIPCHK(c, launch_scan_vec(c->stream, d, true, pl, d_coeff + p0 * B, d_off + p0, d_M + p0, c->scan_part));
-            HIPCHK(c, launch_scan_vec_merge(c->stream, d, true, pl, c->scan_part, d_M + p0, d_lognum + p0, d_mean + p0 * J));
+            HIPCHK(c, launch_scan_vec(c->stream, d, cut, false, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
+            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, false, pl, c->scan_part, d_M + p0, nullptr, nullptr));
+            HIPCHK(c, launch_scan_vec(c->stream, d, cut, true, pl, d_coeff + p0 * B, d_off + p0, d_M + p0, c->scan_part));
+            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, true, pl, c->scan_part, d_M + p0, d_lognum + p0, d_mean + p0 * J));
         }
     }
     HIPCHK(c, hipMemcpyAsync(lognum, d_lognum, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -138,45 +201,34 @@ int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coef
 
 int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan, int64_t r,
                      double* cross, double* within, double* refcol, double* wsum) {
-    int rc = scan_ready(c, "mbar_scan_gram_w");
-    if (rc) return rc;
-    if (!f || !coeff || !f_scan || !within || !refcol || !wsum || L < 1 || r < 0 || r >= L)
-        return fail(c, MBAR_ERR_ARG, "mbar_scan_gram_w: bad argument");
-    if (c->scan_B < 1) return fail(c, MBAR_ERR_STATE, "mbar_scan_gram_w: no basis on this context (mbar_ctx_set_scan first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    bool nan = false;
-    rc = scan_logden(c, f, &nan);
+    int rc = scan_open(c, "mbar_scan_gram_w", f && coeff && f_scan && within && refcol && wsum && L >= 1 && r >= 0 && r < L, false);
     if (rc) return rc;
     const int64_t B = c->scan_B, K = c->K;
     const int J = 1 + (int)c->scan_Q, NW = J * (J + 1) / 2, NV = scan_nv(J);
-    for (int64_t l = 0; l < L; ++l) nan = nan || std::isnan(f_scan[l]);
-    if (nan) {
-        const double q = std::numeric_limits<double>::quiet_NaN();
-        if (cross) std::fill(cross, cross + (size_t)K * L * J, q);
-        std::fill(within, within + L * NW, q);
-        std::fill(refcol, refcol + L * J, q);
-        std::fill(wsum, wsum + L, q);
-        return MBAR_OK;
-    }
-    rc = scan_upload_members(c, L, coeff, offset, f_scan);
-    if (rc) return rc;
-    const ScanData d = scan_data_of(c);
+    bool done = false;
+    ScanData d;
+    rc = scan_begin(c, f, L, coeff, offset, f_scan, (size_t)L,
+                    {{cross, (size_t)K * L * J}, {within, (size_t)(L * NW)}, {refcol, (size_t)(L * J)}, {wsum, (size_t)L}}, &done, &d);
+    if (rc || done) return rc;
     const int nb = cross ? scan_nb_for(K) : 0;
     const int64_t nchunks = (c->N + SCAN_CHUNK - 1) / SCAN_CHUNK;
     const int64_t pw = 64 * scan_mb(J);
-    HIPCHK(c, c->scan_part.grow((size_t)std::max<int64_t>(nchunks, 1) * (size_t)scan_record_doubles(nb, J)));
+    HIPCHK(c, c->scan_part.grow((size_t)std::max<int64_t>(nchunks, 1) * (size_t)scan_record_doubles(nb, J, NV)));
     HIPCHK(c, c->scan_out.grow((size_t)L * (size_t)NV + (cross ? (size_t)K * L * J : 0)));
     double* d_vec = c->scan_out;
     double* d_cross = d_vec + L * NV;
     const double* d_coeff = c->scan_in;
     const double* d_off = d_coeff + L * B;
-    const double* d_fscan = d_off + L;
+    double* d_fscan = c->scan_in.p + L * (B + 1);
+    HIPCHK(c, hipMemcpyAsync(d_fscan, f_scan, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_f(c), f, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ScanWhole cut;
+    cut.ref = r;
     {
         ScopedTimer timer(c, MBAR_TIMER_OTHER);
         for (int64_t p0 = 0; p0 < L; p0 += pw) {  // the resident matrix is read once per panel
-            HIPCHK(c, launch_scan_cross(c->stream, d, nb, c->u, c->ld, K, d_f(c), L, p0, d_coeff, d_off, d_fscan, r, c->scan_part));
-            HIPCHK(c, launch_scan_cross_merge(c->stream, d, nb, K, L, p0, c->scan_part, d_cross, d_vec));
+            HIPCHK(c, launch_scan_cross(c->stream, d, cut, nb, c->u, c->ld, K, d_f(c), L, p0, d_coeff, d_off, d_fscan, c->scan_part));
+            HIPCHK(c, launch_scan_cross_merge(c->stream, d, cut, nb, K, L, p0, c->scan_part, d_cross, d_vec));
         }
     }
     std::vector<double> vec((size_t)L * NV);
@@ -189,6 +241,138 @@ int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coef
         wsum[l] = v[0];
         std::copy(v + 1, v + 1 + J, refcol + l * J);
         std::copy(v + 1 + J, v + NV, within + l * NW);
+    }
+    return MBAR_OK;
+}
+
+// ---- histogram surfaces along a scan ----
+
+int mbar_scan_bins_table(int64_t N, int64_t nbins, const int32_t* label, int32_t* perm_out, int64_t* bin_start_out) {
+    if (N < 0 || nbins < 1 || nbins > 0x7fffffff || (N > 0 && (!label || !perm_out)) || !bin_start_out)
+        return fail(nullptr, MBAR_ERR_ARG, "mbar_scan_bins_table: bad argument");
+    if (N >= ((int64_t)1 << 31)) return fail(nullptr, MBAR_ERR_STATE, "mbar_scan_bins_table: the sorted positions are 32-bit, N must stay below 2^31");
+    if (!bins_table(N, nbins, label, perm_out, bin_start_out)) return fail(nullptr, MBAR_ERR_ARG, "mbar_scan_bins_table: labels must lie in [-1, nbins)");
+    return MBAR_OK;
+}
+
+int mbar_ctx_set_scan_bins(mbar_ctx* c, int64_t nbins, const int32_t* label_host) {
+    int rc = scan_ready(c, "mbar_ctx_set_scan_bins");
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nbins == 0) {
+        release(c);
+        return MBAR_OK;
+    }
+    if (nbins < 0 || nbins > 0x7fffffff || !label_host) return fail(c, MBAR_ERR_ARG, "mbar_ctx_set_scan_bins: bad argument");
+    const int64_t N = c->N;
+    if (N >= ((int64_t)1 << 31)) return fail(c, MBAR_ERR_STATE, "mbar_ctx_set_scan_bins: the sorted positions are 32-bit, N must stay below 2^31");
+    std::vector<int32_t> perm((size_t)std::max<int64_t>(N, 1));
+    std::vector<int64_t> bin_start((size_t)nbins + 1);
+    if (!bins_table(N, nbins, label_host, perm.data(), bin_start.data()))
+        return fail(c, MBAR_ERR_ARG, "mbar_ctx_set_scan_bins: labels must lie in [-1, nbins)");
+    std::vector<int32_t> cbin_a, cbin_b;
+    std::vector<int64_t> c0_a, c0_b;
+    chunk_table(bin_start, SCAN_VCHUNK, cbin_a, c0_a);
+    chunk_table(bin_start, SCAN_CHUNK, cbin_b, c0_b);
+    release(c);
+    HIPCHK(c, c->scanbin_perm.upload(perm.data(), perm.size()));
+    HIPCHK(c, put(c->scanbin_start, bin_start));
+    HIPCHK(c, put(c->scanbin_cbin_a, cbin_a));
+    HIPCHK(c, put(c->scanbin_cbin_b, cbin_b));
+    HIPCHK(c, put(c->scanbin_c0_a, c0_a));
+    HIPCHK(c, put(c->scanbin_c0_b, c0_b));
+    c->scanbin_chunks_a = (int64_t)cbin_a.size();
+    c->scanbin_chunks_b = (int64_t)cbin_b.size();
+    c->scanbin_c0_b_host = std::move(c0_b);
+    c->scanbin_nbins = nbins;
+    return MBAR_OK;
+}
+
+int mbar_scan_bin_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, double* lognum) {
+    int rc = scan_open(c, "mbar_scan_bin_lognum", f && coeff && lognum && L >= 1, true);
+    if (rc) return rc;
+    const int64_t B = c->scan_B, nbins = c->scanbin_nbins;
+    bool done = false;
+    ScanData d;
+    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{lognum, (size_t)L * nbins}}, &done, &d);
+    if (rc || done) return rc;
+    const ScanBinned cut = binned_of(c, false);
+    const int64_t nch = std::max<int64_t>(cut.t.nchunks, 1);
+    const int64_t pw = vec_panel(c, nch, 1, L);
+    HIPCHK(c, c->scan_part.grow((size_t)nch * (size_t)pw));
+    HIPCHK(c, c->scan_out.grow((size_t)L * (size_t)nbins + (size_t)nbins * (size_t)pw));
+    double* d_lognum = c->scan_out;
+    double* d_M = d_lognum + L * nbins;  // [bin][member of the panel]
+    const double* d_coeff = c->scan_in;
+    const double* d_off = d_coeff + L * B;
+    {
+        ScopedTimer timer(c, MBAR_TIMER_OTHER);
+        for (int64_t p0 = 0; p0 < L; p0 += pw) {
+            const int64_t pl = std::min(pw, L - p0);
+            HIPCHK(c, launch_scan_vec(c->stream, d, cut, false, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
+            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, false, pl, c->scan_part, d_M, nullptr, nullptr));
+            HIPCHK(c, launch_scan_vec(c->stream, d, cut, true, pl, d_coeff + p0 * B, d_off + p0, d_M, c->scan_part));
+            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, true, pl, c->scan_part, d_M, d_lognum + p0 * nbins, nullptr));
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(lognum, d_lognum, (size_t)L * nbins * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_bins,
+                         double* cross, double* diag, double* wsum) {
+    int rc = scan_open(c, "mbar_scan_bin_gram_w", f && coeff && f_bins && diag && wsum && L >= 1, true);
+    if (rc) return rc;
+    const int64_t B = c->scan_B, K = c->K, nbins = c->scanbin_nbins;
+    const size_t LB = (size_t)L * (size_t)nbins;
+    bool done = false;
+    ScanData d;
+    rc = scan_begin(c, f, L, coeff, offset, f_bins, LB, {{cross, (size_t)K * LB}, {diag, LB}, {wsum, LB}}, &done, &d);
+    if (rc || done) return rc;
+    HIPCHK(c, c->scanbin_fbins.grow(LB));
+    HIPCHK(c, hipMemcpyAsync(c->scanbin_fbins, f_bins, LB * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ScanBinned cut = binned_of(c, true);
+    const int nb = cross ? scan_nb_for(K) : 0;
+    // groups of whole bins whose records fit the budget ("scan_part_bytes"; a single bin is never split): one sweep per group, and
+    // a (member, bin)'s sums do not depend on the cut
+    const int64_t rec = scan_record_doubles(nb, 1, SCANBIN_NV);
+    const int64_t max_chunks = std::max<int64_t>(c->opt_scan_part_bytes / (rec * (int64_t)sizeof(double)), 1);
+    const std::vector<int64_t>& c0 = c->scanbin_c0_b_host;
+    std::vector<int64_t> group{0};  // first bin of every group, then nbins
+    for (int64_t i = 1; i < nbins; ++i)
+        if (c0[(size_t)i + 1] - c0[(size_t)group.back()] > max_chunks) group.push_back(i);
+    group.push_back(nbins);
+    int64_t worst = 1;
+    for (size_t g = 0; g + 1 < group.size(); ++g) worst = std::max(worst, c0[(size_t)group[g + 1]] - c0[(size_t)group[g]]);
+    HIPCHK(c, c->scan_part.grow((size_t)worst * (size_t)rec));
+    HIPCHK(c, c->scan_out.grow(LB * SCANBIN_NV + (cross ? (size_t)K * LB : 0)));
+    double* d_vec = c->scan_out;
+    double* d_cross = d_vec + LB * SCANBIN_NV;
+    const double* d_coeff = c->scan_in;
+    const double* d_off = d_coeff + L * B;
+    const int64_t pw = 64 * scan_mb(1);
+    HIPCHK(c, hipMemcpyAsync(d_f(c), f, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedTimer timer(c, MBAR_TIMER_OTHER);
+        for (size_t g = 0; g + 1 < group.size(); ++g) {
+            cut.b0_ = group[g], cut.b1_ = group[g + 1];
+            cut.c0_ = c0[(size_t)cut.b0_], cut.c1_ = c0[(size_t)cut.b1_];
+            for (int64_t p0 = 0; p0 < L; p0 += pw) {  // the group's samples of the resident matrix are read once per panel
+                HIPCHK(c, launch_scan_cross(c->stream, d, cut, nb, c->u, c->ld, K, d_f(c), L, p0, d_coeff, d_off, c->scanbin_fbins.p,
+                                            c->scan_part));
+                HIPCHK(c, launch_scan_cross_merge(c->stream, d, cut, nb, K, L, p0, c->scan_part, d_cross, d_vec));
+            }
+        }
+    }
+    std::vector<double> vec(LB * SCANBIN_NV);
+    HIPCHK(c, hipMemcpyAsync(vec.data(), d_vec, vec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (cross) HIPCHK(c, hipMemcpyAsync(cross, d_cross, (size_t)K * LB * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    rc = sync_stream(c);
+    if (rc) return rc;
+    for (size_t x = 0; x < LB; ++x) {
+        wsum[x] = vec[x * SCANBIN_NV];
+        diag[x] = vec[x * SCANBIN_NV + 1];
     }
     return MBAR_OK;
 }

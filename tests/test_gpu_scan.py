@@ -222,8 +222,8 @@ def matrix_case(K, Q):
 
 @pytest.mark.parametrize("shape", instantiation_cases(), ids=case_id)
 def test_every_instantiation_against_long_double_standin(shape):
-    """k_scan_cross<NB, J> for every NB in {1, 2, 4, 8} and J in {1 .. 4} at both ends of the state counts NB serves, and <0, J> through
-    cross=False, at the shapes of ``instantiation_cases`` (a full panel and a panel of 17 members; the sample, tile and chunk edges
+    """k_scan_cross<NB, J, ScanWhole> for every NB in {1, 2, 4, 8} and J in {1 .. 4} at both ends of the state counts NB serves, and
+    <0, J> through cross=False, at the shapes of ``instantiation_cases`` (a full panel and a panel of 17 members; the sample, tile and chunk edges
     with more than one block), with multiplicities 0 .. 3, +inf entries, an unsampled state, and the reference member the last one
     of the last panel.  tests/test_scan_host.py shows on the CPU that these cases suit the stand-in."""
     K, N, L, B, Q = shape

@@ -1,10 +1,10 @@
 """Histogram free energy surfaces along a scan on the MI355X (``mbar_ctx_set_scan_bins`` / ``mbar_scan_bin_lognum`` /
-``mbar_scan_bin_gram_w``, mbar_k_scanbin.hip; ``MBAR.compute_scan_fes``): the two passes against the long-double stand-in
-(tests/scan_fes_standin.py; tests/test_scan_fes_host.py shows on the CPU that the cases suit it), every instantiation of the pass-B
-kernel, the order contract bit for bit (the other members, the other bins, the bin's number, the record budget and the slabs of the
-wrapper change nothing; one bin that holds every sample gives the bits of the scan passes), ``compute_scan_fes`` against the loop
-of ``histogram_fes_labels`` on the device and against the reference's fixture, the bootstrap replicates, and the passes as
-consumers of the context's state.
+``mbar_scan_bin_gram_w``, the binned cut of mbar_k_scan.hip; ``MBAR.compute_scan_fes``): the two passes against the long-double
+stand-in (tests/scan_fes_standin.py; tests/test_scan_fes_host.py shows on the CPU that the cases suit it), every instantiation of
+the pass-B kernel, the order contract bit for bit (the other members, the other bins, the bin's number, the record budget and the
+slabs of the wrapper change nothing; one bin that holds every sample gives the bits of the scan passes), ``compute_scan_fes``
+against the loop of ``histogram_fes_labels`` on the device and against the reference's fixture, the bootstrap replicates, and the
+passes as consumers of the context's state.
 
 Tolerances of the passes are those of tests/test_gpu_scan.py::test_passes_against_long_double_standin: lognum and wsum 1e-11
 absolute, the products rtol 1e-10.  Shapes are (K, N, L, B, nbins)."""
@@ -73,9 +73,9 @@ def test_passes_against_long_double_standin(shape, kind, hard):
 @pytest.mark.parametrize("L", [256, 257], ids=["full-panel", "ragged-panel"])
 @pytest.mark.parametrize("K", [16, 17, 32, 33, 64, 65, 128])
 def test_every_instantiation_against_long_double_standin(K, L):
-    """k_scanbin_cross<NB> for NB in {1, 2, 4, 8} at both ends of the state counts it serves, and <0> through cross=False, with one
-    full panel of 256 members and with a second panel of one; N = 301 in 5 bins (tiles with a tail), multiplicities 0 .. 3, +inf
-    entries, an unsampled state, an emptied bin."""
+    """k_scan_cross<NB, 1, ScanBinned> for NB in {1, 2, 4, 8} at both ends of the state counts it serves, and <0> through
+    cross=False, with one full panel of 256 members and with a second panel of one; N = 301 in 5 bins (tiles with a tail),
+    multiplicities 0 .. 3, +inf entries, an unsampled state, an emptied bin."""
     B = {16: 1, 17: 2, 32: 5, 33: 8, 64: 3, 65: 2, 128: 4}[K]
     case = build_fes_case((K, 301, L, B, 5), True, "mixed")
     with device_matrix(case) as dm:
@@ -135,21 +135,37 @@ def test_pass_a_member_panels_do_not_change_a_bit():
 
 
 # ---- 4. one bin that holds every sample: the bits of the scan passes ------------------------------------------------------------
-@pytest.mark.parametrize("K", [33, 128])
-@pytest.mark.parametrize("N", [2047, 2049, 8191, 8193])
+# K = 9, 17, 33, 128: NB = 1, 2, 4, 8; N on both sides of the chunk edges of pass A (2048) and of pass B (8192), for the smaller K
+# just past each
+ONE_BIN_CASES = [(N, K) for K in (33, 128) for N in (2047, 2049, 8191, 8193)] + [(N, K) for K in (9, 17) for N in (2049, 8193)]
+
+
+@pytest.mark.parametrize("N,K", ONE_BIN_CASES)
 def test_one_bin_is_the_scan_passes_bit_for_bit(N, K):
+    """Both cuts of the samples are one kernel source (k_scan_vec<SUM, Cut>, k_scan_cross<NB, J, Cut> of mbar_k_scan.hip): with one
+    bin that holds every sample the binned cut returns the bits of the whole cut at J = 1, in every instantiation the two share --
+    NB = 1, 2, 4, 8 and, with cross=False, NB = 0, whose sums are also the bits of the calls with the cross block.  L = 70: one
+    ragged panel."""
     L = 70
     case = build_fes_case((K, N, L, 3, 1), True, "sorted")
     assert np.all(case["label"] == 0)
     with device_matrix(case) as dm:
         got = run_fes_passes(dm, case)
+        bare = run_fes_passes(dm, case, cross=False)
         lognum, mean = dm.scan_lognum(case["f"], case["coeff"], case["offset"])
         X, within, refcol, w = dm.scan_gram_w(case["f"], case["coeff"], case["offset"], -lognum, reference=0)
+        X0, within0, refcol0, w0 = dm.scan_gram_w(case["f"], case["coeff"], case["offset"], -lognum, reference=0, cross=False)
+    print("NB", scan_nb_for(K))
     assert np.all(np.isfinite(lognum)) and np.all(X > 0)
     assert bits(got["lognum"][:, 0]) == bits(lognum)
     assert bits(got["cross"][:, :, 0]) == bits(X[:, :, 0])
     assert bits(got["diag"][:, 0]) == bits(within[:, 0, 0])
     assert bits(got["wsum"][:, 0]) == bits(w)
+    # NB = 0 on both sides: across the cuts, and against the calls with the cross block
+    assert bare["cross"] is None and X0 is None
+    assert bits(bare["diag"][:, 0]) == bits(within0[:, 0, 0]) and bits(bare["wsum"][:, 0]) == bits(w0)
+    assert bits(bare["diag"]) == bits(got["diag"]) and bits(bare["wsum"]) == bits(got["wsum"])
+    assert bits(within0) == bits(within) and bits(w0) == bits(w)
 
 
 # ---- 5. compute_scan_fes against the loop of histogram_fes_labels ---------------------------------------------------------------

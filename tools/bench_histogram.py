@@ -45,6 +45,7 @@ def resident_mbar(K, N):
     m = MBAR.__new__(MBAR)  # (the attributes the histogram functions read; the matrix never exists on the host)
     m._dm, m.K, m.N, m.N_k, m.f_k, m._device = dm, K, dm.N_local, N_k, f_k, None
     m.states_with_samples = np.arange(K)
+    m.basis_bn = m.coeff_kb = m.offset_k = None  # (not an object of MBAR.from_linear: u_kn is not rebuilt from a family)
     return m, x, O_k
 
 
