@@ -1,5 +1,5 @@
 // gfx950 (CDNA4 / MI355X) kernels of the MBAR solver hot path: device-side helpers shared by the kernel translation units
-// (mbar_k_eval.hip, mbar_k_gram.hip, mbar_k_quad.hip, mbar_k_pmode.hip, mbar_k_fused.hip, mbar_k_solver.hip).
+// (mbar_k_eval.hip, mbar_k_gram.hip, mbar_k_quad.hip, mbar_k_pmode.hip, mbar_k_fused.hip, mbar_k_loop.hip, mbar_k_rows.hip).
 //
 // Data layout.  u is the (Kp x ld) row-major fp64 matrix of reduced potentials u[k][n] of this
 // rank's column shard (Kp = padded state count, ld = N rounded up to 16; padding is zero-filled and
@@ -93,6 +93,21 @@ __device__ __forceinline__ double wave_max(double x) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) x = fmax(x, __shfl_xor(x, m));
     return x;
+}
+// fixed-order sums / maxima over a workgroup of 256 threads
+__device__ __forceinline__ double block256_sum(double v, double* red /*[4]*/) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ double block256_max(double v, double* red /*[4]*/) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
 
 // exp built for instruction count (gfx950 issues one fp64 VALU op per ~5.6 cycles per SIMD and fp64 MFMA does

@@ -116,17 +116,6 @@ hipError_t launch_lse(hipStream_t s, int nb, int nf, const LaunchGeom& g,
 // enumerates (I,J) with I<=J in row-major order.  Off-diagonal panel pair: nbi x nbj blocks.
 // gram_part: [nwaves][nblk][256], psum_part: [nwaves][16*nb] (diag only; may be null for off-diag).
 LaunchGeom gram_geometry(int tile_rows, bool diag, int num_cu, int64_t ntiles, int64_t grid_override);
-hipError_t launch_row_sub(hipStream_t s, double* row, const double* v, int64_t n);  // row[i] -= v[i]
-hipError_t launch_rows_sub(hipStream_t s, double* dst, const double* src, int64_t ld, int64_t nrows, const double* v, int64_t n);
-hipError_t launch_rows_obs(hipStream_t s, double* dst, const double* obs, const double* state, int64_t ld, int64_t nrows, int64_t n,
-                           double* part, double* shift_out, bool have_min = false);
-hipError_t launch_rows_rsub(hipStream_t s, double* dst, const double* src, int64_t ld, int64_t nrows, int64_t n);
-// rows r < nrows of base (pitch ld, n valid entries): row <- log(row - shift_r), shift_r = min_r - |4 eps min_r| -> shift_out[r]
-// (device); part: scratch of 256 * nrows doubles
-hipError_t launch_rows_logshift(hipStream_t s, double* base, int64_t ld, int64_t nrows, int64_t n, double* part, double* shift_out);
-// rows[i][k] = label[k] == i ? v[k] : +inf,  i < nrows (row pitch ld)
-hipError_t launch_fill_masked_rows(hipStream_t s, double* rows, int64_t ld, int64_t n, int64_t nrows, const double* v,
-                                   const int* label);
 hipError_t launch_gram_diag(hipStream_t s, int nb, const LaunchGeom& g, const double* u,
                             int64_t ld, int64_t N, const double* anum /*indexed from row0*/,
                             const double* logden, int64_t row0, double* gram_part, double* psum_part,
@@ -164,33 +153,8 @@ hipError_t launch_lse_generic(hipStream_t s, int num_cu, const double* u, int64_
 hipError_t launch_colsum_generic(hipStream_t s, int num_cu, const double* u, int64_t ld, int64_t N, int64_t K,
                                  const double* anum, const double* cw, const double* logden,
                                  double* psum_part /*[blocks_x][K]*/, int* blocks_out);
-// out[n] = logden[n] - alpha ln cw[n] (+inf where cw = 0)
-hipError_t launch_shift_logden(hipStream_t s, const double* logden, const double* cw, double alpha, int64_t N,
-                               double* out, const LoopCtl& lc = LoopCtl());
 
-// ---- reductions / small kernels ----------------------------------------------------------------
-// out[i] = sum_p part[p*count + i]; scratch must hold ceil(nparts/32)*count doubles.
-hipError_t launch_reduce(hipStream_t s, const double* part, int64_t nparts, int64_t count,
-                         double* scratch, double* out);
-// robust per-state log-sum-exp over n of (anum_k - u_kn - logden_n): partial (max,sum) per chunk
-hipError_t launch_lognum(hipStream_t s, const double* u, int64_t ld, int64_t N, int64_t K,
-                         const double* anum, const double* logden,
-                         double* pmax /*[K][nchunks]*/, double* psum /*[K][nchunks]*/, int64_t nchunks);
-int64_t lognum_chunks(int64_t N, int64_t K);
-hipError_t launch_lognum_merge(hipStream_t s, const double* pmax, const double* psum, int64_t K,
-                               int64_t nchunks, double* out_max /*[K]*/, double* out_sum /*[K]*/);
-hipError_t launch_logw(hipStream_t s, const double* u, int64_t ld, int64_t N, int64_t K,
-                       const double* f, const double* logden, double* out, int64_t ld_out, bool exponentiate = false);
-// flags |= 1 if any u[k][n] is NaN, |= 2 if any is -inf (k < K, n < N)
-hipError_t launch_check_u(hipStream_t s, const double* u, int64_t ld, int64_t N, int64_t K, int* flags);
-hipError_t launch_generate_harmonic(hipStream_t s, double* u, int64_t ld, int64_t N, int64_t K,
-                                    uint64_t seed, const double* O_k, const double* K_k,
-                                    const int64_t* cumN /*[K+1]*/, int64_t n_global0);
-// device-resident SCI step: sums `nparts` partial psum records (row pitch `rows`), then
-// f' = f - log(psum/N_k) on sampled states, gauge, aden' = f' + ln N_k; f' also goes to f_hist
-hipError_t launch_sci_update(hipStream_t s, const double* part, int64_t nparts, int64_t rows, const double* Nk,
-                             const double* lnNk, int64_t K, int64_t Kp, int first_state, double tol, double* f,
-                             double* aden, double* f_hist, double* delta_out);
+// ---- few states: a whole self-consistent iteration in one launch (mbar_k_eval.hip) ------------------------------------------
 // Few states (K <= 32, single rank): update + sweep of ONE self-consistent iteration in one launch (k_sci_small).  Double
 // buffers by parity p of the iteration: the launch reads rec[p ^ 1] (nrec records of 16 nb doubles: the per-state sums of the
 // previous sweep, one per workgroup of the SAME geometry) and state[p ^ 1] (the previous f), writes rec[p], state[p], the
@@ -214,20 +178,66 @@ struct SciLoopArgs {
 };
 hipError_t launch_sci_small(hipStream_t s, int nb, const LaunchGeom& g, const double* u, int64_t ld, int64_t N, const double* cw,
                             const SciLoopArgs& q);
-// (*overflow, zeroed by the caller, is set when a weight is not finite)
-// cw[sample] += 1 for every draw of the replicate whose sample lies in this shard [n0, n0 + N) (cw zeroed by the caller; the adds are
-// of exact small integers: order-independent).  cum: [K + 1] positions of the states' runs; order: sample index of a position, or NULL
-hipError_t launch_bootstrap_counts(hipStream_t s, uint64_t seed, int64_t replicate, const int64_t* cum, int64_t K, int64_t total,
-                                   const int64_t* order, int64_t n0, int64_t N, double* cw);
-hipError_t launch_weights_from_log(hipStream_t s, const double* v, double p, int64_t n, double* cw, double* cwsq, int* overflow);
+
+// ---- mbar_k_rows.hip: passes over N-vectors, matrix rows and partial records -------------------------------------------------
+// out[i] = sum_p part[p*count + i]; scratch must hold ceil(nparts/32)*count doubles.
+hipError_t launch_reduce(hipStream_t s, const double* part, int64_t nparts, int64_t count,
+                         double* scratch, double* out);
 hipError_t launch_reduce_level1(hipStream_t s, const double* part, int64_t nparts, int64_t count, double* out,
                                 int64_t* nchunks);
-hipError_t launch_mfma_peak(hipStream_t s, int blocks, int iters, double* sink);
 // Two partial-record arrays with the same number of records reduced by one pair of launches (same summation order as
 // launch_reduce on each): outA[i] = sum_p partA[p*countA + i], outB likewise.  scratch: ceil(nparts/32)*(countA+countB).
 hipError_t launch_reduce2(hipStream_t s, const double* partA, int64_t countA, const double* partB, int64_t countB,
                           int64_t nparts, double* scratch, double* outA, double* outB);
+// robust per-state log-sum-exp over n of (anum_k - u_kn - logden_n): partial (max,sum) per chunk
+hipError_t launch_lognum(hipStream_t s, const double* u, int64_t ld, int64_t N, int64_t K,
+                         const double* anum, const double* logden,
+                         double* pmax /*[K][nchunks]*/, double* psum /*[K][nchunks]*/, int64_t nchunks);
+int64_t lognum_chunks(int64_t N, int64_t K);
+hipError_t launch_lognum_merge(hipStream_t s, const double* pmax, const double* psum, int64_t K,
+                               int64_t nchunks, double* out_max /*[K]*/, double* out_sum /*[K]*/);
+hipError_t launch_logw(hipStream_t s, const double* u, int64_t ld, int64_t N, int64_t K,
+                       const double* f, const double* logden, double* out, int64_t ld_out, bool exponentiate = false);
+// flags |= 1 if any u[k][n] is NaN, |= 2 if any is -inf (k < K, n < N)
+hipError_t launch_check_u(hipStream_t s, const double* u, int64_t ld, int64_t N, int64_t K, int* flags);
+// out[n] = logden[n] - alpha ln cw[n] (+inf where cw = 0)
+hipError_t launch_shift_logden(hipStream_t s, const double* logden, const double* cw, double alpha, int64_t N,
+                               double* out, const LoopCtl& lc = LoopCtl());
+hipError_t launch_fill(hipStream_t s, double* v, double value, int64_t n);
+// zero fill at HBM write speed (hipMemsetAsync below 64 KB or for unaligned ranges)
+hipError_t launch_zero(hipStream_t s, void* p, size_t bytes);
+hipError_t launch_sqrt_vec(hipStream_t s, double* dst, const double* src, int64_t n);  // dst[i] = sqrt(src[i])
+// (*overflow, zeroed by the caller, is set when a weight is not finite)
+hipError_t launch_weights_from_log(hipStream_t s, const double* v, double p, int64_t n, double* cw, double* cwsq, int* overflow);
+hipError_t launch_generate_harmonic(hipStream_t s, double* u, int64_t ld, int64_t N, int64_t K,
+                                    uint64_t seed, const double* O_k, const double* K_k,
+                                    const int64_t* cumN /*[K+1]*/, int64_t n_global0);
+// cw[sample] += 1 for every draw of the replicate whose sample lies in this shard [n0, n0 + N) (cw zeroed by the caller; the adds are
+// of exact small integers: order-independent).  cum: [K + 1] positions of the states' runs; order: sample index of a position, or NULL
+hipError_t launch_bootstrap_counts(hipStream_t s, uint64_t seed, int64_t replicate, const int64_t* cum, int64_t K, int64_t total,
+                                   const int64_t* order, int64_t n0, int64_t N, double* cw);
+hipError_t launch_mfma_peak(hipStream_t s, int blocks, int iters, double* sink);
+// 129 .. 256 states: P = exp(aden_k - u_kn - logden_n) (rows = padded state count; padding and sub-normal entries: 0)
+hipError_t launch_make_p(hipStream_t s, int num_cu, const double* u, int64_t ld, int64_t N, int64_t rows, const double* aden,
+                         const double* logden, double* P);
+// rows[i][k] = label[k] == i ? v[k] : +inf,  i < nrows (row pitch ld)
+hipError_t launch_fill_masked_rows(hipStream_t s, double* rows, int64_t ld, int64_t n, int64_t nrows, const double* v,
+                                   const int* label);
+hipError_t launch_row_sub(hipStream_t s, double* row, const double* v, int64_t n);  // row[i] -= v[i]
+hipError_t launch_rows_sub(hipStream_t s, double* dst, const double* src, int64_t ld, int64_t nrows, const double* v, int64_t n);
+hipError_t launch_rows_rsub(hipStream_t s, double* dst, const double* src, int64_t ld, int64_t nrows, int64_t n);
+// rows r < nrows of base (pitch ld, n valid entries): row <- log(row - shift_r), shift_r = min_r - |4 eps min_r| -> shift_out[r]
+// (device); part: scratch of 256 * nrows doubles
+hipError_t launch_rows_logshift(hipStream_t s, double* base, int64_t ld, int64_t nrows, int64_t n, double* part, double* shift_out);
+hipError_t launch_rows_obs(hipStream_t s, double* dst, const double* obs, const double* state, int64_t ld, int64_t nrows, int64_t n,
+                           double* part, double* shift_out, bool have_min = false);
 
+// ---- mbar_k_loop.hip: the K x K work of the solver loops --------------------------------------------------------------------
+// device-resident SCI step: sums `nparts` partial psum records (row pitch `rows`), then
+// f' = f - log(psum/N_k) on sampled states, gauge, aden' = f' + ln N_k; f' also goes to f_hist
+hipError_t launch_sci_update(hipStream_t s, const double* part, int64_t nparts, int64_t rows, const double* Nk,
+                             const double* lnNk, int64_t K, int64_t Kp, int first_state, double tol, double* f,
+                             double* aden, double* f_hist, double* delta_out);
 // In-process all-reduce (several contexts of one process on one device): out[i] = op over the ranks' buffers, in rank order
 struct LoopSrc {
     const double* p[8];
@@ -235,7 +245,7 @@ struct LoopSrc {
 };
 hipError_t launch_loop_reduce(hipStream_t s, const LoopSrc& src, int64_t count, int op /*0 sum, 1 max*/, double* out);
 
-// ---- device-resident adaptive iteration (mbar_solvers.py:575-640 without the host in the loop) --------------------
+// Device-resident adaptive iteration (mbar_solvers.py:575-640 without the host in the loop).
 // State of one solve, all in device memory.  Up to 128 padded states (one diagonal Gram panel).
 struct AdaptArgs {
     const double* gram_red;  // reduced Gram blocks of the panel, block b = (I, J), I <= J, row-major 16 x 16 each
@@ -272,6 +282,19 @@ struct AdaptArgs {
     // K x K Newton solve up to 128 states: 1 = blocked LDL^T on the matrix cores (newton_body_ldlt), 0 = register Gauss-Jordan
     int newton_ldlt;
 };
+// K x K Newton system (gauge-fixed, Gauss-Jordan in registers, one workgroup) + both candidates + sweep inputs
+hipError_t launch_newton(hipStream_t s, const AdaptArgs& a);
+// ... for 128 .. 255 unknowns: blocked Cholesky in device memory (a pair of small kernels per block column of 32);
+// work: NEWTON_CHOL_WORK doubles
+constexpr size_t NEWTON_CHOL_WORK = (size_t)256 * 256 + 8;
+hipError_t launch_newton_chol(hipStream_t s, const AdaptArgs& a, double* work);
+// gradient norms of both candidates, choice (mbar_solvers.py:607), convergence test (:627-640), next Gram operand
+hipError_t launch_select(hipStream_t s, const AdaptArgs& a);
+// selection of one iteration + Newton solve of the next in one launch (fused loop, up to 127 unknowns)
+hipError_t launch_select_newton(hipStream_t s, const AdaptArgs& a);
+// fused loop paused by k_select (CTL_DONE = 3): clear the pause and the Gram request (in front of the Gram sweep)
+hipError_t launch_ctl_resume(hipStream_t s, int* ctl);
+
 // ---- P mode: resident probability matrix P = exp(a0 - u - logden(a0)) (see k_psweep) ----------------------------------
 LaunchGeom psweep_geometry(int nb, int num_cu, int64_t ntiles, int64_t grid_override);
 // cmul: [nf][16 nb] multipliers exp(a - a0); rinv0 = base of the three slot vectors when lc.ctl is set
@@ -296,30 +319,10 @@ hipError_t launch_build_sweep(hipStream_t s, int nb, const LaunchGeom& g, const 
 LaunchGeom build_gram_geometry(int nb, int num_cu, int64_t ntiles, int64_t grid_override);
 hipError_t launch_build_gram(hipStream_t s, int nb, const LaunchGeom& g, const double* u, int64_t ld, int64_t N,
                              const double* aden, const double* wsq, bool general, double* P, double* rinv_slot, double* gram_part);
-
-// 129 .. 256 states: P = exp(aden_k - u_kn - logden_n) (rows = padded state count; padding and sub-normal entries: 0)
-hipError_t launch_make_p(hipStream_t s, int num_cu, const double* u, int64_t ld, int64_t N, int64_t rows, const double* aden,
-                         const double* logden, double* P);
-hipError_t launch_fill(hipStream_t s, double* v, double value, int64_t n);
-// zero fill at HBM write speed (hipMemsetAsync below 64 KB or for unaligned ranges)
-hipError_t launch_zero(hipStream_t s, void* p, size_t bytes);
-hipError_t launch_sqrt_vec(hipStream_t s, double* dst, const double* src, int64_t n);  // dst[i] = sqrt(src[i])
 hipError_t launch_rinv_from_logden(hipStream_t s, const double* ld0, const double* ldv, const double* cw, bool weighted, int64_t N,
                                    double* out);
 hipError_t launch_rinv_weighted(hipStream_t s, const double* rinv, const double* cw, int64_t N, double* out,
                                 const LoopCtl& lc = LoopCtl());
-// K x K Newton system (gauge-fixed, Gauss-Jordan in registers, one workgroup) + both candidates + sweep inputs
-hipError_t launch_newton(hipStream_t s, const AdaptArgs& a);
-// ... for 128 .. 255 unknowns: blocked Cholesky in device memory (a pair of small kernels per block column of 32);
-// work: NEWTON_CHOL_WORK doubles
-constexpr size_t NEWTON_CHOL_WORK = (size_t)256 * 256 + 8;
-hipError_t launch_newton_chol(hipStream_t s, const AdaptArgs& a, double* work);
-// gradient norms of both candidates, choice (mbar_solvers.py:607), convergence test (:627-640), next Gram operand
-hipError_t launch_select(hipStream_t s, const AdaptArgs& a);
-// selection of one iteration + Newton solve of the next in one launch (fused loop, up to 127 unknowns)
-hipError_t launch_select_newton(hipStream_t s, const AdaptArgs& a);
-// fused loop paused by k_select (CTL_DONE = 3): clear the pause and the Gram request (in front of the Gram sweep)
-hipError_t launch_ctl_resume(hipStream_t s, int* ctl);
 
 
 // ---- weighted kernel-density sum (mbar_k_kde.hip; C ABI in mbar_kde.cpp) ---------------------------------------------------

@@ -1,6 +1,6 @@
 """The lane-level numpy statement of the blocked LDL^T Newton solve (tools/newton_ldlt_model.py: registers as 64-vectors, the fp64
 matrix instruction as its documented layout, LDS as dictionaries) against numpy.linalg.solve -- the layout algebra of
-pymbar_amd/csrc/mbar_k_solver.hip::newton_body_ldlt (transposed accumulator storage, pivots from the last row upwards, the ride-along
+pymbar_amd/csrc/mbar_k_loop.hip::newton_body_ldlt (transposed accumulator storage, pivots from the last row upwards, the ride-along
 right-hand side in row 0, the forward substitution with x_0 = -1), checked on the CPU: state counts on both sides of the 16-state block
 boundaries, unsampled states, a gauge state that is not state 0."""
 import importlib.util

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Lane-level numpy model of the blocked LDL^T Newton solve of k_select_newton (pymbar_amd/csrc/mbar_k_solver.hip,
+"""Lane-level numpy model of the blocked LDL^T Newton solve of k_select_newton (pymbar_amd/csrc/mbar_k_loop.hip,
 newton_body_ldlt): every "register" is a 64-vector, the matrix instruction is its documented layout, LDS is a dict.  It pins the
 layout algebra of the kernel on the CPU (no GPU in the build container) and is the executable statement of its algorithm:
 

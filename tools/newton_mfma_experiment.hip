@@ -1,5 +1,5 @@
 // NOT COMPILED -- the source of a round-5 experiment, kept for the record (profiles/r5_newton_mfma_four_pivot.txt).
-// It was a device function of pymbar_amd/csrc/mbar_k_solver.hip (same includes, same helpers: gram_elem, newton_tail, recip_fast,
+// It was a device function of pymbar_amd/csrc/mbar_k_loop.hip (same includes, same helpers: gram_elem, newton_tail, recip_fast,
 // wave_max, AdaptArgs) called from k_select_newton in place of newton_body<16, 8>, parity-green on seven problems (64 .. 127
 // unknowns, unsampled states, group sizes 1 .. 4) to 3e-15 in f -- and no faster than the register version: the step is a chain
 // of dependent fp64 instructions at ~45 clocks each on a lone wave, not arithmetic.
