@@ -223,6 +223,24 @@ int mbar_ctx_fill_masked_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, const 
  * outside [0, K], a column range outside ld_host; MBAR_ERR_STATE: an extension context (mbar_ctx_create_ext).  nrows = 0: MBAR_OK. */
 int mbar_ctx_fill_linear_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
                               int64_t col0_host, const double* coeff, const double* offset);
+/* The same rows from a family with HARMONIC terms -- umbrella sampling on a periodic coordinate, u_k(n) = beta_k [E_n + kappa_k / 2
+ * wrap(chi_n - chi0_k)^2], whose minimum image depends on sample AND state and is linear in no basis:
+ *   u[row0 + r][n] = offset[r] + sum_{b < B} term_b(r, n), b ascending, from the offset:
+ *     kind[b] == 0   linear     u = fma(coeff[r][b], basis[b][n], u)
+ *     kind[b] != 0   harmonic   d = basis[b][n] - center[r][b]
+ *                               period[b] > 0:  m = rint(d * rP), d = fma(-period[b], m, d)      rP = 1.0 / period[b], rounded once
+ *                               q = d * d;  u = fma(coeff[r][b], q, u)
+ * every operation rounded once, nothing else contracted, rint to nearest even (a tie d = +-P / 2 gives the same q either way:
+ * the value is continuous there).  At most MBAR_SCAN_MAX_H terms may be harmonic; period[b] = 0: a harmonic term that is not
+ * periodic; center[nrows][B] and period[B] are read at the harmonic terms only (center NULL: allowed when no term is harmonic;
+ * period NULL: no term is periodic); kind NULL: every term linear, and the rows are the bits of mbar_ctx_fill_linear_rows.  The
+ * scan passes evaluate the same chain (mbar_ctx_set_scan_terms): a scan member with a sampled state's coeff, center and offset
+ * has that state's row to the bit.  Staging, column shard and errors as mbar_ctx_fill_linear_rows; also MBAR_ERR_ARG: more than
+ * MBAR_SCAN_MAX_H harmonic terms, a negative or non-finite period, a non-finite coefficient or centre. */
+#define MBAR_SCAN_MAX_H 4
+int mbar_ctx_fill_family_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
+                              int64_t col0_host, const double* coeff, const double* center, const double* offset, const int32_t* kind,
+                              const double* period);
 /* Fill the shard on the device with the synthetic harmonic ladder of SURVEY.md 8(d):
  * global sample n (n_global0 <= n < n_global0+N_local) belongs to the state given by the
  * cumulative N_k_global, x_n ~ Normal(O_s, K_s^-1/2) from a counter-based RNG keyed by
@@ -362,6 +380,18 @@ int mbar_ctx_set_scan(mbar_ctx* ctx, int64_t B, const double* basis, int64_t Q, 
 int mbar_scan_lognum(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, double* lognum, double* mean);
 int mbar_scan_gram_w(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan,
                      int64_t r, double* cross, double* within, double* refcol, double* wsum);
+/* Scans over a family with HARMONIC terms (a sweep of a restraint centre on a torsion): the chain of mbar_ctx_fill_family_rows.
+ *   mbar_ctx_set_scan_terms     kind[B], period[B] of the basis uploaded by mbar_ctx_set_scan (call it after that one).  kind NULL,
+ *                               or another mbar_ctx_set_scan, returns to the all-linear family.  Drops the centres.  MBAR_ERR_ARG:
+ *                               more than MBAR_SCAN_MAX_H harmonic terms, a negative or non-finite period; MBAR_ERR_STATE: no basis.
+ *   mbar_ctx_set_scan_centers   center[L][B] of the members the next scan calls take (read at the harmonic terms only), kept until
+ *                               replaced; L = 0 drops them.  MBAR_ERR_ARG: a non-finite centre.
+ * mbar_scan_lognum, mbar_scan_gram_w and the two binned passes below then run on the context's family: with a harmonic term set
+ * and the centres missing or of another L they return MBAR_ERR_STATE with a message that names the call, a non-finite
+ * coefficient is MBAR_ERR_ARG.  With every term linear they are the calls, and return the bits, they always were.  Everything
+ * said above of order, determinism and independence of the members holds for either kind. */
+int mbar_ctx_set_scan_terms(mbar_ctx* ctx, const int32_t* kind, const double* period);
+int mbar_ctx_set_scan_centers(mbar_ctx* ctx, int64_t L, const double* center);
 
 /* ---- histogram surfaces along a scan ---------------------------------------------------------
  * The histogram free energy surface of EVERY member of a scan: the bins are labels of the resident samples as in "histogram bins

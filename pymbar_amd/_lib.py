@@ -101,6 +101,8 @@ SIGNATURES = {
     "mbar_ctx_vec_logshift": (C.c_int, [_ctx, _dp, _dp]),
     "mbar_ctx_fill_masked_rows": (C.c_int, [_ctx, C.c_int64, C.c_int64, _dp, C.POINTER(C.c_int32)]),
     "mbar_ctx_fill_linear_rows": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int64, _dp, _dp]),
+    "mbar_ctx_fill_family_rows": (C.c_int, [_ctx, C.c_int64, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int64, _dp, _dp, _dp,
+                                            C.POINTER(C.c_int32), _dp]),
     "mbar_ctx_generate_harmonic": (C.c_int, [_ctx, C.c_uint64, _dp, _dp, _ip, C.c_int64]),
     "mbar_ctx_set_Nk": (C.c_int, [_ctx, _dp]),
     "mbar_ctx_set_sample_weights": (C.c_int, [_ctx, _dp]),
@@ -129,6 +131,8 @@ SIGNATURES = {
     "mbar_ctx_set_scan": (C.c_int, [_ctx, C.c_int64, _dp, C.c_int64, _dp]),
     "mbar_scan_lognum": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
     "mbar_scan_gram_w": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
+    "mbar_ctx_set_scan_terms": (C.c_int, [_ctx, C.POINTER(C.c_int32), _dp]),
+    "mbar_ctx_set_scan_centers": (C.c_int, [_ctx, C.c_int64, _dp]),
     "mbar_ctx_set_scan_bins": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int32)]),
     "mbar_scan_bins_table": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _ip]),
     "mbar_scan_bin_lognum": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp]),

@@ -997,6 +997,61 @@ int mbar_ctx_fill_linear_rows(mbar_ctx* c, int64_t row0, int64_t nrows, int64_t 
     return MBAR_OK;
 }
 
+int mbar_ctx_fill_family_rows(mbar_ctx* c, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
+                              int64_t col0_host, const double* coeff, const double* center, const double* offset, const int32_t* kind,
+                              const double* period) {
+    if (!c || !basis_host || !coeff) return fail(c, MBAR_ERR_ARG, "NULL argument");
+    if (c->ext_base) return fail(c, MBAR_ERR_STATE, "mbar_ctx_fill_family_rows: not offered on an extension context");
+    if (B < 1 || B > SCAN_MAX_B) return fail(c, MBAR_ERR_ARG, "mbar_ctx_fill_family_rows: 1 <= B <= 8 basis vectors");
+    if (!rows_in_range(c, row0, nrows)) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
+    if (col0_host < 0 || ld_host < 0 || col0_host > ld_host || c->N > ld_host - col0_host)
+        return fail(c, MBAR_ERR_ARG, "column range out of bounds");
+    FamilyTerms terms{};
+    if (kind) {
+        int rc = family_terms(c, "mbar_ctx_fill_family_rows", B, kind, period, &terms);
+        if (rc) return rc;
+    }
+    if (terms.mask && !center) return fail(c, MBAR_ERR_ARG, "mbar_ctx_fill_family_rows: a family with harmonic terms needs its centres");
+    for (int64_t x = 0; x < nrows * B; ++x)
+        if (!std::isfinite(coeff[x]) || (terms.mask && !std::isfinite(center[x])))
+            return fail(c, MBAR_ERR_ARG, "mbar_ctx_fill_family_rows: the coefficients and the centres must be finite");
+    if (nrows == 0) return MBAR_OK;
+    if (c->N == 0) {  // (a shard without columns: nothing to write)
+        matrix_touched(c);
+        return MBAR_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // staged as mbar_ctx_fill_linear_rows stages them: the basis shard at the matrix's own pitch, and coeff[nrows][B] |
+    // center[nrows][B] (zeros in a family without a harmonic term) | offset[nrows]; both blocks go back to the cache on return,
+    // after the stream has been drained
+    DevBuf<double> dbasis, dmembers;
+    HIPCHK(c, dbasis.grow((size_t)B * (size_t)c->ld));
+    HIPCHK(c, dmembers.grow((size_t)nrows * (size_t)(2 * B + 1)));
+    double* d_coeff = dmembers;
+    double* d_center = d_coeff + nrows * B;
+    double* d_off = d_center + nrows * B;
+    const size_t members = (size_t)nrows * B * sizeof(double);
+    hipError_t e = hipMemcpy2DAsync(dbasis, (size_t)c->ld * sizeof(double), basis_host + col0_host, (size_t)ld_host * sizeof(double),
+                                    (size_t)c->N * sizeof(double), (size_t)B, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_coeff, coeff, members, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = terms.mask ? hipMemcpyAsync(d_center, center, members, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(d_center, 0, members, c->stream);
+    if (e == hipSuccess)
+        e = offset ? hipMemcpyAsync(d_off, offset, (size_t)nrows * sizeof(double), hipMemcpyHostToDevice, c->stream)
+                   : hipMemsetAsync(d_off, 0, (size_t)nrows * sizeof(double), c->stream);
+    if (e == hipSuccess) {
+        ScopedTimer t(c, MBAR_TIMER_OTHER);
+        e = launch_fill_family_rows(c->stream, c->u + row0 * c->ld, c->ld, c->N, nrows, (int)B, dbasis, c->ld, d_coeff, d_center, d_off, terms);
+    }
+    matrix_touched(c);
+    // (drained on the error path too: the two blocks must not return to the cache with a copy into them in flight)
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, MBAR_ERR_HIP, std::string("mbar_ctx_fill_family_rows: ") + hipGetErrorString(e));
+    flush_timers(c);
+    return MBAR_OK;
+}
+
 int mbar_ctx_download_u(mbar_ctx* c, double* out, int64_t ld_out) {
     if (!c || !out || ld_out < c->N) return fail(c, MBAR_ERR_ARG, "bad argument");
     HIPCHK(c, hipSetDevice(c->device));

@@ -383,6 +383,12 @@ struct mbar_ctx {
     // the partial records of one panel and the merged outputs
     int64_t scan_B = 0, scan_Q = 0;
     DevBuf<double> scan_vec, scan_in, scan_part, scan_out;
+    // the kind of the family's terms (mbar_ctx_set_scan_terms; mask 0: all linear) and, for a family with harmonic terms, the
+    // centres of the next scan calls' members (mbar_ctx_set_scan_centers): [scan_center_L][SCAN_MAX_H], the harmonic terms' in
+    // ascending b (scan_center_L = 0: none)
+    mbar::FamilyTerms scan_terms{};
+    int64_t scan_center_L = 0;
+    DevBuf<double> scan_center;
     // histogram surfaces along a scan (mbar_ctx_set_scan_bins): the samples sorted by bin and the chunk tables of the two passes
     // (chunks of SCAN_VCHUNK / SCAN_CHUNK sorted positions, cut from the start of every bin); the host keeps pass B's chunk
     // offsets to group the bins under the record budget
@@ -673,6 +679,9 @@ int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_
 int passes_ready(mbar_ctx* c, const char* who, const char* family, int64_t max_K);
 // the log-denominators of f into slot 0; *nan_out: the matrix or f is unusable and every output is NaN
 int pass_logden(mbar_ctx* c, const double* f, bool* nan_out);
+// kind[B] (non-zero: harmonic) and period[B] (NULL: no term is periodic; read at the harmonic terms only) of a family as the
+// kernels take them; MBAR_ERR_ARG naming `who` for more than MBAR_SCAN_MAX_H harmonic terms or a negative or non-finite period
+int family_terms(mbar_ctx* c, const char* who, int64_t B, const int32_t* kind, const double* period, FamilyTerms* out);
 
 }  // namespace host
 }  // namespace mbar

@@ -632,6 +632,24 @@ int passes_ready(mbar_ctx* c, const char* who, const char* family, int64_t max_K
     return MBAR_OK;
 }
 
+int family_terms(mbar_ctx* c, const char* who, int64_t B, const int32_t* kind, const double* period, FamilyTerms* out) {
+    FamilyTerms t{};
+    int H = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        if (!kind[b]) continue;
+        const double P = period ? period[b] : 0.0;
+        if (!std::isfinite(P) || P < 0.0 || (P > 0.0 && !std::isfinite(1.0 / P)))
+            return fail(c, MBAR_ERR_ARG, std::string(who) + ": the period of a harmonic term must be finite and not negative (0: not periodic)");
+        if (++H > MBAR_SCAN_MAX_H)
+            return fail(c, MBAR_ERR_ARG, std::string(who) + ": at most " + std::to_string(MBAR_SCAN_MAX_H) + " terms of a family may be harmonic");
+        t.mask |= 1u << b;
+        t.period[b] = P;
+        t.rperiod[b] = P > 0.0 ? 1.0 / P : 0.0;
+    }
+    *out = t;
+    return MBAR_OK;
+}
+
 int pass_logden(mbar_ctx* c, const double* f, bool* nan_out) {
     int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;

@@ -469,27 +469,57 @@ struct ScanBinned {  // the sorted positions of the bins [b0_, b1_), whose chunk
     }
     MBAR_HD int64_t sample(int64_t p) const { return sb.perm[p]; }
 };
-// Cut = ScanWhole or ScanBinned (Q = 0) in all four.
+// The kind of the terms of a member, the second compile-time policy of the scan kernels (and, as FamilyTerms, the wave-uniform
+// argument of the family fill): u_l(n) = offset[l] + sum_b term_b, b ascending, a linear term fma(coeff, basis, u), a harmonic one
+//   dl = basis - center;  P > 0: m = rint(dl rP), dl = fma(-P, m, dl);  u = fma(coeff, dl dl, u)
+// (family_term in mbar_device.h: every operation rounded once).  ScanLinear is the family of mbar_ctx_set_scan alone: its
+// instantiations carry no trace of the other kind.
+constexpr int SCAN_MAX_H = MBAR_SCAN_MAX_H;  // harmonic terms
+struct FamilyTerms {
+    uint32_t mask = 0;           // bit b: term b is harmonic
+    double period[SCAN_MAX_B];   // P_b of a harmonic term (0: not periodic)
+    double rperiod[SCAN_MAX_B];  // 1.0 / P_b, rounded once on the host (0 where P_b = 0)
+};
+struct ScanLinear {
+    static constexpr bool harmonic = false;
+    static constexpr int mb(int J) { return scan_mb(J); }
+    MBAR_HD ScanLinear from(int64_t) const { return *this; }
+};
+struct ScanHarmonic {
+    static constexpr bool harmonic = true;
+    // narrower panels of pass B than the linear family's: with its members' centres next to the coefficients the widest
+    // instantiations (8 blocks of states) would not fit the register file at 4 (J = 1) or 2 (J = 2) blocks of members per wave
+    static constexpr int mb(int J) { return J == 1 ? 2 : 1; }
+    FamilyTerms terms;
+    const double* center;  // [L][SCAN_MAX_H] on the device: the centres of the harmonic terms in ascending b, zeros behind them
+    MBAR_HD ScanHarmonic from(int64_t l0) const {  // the family as the members [l0, L) see it
+        ScanHarmonic h = *this;
+        h.center += l0 * SCAN_MAX_H;
+        return h;
+    }
+};
+// Cut = ScanWhole or ScanBinned (Q = 0), Fam = ScanLinear or ScanHarmonic in the two sweeps; the merges know neither kind.
 // pass A over the members [0, L) of coeff / offset: per-chunk records of the maxima (sum = false: rec[chunk][L]) or of the J scaled
 // sums (rec[chunk][L][J]), and their merge in chunk order into M[bin][L] (bin-major, of this member panel), or into
 // lognum[l][bin] (row pitch nbins) and, on the whole cut, mean[L][J]
-template <class Cut>
-hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, bool sum, int64_t L, const double* coeff, const double* offset,
-                           const double* M, double* rec);
+template <class Cut, class Fam>
+hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, bool sum, int64_t L, const double* coeff,
+                           const double* offset, const double* M, double* rec);
 template <class Cut>
 hipError_t launch_scan_vec_merge(hipStream_t s, const ScanData& d, const Cut& cut, bool sum, int64_t L, const double* rec, double* M,
                                  double* lognum, double* mean);
-// pass B for the panel of members [p0, p0 + 64 scan_mb(J)) of L: part[chunk - c0][scan_record_doubles(nb, J, nv)], then
+// pass B for the panel of members [p0, p0 + 64 mb) of L, mb = Fam::mb(J): part[chunk - c0][scan_record_doubles(nb, J, nv, mb)], then
 // cross[k][l][bin][j] (K x L x nbins x J) and vec[l][bin][nv].  Whole cut: nv = scan_nv(J), vec = wsum | refcol[J] | within[i <= j],
 // fnorm = f_scan[L]; binned cut: J = 1, nv = SCANBIN_NV, vec = wsum | diag, fnorm = f_bins[L][nbins] (+inf: an empty bin of that
 // member, exact zeros).  nb = scan_nb_for(K) blocks of 16 states, or 0: no cross block.
 int scan_nb_for(int64_t K);
-int64_t scan_record_doubles(int nb, int J, int nv);
+int64_t scan_record_doubles(int nb, int J, int nv, int mb);
+template <class Cut, class Fam>
+hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, int nb, const double* u, int64_t ld, int64_t K,
+                             const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset, const double* fnorm,
+                             double* part);
 template <class Cut>
-hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, int nb, const double* u, int64_t ld, int64_t K, const double* f,
-                             int64_t L, int64_t p0, const double* coeff, const double* offset, const double* fnorm, double* part);
-template <class Cut>
-hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int64_t K, int64_t L, int64_t p0,
+hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int mb, int64_t K, int64_t L, int64_t p0,
                                    const double* part, double* cross, double* vec);
 
 // ---- rows of the resident matrix from a linear family (mbar_k_linear.hip; C ABI: mbar_ctx_fill_linear_rows in mbar_capi.cpp) --
@@ -500,6 +530,10 @@ constexpr int FILL_MAX_BLOCKS = 2048;  // grid.x; the column pairs go round it
 // scan_x.  rows (pitch ld) and basis (pitch ldb) 16-byte aligned with even pitches; coeff[nrows][B], offset[nrows] on the device
 hipError_t launch_fill_linear_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis,
                                    int64_t ldb, const double* coeff, const double* offset);
+// the same rows from a family with harmonic terms (mbar_k_family.hip; C ABI: mbar_ctx_fill_family_rows): the chain of family_term,
+// the geometry and the preconditions of launch_fill_linear_rows; center[nrows][B] on the device (read at the harmonic terms only)
+hipError_t launch_fill_family_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis,
+                                   int64_t ldb, const double* coeff, const double* center, const double* offset, const FamilyTerms& terms);
 
 // ---- lagged fluctuation sums of a timeseries (mbar_k_acf.hip; C ABI in mbar_acf.cpp) ----------------------------------------
 constexpr int ACF_WG = 256;                 // threads per workgroup

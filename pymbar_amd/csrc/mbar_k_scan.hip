@@ -37,6 +37,15 @@
 // compiler, "wsum += c_n b_ln" became one fma at every unrolled site of k_scan_cross<0, J> but only at some of the sites of
 // <NB > 0, J> (a rounded product and an addition at the others), so that cross = NULL changed wsum by an ulp wherever a
 // multiplicity c_n makes c_n b_ln inexact.
+//
+// The family.  The two sweeps are also written once for the kind of the members' terms, a second policy next to the cut (Fam =
+// ScanLinear, ScanHarmonic: mbar_internal.h): u_l is the chain of family_term (mbar_device.h) -- the function the fill kernels write
+// the resident rows with -- and a harmonic term fma(coeff, w(basis - center)^2, u) with its minimum image w replaces the linear fma
+// where the wave-uniform mask says so (mbar_ctx_set_scan_terms).  The harmonic policy keeps the centres of
+// its at most SCAN_MAX_H harmonic terms per member in registers next to the coefficients, and therefore narrower panels of pass B
+// (ScanHarmonic::mb: at the linear family's widths the instantiations of 8 blocks of states spilled); under ScanLinear every trace
+// of them is compiled out, the kernels take no family argument, and the sweeps are the operations, in the order, this file had
+// before the policy existed.  The merges know neither kind (the cross merge is told the panel width).
 #include "mbar_device.h"
 
 #pragma clang fp contract(off)
@@ -56,10 +65,13 @@ __device__ __forceinline__ void scan_neumaier(double& s, double& e, double v) {
 
 // One wave per (chunk, 64 members).  SUM = false: rec[chunk][l] = max of x_ln over the chunk's samples with c_n > 0; SUM = true:
 // rec[(chunk L + l) J + j] = sum c_n exp(x_ln - M[bin][l]) t_jn.
-template <bool SUM, class Cut>
+// (FamArg: nothing under ScanLinear, whose kernels keep the argument block -- and with it the instruction stream -- they had before
+// the family policy existed; the ScanHarmonic itself under ScanHarmonic)
+template <bool SUM, class Cut, class Fam, class... FamArg>
 __global__ void __launch_bounds__(SV_THREADS)
 k_scan_vec(ScanData d, Cut cut, int64_t L, const double* __restrict__ coeff, const double* __restrict__ offset,
-           const double* __restrict__ M, double* __restrict__ rec) {
+           const double* __restrict__ M, double* __restrict__ rec, FamArg... fam_arg) {
+    const Fam fam{fam_arg...};
     constexpr int MAX_Q = Cut::binned ? 0 : SCAN_MAX_Q;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (SUM) {
@@ -79,6 +91,8 @@ k_scan_vec(ScanData d, Cut cut, int64_t L, const double* __restrict__ coeff, con
 #pragma unroll
     for (int b = 0; b < SCAN_MAX_B; ++b) cf[b] = (live && b < d.B) ? coeff[l * d.B + b] : 0.0;
     const double off = live ? offset[l] : 0.0;
+    double cen[SCAN_MAX_H];
+    family_load_centers(fam, live, l, cen);
     const double Ml = (SUM && live) ? M[bin * L + l] : 0.0;
     double acc[1 + MAX_Q];
     acc[0] = SUM ? 0.0 : -INFINITY;
@@ -88,7 +102,7 @@ k_scan_vec(ScanData d, Cut cut, int64_t L, const double* __restrict__ coeff, con
         const int64_t n = cut.sample(p);
         const double cn = d.cw ? d.cw[n] : 1.0;
         if (!(cn > 0.0)) continue;
-        const double x = scan_x(d, cf, off, n);
+        const double x = scan_x(d, fam, cf, cen, off, n);
         if (!SUM) {
             acc[0] = fmax(acc[0], x);
         } else {
@@ -152,21 +166,22 @@ k_scan_vec_merge(ScanData d, Cut cut, int64_t L, const double* __restrict__ rec,
 }
 
 // ---- pass B --------------------------------------------------------------------------------------------------------------------
-// Record of one workgroup (one chunk of SCAN_CHUNK positions, panel of 64 MB members), MB = scan_mb(J), NCB = MB J column blocks
+// Record of one workgroup (one chunk of SCAN_CHUNK positions, panel of 64 MB members), MB = Fam::mb(J), NCB = MB J column blocks
 // per wave:
 //   cross part  [wave][I < NB][cb < NCB][r < 4][lane]   the MFMA accumulators as they are: element (state 16 I + (lane >> 4) + 4 r,
 //                                                       member block mb = cb / J, column lane & 15, observable j = cb % J)
 //   vec part    [pm < 64 MB][NV]                        whole cut: wsum | refcol[J] | within[i <= j], NV = scan_nv(J)
 //                                                       binned cut: wsum | diag, NV = SCANBIN_NV
 // Member pm of the panel sits in block pm / 16 = mb * 4 + wave (the blocks go round the waves, so a short panel keeps all four busy).
-template <int NB, int J, class Cut>
+template <int NB, int J, class Cut, class Fam, class... FamArg>
 __global__ void __launch_bounds__(256)
 k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int64_t K, const double* __restrict__ f, int64_t L, int64_t p0,
              const double* __restrict__ coeff, const double* __restrict__ offset, const double* __restrict__ fnorm,
-             double* __restrict__ part) {
+             double* __restrict__ part, FamArg... fam_arg) {
+    const Fam fam{fam_arg...};
     constexpr bool REF = !Cut::binned;  // the reference member
     static_assert(REF || J == 1, "the binned cut takes no observables");
-    constexpr int MB = scan_mb(J), NCB = MB * J, NV = REF ? scan_nv(J) : SCANBIN_NV, Q = J - 1;
+    constexpr int MB = Fam::mb(J), NCB = MB * J, NV = REF ? scan_nv(J) : SCANBIN_NV, Q = J - 1;
     constexpr int VW = REF ? 1 + J : 1;  // where within starts in the vec record
     constexpr int SVB = REF ? 48 : 32;   // where the basis rows start in sv
     constexpr int W_DOUBLES = NB * 16 * SCAN_PITCH;
@@ -188,6 +203,7 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
     mine = __builtin_amdgcn_readfirstlane(mine);
 
     double cf[MB][SCAN_MAX_B], off[MB], fs[MB];
+    double cen[Fam::harmonic ? MB : 1][SCAN_MAX_H];  // (the harmonic family alone keeps its members' centres)
     bool mlive[MB];
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
@@ -197,6 +213,7 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
 #pragma unroll
         for (int b = 0; b < SCAN_MAX_B; ++b) cf[mb][b] = (mlive[mb] && b < d.B) ? coeff[l * d.B + b] : 0.0;
         off[mb] = mlive[mb] ? offset[l] : 0.0;
+        if constexpr (Fam::harmonic) family_load_centers(fam, mlive[mb], l, cen[mb]);
         fs[mb] = mlive[mb] ? fnorm[l * cut.nbins() + bin] : 0.0;
         if constexpr (Cut::binned) {
             if (fs[mb] == INFINITY) {  // an empty bin of this member: exact zeros
@@ -259,10 +276,11 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
                 if constexpr (REF) {
                     double br = 0.0;
                     if (slive) {
-                        double ur = offr;
+                        double ur = offr, cenr[SCAN_MAX_H];  // (its centres are read per tile: sixteen lanes, no registers held)
+                        family_load_centers(fam, true, cut.ref, cenr);
 #pragma unroll
                         for (int b = 0; b < SCAN_MAX_B; ++b)
-                            if (b < d.B) ur = fma(cr[b], d.basis[(int64_t)b * d.ldv + n], ur);
+                            if (b < d.B) ur = family_term(fam, b, ur, cr[b], d.basis[(int64_t)b * d.ldv + n], family_center(fam, b, cenr));
                         br = scan_exp(fsr + (-ur - lden));
                     }
                     sv[32 + fs_s] = br;
@@ -298,7 +316,7 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
                         double uu = off[mb];
 #pragma unroll
                         for (int b = 0; b < SCAN_MAX_B; ++b)
-                            if (b < d.B) uu = fma(cf[mb][b], bas[b], uu);
+                            if (b < d.B) uu = family_term(fam, b, uu, cf[mb][b], bas[b], family_center(fam, b, cen[Fam::harmonic ? mb : 0]));
                         double bv = scan_exp(fs[mb] + (-uu - lden));
                         if (!(cn > 0.0) || !mlive[mb]) bv = 0.0;
                         const double cb = cn * bv;
@@ -354,9 +372,9 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
 template <class Cut>
 __global__ void __launch_bounds__(SV_THREADS)
 k_scan_cross_merge(ScanData d, Cut cut, int NB, int64_t K, int64_t L, int64_t p0, int64_t pl, const double* __restrict__ part,
-                   double* __restrict__ cross, double* __restrict__ vec) {
+                   double* __restrict__ cross, double* __restrict__ vec, int MB) {
     const int J = Cut::binned ? 1 : 1 + d.Q;
-    const int MB = scan_mb(J), NCB = MB * J, NV = Cut::binned ? SCANBIN_NV : scan_nv(J);
+    const int NCB = MB * J, NV = Cut::binned ? SCANBIN_NV : scan_nv(J);
     const int64_t cross_doubles = (int64_t)4 * NB * NCB * 256, stride = cross_doubles + (int64_t)64 * MB * NV;
     const int64_t nbg = cut.b1() - cut.b0(), ncross = NB > 0 ? nbg * pl * J * K : 0;
     int64_t x = (int64_t)blockIdx.x * SV_THREADS + threadIdx.x;
@@ -386,16 +404,21 @@ k_scan_cross_merge(ScanData d, Cut cut, int NB, int64_t K, int64_t L, int64_t p0
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
-template <class Cut>
-hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, bool sum, int64_t L, const double* coeff, const double* offset,
-                           const double* M, double* rec) {
+template <class Cut, class Fam>
+hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, bool sum, int64_t L, const double* coeff,
+                           const double* offset, const double* M, double* rec) {
     const int64_t nchunks = cut.c1(d.N, SCAN_VCHUNK) - cut.c0();
     if (L < 1 || nchunks < 1) return hipSuccess;
     const int64_t gx = (nchunks + SV_THREADS / 64 - 1) / (SV_THREADS / 64);
     const dim3 grid((unsigned)gx, (unsigned)((L + 63) / 64));
     if (gx > 0x7fffffff || grid.y > 65535u) return hipErrorInvalidValue;
-    if (sum) hipLaunchKernelGGL((k_scan_vec<true, Cut>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec);
-    else hipLaunchKernelGGL((k_scan_vec<false, Cut>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec);
+    if constexpr (Fam::harmonic) {
+        if (sum) hipLaunchKernelGGL((k_scan_vec<true, Cut, Fam, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec, fam);
+        else hipLaunchKernelGGL((k_scan_vec<false, Cut, Fam, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec, fam);
+    } else {
+        if (sum) hipLaunchKernelGGL((k_scan_vec<true, Cut, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec);
+        else hipLaunchKernelGGL((k_scan_vec<false, Cut, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec);
+    }
     return hipGetLastError();
 }
 
@@ -417,21 +440,26 @@ int scan_nb_for(int64_t K) {  // blocks of 16 states the cross kernel is instant
     return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
 }
 
-int64_t scan_record_doubles(int nb, int J, int nv) {
-    const int MB = scan_mb(J);
+int64_t scan_record_doubles(int nb, int J, int nv, int MB) {
     return (int64_t)4 * nb * MB * J * 256 + (int64_t)64 * MB * nv;
 }
 
 // the ladder over J: the whole cut is instantiated for J = 1 .. 4, the binned cut for J = 1
-template <int NB, class Cut>
-static hipError_t launch_scan_cross_nb(hipStream_t s, const ScanData& d, const Cut& cut, dim3 grid, size_t lds, const double* u, int64_t ld,
+template <int NB, class Cut, class Fam>
+static hipError_t launch_scan_cross_nb(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, dim3 grid, size_t lds, const double* u, int64_t ld,
                                        int64_t K, const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset,
                                        const double* fnorm, double* part) {
     switch (Cut::binned ? 1 : 1 + d.Q) {
-#define MBAR_CASE(J_)                                                                                                                       \
-    case J_:                                                                                                                                \
-        if constexpr (J_ == 1 || !Cut::binned)                                                                                              \
-            hipLaunchKernelGGL((k_scan_cross<NB, J_, Cut>), grid, dim3(256), lds, s, d, cut, u, ld, K, f, L, p0, coeff, offset, fnorm, part); \
+#define MBAR_CASE(J_)                                                                                                                    \
+    case J_:                                                                                                                             \
+        if constexpr (J_ == 1 || !Cut::binned) {                                                                                         \
+            if constexpr (Fam::harmonic)                                                                                                 \
+                hipLaunchKernelGGL((k_scan_cross<NB, J_, Cut, Fam, Fam>), grid, dim3(256), lds, s, d, cut, u, ld, K, f, L, p0, coeff,    \
+                                   offset, fnorm, part, fam);                                                                            \
+            else                                                                                                                         \
+                hipLaunchKernelGGL((k_scan_cross<NB, J_, Cut, Fam>), grid, dim3(256), lds, s, d, cut, u, ld, K, f, L, p0, coeff, offset, \
+                                   fnorm, part);                                                                                         \
+        }                                                                                                                                \
         break;
         MBAR_CASE(1) MBAR_CASE(2) MBAR_CASE(3) MBAR_CASE(4)
 #undef MBAR_CASE
@@ -441,9 +469,10 @@ static hipError_t launch_scan_cross_nb(hipStream_t s, const ScanData& d, const C
 }
 
 // nb: scan_nb_for(K), or 0 (no cross block: the per-member sums only)
-template <class Cut>
-hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, int nb, const double* u, int64_t ld, int64_t K, const double* f,
-                             int64_t L, int64_t p0, const double* coeff, const double* offset, const double* fnorm, double* part) {
+template <class Cut, class Fam>
+hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, int nb, const double* u, int64_t ld, int64_t K,
+                             const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset, const double* fnorm,
+                             double* part) {
     const int64_t c0 = cut.c0(), c1 = cut.c1(d.N, SCAN_CHUNK);
     if (c1 <= c0 || p0 >= L) return hipSuccess;
     if (K > 16 * (int64_t)nb && nb > 0) return hipErrorInvalidValue;
@@ -456,7 +485,7 @@ hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, i
     const size_t lds = EXP_TABLE_BYTES + ((size_t)nb * 16 * SCAN_PITCH + sv) * sizeof(double);
     switch (nb) {
 #define MBAR_CASE(NB_) \
-    case NB_: return launch_scan_cross_nb<NB_>(s, d, cut, grid, lds, u, ld, K, f, L, p0, coeff, offset, fnorm, part);
+    case NB_: return launch_scan_cross_nb<NB_>(s, d, cut, fam, grid, lds, u, ld, K, f, L, p0, coeff, offset, fnorm, part);
         MBAR_CASE(0) MBAR_CASE(1) MBAR_CASE(2) MBAR_CASE(4) MBAR_CASE(8)
 #undef MBAR_CASE
         default: return hipErrorInvalidValue;
@@ -464,30 +493,36 @@ hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, i
 }
 
 template <class Cut>
-hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int64_t K, int64_t L, int64_t p0,
+hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int mb, int64_t K, int64_t L, int64_t p0,
                                    const double* part, double* cross, double* vec) {
     const int64_t nbg = cut.b1() - cut.b0();
     if (nbg < 1 || p0 >= L || (!Cut::binned && d.N < 1)) return hipSuccess;  // (a bin without a chunk still gets its zeros)
     const int J = Cut::binned ? 1 : 1 + d.Q;
-    const int64_t pl = L - p0 < 64 * scan_mb(J) ? L - p0 : 64 * scan_mb(J);
+    const int64_t pl = L - p0 < 64 * mb ? L - p0 : 64 * mb;
     const int64_t threads = nbg * ((nb > 0 ? pl * J * K : 0) + pl * (Cut::binned ? SCANBIN_NV : scan_nv(J)));
     const int64_t blocks = (threads + SV_THREADS - 1) / SV_THREADS;
     if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_scan_cross_merge<Cut>), dim3((unsigned)blocks), dim3(SV_THREADS), 0, s, d, cut, nb, K, L, p0, pl, part, cross, vec);
+    hipLaunchKernelGGL((k_scan_cross_merge<Cut>), dim3((unsigned)blocks), dim3(SV_THREADS), 0, s, d, cut, nb, K, L, p0, pl, part, cross, vec, mb);
     return hipGetLastError();
 }
 
-#define MBAR_CUT(Cut)                                                                                                                          \
-    template hipError_t launch_scan_vec<Cut>(hipStream_t, const ScanData&, const Cut&, bool, int64_t, const double*, const double*,            \
-                                             const double*, double*);                                                                          \
-    template hipError_t launch_scan_vec_merge<Cut>(hipStream_t, const ScanData&, const Cut&, bool, int64_t, const double*, double*, double*,    \
-                                                   double*);                                                                                   \
-    template hipError_t launch_scan_cross<Cut>(hipStream_t, const ScanData&, const Cut&, int, const double*, int64_t, int64_t, const double*,  \
-                                               int64_t, int64_t, const double*, const double*, const double*, double*);                        \
-    template hipError_t launch_scan_cross_merge<Cut>(hipStream_t, const ScanData&, const Cut&, int, int64_t, int64_t, int64_t, const double*,  \
+#define MBAR_SWEEPS(Cut, Fam)                                                                                                                \
+    template hipError_t launch_scan_vec<Cut, Fam>(hipStream_t, const ScanData&, const Cut&, const Fam&, bool, int64_t, const double*,        \
+                                                  const double*, const double*, double*);                                                    \
+    template hipError_t launch_scan_cross<Cut, Fam>(hipStream_t, const ScanData&, const Cut&, const Fam&, int, const double*, int64_t,       \
+                                                    int64_t, const double*, int64_t, int64_t, const double*, const double*, const double*,   \
+                                                    double*);
+#define MBAR_CUT(Cut)                                                                                                                        \
+    MBAR_SWEEPS(Cut, ScanLinear)                                                                                                             \
+    MBAR_SWEEPS(Cut, ScanHarmonic)                                                                                                           \
+    template hipError_t launch_scan_vec_merge<Cut>(hipStream_t, const ScanData&, const Cut&, bool, int64_t, const double*, double*, double*, \
+                                                   double*);                                                                                 \
+    template hipError_t launch_scan_cross_merge<Cut>(hipStream_t, const ScanData&, const Cut&, int, int, int64_t, int64_t, int64_t,          \
+                                                     const double*,                                                                          \
                                                      double*, double*);
 MBAR_CUT(ScanWhole)
 MBAR_CUT(ScanBinned)
 #undef MBAR_CUT
+#undef MBAR_SWEEPS
 
 }  // namespace mbar

@@ -28,15 +28,47 @@ ScanData scan_data_of(const mbar_ctx* c) {
     return d;
 }
 
+// The two sweeps on the context's family: the linear instantiations unless a harmonic term is set (mbar_ctx_set_scan_terms); l0:
+// the member the coeff / offset pointers of a pass-A panel start at (pass B takes the whole arrays and its own p0).
+ScanHarmonic harmonic_of(const mbar_ctx* c) { return ScanHarmonic{c->scan_terms, c->scan_center.p}; }
+template <class Cut>
+hipError_t sweep_vec(mbar_ctx* c, const ScanData& d, const Cut& cut, bool sum, int64_t l0, int64_t L, const double* coeff, const double* offset,
+                     const double* M, double* rec) {
+    if (c->scan_terms.mask) return launch_scan_vec(c->stream, d, cut, harmonic_of(c).from(l0), sum, L, coeff, offset, M, rec);
+    return launch_scan_vec(c->stream, d, cut, ScanLinear{}, sum, L, coeff, offset, M, rec);
+}
+template <class Cut>
+hipError_t sweep_cross(mbar_ctx* c, const ScanData& d, const Cut& cut, int nb, int64_t L, int64_t p0, const double* coeff, const double* offset,
+                       const double* fnorm) {
+    if (c->scan_terms.mask)
+        return launch_scan_cross(c->stream, d, cut, harmonic_of(c), nb, c->u, c->ld, c->K, d_f(c), L, p0, coeff, offset, fnorm, c->scan_part);
+    return launch_scan_cross(c->stream, d, cut, ScanLinear{}, nb, c->u, c->ld, c->K, d_f(c), L, p0, coeff, offset, fnorm, c->scan_part);
+}
+
+// blocks of 16 members per wave of pass B on the context's family
+int scan_mb_of(const mbar_ctx* c, int J) { return c->scan_terms.mask ? ScanHarmonic::mb(J) : ScanLinear::mb(J); }
+
+void release_terms(mbar_ctx* c) {
+    c->scan_terms = FamilyTerms{};
+    c->scan_center_L = 0;
+    c->scan_center.reset();
+}
+
 // How the four passes open.  scan_open: the limits of the context, the caller's own argument check (args_ok), what the family
 // needs on the context, the device.
-int scan_open(mbar_ctx* c, const std::string& who, bool args_ok, bool binned) {
+int scan_open(mbar_ctx* c, const std::string& who, bool args_ok, bool binned, int64_t L) {
     int rc = scan_ready(c, who.c_str());
     if (rc) return rc;
     if (!args_ok) return fail(c, MBAR_ERR_ARG, who + ": bad argument");
     if (c->scan_B < 1) return fail(c, MBAR_ERR_STATE, who + ": no basis on this context (mbar_ctx_set_scan first)");
     if (binned && c->scan_Q != 0) return fail(c, MBAR_ERR_STATE, who + ": the binned scan passes take a family without observables (Q = 0)");
     if (binned && c->scanbin_nbins < 1) return fail(c, MBAR_ERR_STATE, who + ": no bins on this context (mbar_ctx_set_scan_bins first)");
+    if (c->scan_terms.mask && c->scan_center_L != L)
+        return fail(c, MBAR_ERR_STATE, who + ": the family has harmonic terms and " +
+                                           (c->scan_center_L ? "the centres on this context are those of " + std::to_string(c->scan_center_L) +
+                                                                   " members, not of " + std::to_string(L)
+                                                             : std::string("no centres are set")) +
+                                           " (mbar_ctx_set_scan_centers first)");
     HIPCHK(c, hipSetDevice(c->device));
     return MBAR_OK;
 }
@@ -51,6 +83,9 @@ struct ScanOut {
 int scan_begin(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* fnorm, size_t nnorm,
                std::initializer_list<ScanOut> outs, bool* done, ScanData* d) {
     bool nan = false;
+    if (c->scan_terms.mask)  // (the linear family keeps what it always did with such a member)
+        for (int64_t x = 0; x < L * c->scan_B; ++x)
+            if (!std::isfinite(coeff[x])) return fail(c, MBAR_ERR_ARG, "the coefficients of a family with harmonic terms must be finite");
     int rc = pass_logden(c, f, &nan);
     if (rc) return rc;
     for (size_t x = 0; x < nnorm; ++x) nan = nan || std::isnan(fnorm[x]);
@@ -143,6 +178,7 @@ int mbar_ctx_set_scan(mbar_ctx* c, int64_t B, const double* basis, int64_t Q, co
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    release_terms(c);  // (a new basis, or none: all-linear again)
     if (B == 0) {
         c->scan_B = c->scan_Q = 0;
         c->scan_vec.reset();
@@ -166,8 +202,54 @@ int mbar_ctx_set_scan(mbar_ctx* c, int64_t B, const double* basis, int64_t Q, co
     return MBAR_OK;
 }
 
+int mbar_ctx_set_scan_terms(mbar_ctx* c, const int32_t* kind, const double* period) {
+    int rc = scan_ready(c, "mbar_ctx_set_scan_terms");
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!kind) {
+        release_terms(c);
+        return MBAR_OK;
+    }
+    if (c->scan_B < 1) return fail(c, MBAR_ERR_STATE, "mbar_ctx_set_scan_terms: no basis on this context (mbar_ctx_set_scan first)");
+    FamilyTerms terms;
+    rc = family_terms(c, "mbar_ctx_set_scan_terms", c->scan_B, kind, period, &terms);
+    if (rc) return rc;
+    release_terms(c);  // (centres of another family's slots mean nothing)
+    c->scan_terms = terms;
+    return MBAR_OK;
+}
+
+int mbar_ctx_set_scan_centers(mbar_ctx* c, int64_t L, const double* center) {
+    int rc = scan_ready(c, "mbar_ctx_set_scan_centers");
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (L == 0 || !center) {
+        if (L != 0) return fail(c, MBAR_ERR_ARG, "mbar_ctx_set_scan_centers: NULL centres for L != 0 members");
+        c->scan_center_L = 0;
+        return MBAR_OK;
+    }
+    if (L < 0) return fail(c, MBAR_ERR_ARG, "mbar_ctx_set_scan_centers: L must not be negative");
+    if (c->scan_B < 1) return fail(c, MBAR_ERR_STATE, "mbar_ctx_set_scan_centers: no basis on this context (mbar_ctx_set_scan first)");
+    const int64_t B = c->scan_B;
+    for (int64_t x = 0; x < L * B; ++x)
+        if (!std::isfinite(center[x])) return fail(c, MBAR_ERR_ARG, "mbar_ctx_set_scan_centers: the centres must be finite");
+    // the centres of the harmonic terms, in ascending b, as the kernels keep them: [L][SCAN_MAX_H]
+    std::vector<double> packed((size_t)L * SCAN_MAX_H, 0.0);
+    for (int64_t l = 0; l < L; ++l) {
+        int h = 0;
+        for (int64_t b = 0; b < B; ++b)
+            if ((c->scan_terms.mask >> b) & 1u) packed[(size_t)l * SCAN_MAX_H + h++] = center[l * B + b];
+    }
+    c->scan_center_L = 0;
+    HIPCHK(c, c->scan_center.upload(packed.data(), packed.size()));
+    c->scan_center_L = L;
+    return MBAR_OK;
+}
+
 int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, double* lognum, double* mean) {
-    int rc = scan_open(c, "mbar_scan_lognum", f && coeff && lognum && L >= 1, false);
+    int rc = scan_open(c, "mbar_scan_lognum", f && coeff && lognum && L >= 1, false, L);
     if (rc) return rc;
     const int64_t B = c->scan_B, J = 1 + c->scan_Q;
     bool done = false;
@@ -188,9 +270,9 @@ int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coef
         ScopedTimer timer(c, MBAR_TIMER_OTHER);
         for (int64_t p0 = 0; p0 < L; p0 += pw) {
             const int64_t pl = std::min(pw, L - p0);
-            HIPCHK(c, launch_scan_vec(c->stream, d, cut, false, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
+            HIPCHK(c, sweep_vec(c, d, cut, false, p0, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
             HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, false, pl, c->scan_part, d_M + p0, nullptr, nullptr));
-            HIPCHK(c, launch_scan_vec(c->stream, d, cut, true, pl, d_coeff + p0 * B, d_off + p0, d_M + p0, c->scan_part));
+            HIPCHK(c, sweep_vec(c, d, cut, true, p0, pl, d_coeff + p0 * B, d_off + p0, d_M + p0, c->scan_part));
             HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, true, pl, c->scan_part, d_M + p0, d_lognum + p0, d_mean + p0 * J));
         }
     }
@@ -201,7 +283,7 @@ int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coef
 
 int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan, int64_t r,
                      double* cross, double* within, double* refcol, double* wsum) {
-    int rc = scan_open(c, "mbar_scan_gram_w", f && coeff && f_scan && within && refcol && wsum && L >= 1 && r >= 0 && r < L, false);
+    int rc = scan_open(c, "mbar_scan_gram_w", f && coeff && f_scan && within && refcol && wsum && L >= 1 && r >= 0 && r < L, false, L);
     if (rc) return rc;
     const int64_t B = c->scan_B, K = c->K;
     const int J = 1 + (int)c->scan_Q, NW = J * (J + 1) / 2, NV = scan_nv(J);
@@ -212,8 +294,9 @@ int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coef
     if (rc || done) return rc;
     const int nb = cross ? scan_nb_for(K) : 0;
     const int64_t nchunks = (c->N + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    const int64_t pw = 64 * scan_mb(J);
-    HIPCHK(c, c->scan_part.grow((size_t)std::max<int64_t>(nchunks, 1) * (size_t)scan_record_doubles(nb, J, NV)));
+    const int mb = scan_mb_of(c, J);
+    const int64_t pw = 64 * mb;
+    HIPCHK(c, c->scan_part.grow((size_t)std::max<int64_t>(nchunks, 1) * (size_t)scan_record_doubles(nb, J, NV, mb)));
     HIPCHK(c, c->scan_out.grow((size_t)L * (size_t)NV + (cross ? (size_t)K * L * J : 0)));
     double* d_vec = c->scan_out;
     double* d_cross = d_vec + L * NV;
@@ -227,8 +310,8 @@ int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coef
     {
         ScopedTimer timer(c, MBAR_TIMER_OTHER);
         for (int64_t p0 = 0; p0 < L; p0 += pw) {  // the resident matrix is read once per panel
-            HIPCHK(c, launch_scan_cross(c->stream, d, cut, nb, c->u, c->ld, K, d_f(c), L, p0, d_coeff, d_off, d_fscan, c->scan_part));
-            HIPCHK(c, launch_scan_cross_merge(c->stream, d, cut, nb, K, L, p0, c->scan_part, d_cross, d_vec));
+            HIPCHK(c, sweep_cross(c, d, cut, nb, L, p0, d_coeff, d_off, d_fscan));
+            HIPCHK(c, launch_scan_cross_merge(c->stream, d, cut, nb, mb, K, L, p0, c->scan_part, d_cross, d_vec));
         }
     }
     std::vector<double> vec((size_t)L * NV);
@@ -290,7 +373,7 @@ int mbar_ctx_set_scan_bins(mbar_ctx* c, int64_t nbins, const int32_t* label_host
 }
 
 int mbar_scan_bin_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, double* lognum) {
-    int rc = scan_open(c, "mbar_scan_bin_lognum", f && coeff && lognum && L >= 1, true);
+    int rc = scan_open(c, "mbar_scan_bin_lognum", f && coeff && lognum && L >= 1, true, L);
     if (rc) return rc;
     const int64_t B = c->scan_B, nbins = c->scanbin_nbins;
     bool done = false;
@@ -310,9 +393,9 @@ int mbar_scan_bin_lognum(mbar_ctx* c, const double* f, int64_t L, const double* 
         ScopedTimer timer(c, MBAR_TIMER_OTHER);
         for (int64_t p0 = 0; p0 < L; p0 += pw) {
             const int64_t pl = std::min(pw, L - p0);
-            HIPCHK(c, launch_scan_vec(c->stream, d, cut, false, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
+            HIPCHK(c, sweep_vec(c, d, cut, false, p0, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
             HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, false, pl, c->scan_part, d_M, nullptr, nullptr));
-            HIPCHK(c, launch_scan_vec(c->stream, d, cut, true, pl, d_coeff + p0 * B, d_off + p0, d_M, c->scan_part));
+            HIPCHK(c, sweep_vec(c, d, cut, true, p0, pl, d_coeff + p0 * B, d_off + p0, d_M, c->scan_part));
             HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, true, pl, c->scan_part, d_M, d_lognum + p0 * nbins, nullptr));
         }
     }
@@ -322,7 +405,7 @@ int mbar_scan_bin_lognum(mbar_ctx* c, const double* f, int64_t L, const double* 
 
 int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_bins,
                          double* cross, double* diag, double* wsum) {
-    int rc = scan_open(c, "mbar_scan_bin_gram_w", f && coeff && f_bins && diag && wsum && L >= 1, true);
+    int rc = scan_open(c, "mbar_scan_bin_gram_w", f && coeff && f_bins && diag && wsum && L >= 1, true, L);
     if (rc) return rc;
     const int64_t B = c->scan_B, K = c->K, nbins = c->scanbin_nbins;
     const size_t LB = (size_t)L * (size_t)nbins;
@@ -336,7 +419,8 @@ int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* 
     const int nb = cross ? scan_nb_for(K) : 0;
     // groups of whole bins whose records fit the budget ("scan_part_bytes"; a single bin is never split): one sweep per group, and
     // a (member, bin)'s sums do not depend on the cut
-    const int64_t rec = scan_record_doubles(nb, 1, SCANBIN_NV);
+    const int mb = scan_mb_of(c, 1);
+    const int64_t rec = scan_record_doubles(nb, 1, SCANBIN_NV, mb);
     const int64_t max_chunks = std::max<int64_t>(c->opt_scan_part_bytes / (rec * (int64_t)sizeof(double)), 1);
     const std::vector<int64_t>& c0 = c->scanbin_c0_b_host;
     std::vector<int64_t> group{0};  // first bin of every group, then nbins
@@ -351,7 +435,7 @@ int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* 
     double* d_cross = d_vec + LB * SCANBIN_NV;
     const double* d_coeff = c->scan_in;
     const double* d_off = d_coeff + L * B;
-    const int64_t pw = 64 * scan_mb(1);
+    const int64_t pw = 64 * mb;
     HIPCHK(c, hipMemcpyAsync(d_f(c), f, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
     {
         ScopedTimer timer(c, MBAR_TIMER_OTHER);
@@ -359,9 +443,8 @@ int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* 
             cut.b0_ = group[g], cut.b1_ = group[g + 1];
             cut.c0_ = c0[(size_t)cut.b0_], cut.c1_ = c0[(size_t)cut.b1_];
             for (int64_t p0 = 0; p0 < L; p0 += pw) {  // the group's samples of the resident matrix are read once per panel
-                HIPCHK(c, launch_scan_cross(c->stream, d, cut, nb, c->u, c->ld, K, d_f(c), L, p0, d_coeff, d_off, c->scanbin_fbins.p,
-                                            c->scan_part));
-                HIPCHK(c, launch_scan_cross_merge(c->stream, d, cut, nb, K, L, p0, c->scan_part, d_cross, d_vec));
+                HIPCHK(c, sweep_cross(c, d, cut, nb, L, p0, d_coeff, d_off, c->scanbin_fbins.p));
+                HIPCHK(c, launch_scan_cross_merge(c->stream, d, cut, nb, mb, K, L, p0, c->scan_part, d_cross, d_vec));
             }
         }
     }

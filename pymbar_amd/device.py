@@ -41,6 +41,54 @@ def linear_family_inputs(basis_bn, coeff_rb, offset_r=None, error=ValueError):
     return basis_bn, coeff_rb, offset_r
 
 
+MAX_HARMONIC = 4  # MBAR_SCAN_MAX_H: harmonic terms of a family
+
+
+def family_terms(B, harmonic_b=None, period_b=None, error=ValueError):
+    """``(harmonic_b, period_b)`` of a family of ``B`` terms as a bool mask and float64 periods of shape ``(B,)``, or ``(None,
+    None)`` for the all-linear family (``harmonic_b`` None or all false).  Term ``b`` of member ``l`` is ``coeff[l, b] basis[b, n]``
+    when linear and ``coeff[l, b] w(basis[b, n] - center[l, b])^2`` when harmonic, ``w(d) = d - P rint(d / P)`` the minimum image for
+    ``P = period_b[b] > 0`` and ``d`` itself for 0 (``period_b`` None: no term is periodic).  At most 4 terms may be harmonic;
+    periods are finite and not negative and read at the harmonic terms only."""
+    if harmonic_b is None:
+        if period_b is not None and np.any(np.asarray(period_b) != 0):
+            raise error("period_b without harmonic_b: only a harmonic term can be periodic")
+        return None, None
+    harmonic_b = np.asarray(harmonic_b)
+    if harmonic_b.shape != (B,) or harmonic_b.dtype != np.bool_:
+        raise error("harmonic_b must be a bool mask with one entry per basis vector")
+    period_b = np.zeros(B) if period_b is None else np.array(period_b, dtype=np.float64)
+    if period_b.shape != (B,):
+        raise error("period_b must have one entry per basis vector")
+    if int(harmonic_b.sum()) > MAX_HARMONIC:
+        raise error(f"at most {MAX_HARMONIC} terms of a family may be harmonic")
+    if not np.all(np.isfinite(period_b[harmonic_b])) or np.any(period_b[harmonic_b] < 0):
+        raise error("the period of a harmonic term must be finite and not negative (0: not periodic)")
+    if not harmonic_b.any():
+        return None, None
+    period_b[~harmonic_b] = 0.0
+    return np.ascontiguousarray(harmonic_b), period_b
+
+
+def family_centers(center_rb, R, B, harmonic_b, error=ValueError, name="center_kb"):
+    """The centres ``(R, B)`` of a family's members as a float64 C-contiguous array (entries of linear terms are not read);
+    required whenever a term is harmonic, None otherwise."""
+    from .utils import DataError
+
+    if harmonic_b is None:
+        return None
+    if center_rb is None:
+        raise error(f"{name} is required: the family has harmonic terms")
+    center_rb = np.ascontiguousarray(center_rb, dtype=np.float64)
+    if center_rb.shape != (R, B):
+        raise error(f"{name} must have one row per member and one column per basis vector")
+    if not np.all(np.isfinite(center_rb[:, harmonic_b])):
+        raise DataError(f"{name} must be finite")
+    if not np.all(np.isfinite(center_rb)):  # (what no term reads must still be a number the library accepts)
+        center_rb = np.where(harmonic_b[None, :], center_rb, 0.0)
+    return center_rb
+
+
 class _ContextMatrix:
     """What :class:`DeviceMatrix` and :class:`ExtendedMatrix` share: they own one ``mbar_ctx`` (``_ctx``) and write whole rows of
     it (the row-level assembly of the expectation family).  The two differ in three hooks: where a destination row lives
@@ -211,6 +259,47 @@ class DeviceMatrix(_ContextMatrix):
                                                         _dptr(coeff_rb), _dptr(offset_r)))
 
     @classmethod
+    def from_family(cls, basis_bn, coeff_kb, offset_k=None, center_kb=None, harmonic_b=None, period_b=None, device=None, columns=None,
+                    validate=True):
+        """:meth:`from_linear` for a family with harmonic terms (:func:`family_terms`): ``u[k, n] = offset_k[k] + sum_b term_b``,
+        a harmonic term ``coeff_kb[k, b] w(basis_bn[b, n] - center_kb[k, b])^2`` with its minimum image for ``period_b[b] > 0`` --
+        umbrella sampling on a torsion -- built ON THE DEVICE (``mbar_ctx_fill_family_rows``).  ``validate=False``: the arrays are
+        what :func:`linear_family_inputs`, :func:`family_terms` and :func:`family_centers` returned."""
+        if validate:
+            basis_bn, coeff_kb, offset_k = linear_family_inputs(basis_bn, coeff_kb, offset_k)
+            harmonic_b, period_b = family_terms(basis_bn.shape[0], harmonic_b, period_b)
+            center_kb = family_centers(center_kb, coeff_kb.shape[0], basis_bn.shape[0], harmonic_b)
+        n0, n1 = (0, basis_bn.shape[1]) if columns is None else columns
+        dm = cls(coeff_kb.shape[0], n1 - n0, device=device)
+        try:
+            dm.fill_family_rows(0, basis_bn, coeff_kb, offset_k, center_kb, harmonic_b, period_b, col0=n0, validate=False)
+        except BaseException:
+            dm.close()
+            raise
+        return dm
+
+    def fill_family_rows(self, row0, basis_bn, coeff_rb, offset_r=None, center_rb=None, harmonic_b=None, period_b=None, col0=0,
+                         validate=True):
+        """:meth:`fill_linear_rows` for a family with harmonic terms: rows ``[row0, row0 + R)`` become the chain the scan passes
+        evaluate -- from ``offset_r``, ``b`` ascending, ``fma(coeff, basis, u)`` at a linear term and ``d = basis - center; P > 0:
+        d = fma(-P, rint(d (1 / P)), d); fma(coeff, d d, u)`` at a harmonic one, every operation rounded once.  With no harmonic
+        term the rows are the bits of :meth:`fill_linear_rows`."""
+        if validate:
+            basis_bn, coeff_rb, offset_r = linear_family_inputs(basis_bn, coeff_rb, offset_r)
+            harmonic_b, period_b = family_terms(basis_bn.shape[0], harmonic_b, period_b)
+            center_rb = family_centers(center_rb, coeff_rb.shape[0], basis_bn.shape[0], harmonic_b, name="center_rb")
+        col0 = int(col0)
+        if col0 < 0 or col0 + self.N_local > basis_bn.shape[1]:
+            raise ValueError("basis_bn must cover the columns [col0, col0 + N_local)")
+        self._touched()
+        B, R = basis_bn.shape[0], coeff_rb.shape[0]
+        kind = None if harmonic_b is None else np.ascontiguousarray(harmonic_b, dtype=np.int32)
+        rc = self._lib.mbar_ctx_fill_family_rows(self._ctx, int(row0), R, B, _dptr(basis_bn), basis_bn.shape[1], col0, _dptr(coeff_rb),
+                                                 _dptr(center_rb), _dptr(offset_r),
+                                                 None if kind is None else kind.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(period_b))
+        self._check(rc)
+
+    @classmethod
     def harmonic(cls, O_k, K_k, N_k_global, seed=0, n_global0=0, N_local=None, device=None):
         """Generate the synthetic harmonic ladder of SURVEY.md 8(d) directly in HBM."""
         O_k = np.ascontiguousarray(O_k, dtype=np.float64)
@@ -304,10 +393,13 @@ class DeviceMatrix(_ContextMatrix):
         return X, d, w
 
     # ---- reweighting scans over a linear family of unsampled states (pymbar_amd.scan) -----------------------------------------
-    def set_scan(self, basis_bn=None, t_qn=None):
+    def set_scan(self, basis_bn=None, t_qn=None, harmonic_b=None, period_b=None):
         """The ``B`` basis vectors (``B x N``, ``1 <= B <= 8``) and the ``Q`` shifted observables (``Q x N``, ``Q <= 3``, or
-        None) of a scan, uploaded once (``mbar_ctx_set_scan``).  ``basis_bn=None`` releases them."""
+        None) of a scan, uploaded once (``mbar_ctx_set_scan``).  ``basis_bn=None`` releases them.  ``harmonic_b`` / ``period_b``
+        (:func:`family_terms`): the kind of the family's terms (``mbar_ctx_set_scan_terms``); the four ``scan_*`` methods then
+        need the members' centres ``center_lb``."""
         self._scan = None
+        self._scan_harmonic = None
         if basis_bn is None:
             self._check(self._lib.mbar_ctx_set_scan(self._ctx, 0, None, 0, None))
             return
@@ -320,7 +412,28 @@ class DeviceMatrix(_ContextMatrix):
         if rc == -1:  # MBAR_ERR_ARG: B or Q outside the limits
             raise ValueError(_lib.last_error(self._ctx))
         self._check(rc)
+        harmonic_b, period_b = family_terms(B, harmonic_b, period_b)
+        if harmonic_b is not None:
+            kind = np.ascontiguousarray(harmonic_b, dtype=np.int32)
+            rc = self._lib.mbar_ctx_set_scan_terms(self._ctx, kind.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(period_b))
+            if rc == -1:
+                raise ValueError(_lib.last_error(self._ctx))
+            self._check(rc)
+            self._scan_harmonic = harmonic_b
         self._scan = (B, Q)
+
+    def _scan_centers(self, center_lb, L):
+        """The centres of the members of the next scan call go to the context (a family with harmonic terms needs them)."""
+        harmonic_b = getattr(self, "_scan_harmonic", None)
+        if harmonic_b is None:
+            if center_lb is not None and np.shape(center_lb) != (L, self._scan[0]):
+                raise ValueError("center_lb must have one row per member and one column per basis vector")
+            return
+        center_lb = family_centers(center_lb, L, self._scan[0], harmonic_b, name="center_lb")
+        rc = self._lib.mbar_ctx_set_scan_centers(self._ctx, L, _dptr(center_lb))
+        if rc == -1:
+            raise ValueError(_lib.last_error(self._ctx))
+        self._check(rc)
 
     def _scan_members(self, coeff_lb, offset_l):
         if getattr(self, "_scan", None) is None:
@@ -334,19 +447,20 @@ class DeviceMatrix(_ContextMatrix):
             raise ValueError("offset_l must have one entry per member")
         return coeff_lb, offset_l, L, 1 + self._scan[1]
 
-    def scan_lognum(self, f, coeff_lb, offset_l=None):
+    def scan_lognum(self, f, coeff_lb, offset_l=None, center_lb=None):
         """Pass A of a scan: ``(lognum, mean)`` with ``lognum[l] = log sum_n c_n exp(-u_l(n) - logden_n(f))`` and ``mean[l, j]``
         the average of ``t_j`` (``t_0 = 1``) in member ``l`` (``L x (1 + Q)``)."""
         f = np.ascontiguousarray(f, dtype=np.float64)
         if f.shape != (self.K,):
             raise ValueError(f"f must have shape ({self.K},)")
         coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
+        self._scan_centers(center_lb, L)
         lognum = np.empty(L, dtype=np.float64)
         mean = np.empty((L, J), dtype=np.float64)
         self._check(self._lib.mbar_scan_lognum(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(lognum), _dptr(mean)))
         return lognum, mean
 
-    def scan_gram_w(self, f, coeff_lb, offset_l, f_scan, reference=0, cross=True):
+    def scan_gram_w(self, f, coeff_lb, offset_l, f_scan, reference=0, cross=True, center_lb=None):
         """Pass B of a scan: ``(cross, within, refcol, wsum)`` of the members' normalised weights ``b_ln = exp(f_scan[l] - u_l(n) -
         logden_n(f))`` -- ``cross[k, l, j] = sum_n c_n W_nk b_ln t_jn`` (``None`` with ``cross=False``), ``within[l, i, j] = sum_n
         c_n b_ln^2 t_in t_jn`` (symmetric ``J x J``), ``refcol[l, j] = sum_n c_n b_rn b_ln t_jn`` for the reference member ``r``,
@@ -356,6 +470,7 @@ class DeviceMatrix(_ContextMatrix):
         f_scan = np.ascontiguousarray(f_scan, dtype=np.float64)
         if f.shape != (self.K,) or f_scan.shape != (L,) or not 0 <= int(reference) < L:
             raise ValueError("f must have K entries, f_scan one per member, and the reference must be a member")
+        self._scan_centers(center_lb, L)
         X = np.empty((self.K, L, J), dtype=np.float64) if cross else None
         tri = np.empty((L, J * (J + 1) // 2), dtype=np.float64)
         refcol = np.empty((L, J), dtype=np.float64)
@@ -392,18 +507,19 @@ class DeviceMatrix(_ContextMatrix):
         self._check(rc)
         self._scan_nbins = int(nbins)
 
-    def scan_bin_lognum(self, f, coeff_lb, offset_l=None):
+    def scan_bin_lognum(self, f, coeff_lb, offset_l=None, center_lb=None):
         """Pass A of a binned scan: ``lognum[l, i] = log sum_{n in bin i} c_n exp(-u_l(n) - logden_n(f))`` (``L x nbins``; ``-inf``
         where no sample of the bin has ``c_n > 0``)."""
         f = np.ascontiguousarray(f, dtype=np.float64)
         if f.shape != (self.K,):
             raise ValueError(f"f must have shape ({self.K},)")
         coeff_lb, offset_l, L, _ = self._scan_members(coeff_lb, offset_l)
+        self._scan_centers(center_lb, L)
         lognum = np.empty((L, getattr(self, "_scan_nbins", 0)), dtype=np.float64)
         self._check(self._lib.mbar_scan_bin_lognum(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(lognum)))
         return lognum
 
-    def scan_bin_gram_w(self, f, coeff_lb, offset_l, f_bins, cross=True, slab=None):
+    def scan_bin_gram_w(self, f, coeff_lb, offset_l, f_bins, cross=True, slab=None, center_lb=None):
         """Pass B of a binned scan: ``(cross, diag, wsum)`` of the normalised weights ``Bv = exp(f_bins[l, i] - u_l(n) -
         logden_n(f))`` of member ``l`` on the samples of bin ``i`` -- ``cross[k, l, i] = sum_{n in i} c_n W_nk Bv`` (``None`` with
         ``cross=False``), ``diag[l, i] = sum c_n Bv^2``, ``wsum[l, i] = sum c_n Bv``.  The members go to the device in slabs (of
@@ -424,6 +540,7 @@ class DeviceMatrix(_ContextMatrix):
         for l0 in range(0, L, slab):
             l1 = min(L, l0 + slab)
             Xs = np.empty((self.K, l1 - l0, nbins), dtype=np.float64) if cross and (l0, l1) != (0, L) else X
+            self._scan_centers(None if center_lb is None else center_lb[l0:l1], l1 - l0)
             self._check(self._lib.mbar_scan_bin_gram_w(self._ctx, _dptr(f), l1 - l0, _dptr(coeff_lb[l0:l1]), _dptr(offset_l[l0:l1]),
                                                        _dptr(f_bins[l0:l1]), _dptr(Xs), _dptr(d[l0:l1]), _dptr(w[l0:l1])))
             if cross and Xs is not X:

@@ -163,6 +163,42 @@ class MBAR:
         self._construct(None, N_k, linear=linear, **kwargs)
         return self
 
+    @classmethod
+    def from_family(cls, basis_bn, coeff_kb, N_k, offset_k=None, center_kb=None, harmonic_b=None, period_b=None, **kwargs):
+        """:meth:`from_linear` for sampled states with HARMONIC restraint terms, the family of umbrella sampling on a periodic
+        coordinate: ``u_kn[k, n] = offset_k[k] + sum_b term_b(k, n)`` with a linear term ``coeff_kb[k, b] basis_bn[b, n]`` and,
+        where the bool mask ``harmonic_b`` ``(B,)`` says so, a harmonic one ``coeff_kb[k, b] w(basis_bn[b, n] - center_kb[k, b])^2`` --
+        ``w(d) = d - P rint(d / P)`` the minimum image for ``P = period_b[b] > 0``, ``w(d) = d`` for ``period_b[b] = 0`` (or
+        ``period_b=None``).  A torsion ``chi`` under ``beta_k [E + kappa_k / 2 wrap(chi - chi0_k)^2]`` is ``basis_bn = [E, chi]``,
+        ``coeff_kb[k] = [beta_k, beta_k kappa_k / 2]``, ``center_kb[k] = [0, chi0_k]``, ``harmonic_b = [False, True]``, ``period_b =
+        [0, 360]`` (:func:`pymbar_amd.testsystems.periodic_umbrella_family`).  ``1 <= B <= 8``, at most 4 harmonic terms; ``center_kb``
+        ``(K, B)`` is required when a term is harmonic and read at the harmonic terms only.  With no harmonic term this is
+        :meth:`from_linear`.  The device evaluates one fixed chain of operations, the one :meth:`compute_scan`
+        and :meth:`compute_scan_fes` evaluate for unsampled members: a member with a sampled state's parameters is that state.
+
+        Everything else -- the lazy ``u_kn``, ``kwargs``, the refused ``copy``, ``upload_stats`` -- is :meth:`from_linear`'s.  The
+        object keeps private read-only ``center_kb``, ``harmonic_b``, ``period_b`` next to ``basis_bn``, ``coeff_kb``, ``offset_k``
+        (``None`` on other objects); the scan methods default to the constructor's basis and term kinds."""
+        from .device import family_centers, family_terms, linear_family_inputs
+
+        if "copy" in kwargs:
+            raise ParameterError("MBAR.from_family has no host matrix to copy: the copy keyword is not accepted")
+        if kwargs.get("bootstrap_rng", "reference") not in ("reference", "device"):
+            raise ParameterError("bootstrap_rng must be 'reference' or 'device'")
+        basis_bn, coeff_kb, offset_k = linear_family_inputs(basis_bn, coeff_kb, offset_k, error=ParameterError)
+        harmonic_b, period_b = family_terms(basis_bn.shape[0], harmonic_b, period_b, error=ParameterError)
+        center_kb = family_centers(center_kb, coeff_kb.shape[0], basis_bn.shape[0], harmonic_b, error=ParameterError)
+        if np.sum(np.asarray(N_k, dtype=np.int64)) != basis_bn.shape[1] or np.shape(N_k) != (coeff_kb.shape[0],):
+            raise ParameterError("N_k must have one entry per row of coeff_kb, and the sum of all N_k must equal the total number "
+                                 "of samples (length of second dimension of basis_bn).")
+        linear = (_private_copy_flat(basis_bn), np.array(coeff_kb), np.array(offset_k))
+        family = None if harmonic_b is None else (np.array(center_kb), np.array(harmonic_b), np.array(period_b))
+        for a in linear + (family or ()):
+            a.setflags(write=False)
+        self = cls.__new__(cls)
+        self._construct(None, N_k, linear=linear, family=family, **kwargs)
+        return self
+
     # ---- the host matrix -------------------------------------------------------------------------------------------
     @property
     def u_kn(self):
@@ -238,14 +274,19 @@ class MBAR:
 
         if getattr(self, "_dm", None) is None:
             t0 = _time.perf_counter()
-            self._dm = DeviceMatrix.from_linear(self.basis_bn, self.coeff_kb, self.offset_k, device=device, validate=False)  # (checked by from_linear)
+            if self.harmonic_b is not None:  # (made by from_family, and checked there)
+                self._dm = DeviceMatrix.from_family(self.basis_bn, self.coeff_kb, self.offset_k, self.center_kb, self.harmonic_b,
+                                                    self.period_b, device=device, validate=False)
+            else:
+                self._dm = DeviceMatrix.from_linear(self.basis_bn, self.coeff_kb, self.offset_k, device=device, validate=False)  # (checked by from_linear)
             self._linear_upload_s = _time.perf_counter() - t0
         return self._dm
 
     def _construct(self, u_kn, N_k, maximum_iterations=10000, relative_tolerance=1.0e-7, verbose=False, initial_f_k=None,
                    solver_protocol=None, initialize="zeros", x_kindices=None, n_bootstraps=0, bootstrap_solver_protocol=None, rseed=None,
-                   device=None, copy=True, bootstrap_rng="reference", linear=None):
-        """The constructor: of a host matrix ``u_kn``, or (``linear = (basis_bn, coeff_kb, offset_k)``, checked) of a linear family."""
+                   device=None, copy=True, bootstrap_rng="reference", linear=None, family=None):
+        """The constructor: of a host matrix ``u_kn``, or (``linear = (basis_bn, coeff_kb, offset_k)``, checked) of a linear family,
+        with ``family = (center_kb, harmonic_b, period_b)`` (checked) of one with harmonic terms."""
         from .device import DeviceMatrix
 
         if bootstrap_rng not in ("reference", "device"):  # (before the upload and the main solve: a typo must not cost either)
@@ -253,6 +294,7 @@ class MBAR:
         self.N_k = np.array(N_k, dtype=np.int64)
         self.N = int(np.sum(self.N_k))
         self.basis_bn, self.coeff_kb, self.offset_k = (None, None, None) if linear is None else linear
+        self.center_kb, self.harmonic_b, self.period_b = (None, None, None) if family is None else family
         self._u_kn = None
         self._dm = None
         early_upload = None if linear is not None else self._keep_host_matrix(u_kn, copy, device)
@@ -285,7 +327,12 @@ class MBAR:
             indices = self.rng.choice(np.arange(self.N), maxpoint)
             if self.verbose:
                 if linear is not None:  # (the <= 50 columns from the basis, on the host: no download for a log line)
-                    sub = self.coeff_kb @ self.basis_bn[:, indices] + self.offset_k[:, None]
+                    if family is not None:
+                        from .testsystems import family_u_kn
+
+                        sub = family_u_kn(self.basis_bn[:, indices], self.coeff_kb, self.offset_k, *family)
+                    else:
+                        sub = self.coeff_kb @ self.basis_bn[:, indices] + self.offset_k[:, None]
                 else:
                     sub = self.u_kn[:, indices]
                 for k in range(K):

@@ -107,12 +107,12 @@ def _qform(g, a, b):
     return out
 
 
-def _analytical(mbar, dm, coeff_lb, offset_l, f, mean, reference, approximate, warning_cutoff):
+def _analytical(mbar, dm, coeff_lb, offset_l, f, mean, reference, approximate, warning_cutoff, cen={}):
     """``(dDelta_f, sigma)`` from pass B.  Member ``l`` contributes the columns ``z_l0 = b_l`` and ``z_lj = b_l t_j / mean_lj``;
     the cross block is bilinear, so the ``1 / mean`` scaling happens here."""
     L, J = mean.shape
     r = int(reference)
-    cross, within, refcol, wsum = dm.scan_gram_w(mbar.f_k, coeff_lb, offset_l, f, reference=r, cross=not approximate)
+    cross, within, refcol, wsum = dm.scan_gram_w(mbar.f_k, coeff_lb, offset_l, f, reference=r, cross=not approximate, **cen)
     check_w_sums(wsum, 0.0)
     # z . z' of the columns that meet: b_l b_l, b_l b_r, (b_l t_j)(b_l t_j), (b_l t_j) b_l
     bb, br, rr = within[:, 0, 0], refcol[:, 0], within[r, 0, 0]
@@ -150,8 +150,25 @@ def _family_basis(mbar, basis_bn, coeff_lb):
     return mbar.basis_bn
 
 
+def _family_kinds(mbar, basis_given, B, L, center_lb, harmonic_b, period_b):
+    """``(set_scan keywords, scan_* keywords)`` of a scan call's term kinds and centres: empty for the linear family (the handle
+    is then driven exactly as before the harmonic kind existed).  With ``basis_bn=None`` and no kinds given they are those of
+    the object ``MBAR.from_family`` made; the centres are the call's own, required whenever a term is harmonic."""
+    from .device import family_centers, family_terms
+
+    if basis_given is None and harmonic_b is None and period_b is None:
+        harmonic_b, period_b = getattr(mbar, "harmonic_b", None), getattr(mbar, "period_b", None)
+    harmonic_b, period_b = family_terms(B, harmonic_b, period_b, error=ParameterError)
+    if harmonic_b is None:
+        if center_lb is not None and np.shape(center_lb) != (L, B):
+            raise ParameterError("center_lb must have shape (L, B)")
+        return {}, {}
+    center_lb = family_centers(center_lb, L, B, harmonic_b, error=ParameterError, name="center_lb")
+    return dict(harmonic_b=harmonic_b, period_b=period_b), dict(center_lb=center_lb)
+
+
 def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, reference=0, compute_uncertainty=True, uncertainty_method=None,
-                 warning_cutoff=1.0e-10):
+                 warning_cutoff=1.0e-10, center_lb=None, harmonic_b=None, period_b=None):
     """Free energies, averages and their uncertainties along a linear family of unsampled states.
 
     Member ``l`` is the state ``u_l(n) = sum_b coeff_lb[l, b] basis_bn[b, n] + offset_l[l]``; ``basis_bn`` is ``(B, N)`` with ``1 <=
@@ -162,7 +179,13 @@ def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, r
     ``uncertainty_method``: None / "svd-ew" (the bordered form), "approximate", "bootstrap" (adds ``bootstrapped_f`` ``(n_bootstraps,
     L)`` and ``bootstrapped_observables`` ``(n_bootstraps, Q, L)``; the uncertainties are the ``std`` over replicates as
     ``compute_perturbed_free_energies`` and ``compute_expectations`` take it); "svd" needs the weight matrix itself and is not
-    offered."""
+    offered.
+
+    ``center_lb`` ``(L, B)``, ``harmonic_b``, ``period_b`` ``(B,)``: a family with harmonic terms (``MBAR.from_family``) -- a sweep of
+    a restraint centre on a torsion.  Term ``b`` of member ``l`` is then ``coeff_lb[l, b] w(basis_bn[b, n] - center_lb[l, b])^2``
+    where ``harmonic_b[b]``, with the minimum image ``w`` for ``period_b[b] > 0``.  With ``basis_bn=None`` the kinds default to the
+    constructor's; ``center_lb`` is required whenever a term is harmonic.  The uncertainties are formed as for a linear family."""
+    basis_given = basis_bn
     if uncertainty_method == "svd":
         raise ParameterError("uncertainty_method 'svd' needs the weight matrix itself and is not offered for scans")
     if uncertainty_method not in (None, "svd-ew", "approximate", "bootstrap"):
@@ -171,13 +194,14 @@ def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, r
     if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
         raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
     basis_bn, coeff_lb, offset_l, A_qn, L = _check_inputs(mbar, _family_basis(mbar, basis_bn, coeff_lb), coeff_lb, offset_l, A_qn, reference)
+    kinds, cen = _family_kinds(mbar, basis_given, basis_bn.shape[0], L, center_lb, harmonic_b, period_b)
     dm = _scan_matrix(mbar)
     Q = len(A_qn)
     t_qn, shift = _shifted(A_qn)
     dm.set_Nk(mbar.N_k)
-    dm.set_scan(basis_bn, t_qn)
+    dm.set_scan(basis_bn, t_qn, **kinds)
     try:
-        lognum, mean = dm.scan_lognum(mbar.f_k, coeff_lb, offset_l)
+        lognum, mean = dm.scan_lognum(mbar.f_k, coeff_lb, offset_l, **cen)
         f = -lognum
         out = dict(f=f, Delta_f=f - f[int(reference)])
         if Q:
@@ -188,7 +212,7 @@ def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, r
             try:
                 for b in range(mbar.n_bootstraps):
                     mbar._set_bootstrap_weights(dm, b)
-                    ln_b, mean_b = dm.scan_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l)
+                    ln_b, mean_b = dm.scan_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l, **cen)
                     fb[b] = -ln_b
                     Ab[b] = mean_b[:, 1:].T + shift[:, None]
             finally:
@@ -200,7 +224,7 @@ def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, r
                     out["sigma"] = np.std(Ab, axis=0)
         elif compute_uncertainty:
             out["dDelta_f"], sigma = _analytical(mbar, dm, coeff_lb, offset_l, f, mean, reference, uncertainty_method == "approximate",
-                                                 warning_cutoff)
+                                                 warning_cutoff, cen)
             if Q:
                 out["sigma"] = sigma
     finally:
@@ -232,12 +256,12 @@ def _neg_logsumexp_neg(f_raw):
     return -(m + np.log(s))
 
 
-def _fes_analytical(mbar, dm, coeff_lb, offset_l, f_raw, j_l, approximate):
+def _fes_analytical(mbar, dm, coeff_lb, offset_l, f_raw, j_l, approximate, cen={}):
     """``df_i`` of every member from pass B: ``Theta_ij = delta_ij d_li + y_li^T diag(g) y_lj`` (DESIGN.md section 16's border,
     per member), ``df^2 = Theta_ii + Theta_jj - 2 Theta_ij``."""
     L = len(f_raw)
     rows = np.arange(L)
-    cross, d, wsum = dm.scan_bin_gram_w(mbar.f_k, coeff_lb, offset_l, f_raw, cross=not approximate)
+    cross, d, wsum = dm.scan_bin_gram_w(mbar.f_k, coeff_lb, offset_l, f_raw, cross=not approximate, **cen)
     check_w_sums(wsum.ravel(), 0.0)
     dj = d[rows, j_l][:, None]
     if approximate:
@@ -251,7 +275,7 @@ def _fes_analytical(mbar, dm, coeff_lb, offset_l, f_raw, j_l, approximate):
 
 
 def compute_scan_fes(mbar, basis_bn=None, coeff_lb=None, offset_l=None, sample_label=None, reference="from-lowest", reference_label=None,
-                     uncertainty_method=None, theta_method=None, warning_cutoff=1.0e-10):
+                     uncertainty_method=None, theta_method=None, warning_cutoff=1.0e-10, center_lb=None, harmonic_b=None, period_b=None):
     """Histogram free energy surfaces of every member of a linear family of unsampled states: row ``l`` of every returned array
     is what ``fes.histogram_fes_labels(mbar, coeff_lb[l] @ basis_bn + offset_l[l], sample_label, reference, reference_label, ...)``
     returns, without a dense ``u_l``, an upload or a read of the resident matrix per member.
@@ -264,8 +288,11 @@ def compute_scan_fes(mbar, basis_bn=None, coeff_lb=None, offset_l=None, sample_l
     (``df_i``; ``theta_method`` None / "svd-ew": the bordered form, "approximate": the bin block alone, "svd": not offered) or
     "bootstrap" (``bootstrapped_f_raw`` ``(n_bootstraps, L, nbins)`` and ``df_i``, the ``std`` over the replicates of ``f^b_li -
     f^b_lj`` with ``j`` from the main estimate; a replicate that emptied the bin or the reference bin is left out, fewer than two
-    usable replicates give NaN)."""
+    usable replicates give NaN).  ``center_lb``, ``harmonic_b``, ``period_b``: a family with harmonic terms, as in
+    :func:`compute_scan`."""
     from .fes import _check_labels
+
+    basis_given = basis_bn
 
     if uncertainty_method not in (None, "analytical", "bootstrap"):
         raise ParameterError(f"Uncertainty_method {uncertainty_method} is not a valid option")
@@ -290,12 +317,13 @@ def compute_scan_fes(mbar, basis_bn=None, coeff_lb=None, offset_l=None, sample_l
             raise ParameterError("Specified reference point for FES not given")
     elif reference != "from-lowest":
         raise ParameterError(f"reference point method {reference} is not supported for histogram surfaces here")
+    kinds, cen = _family_kinds(mbar, basis_given, basis_bn.shape[0], L, center_lb, harmonic_b, period_b)
     dm = _scan_fes_matrix(mbar)
     dm.set_Nk(mbar.N_k)
-    dm.set_scan(basis_bn, None)
+    dm.set_scan(basis_bn, None, **kinds)
     try:
         dm.set_scan_bins(nbins, sample_label)
-        f_raw = -dm.scan_bin_lognum(mbar.f_k, coeff_lb, offset_l)
+        f_raw = -dm.scan_bin_lognum(mbar.f_k, coeff_lb, offset_l, **cen)
         j_l = _reference_bins(f_raw, reference, reference_label)
         rows = np.arange(L)
         out = dict(f_raw=f_raw, f_i=f_raw - f_raw[rows, j_l][:, None], reference=j_l, f=_neg_logsumexp_neg(f_raw))
@@ -304,7 +332,7 @@ def compute_scan_fes(mbar, basis_bn=None, coeff_lb=None, offset_l=None, sample_l
             try:
                 for b in range(mbar.n_bootstraps):
                     mbar._set_bootstrap_weights(dm, b)
-                    fb[b] = -dm.scan_bin_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l)
+                    fb[b] = -dm.scan_bin_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l, **cen)
             finally:
                 dm.set_sample_weights(None)
             out["bootstrapped_f_raw"] = fb
@@ -318,7 +346,7 @@ def compute_scan_fes(mbar, basis_bn=None, coeff_lb=None, offset_l=None, sample_l
                 df[ok] = np.nanstd(fall[:, ok], axis=0)
             out["df_i"] = df
         elif uncertainty_method == "analytical":
-            out["df_i"] = _fes_analytical(mbar, dm, coeff_lb, offset_l, f_raw, j_l, theta_method == "approximate")
+            out["df_i"] = _fes_analytical(mbar, dm, coeff_lb, offset_l, f_raw, j_l, theta_method == "approximate", cen)
     finally:
         dm.set_scan_bins(0)
         dm.set_scan(None)

@@ -155,6 +155,55 @@ def config5(seed=0, K=40, n_per_state=2500, unsampled=(7, 23)):
     return harmonic_u_kn(O_k, K_k, N_k, seed=seed) + (O_k, K_k)
 
 
+def family_u_kn(basis_bn, coeff_kb, offset_k=None, center_kb=None, harmonic_b=None, period_b=None):
+    """The dense ``(K, N)`` matrix of a family with harmonic terms (``MBAR.from_family``) in plain numpy: ``u[k, n] = offset_k[k] +
+    sum_b term_b``, a linear term ``coeff_kb[k, b] basis_bn[b, n]``, a harmonic one ``coeff_kb[k, b] w(basis_bn[b, n] - center_kb[k,
+    b])^2`` with the minimum image ``w(d) = d - P rint(d / P)`` for ``P = period_b[b] > 0`` and ``w(d) = d`` for 0.  The statement of
+    the family, not the device's rounding: the kernels evaluate one fixed chain of fused operations."""
+    basis_bn = np.asarray(basis_bn, dtype=np.float64)
+    coeff_kb = np.asarray(coeff_kb, dtype=np.float64)
+    K, B = coeff_kb.shape
+    u = np.zeros((K, basis_bn.shape[1])) + (0.0 if offset_k is None else np.asarray(offset_k, dtype=np.float64)[:, None])
+    harmonic_b = np.zeros(B, dtype=bool) if harmonic_b is None else np.asarray(harmonic_b, dtype=bool)
+    period_b = np.zeros(B) if period_b is None else np.asarray(period_b, dtype=np.float64)
+    for b in range(B):
+        if harmonic_b[b]:
+            d = basis_bn[b][None, :] - np.asarray(center_kb, dtype=np.float64)[:, b:b + 1]
+            if period_b[b] > 0:
+                d = d - period_b[b] * np.rint(d / period_b[b])
+            u += coeff_kb[:, b:b + 1] * d * d
+        else:
+            u += coeff_kb[:, b:b + 1] * basis_bn[b][None, :]
+    return u
+
+
+def periodic_umbrella_family(K=6, n_per_state=300, kappa=0.002, barrier=1.5, beta_k=None, seed=0):
+    """Umbrella sampling of a torsion ``chi`` (degrees, period 360) on the cosine potential ``E(chi) = barrier (1 + cos(3 chi))``:
+    ``K`` umbrellas ``u_k = beta_k [E + kappa / 2 wrap(chi - chi0_k)^2]`` with centres spread evenly over ``[-180, 180)``,
+    ``n_per_state`` samples each, drawn from the exact density of their umbrella by inversion on a grid of 0.01 degrees.  Returns
+    ``(basis_bn, coeff_kb, center_kb, harmonic_b, period_b, offset_k, N_k)`` as ``MBAR.from_family`` takes them: the basis is ``[E_n,
+    chi_n]``, the first term linear (``beta_k``), the second harmonic with period 360 (``beta_k kappa / 2`` around ``chi0_k``).
+    The umbrellas next to +-180 hold samples on both sides of the seam."""
+    rng = np.random.default_rng(seed)
+    chi0_k = -180.0 + 360.0 * (np.arange(K) + 0.5) / K
+    beta_k = np.ones(K) if beta_k is None else np.asarray(beta_k, dtype=np.float64)
+    energy = lambda chi: barrier * (1.0 + np.cos(np.deg2rad(3.0 * chi)))
+    edges = np.linspace(-180.0, 180.0, 36001)
+    mid = 0.5 * (edges[1:] + edges[:-1])
+    chi_n = np.empty(K * n_per_state)
+    for k in range(K):
+        d = mid - chi0_k[k]
+        d -= 360.0 * np.rint(d / 360.0)
+        cdf = np.cumsum(np.exp(-beta_k[k] * (energy(mid) + 0.5 * kappa * d * d)))
+        cell = np.searchsorted(cdf, rng.random(n_per_state) * cdf[-1])
+        chi_n[k * n_per_state:(k + 1) * n_per_state] = edges[cell] + rng.random(n_per_state) * (edges[1] - edges[0])
+    basis_bn = np.stack([energy(chi_n), chi_n])
+    coeff_kb = np.stack([beta_k, 0.5 * beta_k * kappa], axis=1)
+    center_kb = np.stack([np.zeros(K), chi0_k], axis=1)
+    return (basis_bn, coeff_kb, center_kb, np.array([False, True]), np.array([0.0, 360.0]), np.zeros(K),
+            np.full(K, n_per_state, dtype=np.int64))
+
+
 def correlated_timeseries_example(N=10000, tau=5.0, seed=None):
     """A Gaussian AR(1) series of length N with correlation time tau (Janke, Eq. 41), as float32.
 
