@@ -210,37 +210,36 @@ int mbar_ctx_vec_logshift(mbar_ctx* ctx, const double* A, double* shift_out);
  * built on the device from ONE vector and ONE label array -- the N x (K + nbins) host matrix of the reference is never
  * formed.  A +inf entry is a sample of weight zero in that state. */
 int mbar_ctx_fill_masked_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, const double* v_host, const int32_t* label_host);
-/* Rows of the resident matrix from a LINEAR FAMILY instead of an upload: rows [row0, row0 + nrows) become
- *   u[row0 + r][n] = fma(coeff[r][B-1], basis[B-1][n], ... fma(coeff[r][0], basis[0][n], offset[r]))        0 <= n < N_local
- * -- a temperature ladder beta_k E, pressures beta (E + p_k V), harmonic umbrellas (linear in E, x^2, x, 1), linear alchemical
- * coupling: every sampled state of such a simulation is B <= MBAR_SCAN_MAX_B coefficients over B shared per-sample vectors, and
- * 8 B N bytes cross the bus instead of 8 K N.  basis_host[B][ld_host] is C-contiguous and its columns [col0_host, col0_host +
- * N_local) are this context's samples (a rank passes the whole basis and its shard origin, as with mbar_ctx_upload_u; no
- * communication); coeff[nrows][B]; offset[nrows] or NULL (zeros).  The chain is the one the scan passes evaluate (mbar_scan_lognum):
- * a scan member with a sampled state's coefficients has that state's u to the bit.  The basis shard is staged in a temporary
- * device block that is released before return; the call returns with the stream idle.  Any K the context supports; nothing is
- * written outside the row range or behind column N_local.  MBAR_ERR_ARG: NULL basis_host / coeff, B outside [1, 8], a row range
- * outside [0, K], a column range outside ld_host; MBAR_ERR_STATE: an extension context (mbar_ctx_create_ext).  nrows = 0: MBAR_OK. */
-int mbar_ctx_fill_linear_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
-                              int64_t col0_host, const double* coeff, const double* offset);
-/* The same rows from a family with HARMONIC terms -- umbrella sampling on a periodic coordinate, u_k(n) = beta_k [E_n + kappa_k / 2
- * wrap(chi_n - chi0_k)^2], whose minimum image depends on sample AND state and is linear in no basis:
- *   u[row0 + r][n] = offset[r] + sum_{b < B} term_b(r, n), b ascending, from the offset:
+/* Rows of the resident matrix from a FAMILY OF STATES instead of an upload: rows [row0, row0 + nrows) become
+ *   u[row0 + r][n] = offset[r] + sum_{b < B} term_b(r, n), b ascending, from the offset:                    0 <= n < N_local
  *     kind[b] == 0   linear     u = fma(coeff[r][b], basis[b][n], u)
  *     kind[b] != 0   harmonic   d = basis[b][n] - center[r][b]
  *                               period[b] > 0:  m = rint(d * rP), d = fma(-period[b], m, d)      rP = 1.0 / period[b], rounded once
  *                               q = d * d;  u = fma(coeff[r][b], q, u)
  * every operation rounded once, nothing else contracted, rint to nearest even (a tie d = +-P / 2 gives the same q either way:
- * the value is continuous there).  At most MBAR_SCAN_MAX_H terms may be harmonic; period[b] = 0: a harmonic term that is not
- * periodic; center[nrows][B] and period[B] are read at the harmonic terms only (center NULL: allowed when no term is harmonic;
- * period NULL: no term is periodic); kind NULL: every term linear, and the rows are the bits of mbar_ctx_fill_linear_rows.  The
- * scan passes evaluate the same chain (mbar_ctx_set_scan_terms): a scan member with a sampled state's coeff, center and offset
- * has that state's row to the bit.  Staging, column shard and errors as mbar_ctx_fill_linear_rows; also MBAR_ERR_ARG: more than
- * MBAR_SCAN_MAX_H harmonic terms, a negative or non-finite period, a non-finite coefficient or centre. */
+ * the value is continuous there).  Linear terms alone are a temperature ladder beta_k E, pressures beta (E + p_k V), harmonic
+ * umbrellas (linear in E, x^2, x, 1), linear alchemical coupling; a harmonic term is umbrella sampling on a periodic coordinate,
+ * u_k(n) = beta_k [E_n + kappa_k / 2 wrap(chi_n - chi0_k)^2], whose minimum image depends on sample AND state and is linear in no
+ * basis.  Every sampled state of such a simulation is B <= MBAR_SCAN_MAX_B parameters over B shared per-sample vectors, and 8 B N
+ * bytes cross the bus instead of 8 K N.  basis_host[B][ld_host] is C-contiguous and its columns [col0_host, col0_host + N_local)
+ * are this context's samples (a rank passes the whole basis and its shard origin, as with mbar_ctx_upload_u; no communication);
+ * coeff[nrows][B]; offset[nrows] or NULL (zeros).  At most MBAR_SCAN_MAX_H terms may be harmonic; period[b] = 0: a harmonic term
+ * that is not periodic; center[nrows][B] and period[B] are read at the harmonic terms only (center NULL: allowed when no term is
+ * harmonic; period NULL: no term is periodic); kind NULL: every term linear.  The chain is the one the scan passes evaluate
+ * (mbar_scan_lognum, mbar_ctx_set_scan_terms): a scan member with a sampled state's coeff, center and offset has that state's row
+ * to the bit.  The basis shard is staged in a temporary device block that is released before return; the call returns with the
+ * stream idle.  Any K the context supports; nothing is written outside the row range or behind column N_local.  MBAR_ERR_ARG: NULL
+ * basis_host / coeff, B outside [1, 8], a row range outside [0, K], a column range outside ld_host, more than MBAR_SCAN_MAX_H
+ * harmonic terms, a negative or non-finite period, harmonic terms without center, a non-finite coefficient or centre;
+ * MBAR_ERR_STATE: an extension context (mbar_ctx_create_ext).  nrows = 0: MBAR_OK. */
 #define MBAR_SCAN_MAX_H 4
 int mbar_ctx_fill_family_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
                               int64_t col0_host, const double* coeff, const double* center, const double* offset, const int32_t* kind,
                               const double* period);
+/* mbar_ctx_fill_family_rows with center = kind = period = NULL, a LINEAR FAMILY: u[row0 + r][n] = fma(coeff[r][B-1], basis[B-1][n],
+ * ... fma(coeff[r][0], basis[0][n], offset[r])), the same bits, and the coefficients are not looked at on the host. */
+int mbar_ctx_fill_linear_rows(mbar_ctx* ctx, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
+                              int64_t col0_host, const double* coeff, const double* offset);
 /* Fill the shard on the device with the synthetic harmonic ladder of SURVEY.md 8(d):
  * global sample n (n_global0 <= n < n_global0+N_local) belongs to the state given by the
  * cumulative N_k_global, x_n ~ Normal(O_s, K_s^-1/2) from a counter-based RNG keyed by

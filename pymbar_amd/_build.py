@@ -15,7 +15,7 @@ LIB = os.path.join(CSRC, "libmbar_hip.so")
 # rounds 1-3; an edit to one family recompiles that family): shared device helpers in mbar_device.h.
 KERNEL_SOURCES = ["mbar_k_eval.hip", "mbar_k_gram.hip", "mbar_k_quad.hip", "mbar_k_pmode.hip", "mbar_k_fused.hip", "mbar_k_loop.hip",
                   "mbar_k_rows.hip", "mbar_k_kde.hip", "mbar_k_acf.hip", "mbar_k_bar.hip", "mbar_k_bspline.hip", "mbar_k_batch.hip", "mbar_k_hist.hip",
-                  "mbar_k_scan.hip", "mbar_k_linear.hip", "mbar_k_family.hip"]
+                  "mbar_k_scan.hip", "mbar_k_family.hip"]
 HOST_SOURCES = ["mbar_capi.cpp", "mbar_loops.cpp", "mbar_comm.cpp", "mbar_host.cpp", "mbar_kde.cpp", "mbar_acf.cpp",
                 "mbar_bar.cpp", "mbar_bspline.cpp", "mbar_batch.cpp", "mbar_hist.cpp", "mbar_scan.cpp"]  # (shared header: mbar_ctx.h)
 SOURCES = KERNEL_SOURCES + HOST_SOURCES

@@ -956,14 +956,21 @@ int mbar_ctx_fill_masked_rows(mbar_ctx* c, int64_t row0, int64_t nrows, const do
     return MBAR_OK;
 }
 
-int mbar_ctx_fill_linear_rows(mbar_ctx* c, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
-                              int64_t col0_host, const double* coeff, const double* offset) {
+// mbar_ctx_fill_family_rows and mbar_ctx_fill_linear_rows (who) are one call.  What both refuse first, in this order:
+static int fill_rows_refused(mbar_ctx* c, const char* who, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
+                             int64_t col0_host, const double* coeff) {
     if (!c || !basis_host || !coeff) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (c->ext_base) return fail(c, MBAR_ERR_STATE, "mbar_ctx_fill_linear_rows: not offered on an extension context");
-    if (B < 1 || B > SCAN_MAX_B) return fail(c, MBAR_ERR_ARG, "mbar_ctx_fill_linear_rows: 1 <= B <= 8 basis vectors");
+    if (c->ext_base) return fail(c, MBAR_ERR_STATE, std::string(who) + ": not offered on an extension context");
+    if (B < 1 || B > SCAN_MAX_B) return fail(c, MBAR_ERR_ARG, std::string(who) + ": 1 <= B <= 8 basis vectors");
     if (!rows_in_range(c, row0, nrows)) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
     if (col0_host < 0 || ld_host < 0 || col0_host > ld_host || c->N > ld_host - col0_host)
         return fail(c, MBAR_ERR_ARG, "column range out of bounds");
+    return MBAR_OK;
+}
+
+// and the fill itself, of arguments that passed fill_rows_refused; center is read when terms.mask names a harmonic term
+static int fill_rows(mbar_ctx* c, const char* who, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
+                     int64_t col0_host, const double* coeff, const double* center, const double* offset, const FamilyTerms& terms) {
     if (nrows == 0) return MBAR_OK;
     if (c->N == 0) {  // (a shard without columns: nothing to write)
         matrix_touched(c);
@@ -971,85 +978,60 @@ int mbar_ctx_fill_linear_rows(mbar_ctx* c, int64_t row0, int64_t nrows, int64_t 
     }
     HIPCHK(c, hipSetDevice(c->device));
     // the basis shard in a block of the cache, at the matrix's own pitch (whole 16-sample tiles: every column pair is aligned; what
-    // lies behind column N_local of the block is never read), and coeff[nrows][B] | offset[nrows]; both go back to the cache on
-    // return, after the stream has been drained
+    // lies behind column N_local of the block is never read), and coeff[nrows][B] | offset[nrows] | center[nrows][B] (with a
+    // harmonic term only: the kernel of a family without one does not read them); both blocks go back to the cache on return,
+    // after the stream has been drained
     DevBuf<double> dbasis, dmembers;
     HIPCHK(c, dbasis.grow((size_t)B * (size_t)c->ld));
-    HIPCHK(c, dmembers.grow((size_t)nrows * (size_t)(B + 1)));
+    HIPCHK(c, dmembers.grow((size_t)nrows * (size_t)((terms.mask ? 2 : 1) * B + 1)));
     double* d_coeff = dmembers;
-    double* d_off = dmembers + nrows * B;
+    double* d_off = d_coeff + nrows * B;
+    double* d_center = terms.mask ? d_off + nrows : nullptr;
+    const size_t members = (size_t)nrows * B * sizeof(double);
     hipError_t e = hipMemcpy2DAsync(dbasis, (size_t)c->ld * sizeof(double), basis_host + col0_host, (size_t)ld_host * sizeof(double),
                                     (size_t)c->N * sizeof(double), (size_t)B, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_coeff, coeff, (size_t)nrows * B * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_coeff, coeff, members, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
         e = offset ? hipMemcpyAsync(d_off, offset, (size_t)nrows * sizeof(double), hipMemcpyHostToDevice, c->stream)
                    : hipMemsetAsync(d_off, 0, (size_t)nrows * sizeof(double), c->stream);
+    if (e == hipSuccess && d_center) e = hipMemcpyAsync(d_center, center, members, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         ScopedTimer t(c, MBAR_TIMER_OTHER);
-        e = launch_fill_linear_rows(c->stream, c->u + row0 * c->ld, c->ld, c->N, nrows, (int)B, dbasis, c->ld, d_coeff, d_off);
+        e = launch_fill_rows(c->stream, c->u + row0 * c->ld, c->ld, c->N, nrows, (int)B, dbasis, c->ld, d_coeff, d_center, d_off, terms);
     }
     matrix_touched(c);
     // (drained on the error path too: the two blocks must not return to the cache with a copy into them in flight)
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(c, MBAR_ERR_HIP, std::string("mbar_ctx_fill_linear_rows: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, MBAR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     flush_timers(c);
     return MBAR_OK;
+}
+
+int mbar_ctx_fill_linear_rows(mbar_ctx* c, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
+                              int64_t col0_host, const double* coeff, const double* offset) {
+    const char* who = "mbar_ctx_fill_linear_rows";
+    int rc = fill_rows_refused(c, who, row0, nrows, B, basis_host, ld_host, col0_host, coeff);
+    if (rc) return rc;
+    return fill_rows(c, who, row0, nrows, B, basis_host, ld_host, col0_host, coeff, nullptr, offset, FamilyTerms{});
 }
 
 int mbar_ctx_fill_family_rows(mbar_ctx* c, int64_t row0, int64_t nrows, int64_t B, const double* basis_host, int64_t ld_host,
                               int64_t col0_host, const double* coeff, const double* center, const double* offset, const int32_t* kind,
                               const double* period) {
-    if (!c || !basis_host || !coeff) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    if (c->ext_base) return fail(c, MBAR_ERR_STATE, "mbar_ctx_fill_family_rows: not offered on an extension context");
-    if (B < 1 || B > SCAN_MAX_B) return fail(c, MBAR_ERR_ARG, "mbar_ctx_fill_family_rows: 1 <= B <= 8 basis vectors");
-    if (!rows_in_range(c, row0, nrows)) return fail(c, MBAR_ERR_ARG, "row range out of bounds");
-    if (col0_host < 0 || ld_host < 0 || col0_host > ld_host || c->N > ld_host - col0_host)
-        return fail(c, MBAR_ERR_ARG, "column range out of bounds");
+    const char* who = "mbar_ctx_fill_family_rows";
+    int rc = fill_rows_refused(c, who, row0, nrows, B, basis_host, ld_host, col0_host, coeff);
+    if (rc) return rc;
     FamilyTerms terms{};
     if (kind) {
-        int rc = family_terms(c, "mbar_ctx_fill_family_rows", B, kind, period, &terms);
+        rc = family_terms(c, who, B, kind, period, &terms);
         if (rc) return rc;
     }
     if (terms.mask && !center) return fail(c, MBAR_ERR_ARG, "mbar_ctx_fill_family_rows: a family with harmonic terms needs its centres");
     for (int64_t x = 0; x < nrows * B; ++x)
         if (!std::isfinite(coeff[x]) || (terms.mask && !std::isfinite(center[x])))
             return fail(c, MBAR_ERR_ARG, "mbar_ctx_fill_family_rows: the coefficients and the centres must be finite");
-    if (nrows == 0) return MBAR_OK;
-    if (c->N == 0) {  // (a shard without columns: nothing to write)
-        matrix_touched(c);
-        return MBAR_OK;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    // staged as mbar_ctx_fill_linear_rows stages them: the basis shard at the matrix's own pitch, and coeff[nrows][B] |
-    // center[nrows][B] (zeros in a family without a harmonic term) | offset[nrows]; both blocks go back to the cache on return,
-    // after the stream has been drained
-    DevBuf<double> dbasis, dmembers;
-    HIPCHK(c, dbasis.grow((size_t)B * (size_t)c->ld));
-    HIPCHK(c, dmembers.grow((size_t)nrows * (size_t)(2 * B + 1)));
-    double* d_coeff = dmembers;
-    double* d_center = d_coeff + nrows * B;
-    double* d_off = d_center + nrows * B;
-    const size_t members = (size_t)nrows * B * sizeof(double);
-    hipError_t e = hipMemcpy2DAsync(dbasis, (size_t)c->ld * sizeof(double), basis_host + col0_host, (size_t)ld_host * sizeof(double),
-                                    (size_t)c->N * sizeof(double), (size_t)B, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_coeff, coeff, members, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = terms.mask ? hipMemcpyAsync(d_center, center, members, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(d_center, 0, members, c->stream);
-    if (e == hipSuccess)
-        e = offset ? hipMemcpyAsync(d_off, offset, (size_t)nrows * sizeof(double), hipMemcpyHostToDevice, c->stream)
-                   : hipMemsetAsync(d_off, 0, (size_t)nrows * sizeof(double), c->stream);
-    if (e == hipSuccess) {
-        ScopedTimer t(c, MBAR_TIMER_OTHER);
-        e = launch_fill_family_rows(c->stream, c->u + row0 * c->ld, c->ld, c->N, nrows, (int)B, dbasis, c->ld, d_coeff, d_center, d_off, terms);
-    }
-    matrix_touched(c);
-    // (drained on the error path too: the two blocks must not return to the cache with a copy into them in flight)
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(c, MBAR_ERR_HIP, std::string("mbar_ctx_fill_family_rows: ") + hipGetErrorString(e));
-    flush_timers(c);
-    return MBAR_OK;
+    return fill_rows(c, who, row0, nrows, B, basis_host, ld_host, col0_host, coeff, center, offset, terms);
 }
 
 int mbar_ctx_download_u(mbar_ctx* c, double* out, int64_t ld_out) {

@@ -698,7 +698,7 @@ static inline bool stage_offsets_wide(int64_t ld) { return (uint64_t)ld * 56u + 
 hipError_t launch_fused_quad(hipStream_t s, int nbt, const LaunchGeom& g, const double* P, int64_t ld, int64_t N, const double* cmul,
                              const double* cw, const double* wsq, double* rinv0, double* gp, double* pp, const LoopCtl& lc);
 
-// ---- the scan kernels (mbar_k_scan.hip); mbar_k_linear.hip follows the same chain ---------------------------------------------
+// ---- the scan kernels (mbar_k_scan.hip); the fill kernel of mbar_k_family.hip follows the same chain --------------------------
 // One term of a member's chain, THE statement of it on the device: the fill kernels and both scan passes come through here, so a
 // scan member with a sampled state's parameters has that state's row to the bit.  u: the chain so far, v = basis[b][n], c: the
 // member's centre of term b (read at a harmonic term only).  The kind of term b is wave-uniform (terms.mask); the linear family

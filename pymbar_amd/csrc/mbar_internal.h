@@ -522,18 +522,17 @@ template <class Cut>
 hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int mb, int64_t K, int64_t L, int64_t p0,
                                    const double* part, double* cross, double* vec);
 
-// ---- rows of the resident matrix from a linear family (mbar_k_linear.hip; C ABI: mbar_ctx_fill_linear_rows in mbar_capi.cpp) --
+// ---- rows of the resident matrix from a family of states (mbar_k_family.hip; C ABI: mbar_ctx_fill_family_rows and ----------
+// ---- mbar_ctx_fill_linear_rows in mbar_capi.cpp) -----------------------------------------------------------------------------
 constexpr int FILL_THREADS = 256;      // a lane owns two adjacent columns: 512 columns per workgroup and pass
 constexpr int FILL_ROWS = 128;         // rows a lane writes from one read of its basis values (grid.y = row groups)
 constexpr int FILL_MAX_BLOCKS = 2048;  // grid.x; the column pairs go round it
-// rows[r][n] = fma(coeff[r][B-1], basis[B-1][n], ... fma(coeff[r][0], basis[0][n], offset[r])) for r < nrows, n < N: the chain of
-// scan_x.  rows (pitch ld) and basis (pitch ldb) 16-byte aligned with even pitches; coeff[nrows][B], offset[nrows] on the device
-hipError_t launch_fill_linear_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis,
-                                   int64_t ldb, const double* coeff, const double* offset);
-// the same rows from a family with harmonic terms (mbar_k_family.hip; C ABI: mbar_ctx_fill_family_rows): the chain of family_term,
-// the geometry and the preconditions of launch_fill_linear_rows; center[nrows][B] on the device (read at the harmonic terms only)
-hipError_t launch_fill_family_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis,
-                                   int64_t ldb, const double* coeff, const double* center, const double* offset, const FamilyTerms& terms);
+// rows[r][n] = offset[r] + sum_b term_b for r < nrows, n < N: the chain of family_term and scan_x, b ascending.  rows (pitch ld) and
+// basis (pitch ldb) 16-byte aligned with even pitches; coeff[nrows][B], center[nrows][B], offset[nrows] on the device.
+// terms.mask == 0, every term linear, rows[r][n] = fma(coeff[r][B-1], basis[B-1][n], ... fma(coeff[r][0], basis[0][n], offset[r])):
+// the ScanLinear instantiation, which never reads center (NULL will do); otherwise the FamilyTerms one
+hipError_t launch_fill_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis, int64_t ldb,
+                            const double* coeff, const double* center, const double* offset, const FamilyTerms& terms);
 
 // ---- lagged fluctuation sums of a timeseries (mbar_k_acf.hip; C ABI in mbar_acf.cpp) ----------------------------------------
 constexpr int ACF_WG = 256;                 // threads per workgroup

@@ -230,41 +230,29 @@ class DeviceMatrix(_ContextMatrix):
     @classmethod
     def from_linear(cls, basis_bn, coeff_kb, offset_k=None, device=None, columns=None, validate=True):
         """The matrix ``u[k, n] = sum_b coeff_kb[k, b] basis_bn[b, n] + offset_k[k]`` of a linear family, built ON THE DEVICE from
-        the ``B <= 8`` basis vectors (``mbar_ctx_fill_linear_rows``): ``8 B N`` bytes cross the bus instead of ``8 K N``.
-        ``columns=(n0, n1)`` as in :meth:`from_host`: only that slice of the samples (this rank's shard).  ``validate=False``: the
-        three arrays are what :func:`linear_family_inputs` returned (no second pass over the basis)."""
+        the ``B <= 8`` basis vectors: :meth:`from_family` without a harmonic term.  ``validate=False``: the three arrays are what
+        :func:`linear_family_inputs` returned (no second pass over the basis)."""
         if validate:
             basis_bn, coeff_kb, offset_k = linear_family_inputs(basis_bn, coeff_kb, offset_k)
-        n0, n1 = (0, basis_bn.shape[1]) if columns is None else columns
-        dm = cls(coeff_kb.shape[0], n1 - n0, device=device)
-        try:
-            dm.fill_linear_rows(0, basis_bn, coeff_kb, offset_k, col0=n0, validate=False)
-        except BaseException:
-            dm.close()
-            raise
-        return dm
+        return cls.from_family(basis_bn, coeff_kb, offset_k, device=device, columns=columns, validate=False)
 
     def fill_linear_rows(self, row0, basis_bn, coeff_rb, offset_r=None, col0=0, validate=True):
         """Rows ``[row0, row0 + R)`` become ``fma(coeff_rb[r, B-1], basis_bn[B-1, n], ... fma(coeff_rb[r, 0], basis_bn[0, n],
-        offset_r[r]))`` -- the chain of the scan passes -- on the device.  ``basis_bn`` is ``(B, >= col0 + N_local)``: its columns
-        ``[col0, col0 + N_local)`` are this matrix's samples.  ``validate=False`` as in :meth:`from_linear`."""
+        offset_r[r]))`` -- the chain of the scan passes -- on the device: :meth:`fill_family_rows` without a harmonic term.
+        ``validate=False`` as in :meth:`from_linear`."""
         if validate:
             basis_bn, coeff_rb, offset_r = linear_family_inputs(basis_bn, coeff_rb, offset_r)
-        col0 = int(col0)
-        if col0 < 0 or col0 + self.N_local > basis_bn.shape[1]:
-            raise ValueError("basis_bn must cover the columns [col0, col0 + N_local)")
-        self._touched()
-        B, R = basis_bn.shape[0], coeff_rb.shape[0]
-        self._check(self._lib.mbar_ctx_fill_linear_rows(self._ctx, int(row0), R, B, _dptr(basis_bn), basis_bn.shape[1], col0,
-                                                        _dptr(coeff_rb), _dptr(offset_r)))
+        self.fill_family_rows(row0, basis_bn, coeff_rb, offset_r, col0=col0, validate=False)
 
     @classmethod
     def from_family(cls, basis_bn, coeff_kb, offset_k=None, center_kb=None, harmonic_b=None, period_b=None, device=None, columns=None,
                     validate=True):
-        """:meth:`from_linear` for a family with harmonic terms (:func:`family_terms`): ``u[k, n] = offset_k[k] + sum_b term_b``,
-        a harmonic term ``coeff_kb[k, b] w(basis_bn[b, n] - center_kb[k, b])^2`` with its minimum image for ``period_b[b] > 0`` --
-        umbrella sampling on a torsion -- built ON THE DEVICE (``mbar_ctx_fill_family_rows``).  ``validate=False``: the arrays are
-        what :func:`linear_family_inputs`, :func:`family_terms` and :func:`family_centers` returned."""
+        """The matrix of a family of states (:func:`family_terms`), ``u[k, n] = offset_k[k] + sum_b term_b``, built ON THE DEVICE
+        from the ``B <= 8`` basis vectors (``mbar_ctx_fill_family_rows``): ``8 B N`` bytes cross the bus instead of ``8 K N``.  A
+        linear term is ``coeff_kb[k, b] basis_bn[b, n]``, a harmonic one ``coeff_kb[k, b] w(basis_bn[b, n] - center_kb[k, b])^2``
+        with its minimum image for ``period_b[b] > 0`` -- umbrella sampling on a torsion.  ``columns=(n0, n1)`` as in
+        :meth:`from_host`: only that slice of the samples (this rank's shard).  ``validate=False``: the arrays are what
+        :func:`linear_family_inputs`, :func:`family_terms` and :func:`family_centers` returned."""
         if validate:
             basis_bn, coeff_kb, offset_k = linear_family_inputs(basis_bn, coeff_kb, offset_k)
             harmonic_b, period_b = family_terms(basis_bn.shape[0], harmonic_b, period_b)
@@ -280,10 +268,11 @@ class DeviceMatrix(_ContextMatrix):
 
     def fill_family_rows(self, row0, basis_bn, coeff_rb, offset_r=None, center_rb=None, harmonic_b=None, period_b=None, col0=0,
                          validate=True):
-        """:meth:`fill_linear_rows` for a family with harmonic terms: rows ``[row0, row0 + R)`` become the chain the scan passes
-        evaluate -- from ``offset_r``, ``b`` ascending, ``fma(coeff, basis, u)`` at a linear term and ``d = basis - center; P > 0:
-        d = fma(-P, rint(d (1 / P)), d); fma(coeff, d d, u)`` at a harmonic one, every operation rounded once.  With no harmonic
-        term the rows are the bits of :meth:`fill_linear_rows`."""
+        """Rows ``[row0, row0 + R)`` become the chain the scan passes evaluate -- from ``offset_r``, ``b`` ascending,
+        ``fma(coeff, basis, u)`` at a linear term and ``d = basis - center; P > 0: d = fma(-P, rint(d (1 / P)), d); fma(coeff, d d,
+        u)`` at a harmonic one, every operation rounded once -- on the device.  ``basis_bn`` is ``(B, >= col0 + N_local)``: its
+        columns ``[col0, col0 + N_local)`` are this matrix's samples.  With no harmonic term the library runs the kernel of the
+        linear family."""
         if validate:
             basis_bn, coeff_rb, offset_r = linear_family_inputs(basis_bn, coeff_rb, offset_r)
             harmonic_b, period_b = family_terms(basis_bn.shape[0], harmonic_b, period_b)

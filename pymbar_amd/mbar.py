@@ -146,22 +146,7 @@ class MBAR:
         matrix to copy).  The object keeps private read-only copies ``basis_bn``, ``coeff_kb``, ``offset_k`` (``None`` on an object
         made by the constructor); ``compute_scan`` / ``compute_scan_fes`` default to that basis.  ``upload_stats``: ``upload_s`` is the
         basis upload plus the fill, ``upload_GBps`` counts the ``8 B N`` bytes that crossed the bus."""
-        from .device import linear_family_inputs
-
-        if "copy" in kwargs:
-            raise ParameterError("MBAR.from_linear has no host matrix to copy: the copy keyword is not accepted")
-        if kwargs.get("bootstrap_rng", "reference") not in ("reference", "device"):
-            raise ParameterError("bootstrap_rng must be 'reference' or 'device'")
-        basis_bn, coeff_kb, offset_k = linear_family_inputs(basis_bn, coeff_kb, offset_k, error=ParameterError)
-        if np.sum(np.asarray(N_k, dtype=np.int64)) != basis_bn.shape[1] or np.shape(N_k) != (coeff_kb.shape[0],):
-            raise ParameterError("N_k must have one entry per row of coeff_kb, and the sum of all N_k must equal the total number "
-                                 "of samples (length of second dimension of basis_bn).")
-        linear = (_private_copy_flat(basis_bn), np.array(coeff_kb), np.array(offset_k))  # (private copies: the caller's arrays stay theirs)
-        for a in linear:
-            a.setflags(write=False)
-        self = cls.__new__(cls)
-        self._construct(None, N_k, linear=linear, **kwargs)
-        return self
+        return cls._from_family("from_linear", basis_bn, coeff_kb, N_k, offset_k, **kwargs)
 
     @classmethod
     def from_family(cls, basis_bn, coeff_kb, N_k, offset_k=None, center_kb=None, harmonic_b=None, period_b=None, **kwargs):
@@ -179,10 +164,15 @@ class MBAR:
         Everything else -- the lazy ``u_kn``, ``kwargs``, the refused ``copy``, ``upload_stats`` -- is :meth:`from_linear`'s.  The
         object keeps private read-only ``center_kb``, ``harmonic_b``, ``period_b`` next to ``basis_bn``, ``coeff_kb``, ``offset_k``
         (``None`` on other objects); the scan methods default to the constructor's basis and term kinds."""
+        return cls._from_family("from_family", basis_bn, coeff_kb, N_k, offset_k, center_kb, harmonic_b, period_b, **kwargs)
+
+    @classmethod
+    def _from_family(cls, method, basis_bn, coeff_kb, N_k, offset_k=None, center_kb=None, harmonic_b=None, period_b=None, **kwargs):
+        """:meth:`from_family`, and :meth:`from_linear` as the family without harmonic arguments (``method``: the caller's name)."""
         from .device import family_centers, family_terms, linear_family_inputs
 
         if "copy" in kwargs:
-            raise ParameterError("MBAR.from_family has no host matrix to copy: the copy keyword is not accepted")
+            raise ParameterError(f"MBAR.{method} has no host matrix to copy: the copy keyword is not accepted")
         if kwargs.get("bootstrap_rng", "reference") not in ("reference", "device"):
             raise ParameterError("bootstrap_rng must be 'reference' or 'device'")
         basis_bn, coeff_kb, offset_k = linear_family_inputs(basis_bn, coeff_kb, offset_k, error=ParameterError)
@@ -191,12 +181,14 @@ class MBAR:
         if np.sum(np.asarray(N_k, dtype=np.int64)) != basis_bn.shape[1] or np.shape(N_k) != (coeff_kb.shape[0],):
             raise ParameterError("N_k must have one entry per row of coeff_kb, and the sum of all N_k must equal the total number "
                                  "of samples (length of second dimension of basis_bn).")
-        linear = (_private_copy_flat(basis_bn), np.array(coeff_kb), np.array(offset_k))
-        family = None if harmonic_b is None else (np.array(center_kb), np.array(harmonic_b), np.array(period_b))
-        for a in linear + (family or ()):
-            a.setflags(write=False)
+        # (private copies: the caller's arrays stay theirs; the last three are None in a family without a harmonic term)
+        family = (_private_copy_flat(basis_bn), np.array(coeff_kb), np.array(offset_k)) + tuple(
+            None if a is None else np.array(a) for a in (center_kb, harmonic_b, period_b))
+        for a in family:
+            if a is not None:
+                a.setflags(write=False)
         self = cls.__new__(cls)
-        self._construct(None, N_k, linear=linear, family=family, **kwargs)
+        self._construct(None, N_k, family=family, **kwargs)
         return self
 
     # ---- the host matrix -------------------------------------------------------------------------------------------
@@ -274,32 +266,28 @@ class MBAR:
 
         if getattr(self, "_dm", None) is None:
             t0 = _time.perf_counter()
-            if self.harmonic_b is not None:  # (made by from_family, and checked there)
-                self._dm = DeviceMatrix.from_family(self.basis_bn, self.coeff_kb, self.offset_k, self.center_kb, self.harmonic_b,
-                                                    self.period_b, device=device, validate=False)
-            else:
-                self._dm = DeviceMatrix.from_linear(self.basis_bn, self.coeff_kb, self.offset_k, device=device, validate=False)  # (checked by from_linear)
+            self._dm = DeviceMatrix.from_family(self.basis_bn, self.coeff_kb, self.offset_k, self.center_kb, self.harmonic_b,
+                                                self.period_b, device=device, validate=False)  # (checked by _from_family)
             self._linear_upload_s = _time.perf_counter() - t0
         return self._dm
 
     def _construct(self, u_kn, N_k, maximum_iterations=10000, relative_tolerance=1.0e-7, verbose=False, initial_f_k=None,
                    solver_protocol=None, initialize="zeros", x_kindices=None, n_bootstraps=0, bootstrap_solver_protocol=None, rseed=None,
-                   device=None, copy=True, bootstrap_rng="reference", linear=None, family=None):
-        """The constructor: of a host matrix ``u_kn``, or (``linear = (basis_bn, coeff_kb, offset_k)``, checked) of a linear family,
-        with ``family = (center_kb, harmonic_b, period_b)`` (checked) of one with harmonic terms."""
+                   device=None, copy=True, bootstrap_rng="reference", family=None):
+        """The constructor: of a host matrix ``u_kn``, or of ``family = (basis_bn, coeff_kb, offset_k, center_kb, harmonic_b,
+        period_b)`` (checked; the last three None without a harmonic term)."""
         from .device import DeviceMatrix
 
         if bootstrap_rng not in ("reference", "device"):  # (before the upload and the main solve: a typo must not cost either)
             raise ParameterError("bootstrap_rng must be 'reference' or 'device'")
         self.N_k = np.array(N_k, dtype=np.int64)
         self.N = int(np.sum(self.N_k))
-        self.basis_bn, self.coeff_kb, self.offset_k = (None, None, None) if linear is None else linear
-        self.center_kb, self.harmonic_b, self.period_b = (None, None, None) if family is None else family
+        self.basis_bn, self.coeff_kb, self.offset_k, self.center_kb, self.harmonic_b, self.period_b = family or (None,) * 6
         self._u_kn = None
         self._dm = None
-        early_upload = None if linear is not None else self._keep_host_matrix(u_kn, copy, device)
+        early_upload = None if family is not None else self._keep_host_matrix(u_kn, copy, device)
         try:
-            if linear is not None:
+            if family is not None:
                 K, N = self.coeff_kb.shape[0], self.basis_bn.shape[1]
             else:
                 if self.u_kn.ndim != 2:
@@ -326,13 +314,10 @@ class MBAR:
             maxpoint = min(50, self.N)
             indices = self.rng.choice(np.arange(self.N), maxpoint)
             if self.verbose:
-                if linear is not None:  # (the <= 50 columns from the basis, on the host: no download for a log line)
-                    if family is not None:
-                        from .testsystems import family_u_kn
+                if family is not None:  # (the <= 50 columns from the basis, on the host: no download for a log line)
+                    from .testsystems import family_u_kn
 
-                        sub = family_u_kn(self.basis_bn[:, indices], self.coeff_kb, self.offset_k, *family)
-                    else:
-                        sub = self.coeff_kb @ self.basis_bn[:, indices] + self.offset_k[:, None]
+                    sub = family_u_kn(self.basis_bn[:, indices], *family[1:])
                 else:
                     sub = self.u_kn[:, indices]
                 for k in range(K):
@@ -357,7 +342,7 @@ class MBAR:
                     raise ParameterError("initial_f_k must be a {:d}-dimensional np array.".format(K))
                 self.f_k = initial_f_k - initial_f_k[0]
             else:
-                if linear is not None and initialize in ("mean-reduced-potential", "BAR"):
+                if family is not None and initialize in ("mean-reduced-potential", "BAR"):
                     self._linear_matrix(device)  # (these two read u_kn: the matrix is built now and downloaded)
                 self._initializeFreeEnergies(verbose, method=initialize)
 
@@ -386,13 +371,13 @@ class MBAR:
                 raise early_upload["err"]
             self._dm = early_upload["dm"]
             _dt = early_upload["dt"]
-        elif linear is not None:
+        elif family is not None:
             self._linear_matrix(device)
             _dt = self._linear_upload_s
         else:
             self._dm = DeviceMatrix.from_host(self.u_kn, device=device)
             _dt = _time.perf_counter() - _t0
-        _bus_rows = K if linear is None else self.basis_bn.shape[0]  # (a linear family: only the basis crossed the bus)
+        _bus_rows = K if family is None else self.basis_bn.shape[0]  # (a linear family: only the basis crossed the bus)
         self.upload_stats = dict(upload_s=_dt, upload_GBps=8.0 * _bus_rows * N / _dt * 1e-9 if _dt > 0 else float("inf"))
         self.f_k = mbar_solvers.solve_mbar_for_all_states(self._dm, self.N_k, self.f_k, self.states_with_samples,
                                                           solver_protocol)

@@ -1,4 +1,4 @@
-"""CPU stand-in of the harmonic-family builders and scan passes of ``pymbar_amd.device.DeviceMatrix`` -- TEST INFRASTRUCTURE ONLY.
+"""CPU stand-in of the family builders and scan passes of ``pymbar_amd.device.DeviceMatrix`` -- TEST INFRASTRUCTURE ONLY.
 
 ``u_model_family`` is the exact statement of the chain the fill kernel and both scan passes evaluate (``family_term``,
 pymbar_amd/csrc/mbar_device.h): from the offset, ``b`` ascending, a linear term ``u = fma(cf, v, u)``, a harmonic one
@@ -6,9 +6,10 @@ pymbar_amd/csrc/mbar_device.h): from the offset, ``b`` ascending, a linear term 
     d = v - c;  P > 0: m = rint(d * rP), d = fma(-P, m, d)  (rP = 1.0 / P);  q = d * d;  u = fma(cf, q, u)
 
 every operation rounded once: the exact vectorised ``fma`` of ``tests/device_math_model.py``, numpy's ``rint`` (ties to even) and
-plain float64 ``-`` and ``*``.  ``FamilyOracleMatrix`` feeds the long-double stand-ins of the passes (tests/scan_standin.py,
-tests/scan_fes_standin.py) the model's ``u_l`` and gives the oracle handle ``from_family`` / ``fill_family_rows``.  Nothing under
-``pymbar_amd/`` imports this.
+plain float64 ``-`` and ``*``.  ``u_model`` is its name without harmonic terms, the linear family: one fma per term.
+``FamilyOracleMatrix`` feeds the long-double stand-ins of the passes (tests/scan_standin.py, tests/scan_fes_standin.py) the
+model's ``u_l`` and gives the oracle handle ``from_family`` / ``fill_family_rows`` and, as forwards like the real class's,
+``from_linear`` / ``fill_linear_rows``.  Nothing under ``pymbar_amd/`` imports this.
 
 Also the builder of the cases the harmonic passes are tested at (``build_family_case``) and the instantiation matrix of the
 harmonic policy's pass-B kernel (``family_instantiation_cases``)."""
@@ -16,7 +17,6 @@ import numpy as np
 
 from pymbar_amd import testsystems
 from tests.device_math_model import fma
-from tests.linear_standin import LinearOracleMatrix
 from tests.scan_fes_standin import ScanFesOracleMatrix
 from tests.scan_standin import scan_nb_for
 
@@ -48,13 +48,29 @@ def u_model_family(basis_bn, coeff_kb, offset_k=None, center_kb=None, harmonic_b
     return np.ascontiguousarray(u)
 
 
-class FamilyOracleMatrix(ScanFesOracleMatrix, LinearOracleMatrix):
+def u_model(basis_bn, coeff_kb, offset_k=None):
+    """``u[k, n] = fma(coeff[k, B-1], basis[B-1, n], ... fma(coeff[k, 0], basis[0, n], offset[k]))``, (K, N) float64: the model
+    without harmonic terms."""
+    return u_model_family(basis_bn, coeff_kb, offset_k)
+
+
+class FamilyOracleMatrix(ScanFesOracleMatrix):
     """The long-double scan passes (whole and binned cut) on members whose ``u_l`` is the model's, and the family builders."""
 
+    created = 0  # handles made since a test last reset it ("before any device matrix is created")
+
     def __init__(self, u_shard, allreduce=None):
+        type(self).created += 1
         super().__init__(u_shard, allreduce=allreduce)
         self._kinds = None
         self._centers = None
+
+    @classmethod
+    def from_linear(cls, basis_bn, coeff_kb, offset_k=None, device=None, columns=None, validate=True):
+        return cls.from_family(basis_bn, coeff_kb, offset_k, device=device, columns=columns, validate=validate)
+
+    def fill_linear_rows(self, row0, basis_bn, coeff_rb, offset_r=None, col0=0, validate=True):
+        self.fill_family_rows(row0, basis_bn, coeff_rb, offset_r, col0=col0, validate=validate)
 
     @classmethod
     def from_family(cls, basis_bn, coeff_kb, offset_k=None, center_kb=None, harmonic_b=None, period_b=None, device=None, columns=None,

@@ -68,10 +68,15 @@ def test_wrap_model_is_the_minimum_image():
 
 
 def test_model_without_harmonic_terms_is_the_linear_model(umbrella):
-    from tests.linear_standin import u_model
+    from tests.device_math_model import fma
+    from tests.family_standin import u_model
 
     a = u_model_family(umbrella["basis"], umbrella["coeff"], umbrella["offset"])
     assert np.array_equal(a, u_model(umbrella["basis"], umbrella["coeff"], umbrella["offset"]))
+    chain = np.repeat(umbrella["offset"][:, None], umbrella["basis"].shape[1], axis=1)  # (the linear chain written out: one fma per term)
+    for b in range(umbrella["basis"].shape[0]):
+        chain = fma(umbrella["coeff"][:, b:b + 1], umbrella["basis"][b][None, :], chain)
+    assert np.array_equal(a, chain)
     assert np.array_equal(a, u_model_family(umbrella["basis"], umbrella["coeff"], umbrella["offset"], umbrella["center"], [False, False], [0.0, 360.0]))
 
 

@@ -1,7 +1,7 @@
 """Families with harmonic terms on the MI355X (``mbar_ctx_fill_family_rows``, mbar_k_family.hip; ``mbar_ctx_set_scan_terms`` /
 ``mbar_ctx_set_scan_centers`` and the harmonic policy of mbar_k_scan.hip; ``MBAR.from_family``, ``compute_scan`` /
 ``compute_scan_fes`` with periodic members): the fill bit for bit against the model of the chain (tests/family_standin.py), the
-all-linear family through the new entry points against the bits of the old ones, the passes against the long-double stand-in at
+all-linear family through either entry point and at every B, the passes against the long-double stand-in at
 the tolerances of tests/test_gpu_scan.py (lognum and wsum 1e-11 absolute, the products rtol 1e-10) and at every (NB, J) the
 harmonic policy is compiled for, fill and scan on one chain, the binned cut, the class journey, the reference's fixture and the
 refusals of the library.  Shapes are (K, N, L, B, H, Q)."""
@@ -17,7 +17,7 @@ from pymbar_amd.device import DeviceMatrix, _dptr
 from tests.conftest import load_golden
 from tests.family_standin import (PASS_SHAPES, FamilyOracleMatrix, build_family_case, family_case_id, family_instantiation_cases,
                                   load_family_case, run_family_fes_passes, run_family_passes, u_model_family)
-from tests.linear_standin import u_model
+from tests.family_standin import u_model
 from tests.scan_fes_standin import build_fes_case, check_passes, check_row_against_label_path, run_fes_passes
 from tests.scan_fes_standin import load_case as load_fes_case
 from tests.scan_standin import build_case, run_passes
@@ -60,11 +60,25 @@ def fill_family(R, N, B, seed=0):
     return basis, coeff, center, rng.normal(0.0, 1.0, R), harmonic, period
 
 
-@pytest.mark.parametrize("shape", [(130, 1027, 3), (5, 1, 1)], ids=lambda s: "R%d-N%d-B%d" % s)
+EVERY_B = range(1, 9)  # every B the fill kernel is compiled for, under both policies
+
+
+def every_b_family(B):
+    """131 rows over 259 samples with H = min(B, 1 + B % 4) harmonic terms among the B: the row-group seam at 128 and a remainder of
+    the row loop's unroll by 2 and by 4; 129 column pairs -- a second workgroup with one pair -- and the odd column."""
+    case = build_family_case((3, 259, 131, B, min(B, 1 + B % 4), 0))
+    return case["basis"], case["coeff"], case["center"], case["offset"], case["harmonic_b"], case["period_b"]
+
+
+@pytest.mark.parametrize("shape", [(130, 1027, 3), (5, 1, 1)] + [(131, 259, "every%d" % B) for B in EVERY_B],
+                         ids=lambda s: "R%d-N%d-B%s" % s)
 def test_fill_has_the_models_bits(shape):
-    """130 rows: the row-group seam at 128; N = 1027: two workgroups of column pairs and the odd column; N = 1: the odd column alone"""
+    """130 rows: the row-group seam at 128; N = 1027: two workgroups of column pairs and the odd column; N = 1: the odd column alone;
+    every1 .. every8: the harmonic policy at every B it is compiled for (every_b_family)"""
     R, N, B = shape
-    basis, coeff, center, off, hb, pb = fill_family(R, N, B)
+    every = isinstance(B, str)
+    basis, coeff, center, off, hb, pb = every_b_family(int(B[5:])) if every else fill_family(R, N, B)
+    assert basis.shape[1] == N and coeff.shape[0] == R and hb.any()
     want = u_model_family(basis, coeff, off, center, hb, pb)
     with DeviceMatrix.from_family(basis, coeff, off, center, hb, pb) as dm:
         got = dm.to_host()
@@ -73,7 +87,7 @@ def test_fill_has_the_models_bits(shape):
     assert np.array_equal(got, want)
     # the probes are what they are there for: a tie gives (P / 2)^2 from either side, a whole period gives 0
     hp = 1 if B == 3 else 0
-    if N >= len(PROBES):
+    if not every and N >= len(PROBES):
         one = u_model_family(basis[hp:hp + 1], np.ones((1, 1)), None, center[:1, hp:hp + 1], [True], [P])[0]
         assert one[1] == one[2] == (0.5 * P) ** 2 and one[7] == one[8] == 0.0 and one[3] < one[1] and one[4] < one[1]
 
@@ -110,16 +124,42 @@ def test_partial_fill_padding_and_shards():
 
 
 # ---- the linear policy is what it was ---------------------------------------------------------------------------------------
+def capi_fill(symbol, basis, coeff, off, *family):
+    """The rows of one direct call of an exported fill entry point (``family``: center, kind, period behind the linear one's
+    arguments) on an empty matrix."""
+    ptr = lambda a, t=C.c_double: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    R, (B, N) = coeff.shape[0], basis.shape
+    with DeviceMatrix.empty(R, N) as dm:
+        args = [dm._ctx, 0, R, B, ptr(basis), N, 0, ptr(coeff)]
+        if family:
+            center, kind, period = family
+            args += [ptr(center), ptr(off), ptr(kind, C.c_int32), ptr(period)]
+        else:
+            args += [ptr(off)]
+        dm._check(getattr(dm._lib, symbol)(*args))
+        return dm.to_host()
+
+
 def test_all_linear_family_returns_the_bits_of_the_linear_entry_points():
     shape = LINEAR_SHAPES[1]
     case = build_case(shape, True)
     K, N, L, B, Q = shape
     none = np.zeros(B, dtype=bool)
     zeros = np.zeros((L, B))
-    with DeviceMatrix.from_linear(case["basis"], case["coeff"][:K], case["offset"][:K]) as a, \
-            DeviceMatrix.from_family(case["basis"], case["coeff"][:K], case["offset"][:K], np.zeros((K, B)), none, np.zeros(B)) as b:
-        ua, ub = a.to_host(), b.to_host()
+    # the fill: one direct call per exported symbol
+    basis, coeff, off = (np.ascontiguousarray(case[k], dtype=np.float64) for k in ("basis", "coeff", "offset"))
+    ua = capi_fill("mbar_ctx_fill_linear_rows", basis, coeff[:K].copy(), off[:K].copy())
+    ub = capi_fill("mbar_ctx_fill_family_rows", basis, coeff[:K].copy(), off[:K].copy(), np.zeros((K, B)), np.zeros(B, dtype=np.int32), np.zeros(B))
     assert np.array_equal(ua, ub) and np.array_equal(ua, u_model(case["basis"], case["coeff"][:K], case["offset"][:K]))
+    # and at every B the linear policy is compiled for, on the rows and columns of every_b_family: kind NULL, and kind all zero
+    # with centres and periods set and ignored
+    for b in EVERY_B:
+        basis, coeff, center, off, _, pb = every_b_family(b)
+        want = u_model(basis, coeff, off)
+        lin = capi_fill("mbar_ctx_fill_linear_rows", basis, coeff, off)
+        null = capi_fill("mbar_ctx_fill_family_rows", basis, coeff, off, None, None, None)
+        zero = capi_fill("mbar_ctx_fill_family_rows", basis, coeff, off, center, np.zeros(b, dtype=np.int32), pb)
+        assert bits(lin) == bits(want) and bits(null) == bits(want) and bits(zero) == bits(want), b
     fcase = build_fes_case((K, N, L, B, 7), True)
     with DeviceMatrix.from_host(case["u"]) as dm:
         dm.set_Nk(case["N_k"])

@@ -1,6 +1,6 @@
-"""``k_fill_linear_rows`` / ``mbar_ctx_fill_linear_rows`` / ``MBAR.from_linear`` on an MI355X.
+"""The linear policy of ``k_fill_rows`` (mbar_k_family.hip) / ``mbar_ctx_fill_linear_rows`` / ``MBAR.from_linear`` on an MI355X.
 
-The exact statement of the kernel is ``u_model`` (tests/linear_standin.py): the scan passes' fma chain -- from the offset, ``b``
+The exact statement of the kernel is ``u_model`` (tests/family_standin.py): the scan passes' fma chain -- from the offset, ``b``
 ascending, one fma per term -- evaluated with the exact ``fma`` of tests/device_math_model.py.  "Same bits" is ``np.array_equal``.
 The class tests compare with ``MBAR(u_model, N_k)`` on the same device: the same resident matrix, so the same bits in everything
 computed from it."""
@@ -17,10 +17,10 @@ from pymbar_amd.device import DeviceMatrix, LoopbackGroup  # noqa: E402
 from pymbar_amd.distributed import shard_bounds  # noqa: E402
 from pymbar_amd.utils import DataError, ParameterError  # noqa: E402
 from tests.conftest import load_golden  # noqa: E402
-from tests.linear_standin import u_model  # noqa: E402
+from tests.family_standin import u_model  # noqa: E402
 from tests.test_gpu_loopback import run_ranks  # noqa: E402
 
-# The geometry of k_fill_linear_rows (mbar_internal.h): a lane owns 2 adjacent columns, 256 lanes per workgroup, at most 2048
+# The geometry of k_fill_rows (mbar_internal.h): a lane owns 2 adjacent columns, 256 lanes per workgroup, at most 2048
 # workgroups along the columns (the pairs go round them), 128 rows per row group (grid.y), the row loop unrolled by 4.  One pass of
 # the largest grid covers 2048 * 256 * 2 = 1048576 columns; N2 is one more than twice that: a full pass, a full second pass and
 # the odd last column.

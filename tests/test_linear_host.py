@@ -10,12 +10,12 @@ import pymbar_amd
 import pymbar_amd.device
 from pymbar_amd import testsystems as ts
 from pymbar_amd.utils import DataError, ParameterError
-from tests.linear_standin import LinearOracleMatrix, u_model
+from tests.family_standin import FamilyOracleMatrix, u_model
 
 
 @pytest.fixture(autouse=True)
 def standin(monkeypatch):
-    monkeypatch.setattr(pymbar_amd.device, "DeviceMatrix", LinearOracleMatrix)
+    monkeypatch.setattr(pymbar_amd.device, "DeviceMatrix", FamilyOracleMatrix)
 
 
 @pytest.fixture(scope="module")
@@ -127,11 +127,11 @@ def test_argument_errors_come_before_any_device_matrix(family):
         (DataError, (basis, infc, N_k), dict(offset_k=offset)),
         (DataError, (basis, coeff, N_k), dict(offset_k=nano)),
     ]
-    LinearOracleMatrix.created = 0
+    FamilyOracleMatrix.created = 0
     for exc, args, kwargs in cases:
         with pytest.raises(exc):
             pymbar_amd.MBAR.from_linear(*args, **kwargs)
-    assert LinearOracleMatrix.created == 0
+    assert FamilyOracleMatrix.created == 0
     with pytest.raises(TypeError):
         pymbar_amd.MBAR.from_linear(basis, coeff, N_k, no_such_keyword=1)
     # the constructor's own errors keep their meaning
