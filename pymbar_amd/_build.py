@@ -16,8 +16,9 @@ LIB = os.path.join(CSRC, "libmbar_hip.so")
 KERNEL_SOURCES = ["mbar_k_eval.hip", "mbar_k_gram.hip", "mbar_k_quad.hip", "mbar_k_pmode.hip", "mbar_k_fused.hip", "mbar_k_loop.hip",
                   "mbar_k_rows.hip", "mbar_k_kde.hip", "mbar_k_acf.hip", "mbar_k_bar.hip", "mbar_k_bspline.hip", "mbar_k_batch.hip", "mbar_k_hist.hip",
                   "mbar_k_scan.hip", "mbar_k_family.hip"]
-HOST_SOURCES = ["mbar_capi.cpp", "mbar_loops.cpp", "mbar_comm.cpp", "mbar_host.cpp", "mbar_kde.cpp", "mbar_acf.cpp",
-                "mbar_bar.cpp", "mbar_bspline.cpp", "mbar_batch.cpp", "mbar_hist.cpp", "mbar_scan.cpp"]  # (shared header: mbar_ctx.h)
+HOST_SOURCES = ["mbar_capi.cpp", "mbar_eval.cpp", "mbar_rows.cpp", "mbar_ext.cpp", "mbar_loops.cpp", "mbar_comm.cpp", "mbar_host.cpp",
+                "mbar_kde.cpp", "mbar_acf.cpp", "mbar_bar.cpp", "mbar_bspline.cpp", "mbar_batch.cpp", "mbar_hist.cpp",
+                "mbar_scan.cpp"]  # (shared header: mbar_ctx.h)
 SOURCES = KERNEL_SOURCES + HOST_SOURCES
 COMMON_DEPS = ["mbar_internal.h", os.path.join("..", "..", "include", "mbar_hip.h")]
 HOST_DEPS = ["mbar_ctx.h"]
@@ -53,7 +54,8 @@ def build_library(force=False, verbose=True):
                 os.remove(os.path.join(CSRC, f))
     if not _stale(LIB, DEPS) and not force:
         return LIB
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 2)) as ex:
+    # (MAX_JOBS: what a build may use where the machine reports more processors than the job has been given)
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), int(os.environ.get("MAX_JOBS", 16)))) as ex:
         objs = list(ex.map(_compile, SOURCES))
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
     subprocess.run(cmd, check=True, cwd=CSRC)

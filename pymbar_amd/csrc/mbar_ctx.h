@@ -1,7 +1,14 @@
 // Internal header of the host side of libmbar_hip.so (not part of the public ABI): the context, the caching allocator, and the
-// helpers the translation units of the host side share -- mbar_capi.cpp (contexts, uploads, options, evaluations), mbar_loops.cpp
-// (the solver loops the reference writes in Python), mbar_comm.cpp (RCCL loader, in-process transport, all-reduce),
-// mbar_host.cpp (allocator state, host-side K x K linear algebra, content digest).
+// helpers the translation units of the context layer share, one file per role:
+//   mbar_capi.cpp   context lifecycle and buffers (constructors, destroy, ensure / reserve, options, N_k, sample weights,
+//                   bootstrap draws, timing)
+//   mbar_eval.cpp   the evaluation engine (run_lse, the Gram plans, run_gram, eval_core) and the evaluation entry points
+//   mbar_rows.cpp   every writer of the resident matrix, and its download
+//   mbar_ext.cpp    the entry points that take an extension context and its base
+//   mbar_loops.cpp  the solver loops the reference writes in Python
+//   mbar_scan.cpp, mbar_hist.cpp  the scan passes and the binned passes
+//   mbar_comm.cpp   RCCL loader, in-process transport, all-reduce
+//   mbar_host.cpp   allocator state, host-side K x K linear algebra, content digest
 // The handles of the other backends (mbar_kde.cpp, mbar_acf.cpp, mbar_bar.cpp, mbar_bspline.cpp, mbar_batch.cpp) share the layer
 // below the context: Handle, DevBuf, create_handle / destroy_handle, ColumnPasses, run_passes.
 #pragma once
@@ -620,20 +627,36 @@ struct GramPlan {
     size_t total_blocks = 0;
 };
 
-// ---- shared functions (definitions: see the file list above) ----
+// ---- mbar_capi.cpp: context lifecycle and buffers ----
 void flush_timers(mbar_ctx* c);
 int sync_stream(mbar_ctx* c);
 int drop_graphs(mbar_ctx* c);
+// The sizing rule of the context's work buffers: an entry point sizes part, scratch, red / hred for everything it is about to
+// enqueue BEFORE its first launch -- ensure / ensure_red / reserve are never reached with work of the same call in flight (a
+// block they replace goes back to the shared pool at once).  Should a call get there all the same, they drain the stream first.
 int ensure(mbar_ctx* c, DevBuf<double>& buf, size_t want);  // grow, after drop_graphs: captured graphs hold these pointers
+int ensure_red(mbar_ctx* c, size_t want);                   // red and its pinned mirror grow together
+// What the launches of one call need of part and of the level-1 reduction scratch: the largest of their per-wave record sets
+struct RecordNeed {
+    size_t part = 0, scratch = 0;
+    void add(int nwaves, size_t rec) {  // one launch that leaves `nwaves` records of `rec` doubles
+        part = std::max(part, (size_t)nwaves * rec);
+        scratch = std::max(scratch, ((size_t)nwaves / 32 + 1) * rec);
+    }
+};
+int reserve(mbar_ctx* c, const RecordNeed& need);
 int need_zeroed_vec(mbar_ctx* c, DevBuf<double>& v);  // one ld-vector, allocated and zeroed at its first use
 int refresh_poison(mbar_ctx* c);
+// What the binned passes (mbar_hist.cpp) and the scan passes (mbar_scan.cpp) ask of a context before anything else.
+// family: "the binned passes" / "the scan passes", as the messages word it; max_K: the most states the family serves, 0: no limit.
+int passes_ready(mbar_ctx* c, const char* who, const char* family, int64_t max_K);
+// the refusal of the entry points an extension context does not serve
+inline int ext_holds_rows_only(mbar_ctx* c, const char* who) {
+    return fail(c, MBAR_ERR_STATE, std::string(who) + ": an extension context holds rows only (mbar_lognum_ext / mbar_gram_w_ext sweep them)");
+}
+
+// ---- mbar_eval.cpp: the evaluation engine ----
 bool f_is_finite(const mbar_ctx* c, const double* f, int nf);
-bool loop_barrier(mbar_loopback* g);
-void loop_break(mbar_loopback* g);
-int allreduce_loop(mbar_ctx* c, double* dev, int64_t count, int op);
-int allreduce_dev(mbar_ctx* c, double* dev, int64_t count, int op);
-int allreduce_host(mbar_ctx* c, double* host, int64_t count, int op);
-int agree_with_rank0(mbar_ctx* c, double* v, int64_t count);
 bool wide_pitch(const mbar_ctx* c);
 int lse_variant_for(const mbar_ctx* c);
 bool use_fast(const mbar_ctx* c);
@@ -645,26 +668,87 @@ GramPlan gram_plan_pmode(int64_t Kp);
 bool use_quad(const mbar_ctx* c);
 GramPlan plan_for(const mbar_ctx* c);
 int quad_live_blocks(const mbar_ctx* c);
+// part and scratch for every launch of run_gram on this plan (pmode: on a resident probability matrix); geom (if any) receives the
+// launch geometry of every item.  run_gram calls it itself; a caller that enqueues anything before run_gram calls it first.
+int reserve_gram(mbar_ctx* c, const GramPlan& plan, bool pmode, std::vector<LaunchGeom>* geom = nullptr);
 int run_gram(mbar_ctx* c, const double* anum_dev, const double* logden, size_t red_off, const GramPlan& plan, const double* pmat = nullptr);
+// One Gram launch and the reduction of its per-wave records: `nwaves` records of `rec` doubles, which launch() (a callable that
+// returns an MBAR code) leaves in c->part, summed into `dst`.  part and scratch hold them already (reserve).
+template <class Launch>
+int launch_and_reduce(mbar_ctx* c, int nwaves, size_t rec, double* dst, Launch&& launch) {
+    {
+        ScopedTimer t(c, MBAR_TIMER_GRAM);
+        int rc = launch();
+        if (rc) return rc;
+    }
+    ScopedTimer t(c, MBAR_TIMER_REDUCE);
+    HIPCHK(c, launch_reduce(c->stream, c->part, nwaves, (int64_t)rec, c->scratch, dst));
+    return MBAR_OK;
+}
+// logden with the multiplicities of `w` folded in, logden - alpha ln c_n, written to w->lden_eff on `stream` (unweighted: logden
+// stays): alpha 1/2 where each of two operands carries sqrt(c_n) (Gram sweeps), 1 for sum_n c_n exp(...)
+hipError_t fold_weights(mbar_ctx* w, hipStream_t stream, double alpha, const double*& logden);
+// f[K] padded with -inf (an operand that is zero) to `rows` entries
+std::vector<double> padded_operand(const double* f, int64_t K, int64_t rows);
+// the first `total` doubles of red, all-reduced, in hred; the stream is idle afterwards
+int fetch_red(mbar_ctx* c, size_t total);
 void gram_operand_sums(const double* G, int64_t K, const double* w, double* out);
 void unpack_gram(const GramPlan& plan, const double* blocks, int64_t K, double* G);
 // psum[k] = sum_j G[k][j] from the reduced upper-triangular blocks of ONE diagonal panel of nb x 16 states (host copy; block (I, J >= I)
 // at ((I nb - I (I - 1) / 2) + (J - I)) * 256, element (r, q) at r * 16 + q): with the rows of p summing to one that is sum_n c_n p_kn.
 void gram_row_sums(const double* blocks, int nb, int64_t K, double* psum);
-void unpack_gram_to_hessian(const GramPlan& plan, const double* blocks, int64_t K, const double* factor, const int* pos, int m, double* H,
-                            int threads);
-int ensure_red(mbar_ctx* c, size_t want);
 int64_t lse_rows(const mbar_ctx* c);
+// A NaN or -inf entry of the matrix, or a non-finite f_k of a state with samples, makes every sum NaN (the reference's logsumexp
+// over all samples propagates it into every f_k): no sweep runs, eval_core and the entry points built on it fill their outputs
+// with NaN and return MBAR_OK
+inline bool unusable(const mbar_ctx* c, const double* f, int nf = 1) { return c->u_poison || !f_is_finite(c, f, nf); }
+inline void fill_nan(double* out, size_t n) {
+    if (out) std::fill(out, out + n, std::numeric_limits<double>::quiet_NaN());
+}
 int eval_core(mbar_ctx* c, const double* f, int nf, unsigned flags, double* ld0, double* ld1, double* psum,
               double* sumlogden, double* gram);
+// the log-denominators of f into slot 0; *nan_out: the matrix or f is unusable and every output is NaN
+int pass_logden(mbar_ctx* c, const double* f, bool* nan_out);
+// One log-normaliser sweep: log sum_n c_n exp(-row_kn - logden_n) of the K rows of `c` (a context, or an extension) against the
+// log-denominators in slot 0 of `den` (c itself, or the extension's base) and den's multiplicities, as per-row maximum hm and
+// sum hs of this rank: the normaliser is hm + log(hs)
+int lognum_sweep(mbar_ctx* c, mbar_ctx* den, std::vector<double>& hm, std::vector<double>& hs);
+
+// ---- mbar_rows.cpp: the writers of the matrix ----
+// What every writer of the matrix leaves behind: the poison flags (and with them the log-denominators kept in slot 0, see
+// refresh_poison), the resident probability matrix and the last solve's sums all describe the matrix as it was
+inline void matrix_touched(mbar_ctx* c) {
+    c->u_checked = false;
+    c->P_valid = false;
+    c->last_psum.clear();
+}
+// rows [row0, row0 + nrows) are rows of the context
+inline bool rows_in_range(const mbar_ctx* c, int64_t row0, int64_t nrows) { return row0 >= 0 && nrows >= 0 && row0 + nrows <= c->K; }
+// kind[B] (non-zero: harmonic) and period[B] (NULL: no term is periodic; read at the harmonic terms only) of a family as the
+// kernels take them; MBAR_ERR_ARG naming `who` for more than MBAR_SCAN_MAX_H harmonic terms or a negative or non-finite period
+int family_terms(mbar_ctx* c, const char* who, int64_t B, const int32_t* kind, const double* period, FamilyTerms* out);
+
+// ---- mbar_comm.cpp: transports ----
+bool loop_barrier(mbar_loopback* g);
+void loop_break(mbar_loopback* g);
+int allreduce_loop(mbar_ctx* c, double* dev, int64_t count, int op);
+int allreduce_dev(mbar_ctx* c, double* dev, int64_t count, int op);
+int allreduce_host(mbar_ctx* c, double* host, int64_t count, int op);
+int agree_with_rank0(mbar_ctx* c, double* v, int64_t count);
+
+// ---- mbar_host.cpp: host-side K x K algebra ----
 double now_ms();
 bool chol_solve(std::vector<double>& A, std::vector<double>& b, int m);
 int host_team_size(int m);
 bool chol_solve_blocked(const double* A, size_t lda, std::vector<double>& b, int m, int threads);
 void host_team_run(int threads, const std::function<void(int)>& fn);  // fn(0) on the caller, fn(1 .. threads-1) on the parked team
-int host_team_size(int m);
 void jacobi_eigh(std::vector<double> A, int m, std::vector<double>& w, std::vector<double>& V);
 void newton_direction(const std::vector<double>& H, const std::vector<double>& g, int m, std::vector<double>& x);
+// the host-driven loop's Newton matrix straight from the reduced Gram blocks, dealt over the host team
+void unpack_gram_to_hessian(const GramPlan& plan, const double* blocks, int64_t K, const double* factor, const int* pos, int m, double* H,
+                            int threads);
+
+// ---- mbar_loops.cpp: the solver loops ----
 int adaptive_host_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t maxiter, int64_t min_sc_iter, double gamma,
                        int check_convergence, double* history, int64_t history_rows, mbar_solve_result& res,
                        std::vector<double>& psum, double& max_delta);
@@ -674,14 +758,6 @@ int agree_all_ok(mbar_ctx* c, bool& ok);
 int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t maxiter, int64_t min_sc_iter, double gamma,
                          int check_convergence, double* history, int64_t history_rows, mbar_solve_result& res,
                          std::vector<double>& psum, double& max_delta, bool& handed_back);
-// What the binned passes (mbar_hist.cpp) and the scan passes (mbar_scan.cpp) ask of a context before anything else (mbar_host.cpp).
-// family: "the binned passes" / "the scan passes", as the messages word it; max_K: the most states the family serves, 0: no limit.
-int passes_ready(mbar_ctx* c, const char* who, const char* family, int64_t max_K);
-// the log-denominators of f into slot 0; *nan_out: the matrix or f is unusable and every output is NaN
-int pass_logden(mbar_ctx* c, const double* f, bool* nan_out);
-// kind[B] (non-zero: harmonic) and period[B] (NULL: no term is periodic; read at the harmonic terms only) of a family as the
-// kernels take them; MBAR_ERR_ARG naming `who` for more than MBAR_SCAN_MAX_H harmonic terms or a negative or non-finite period
-int family_terms(mbar_ctx* c, const char* who, int64_t B, const int32_t* kind, const double* period, FamilyTerms* out);
 
 }  // namespace host
 }  // namespace mbar

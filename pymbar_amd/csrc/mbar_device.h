@@ -122,7 +122,7 @@ __device__ __forceinline__ double block256_max(double v, double* red /*[4]*/) {
 //   function; tests/test_gpu_device_math.py asserts that the device returns the model's bits.
 //   exp(-inf) = 0 through the clamp, overflow gives inf through
 //   ldexp; NaN arguments are laundered to 0 by the clamp, which is why NaN / -inf entries of u_kn and non-finite f_k
-//   are detected at the boundary instead (mbar_capi.cpp).
+//   are detected at the boundary instead (mbar_eval.cpp).
 #include "exp2_table.inc"
 #include "log_table.inc"
 constexpr double LOG2E = 0x1.71547652b82fep+0, LN2 = 0x1.62e42fefa39efp-1;
@@ -456,7 +456,7 @@ __device__ __forceinline__ void lse_math2(double (&x0)[NB], double (&x1)[NB], co
     }
     // Second candidate: e'_k = e_k c_k.  Only its sum needs the products (an FMA dot instead of NB multiplies + a
     // tree of adds); the per-state accumulator takes the UNSCALED e_k r' and the constant c_k is applied once to
-    // the reduced sums on the host (mbar_capi.cpp: eval_core).
+    // the reduced sums on the host (mbar_eval.cpp: eval_core).
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
         s0[f] = f == 0 ? tree_sum<NB>(x0) : dot_sum<NB>(x0, c);

@@ -1,6 +1,7 @@
 // Host-only parts of libmbar_hip.so: the state of the caching allocator, the K x K linear algebra of the host-driven loop (Cholesky
 // factorisation of the gauge-fixed Hessian -- blocked and threaded from 320 / 448 unknowns -- with a Jacobi pseudo-inverse
-// fallback: the minimum-norm semantics of numpy.linalg.lstsq, mbar_solvers.py:582-583), the content digest behind the resident
+// fallback: the minimum-norm semantics of numpy.linalg.lstsq, mbar_solvers.py:582-583; the Hessian is assembled from the reduced
+// Gram blocks here too), the content digest behind the resident
 // cache of host matrices, the host face of the bootstrap stream, and the out-of-line parts of the handle layer (open_device,
 // ColumnPasses::upload).  Nothing here touches a kernel.
 #include "mbar_ctx.h"
@@ -621,42 +622,40 @@ void newton_direction(const std::vector<double>& H, const std::vector<double>& g
     for (int k = 0; k < m; ++k) x[k] = y[k] - y[0];
 }
 
-int passes_ready(mbar_ctx* c, const char* who, const char* family, int64_t max_K) {
-    if (!c) return fail(c, MBAR_ERR_ARG, "NULL argument");
-    const std::string head = std::string(who) + ": ", fam = family;
-    if (c->ext_base) return fail(c, MBAR_ERR_STATE, head + "an extension context holds rows only");
-    if (c->nranks > 1 || stream_transport(c) || c->host_reduce)
-        return fail(c, MBAR_ERR_STATE, head + fam + " serve single-rank contexts only (a transport is attached)");
-    if (wide_pitch(c)) return fail(c, MBAR_ERR_STATE, head + fam + " do not serve wide-pitch matrices (row pitch x 56 bytes >= 4 GiB)");
-    if (max_K > 0 && c->K > max_K) return fail(c, MBAR_ERR_STATE, head + fam + " serve at most " + std::to_string(max_K) + " states");
-    return MBAR_OK;
-}
-
-int family_terms(mbar_ctx* c, const char* who, int64_t B, const int32_t* kind, const double* period, FamilyTerms* out) {
-    FamilyTerms t{};
-    int H = 0;
-    for (int64_t b = 0; b < B; ++b) {
-        if (!kind[b]) continue;
-        const double P = period ? period[b] : 0.0;
-        if (!std::isfinite(P) || P < 0.0 || (P > 0.0 && !std::isfinite(1.0 / P)))
-            return fail(c, MBAR_ERR_ARG, std::string(who) + ": the period of a harmonic term must be finite and not negative (0: not periodic)");
-        if (++H > MBAR_SCAN_MAX_H)
-            return fail(c, MBAR_ERR_ARG, std::string(who) + ": at most " + std::to_string(MBAR_SCAN_MAX_H) + " terms of a family may be harmonic");
-        t.mask |= 1u << b;
-        t.period[b] = P;
-        t.rperiod[b] = P > 0.0 ? 1.0 / P : 0.0;
+// The host-driven loop's Newton matrix straight from the reduced blocks (one pass instead of blocks -> K x K matrix -> scaling ->
+// m x m matrix): H[i][j] = -G[k_i][k_j] f[k_i] f[k_j] over the states with samples (pos[k] = position of state k among them, -1:
+// none; f: the per-state factors the P-mode sweep leaves out, or nullptr), both triangles; the blocks are dealt over the host team.
+void unpack_gram_to_hessian(const GramPlan& plan, const double* blocks, int64_t K, const double* factor, const int* pos, int m, double* H,
+                            int threads) {
+    struct Blk { const double* p; int64_t gi0, gj0; bool tri; };
+    std::vector<Blk> list;
+    list.reserve(plan.total_blocks);
+    for (const auto& it : plan.items) {
+        int b = 0;
+        for (int I = 0; I < it.nbi; ++I)
+            for (int J = it.diag ? I : 0; J < it.nbj; ++J) list.push_back({blocks + (it.off + b++) * 256, it.ri + 16 * I, it.rj + 16 * J, it.diag && I == J});
     }
-    *out = t;
-    return MBAR_OK;
+    const int T = std::max(1, std::min<int>(threads, (int)list.size() / 64));
+    host_team_run(T, [&](int t) {
+        for (size_t n = t; n < list.size(); n += T) {
+            const Blk& bk = list[n];
+            for (int r = 0; r < 16; ++r) {
+                const int64_t gi = bk.gi0 + r;
+                const int i = gi < K ? pos[gi] : -1;
+                if (i < 0) continue;
+                const double fi = factor ? -factor[gi] : -1.0;
+                for (int q = bk.tri ? r : 0; q < 16; ++q) {
+                    const int64_t gj = bk.gj0 + q;
+                    const int j = gj < K ? pos[gj] : -1;
+                    if (j < 0) continue;
+                    const double v = bk.p[r * 16 + q] * (factor ? fi * factor[gj] : fi);
+                    H[(size_t)i * m + j] = v;
+                    H[(size_t)j * m + i] = v;
+                }
+            }
+        }
+    });
 }
-
-int pass_logden(mbar_ctx* c, const double* f, bool* nan_out) {
-    int rc = eval_core(c, f, 1, 0, c->logden[0], nullptr, nullptr, nullptr, nullptr);
-    if (rc) return rc;
-    *nan_out = c->u_poison || !f_is_finite(c, f, 1);
-    return MBAR_OK;
-}
-
 
 }  // namespace host
 }  // namespace mbar

@@ -1,5 +1,5 @@
-// Internal interface between the host side (mbar_capi.cpp, mbar_loops.cpp, mbar_comm.cpp, mbar_host.cpp; their shared header is
-// mbar_ctx.h) and the gfx950 kernels (mbar_k_*.hip).  Not part of the public ABI.
+// Internal interface between the host side (the mbar_*.cpp files; mbar_ctx.h, their shared header, lists them by role) and the
+// gfx950 kernels (mbar_k_*.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -523,7 +523,7 @@ hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& 
                                    const double* part, double* cross, double* vec);
 
 // ---- rows of the resident matrix from a family of states (mbar_k_family.hip; C ABI: mbar_ctx_fill_family_rows and ----------
-// ---- mbar_ctx_fill_linear_rows in mbar_capi.cpp) -----------------------------------------------------------------------------
+// ---- mbar_ctx_fill_linear_rows in mbar_rows.cpp) -----------------------------------------------------------------------------
 constexpr int FILL_THREADS = 256;      // a lane owns two adjacent columns: 512 columns per workgroup and pass
 constexpr int FILL_ROWS = 128;         // rows a lane writes from one read of its basis values (grid.y = row groups)
 constexpr int FILL_MAX_BLOCKS = 2048;  // grid.x; the column pairs go round it

@@ -9,7 +9,7 @@
 //
 // the chain of family_term (mbar_device.h), which the scan passes of mbar_k_scan.hip evaluate too: a scan member with a sampled
 // state's parameters has that state's u to the bit.  A harmonic term is umbrella sampling on a periodic coordinate, u_r(n) = beta_r
-// [E_n + kappa_r / 2 wrap(chi_n - chi0_r)^2].  One of the translation units of libmbar_hip.so; the host side is mbar_capi.cpp, the
+// [E_n + kappa_r / 2 wrap(chi_n - chi0_r)^2].  One of the translation units of libmbar_hip.so; the host side is mbar_rows.cpp, the
 // launcher declaration is in mbar_internal.h.  DESIGN.md section 19 has the geometry and the byte counts, section 20 the chain and its cost.
 //
 // Store-bound: 8 nrows N bytes out, 8 B N in per row group.  A lane owns the two adjacent columns 2 p, 2 p + 1 (the row pitch is a

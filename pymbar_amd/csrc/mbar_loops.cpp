@@ -116,10 +116,7 @@ int adaptive_host_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t 
             HIPCHK(c, launch_reduce(c->stream, c->part, blocks, (int64_t)n_ps, c->scratch, c->red));
             HIPCHK(c, launch_reduce(c->stream, obj_part, blocks, 2, c->scratch, c->red + n_ps));
         }
-        r2 = allreduce_dev(c, c->red, (int64_t)total, 0);
-        if (r2) return r2;
-        HIPCHK(c, hipMemcpyAsync(c->hred, c->red, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        r2 = sync_stream(c);
+        r2 = fetch_red(c, total);
         if (r2) return r2;
         for (int64_t k = 0; k < K; ++k) {
             ps2[k] = c->hred[(size_t)k];
@@ -138,6 +135,7 @@ int adaptive_host_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t 
             const GramPlan& pl = hp ? plan_p : plan;
             const size_t n_gram = pl.total_blocks * 256, total = n_gram;
             rc = ensure_red(c, total);
+            if (!rc) rc = reserve_gram(c, pl, hp);  // (what is queued below before run_gram must not see the buffers replaced)
             if (rc) return rc;
             std::vector<double> an((size_t)c->Kp);
             build_aden(c, f.data(), an.data(), c->Kp);
@@ -164,10 +162,7 @@ int adaptive_host_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t 
                 rc = run_gram(c, d_anum(c), c->logden[cur], 0, pl);
             }
             if (rc) return rc;
-            rc = allreduce_dev(c, c->red, (int64_t)total, 0);
-            if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->hred, c->red, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            rc = sync_stream(c);
+            rc = fetch_red(c, total);
             if (rc) return rc;
             const double t_u0 = dbg ? now_ms() : 0.0;
             // H = -Gram (with the per-state factors the P-mode sweep leaves out), m x m over the sampled states; + diag below
@@ -388,15 +383,22 @@ int plan_device_loop(mbar_ctx* c, const std::vector<double>& f, int check_conver
     int arc = ensure_ad(c, history ? history_rows : 0);
     if (!arc && wide && c->chol.grow(NEWTON_CHOL_WORK) != hipSuccess)
         arc = fail(c, MBAR_ERR_HIP, "allocation of the Newton workspace failed");
+    // (a new P is zeroed below, once the buffers are sized: nothing of this call is queued before that.  A return before the fill
+    // gives the block back: a P that stays is one that has been zeroed)
+    struct FreshP {
+        mbar_ctx* c;
+        bool pending;
+        ~FreshP() { if (pending) c->P.reset(); }
+        operator bool() const { return pending; }
+    } zero_p{c, false};
     if (!arc && pmode && !c->P) {
         arc = drop_graphs(c);
         if (!arc) {
-            if (c->P.grow((size_t)Kp * c->ld) != hipSuccess) {
+            zero_p.pending = c->P.grow((size_t)Kp * c->ld) == hipSuccess;
+            if (!zero_p) {
                 (void)hipGetLastError();
                 c->P_failed = true;
                 pmode = false;
-            } else if (launch_zero(c->stream, c->P, (size_t)Kp * c->ld * sizeof(double)) != hipSuccess) {
-                arc = fail(c, MBAR_ERR_HIP, "zero fill of P failed");
             }
         }
     }
@@ -469,6 +471,10 @@ int plan_device_loop(mbar_ctx* c, const std::vector<double>& f, int check_conver
                      std::max(((size_t)std::max(gg.nwaves, gl.nwaves) / 32 + 1) * (rec_g + rec_l + 2), ((size_t)gb.nwaves / 32 + 1) * (Kp + rec_g)));
     if (!arc && c->weighted && !c->lden_eff) arc = fail(c, MBAR_ERR_STATE, "weighted context without its logden buffer");
     if (!arc && fused) arc = ensure(c, c->part_g, (size_t)gl.nwaves * rec_g);
+    if (!arc && zero_p) {
+        if (launch_zero(c->stream, c->P, (size_t)Kp * c->ld * sizeof(double)) == hipSuccess) zero_p.pending = false;
+        else arc = fail(c, MBAR_ERR_HIP, "zero fill of P failed");
+    }
     {
         bool ok = arc == MBAR_OK;
         const std::string local_err = c->error;
@@ -1032,7 +1038,7 @@ extern "C" {
 
 int mbar_solve_adaptive(mbar_ctx* c, double* f_inout, double tol, int64_t maxiter, int64_t min_sc_iter, double gamma,
                         int check_convergence, double* history, int64_t history_rows, mbar_solve_result* result) {
-    if (c && c->ext_base) return fail(c, MBAR_ERR_STATE, "mbar_solve_adaptive: an extension context holds rows only (mbar_lognum_ext / mbar_gram_w_ext sweep them)");
+    if (c && c->ext_base) return ext_holds_rows_only(c, "mbar_solve_adaptive");
     if (!c || !f_inout) return fail(c, MBAR_ERR_ARG, "NULL argument");
     if (!c->have_Nk) return fail(c, MBAR_ERR_STATE, "mbar_ctx_set_Nk has not been called");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1109,7 +1115,7 @@ int mbar_ctx_last_solve_psum(mbar_ctx* c, double* psum_out) {
 
 int mbar_solve_sci(mbar_ctx* c, double* f_inout, double tol, int64_t maxiter, int check_convergence,
                    mbar_solve_result* result) {
-    if (c && c->ext_base) return fail(c, MBAR_ERR_STATE, "mbar_solve_sci: an extension context holds rows only (mbar_lognum_ext / mbar_gram_w_ext sweep them)");
+    if (c && c->ext_base) return ext_holds_rows_only(c, "mbar_solve_sci");
     if (!c || !f_inout) return fail(c, MBAR_ERR_ARG, "NULL argument");
     if (!c->have_Nk) return fail(c, MBAR_ERR_STATE, "mbar_ctx_set_Nk has not been called");
     HIPCHK(c, hipSetDevice(c->device));

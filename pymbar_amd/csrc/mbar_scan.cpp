@@ -75,13 +75,15 @@ int scan_open(mbar_ctx* c, const std::string& who, bool args_ok, bool binned, in
 
 // scan_begin, once the sizes are known: the log-denominators of f; with an unusable matrix or f, or a NaN among the members'
 // normalisers fnorm[nnorm] (NULL: none), every output is filled with NaN and *done is set (the call returns MBAR_OK); otherwise
-// coeff | offset (NULL: zeros) | room for L normalisers go to the device and *d is the family as the kernels see it.
+// scan_part / scan_out are sized for the call's partial records and merged outputs (part_doubles, out_doubles: before anything of
+// the call is queued), coeff | offset (NULL: zeros) | room for L normalisers go to the device and *d is the family as the kernels
+// see it.
 struct ScanOut {
     double* p;  // (NULL: not asked for)
     size_t n;
 };
 int scan_begin(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* fnorm, size_t nnorm,
-               std::initializer_list<ScanOut> outs, bool* done, ScanData* d) {
+               std::initializer_list<ScanOut> outs, size_t part_doubles, size_t out_doubles, bool* done, ScanData* d) {
     bool nan = false;
     if (c->scan_terms.mask)  // (the linear family keeps what it always did with such a member)
         for (int64_t x = 0; x < L * c->scan_B; ++x)
@@ -97,6 +99,8 @@ int scan_begin(mbar_ctx* c, const double* f, int64_t L, const double* coeff, con
     }
     const int64_t B = c->scan_B;
     HIPCHK(c, c->scan_in.grow((size_t)L * (size_t)(B + 2)));
+    HIPCHK(c, c->scan_part.grow(part_doubles));
+    HIPCHK(c, c->scan_out.grow(out_doubles));
     double* d_coeff = c->scan_in;
     double* d_off = d_coeff + L * B;
     HIPCHK(c, hipMemcpyAsync(d_coeff, coeff, (size_t)L * B * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -254,12 +258,11 @@ int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coef
     const int64_t B = c->scan_B, J = 1 + c->scan_Q;
     bool done = false;
     ScanData d;
-    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{lognum, (size_t)L}, {mean, (size_t)(L * J)}}, &done, &d);
-    if (rc || done) return rc;
     const int64_t nchunks = std::max<int64_t>((c->N + SCAN_VCHUNK - 1) / SCAN_VCHUNK, 1);
     const int64_t pw = vec_panel(c, nchunks, J, L);
-    HIPCHK(c, c->scan_part.grow((size_t)nchunks * (size_t)pw * (size_t)J));
-    HIPCHK(c, c->scan_out.grow((size_t)L * (size_t)(2 + J)));
+    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{lognum, (size_t)L}, {mean, (size_t)(L * J)}},
+                    (size_t)nchunks * (size_t)pw * (size_t)J, (size_t)L * (size_t)(2 + J), &done, &d);
+    if (rc || done) return rc;
     double* d_M = c->scan_out;
     double* d_lognum = d_M + L;
     double* d_mean = d_lognum + L;
@@ -289,15 +292,15 @@ int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coef
     const int J = 1 + (int)c->scan_Q, NW = J * (J + 1) / 2, NV = scan_nv(J);
     bool done = false;
     ScanData d;
-    rc = scan_begin(c, f, L, coeff, offset, f_scan, (size_t)L,
-                    {{cross, (size_t)K * L * J}, {within, (size_t)(L * NW)}, {refcol, (size_t)(L * J)}, {wsum, (size_t)L}}, &done, &d);
-    if (rc || done) return rc;
     const int nb = cross ? scan_nb_for(K) : 0;
     const int64_t nchunks = (c->N + SCAN_CHUNK - 1) / SCAN_CHUNK;
     const int mb = scan_mb_of(c, J);
     const int64_t pw = 64 * mb;
-    HIPCHK(c, c->scan_part.grow((size_t)std::max<int64_t>(nchunks, 1) * (size_t)scan_record_doubles(nb, J, NV, mb)));
-    HIPCHK(c, c->scan_out.grow((size_t)L * (size_t)NV + (cross ? (size_t)K * L * J : 0)));
+    rc = scan_begin(c, f, L, coeff, offset, f_scan, (size_t)L,
+                    {{cross, (size_t)K * L * J}, {within, (size_t)(L * NW)}, {refcol, (size_t)(L * J)}, {wsum, (size_t)L}},
+                    (size_t)std::max<int64_t>(nchunks, 1) * (size_t)scan_record_doubles(nb, J, NV, mb),
+                    (size_t)L * (size_t)NV + (cross ? (size_t)K * L * J : 0), &done, &d);
+    if (rc || done) return rc;
     double* d_vec = c->scan_out;
     double* d_cross = d_vec + L * NV;
     const double* d_coeff = c->scan_in;
@@ -378,13 +381,12 @@ int mbar_scan_bin_lognum(mbar_ctx* c, const double* f, int64_t L, const double* 
     const int64_t B = c->scan_B, nbins = c->scanbin_nbins;
     bool done = false;
     ScanData d;
-    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{lognum, (size_t)L * nbins}}, &done, &d);
-    if (rc || done) return rc;
     const ScanBinned cut = binned_of(c, false);
     const int64_t nch = std::max<int64_t>(cut.t.nchunks, 1);
     const int64_t pw = vec_panel(c, nch, 1, L);
-    HIPCHK(c, c->scan_part.grow((size_t)nch * (size_t)pw));
-    HIPCHK(c, c->scan_out.grow((size_t)L * (size_t)nbins + (size_t)nbins * (size_t)pw));
+    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{lognum, (size_t)L * nbins}}, (size_t)nch * (size_t)pw,
+                    (size_t)L * (size_t)nbins + (size_t)nbins * (size_t)pw, &done, &d);
+    if (rc || done) return rc;
     double* d_lognum = c->scan_out;
     double* d_M = d_lognum + L * nbins;  // [bin][member of the panel]
     const double* d_coeff = c->scan_in;
@@ -411,10 +413,6 @@ int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* 
     const size_t LB = (size_t)L * (size_t)nbins;
     bool done = false;
     ScanData d;
-    rc = scan_begin(c, f, L, coeff, offset, f_bins, LB, {{cross, (size_t)K * LB}, {diag, LB}, {wsum, LB}}, &done, &d);
-    if (rc || done) return rc;
-    HIPCHK(c, c->scanbin_fbins.grow(LB));
-    HIPCHK(c, hipMemcpyAsync(c->scanbin_fbins, f_bins, LB * sizeof(double), hipMemcpyHostToDevice, c->stream));
     ScanBinned cut = binned_of(c, true);
     const int nb = cross ? scan_nb_for(K) : 0;
     // groups of whole bins whose records fit the budget ("scan_part_bytes"; a single bin is never split): one sweep per group, and
@@ -429,8 +427,11 @@ int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* 
     group.push_back(nbins);
     int64_t worst = 1;
     for (size_t g = 0; g + 1 < group.size(); ++g) worst = std::max(worst, c0[(size_t)group[g + 1]] - c0[(size_t)group[g]]);
-    HIPCHK(c, c->scan_part.grow((size_t)worst * (size_t)rec));
-    HIPCHK(c, c->scan_out.grow(LB * SCANBIN_NV + (cross ? (size_t)K * LB : 0)));
+    HIPCHK(c, c->scanbin_fbins.grow(LB));  // (the stream is idle here)
+    rc = scan_begin(c, f, L, coeff, offset, f_bins, LB, {{cross, (size_t)K * LB}, {diag, LB}, {wsum, LB}}, (size_t)worst * (size_t)rec,
+                    LB * SCANBIN_NV + (cross ? (size_t)K * LB : 0), &done, &d);
+    if (rc || done) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->scanbin_fbins, f_bins, LB * sizeof(double), hipMemcpyHostToDevice, c->stream));
     double* d_vec = c->scan_out;
     double* d_cross = d_vec + LB * SCANBIN_NV;
     const double* d_coeff = c->scan_in;

@@ -1,6 +1,8 @@
-"""The context behind the C ABI (pymbar_amd/csrc/mbar_capi.cpp, mbar_ctx.h): what every writer of the resident matrix must leave
-behind, and buffers that grow while captured graphs hold their addresses.  Everything is compared bit for bit (``array_equal``, NaN
-equal to NaN) with fresh contexts that saw only the final state.  Needs a real MI355X: run with ``-m gpu``."""
+"""The context behind the C ABI (pymbar_amd/csrc/mbar_ctx.h; mbar_capi.cpp the context and its buffers, mbar_eval.cpp the sweeps,
+mbar_rows.cpp the writers of the matrix, mbar_ext.cpp the extension's entry points): what every writer of the resident matrix must
+leave behind, buffers that grow while captured graphs hold their addresses, and the first call of a fresh context, which sizes the
+buffers of all its launches before the first one.  Everything is compared bit for bit (``array_equal``, NaN equal to NaN) with
+fresh contexts that saw only the final state.  Needs a real MI355X: run with ``-m gpu``."""
 import ctypes as C
 
 import numpy as np
@@ -267,3 +269,93 @@ def test_buffers_that_grow_under_captured_graphs(weighted):
     for (tag, step), g in zip(steps, got):
         with context() as fresh:
             assert_same(g, step(fresh), tag)
+
+
+# ---- 3. the first call of a fresh context -----------------------------------------------------------------------------
+
+def _counts(N, seed):
+    """small integer multiplicities, some of them zero"""
+    return np.random.default_rng(seed).integers(0, 4, size=N).astype(np.float64)
+
+
+# (K, N, gram_quad or None: the default): few states (the evaluation sweep's records are the small ones, the Gram panel's the large
+# ones), one full 128-state panel, 129 .. 256 states as ONE panel and as 128-state panels with their rectangles, and 257 .. 1024
+# states (the split evaluation sweep, then a plan of three diagonal panels and four rectangles of unequal record sizes)
+FIRST_CALLS = [(16, 4000, None), (128, 3000, None), (200, 3000, 1), (200, 3000, 0), (300, 2000, None)]
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("K,N,quad", FIRST_CALLS)
+def test_first_evaluation_with_gram_of_a_fresh_context(K, N, quad, weighted):
+    """An evaluation with the Gram matrix as the FIRST call of a context sizes the per-wave records and the reduction scratch for
+    the evaluation sweep and for every launch of the Gram plan before anything is queued.  Its outputs are those of the same call
+    repeated on that context (nothing grows any more), and those of a context whose buffers mbar_gram_w grew first."""
+    u, N_k, f = random_problem(K, N, seed=K + N)
+    c_n = _counts(N, K) if weighted else None
+
+    def context():
+        dm = DeviceMatrix.from_host(u)
+        dm.set_Nk(N_k)
+        dm.set_sample_weights(c_n)
+        if quad is not None:
+            dm.set_option("gram_quad", quad)
+        return dm
+
+    names = ("psum", "sumlogden", "gram")
+    with context() as dm:
+        first = dict(zip(names, dm.eval(f, gram=True)))
+        again = dict(zip(names, dm.eval(f, gram=True)))
+    with context() as grown:
+        grown.gram_w(f)
+        after = dict(zip(names, grown.eval(f, gram=True)))
+    assert np.isfinite(first["gram"]).all() and first["gram"].shape == (K, K)
+    assert_same(again, first, "the same call again")
+    assert_same(after, first, "after mbar_gram_w grew the buffers")
+
+
+def test_first_thin_gram_of_a_fresh_extension():
+    """A base of K = 120 states (padded to 128), N = 3000, with 5 appended rows: W^T W of the pair from the base's kept W^T W -- the
+    144-row rectangle, then the 16 x 16 block of the appended rows, whose launch geometry and record size differ -- as the first
+    call of the extension and once more: the two launches' buffers are sized together, and both calls return the same bits."""
+    K, R, N = 120, 5, 3000
+    u, N_k, f = random_problem(K, N, seed=K + N)
+    rng = np.random.default_rng(R)
+    rows = u[rng.integers(0, K, size=R)] * 1.1 + rng.uniform(-0.5, 0.5, size=(R, 1))
+    f_all = np.concatenate([f, np.linspace(-0.5, 0.5, R)])
+    with DeviceMatrix.from_host(u) as base:
+        base.set_Nk(N_k)
+        e = base.extend(R)
+        assert e is not None
+        try:
+            e.upload_rows(K, rows)
+            first = dict(zip(("gram", "wsum"), e.gram_w(f_all)))
+            again = dict(zip(("gram", "wsum"), e.gram_w(f_all)))
+        finally:
+            e.close()
+    assert np.isfinite(first["gram"]).all() and first["gram"].shape == (K + R, K + R)
+    assert_same(again, first, "the same call again")
+
+
+# ---- 4. the self-consistent iteration on the evaluation sweeps that are not the fast one ----------------------------------------
+
+@pytest.mark.parametrize("K,N,force_generic", [(300, 2000, 0), (40, 2001, 1)])
+def test_solve_sci_iterates_on_the_device_copy_of_aden(K, N, force_generic):
+    """More than 256 states (the split sweep) and force_generic = 1 (the layout-agnostic kernels): mbar_solve_sci drives run_lse
+    itself, and between two sweeps only the update kernel writes the next a_k = f_k + ln N_k, on the device.  The context has
+    evaluated at ANOTHER f before, so the host staging holds that call's a_k: a sweep that took its a_k from anywhere but the
+    device vector would stall there.  The solve converges, and what it returns is a fixed point of the oracle's self-consistent
+    update: with the relative stop test at tol = 1e-9 and |f| < 10 the last step was below 1e-8, rounding of the sums over 2000
+    samples is orders below that, so 1e-7 bounds the residual."""
+    from oracle import mbar_oracle as oracle
+
+    u, N_k, f_other = random_problem(K, N, seed=K + N)
+    with DeviceMatrix.from_host(u) as dm:
+        dm.set_Nk(N_k)
+        dm.set_option("force_generic", force_generic)
+        dm.eval(f_other + 1.0)
+        f, res = dm.solve_sci(np.zeros(K), tol=1e-9, maxiter=20000)
+    assert res["success"] and res["iterations"] > 2
+    sampled = N_k > 0
+    assert np.abs(f[sampled]).max() < 10.0
+    step = oracle.self_consistent_update(u, N_k.astype(np.float64), f)
+    assert np.abs((step - step[0])[sampled] - (f - f[0])[sampled]).max() < 1e-7

@@ -6,8 +6,8 @@ prints its per-tile averages at the end of each launch):
 
     cd pymbar_amd/csrc
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DMBAR_RECT_STAMPS -x hip -c mbar_k_quad.hip -o /tmp/quad_stamps.o
-    hipcc --offload-arch=gfx950 -shared -fPIC -o ../../scratch/libmbar_hip_stamps.so /tmp/quad_stamps.o mbar_k_eval.o mbar_k_gram.o \
-          mbar_k_pmode.o mbar_k_fused.o mbar_k_loop.o mbar_k_rows.o mbar_capi.o mbar_loops.o mbar_comm.o mbar_host.o -ldl
+    hipcc --offload-arch=gfx950 -shared -fPIC -o ../../scratch/libmbar_hip_stamps.so /tmp/quad_stamps.o \
+          $(PYTHONPATH=../.. python -c "from pymbar_amd import _build as b; print(' '.join(s.rsplit('.', 1)[0] + '.o' for s in b.SOURCES if s != 'mbar_k_quad.hip'))") -ldl
     MBAR_HIP_LIBRARY=$PWD/../../scratch/libmbar_hip_stamps.so python tools/gram_rect_stamps.py 512
 
 Output committed as profiles/r5_gram_rect_tile_anatomy.txt."""
