@@ -16,8 +16,8 @@ LIB = os.path.join(CSRC, "libmbar_hip.so")
 KERNEL_SOURCES = ["mbar_k_eval.hip", "mbar_k_gram.hip", "mbar_k_quad.hip", "mbar_k_pmode.hip", "mbar_k_fused.hip", "mbar_k_loop.hip",
                   "mbar_k_rows.hip", "mbar_k_kde.hip", "mbar_k_acf.hip", "mbar_k_bar.hip", "mbar_k_bspline.hip", "mbar_k_batch.hip", "mbar_k_hist.hip",
                   "mbar_k_scan.hip", "mbar_k_family.hip"]
-HOST_SOURCES = ["mbar_capi.cpp", "mbar_eval.cpp", "mbar_rows.cpp", "mbar_ext.cpp", "mbar_loops.cpp", "mbar_comm.cpp", "mbar_host.cpp",
-                "mbar_kde.cpp", "mbar_acf.cpp", "mbar_bar.cpp", "mbar_bspline.cpp", "mbar_batch.cpp", "mbar_hist.cpp",
+HOST_SOURCES = ["mbar_capi.cpp", "mbar_eval.cpp", "mbar_rows.cpp", "mbar_ext.cpp", "mbar_loops.cpp", "mbar_loop_device.cpp",
+                "mbar_loop_host.cpp", "mbar_comm.cpp", "mbar_host.cpp", "mbar_kde.cpp", "mbar_acf.cpp", "mbar_bar.cpp", "mbar_bspline.cpp", "mbar_batch.cpp", "mbar_hist.cpp",
                 "mbar_scan.cpp"]  # (shared header: mbar_ctx.h)
 SOURCES = KERNEL_SOURCES + HOST_SOURCES
 COMMON_DEPS = ["mbar_internal.h", os.path.join("..", "..", "include", "mbar_hip.h")]

@@ -5,7 +5,8 @@
 //   mbar_eval.cpp   the evaluation engine (run_lse, the Gram plans, run_gram, eval_core) and the evaluation entry points
 //   mbar_rows.cpp   every writer of the resident matrix, and its download
 //   mbar_ext.cpp    the entry points that take an extension context and its base
-//   mbar_loops.cpp  the solver loops the reference writes in Python
+//   mbar_loops.cpp  the two solve entry points, the self-consistent loop, and what the solver loops share
+//   mbar_loop_device.cpp, mbar_loop_host.cpp  the adaptive loop the reference writes in Python: device-resident, host-driven
 //   mbar_scan.cpp, mbar_hist.cpp  the scan passes and the binned passes
 //   mbar_comm.cpp   RCCL loader, in-process transport, all-reduce
 //   mbar_host.cpp   allocator state, host-side K x K linear algebra, content digest
@@ -748,13 +749,33 @@ void newton_direction(const std::vector<double>& H, const std::vector<double>& g
 void unpack_gram_to_hessian(const GramPlan& plan, const double* blocks, int64_t K, const double* factor, const int* pos, int m, double* H,
                             int threads);
 
-// ---- mbar_loops.cpp: the solver loops ----
+// ---- mbar_loops.cpp: what the solver loops share ----
+// What both solve entry points do before their first real step: the refusals, the device made current, *t0 (now_ms()), slot 0's
+// log-denominators declared stale -- `guard` repeats that on EVERY way out, error returns included: the loops use the slot vectors
+// for their own purposes, and an evaluation inside them marks slot 0 valid again before the loop overwrites it -- and the poison
+// flags brought up to date.  What a poisoned matrix or a non-finite start means is the caller's business.
+struct Ld0Guard {
+    mbar_ctx* c = nullptr;
+    ~Ld0Guard() { if (c) c->ld0_valid = false; }
+};
+int enter_solve(mbar_ctx* c, const double* f_inout, const char* who, Ld0Guard& guard, double* t0);
+// A decision that changes the SEQUENCE of collectives must be the same on every rank: `ok` is MIN-reduced over the ranks
+int agree_all_ok(mbar_ctx* c, bool& ok);
+// Captures `batch` calls of enqueue(b), b = 0 .. batch - 1, on the context's stream and instantiates them as *exec (which must be
+// null).  Nothing may allocate inside enqueue; the eager warm-up that sets the kernel attributes stays with the caller.
+int capture_batch(mbar_ctx* c, hipGraphExec_t* exec, int64_t batch, const std::function<int(int64_t)>& enqueue);
+// MBAR_DEBUG_STAMPS: *out = the context's stamp buffer (STAMP_WORDS words: 64 launches x 16 and one spare row), allocated at its
+// first use and zeroed on the stream -- all of it; nullptr when the variable is not set
+constexpr size_t STAMP_WORDS = 65 * 16;
+int debug_stamps(mbar_ctx* c, long long** out);
+
+// ---- mbar_loop_host.cpp: the host-driven adaptive loop ----
 int adaptive_host_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t maxiter, int64_t min_sc_iter, double gamma,
                        int check_convergence, double* history, int64_t history_rows, mbar_solve_result& res,
                        std::vector<double>& psum, double& max_delta);
+
+// ---- mbar_loop_device.cpp: the device-resident adaptive loop ----
 bool device_loop_eligible(const mbar_ctx* c);
-int ensure_ad(mbar_ctx* c, int64_t hist_rows);
-int agree_all_ok(mbar_ctx* c, bool& ok);
 int adaptive_device_loop(mbar_ctx* c, std::vector<double>& f, double tol, int64_t maxiter, int64_t min_sc_iter, double gamma,
                          int check_convergence, double* history, int64_t history_rows, mbar_solve_result& res,
                          std::vector<double>& psum, double& max_delta, bool& handed_back);

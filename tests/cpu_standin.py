@@ -185,7 +185,7 @@ class OracleMatrix:
         self._reduce(buf)
         return buf[: self.K * self.K].reshape(self.K, self.K).copy(), buf[self.K * self.K :].copy()
 
-    # ---- model of mbar_solve_adaptive / mbar_solve_sci (pymbar_amd/csrc/mbar_loops.cpp) -------------
+    # ---- model of mbar_solve_adaptive / mbar_solve_sci (pymbar_amd/csrc/mbar_loops.cpp, mbar_loop_*.cpp) ----
     def solve_adaptive(self, f, tol=1e-12, maxiter=10000, min_sc_iter=2, gamma=1.0, check_convergence=True,
                        history_rows=0):
         f = np.array(f, dtype=np.float64)

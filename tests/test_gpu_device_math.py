@@ -523,7 +523,7 @@ def model_p(u, live, f0, builder):
 
 
 P_BUILDERS = [
-    # (builder, K, options, weighted): which kernel writes P (mbar_loops.cpp)
+    # (builder, K, options, weighted): which kernel writes P (mbar_loop_device.cpp)
     ("k_build_gram", 48, {}, False), ("k_build_gram", 128, {}, False), ("k_build_gram", 48, {}, True),
     ("k_build_sweep", 48, {"fused": 0}, False), ("k_build_sweep", 128, {"fused": 0}, False), ("k_build_sweep", 48, {"fused": 0}, True),
     ("k_gram_quad", 160, {}, False), ("k_gram_quad", 256, {}, False),
@@ -624,7 +624,7 @@ def test_resident_probability_matrix_elementwise(DM, builder, K, options, weight
     kernel, but that matrix is not the device-resident loop's -- it is never marked valid for a warm start -- and the download hook
     refuses it; the kernel is the one checked here.)
     With sample weights P itself is unweighted (the multiplicity rides on the operand only).
-    Limitation: WHICH kernel and template branch wrote P follows from mbar_loops.cpp and is not observable through the C ABI (the
+    Limitation: WHICH kernel and template branch wrote P follows from mbar_loop_device.cpp and is not observable through the C ABI (the
     result record counts builds, not kernels); GENERAL = false / true of k_build_gram give the same bits on these matrices, so a
     plain solve that went through GENERAL = true would pass here."""
     unsampled = (5, K - 2)
