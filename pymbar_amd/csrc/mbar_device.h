@@ -55,6 +55,13 @@ __device__ __forceinline__ double row16_bcast(double x) {
     asm("v_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(x), "n"(N));
     return r;
 }
+// acc += x * (lane N of r's 16-lane row): the broadcast rides in the fused multiply-add's own DPP operand -- the same operation, and
+// the same bits, as fma(x, row16_bcast<N>(r), acc) without the move.  (As with every DPP read the compiler cannot see: r must have
+// been written at least two wait states earlier.)
+template <int N>
+__device__ __forceinline__ void fmac_row16_bcast(double& acc, double r, double x) {
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(r), "v"(x), "n"(N));
+}
 __device__ __forceinline__ double row16_sum(double x) {
     x += dpp_move<0xB1>(x);
     x += dpp_move<0x4E>(x);
