@@ -1,9 +1,10 @@
 // Host side of the lagged fluctuation sums (include/mbar_hip.h, "timeseries"): the mbar_acf handle (on the handle layer of
-// mbar_ctx.h), which keeps one series (or the concatenation of K segments) resident on a device with its suffix sums, the lag
+// mbar_handle.h), which keeps one series (or the concatenation of K segments) resident on a device with its suffix sums, the lag
 // schedule of the reference's stopping rule and the raw lag sums.  Kernels: mbar_k_acf.hip.
 #include <cmath>
 
-#include "mbar_ctx.h"
+#include "mbar_handle.h"
+#include "mbar_acf.h"
 
 using namespace mbar;
 using namespace mbar::host;

@@ -1,10 +1,11 @@
 // Host side of the BAR and EXP estimators (include/mbar_hip.h, "BAR and EXP estimators"): the mbar_bar handle (on the handle
-// layer of mbar_ctx.h), which keeps P problems' forward and reverse work values resident on a device, cut into chunks with their
+// layer of mbar_handle.h), which keeps P problems' forward and reverse work values resident on a device, cut into chunks with their
 // minima, and drives the root find.
-// Kernels: mbar_k_bar.hip; the root find's state machine: bar_advance in mbar_internal.h.
+// Kernels: mbar_k_bar.hip; the root find's state machine: bar_advance in mbar_bar.h.
 #include <cmath>
 
-#include "mbar_ctx.h"
+#include "mbar_handle.h"
+#include "mbar_bar.h"
 
 using namespace mbar;
 using namespace mbar::host;

@@ -1,12 +1,14 @@
 // Host side of mbar_batch (include/mbar_hip.h, "many small MBAR problems in one call"): the handle (on the handle layer of
-// mbar_ctx.h), which keeps P problems' reduced potentials resident on a device, cut into chunks, and drives their adaptive loops.
+// mbar_handle.h), which keeps P problems' reduced potentials resident on a device, cut into chunks, and drives their adaptive loops.
 // Replica slots (bootstrap replicates: solves that share a problem's block and weigh its samples by draw counts) are a second
 // set of chunks, records and states over the same blocks.  Extension rows (the expectation family: new states and observables as
 // states with no samples) lie next to the blocks, with the two passes over them.  Kernels: mbar_k_batch.hip; the loop's state
-// machine: batch_advance in mbar_internal.h.
+// machine: batch_advance in mbar_batch.h.
 #include <cmath>
+#include <memory>
 
-#include "mbar_ctx.h"
+#include "mbar_handle.h"
+#include "mbar_batch.h"
 
 using namespace mbar;
 using namespace mbar::host;

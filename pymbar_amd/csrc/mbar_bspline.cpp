@@ -1,9 +1,10 @@
 // Host side of the weighted B-spline moments (include/mbar_hip.h, "weighted B-spline moments"): the mbar_bspline handle (on the
-// handle layer of mbar_ctx.h, which also holds its weight columns), the grid (sample chunks x output tiles) and the
+// handle layer of mbar_handle.h, which also holds its weight columns), the grid (sample chunks x output tiles) and the
 // transpose of the combined sums into G x C x nbasis.  Kernels: mbar_k_bspline.hip.
 #include <cmath>
 
-#include "mbar_ctx.h"
+#include "mbar_handle.h"
+#include "mbar_bspline.h"
 
 using namespace mbar;
 using namespace mbar::host;

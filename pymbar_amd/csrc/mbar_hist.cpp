@@ -2,6 +2,7 @@
 // array (built once per mbar_ctx_set_bins, O(N)), the tiling of the bins under the record budget, and the two binned passes over
 // the context's resident matrix.  Kernels: mbar_k_hist.hip.
 #include "mbar_ctx.h"
+#include "mbar_hist.h"
 
 using namespace mbar;
 using namespace mbar::host;

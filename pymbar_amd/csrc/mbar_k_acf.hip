@@ -1,6 +1,6 @@
 // gfx950 (CDNA4 / MI355X) kernels of the lagged fluctuation sums behind pymbar_amd.timeseries (statistical inefficiency,
 // equilibration detection, correlation functions).  One of the translation units of libmbar_hip.so: launchers declared in
-// mbar_internal.h, C ABI in mbar_acf.cpp, design and numbers in DESIGN.md ("Timeseries").
+// mbar_acf.h, C ABI in mbar_acf.cpp, design and numbers in DESIGN.md ("Timeseries").
 //
 // The series is held shifted by one constant per series (A' = A - m_A, B' = B - m_B), padded with zeros to the pitch ldx (a
 // multiple of ACF_TILE, > T), with rem[n] = the positions left in n's segment (the partner n + t is valid iff t < rem[n]).  For a
@@ -16,6 +16,7 @@
 // tiles, so that the expansion of X stays exact where an origin's mean lies many sigma from the shift.  No atomics; every
 // reduction has a fixed order, so two identical calls return identical bits.
 #include "mbar_device.h"
+#include "mbar_acf.h"
 
 #pragma clang fp contract(off)
 

@@ -1,5 +1,5 @@
 // gfx950 (CDNA4 / MI355X) kernels of the BAR and EXP estimators behind pymbar_amd.other_estimators.  One of the translation units
-// of libmbar_hip.so: launchers declared in mbar_internal.h, C ABI in mbar_bar.cpp, design and numbers in DESIGN.md ("BAR and EXP").
+// of libmbar_hip.so: launchers declared in mbar_bar.h, C ABI in mbar_bar.cpp, design and numbers in DESIGN.md ("BAR and EXP").
 //
 // Every side (forward or reverse work values of one problem) is cut into chunks of MBAR_BAR_CHUNK values; one workgroup handles
 // one chunk.  The Fermi factor's log, log f(x) = -softplus(x), is decreasing in w on both sides (x_F = M + w - DeltaF,
@@ -8,12 +8,13 @@
 // overflow, and none is lost to underflow that is not below 2^-1074 of the chunk's largest.
 //   k_bar_eval     every chunk of every running problem at its one or two requested DeltaF values, one load of w for both
 //   k_bar_step     one workgroup per problem: merges the partials of each side in a fixed order and advances the problem's root
-//                  find (bar_advance, mbar_internal.h) -- or stores the sums for mbar_bar_zero
+//                  find (bar_advance, mbar_bar.h) -- or stores the sums for mbar_bar_zero
 //   k_bar_mom*     the one-sided moments of EXP: logsumexp(-w), sum x and sum (x - mean)^2 of x = exp(-w - max(-w)), sum w and
 //                  sum (w - mean)^2, each a fixed-order two-level reduction
 // No atomics: every reduction has a fixed order that depends on the side's length alone, so two identical calls return identical
 // bits and a problem's answer does not depend on the other problems of the batch.
 #include "mbar_device.h"
+#include "mbar_bar.h"
 
 namespace mbar {
 

@@ -1,5 +1,5 @@
 // gfx950 (CDNA4 / MI355X) kernels of mbar_batch: many small MBAR problems (K <= 64 states each) solved side by side.  One of the
-// translation units of libmbar_hip.so: launchers declared in mbar_internal.h, C ABI in mbar_batch.cpp, design and numbers in
+// translation units of libmbar_hip.so: launchers declared in mbar_batch.h, C ABI in mbar_batch.cpp, design and numbers in
 // DESIGN.md ("Many small MBAR problems").
 //
 // Every problem's columns are cut into chunks of MBAR_BATCH_CHUNK samples; one workgroup of 256 threads handles one chunk, one
@@ -12,15 +12,15 @@
 //                  16 states at a time; the Gram matrix is VALU outer products of 64-sample tiles staged in LDS, each thread
 //                  owning a 1x1, 2x2 or 4x4 block.
 //   k_batch_step   one workgroup per problem: merges the chunk partials in chunk order, advances the problem's adaptive loop
-//                  (batch_advance, mbar_internal.h) and, when it asks for one, factors the gauge-fixed Newton system in LDS
+//                  (batch_advance, mbar_batch.h) and, when it asks for one, factors the gauge-fixed Newton system in LDS
 //                  (LDL^T, one barrier pair per pivot).
-//   k_batch_draw   bootstrap draw counts of many replica slots in one launch (the counter-based stream of mbar_internal.h).
+//   k_batch_draw   bootstrap draw counts of many replica slots in one launch (the counter-based stream of mbar_common.h).
 //   k_batch_ext_*  the extension rows of the problems (new states and observables of the expectation family, MBARBatch): per row
 //                  the chunk maximum and scaled sum in log space (k_batch_ext_sums, merged by k_batch_ext_sums_merge), and the
 //                  augmented Gram matrix Q^T Q of up to 128 columns, Q = [W | the rows' weight columns] (k_batch_ext_gram: 32-sample
 //                  tiles in LDS, each thread a block of up to 8x8, one record per run of MBAR_BATCH_EXT_RUN chunks, merged in run
 //                  order by k_batch_ext_gram_merge).
-// Replica slots (bootstrap replicates, BatchData in mbar_internal.h) share their base problem's block and run the weighted
+// Replica slots (bootstrap replicates, BatchData in mbar_batch.h) share their base problem's block and run the weighted
 // instantiation of k_batch_eval: sample n counts c_n >= 0 times.  Its log-denominator is unchanged; the chunk maximum of a state
 // is taken over the samples with c_n > 0 and its sum is sum_n c_n exp(. - maximum); the Gram operands are scaled by sqrt(c_n) when
 // the tile is staged, so that sum_n c_n q q^T stays bit-symmetric.  k_batch_step does not know about multiplicities.
@@ -28,6 +28,7 @@
 // that depends on the problem alone, so two identical calls return identical bits and a problem's (or a slot's) answer does not
 // depend on the other problems of the batch.
 #include "mbar_device.h"
+#include "mbar_batch.h"
 
 namespace mbar {
 

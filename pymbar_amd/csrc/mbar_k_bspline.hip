@@ -1,7 +1,7 @@
 // gfx950 (CDNA4 / MI355X) kernels of the weighted B-spline moments behind the spline surfaces of pymbar_amd.FES:
 //   M[g, c, i] = sum over the samples n of group g of V[n, c] B_{i,k,t}(x_n),   i = 0 .. nbasis - 1
 // with B_{i,k,t} what scipy.interpolate.BSpline(t, e_i, k) returns with extrapolate=True.  One of the translation units of
-// libmbar_hip.so; the host side is mbar_bspline.cpp, the launcher declarations are in mbar_internal.h.  DESIGN.md ("Spline
+// libmbar_hip.so; the host side is mbar_bspline.cpp, the launcher declarations are in mbar_bspline.h.  DESIGN.md ("Spline
 // surfaces") has the numbers.
 //
 // Layout.  Samples x: [N], group labels g: [N] int32 (NULL: one group), weights of one column batch V: [N][CB].  The knots sit in
@@ -19,6 +19,7 @@
 // identical bits.  A wave costs one round per distinct cell among its 64 samples: umbrella data (ordered by state, a few
 // intervals per state) needs one or two, random x over many groups and intervals up to 64.
 #include "mbar_device.h"
+#include "mbar_bspline.h"
 
 namespace mbar {
 

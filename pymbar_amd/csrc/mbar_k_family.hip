@@ -7,10 +7,10 @@
 //                                                                                    P_b > 0: dl = fma(-P_b, rint(dl rP_b), dl)
 //                                                                                    fma(coeff[r][b], dl dl, u)
 //
-// the chain of family_term (mbar_device.h), which the scan passes of mbar_k_scan.hip evaluate too: a scan member with a sampled
+// the chain of family_term (mbar_scan_device.h), which the scan passes of mbar_k_scan.hip evaluate too: a scan member with a sampled
 // state's parameters has that state's u to the bit.  A harmonic term is umbrella sampling on a periodic coordinate, u_r(n) = beta_r
 // [E_n + kappa_r / 2 wrap(chi_n - chi0_r)^2].  One of the translation units of libmbar_hip.so; the host side is mbar_rows.cpp, the
-// launcher declaration is in mbar_internal.h.  DESIGN.md section 19 has the geometry and the byte counts, section 20 the chain and its cost.
+// launcher declaration is in mbar_scan.h.  DESIGN.md section 19 has the geometry and the byte counts, section 20 the chain and its cost.
 //
 // Store-bound: 8 nrows N bytes out, 8 B N in per row group.  A lane owns the two adjacent columns 2 p, 2 p + 1 (the row pitch is a
 // multiple of 16 doubles and the matrix starts on an allocation, so the pair is one aligned 16-byte store), reads its 2 B basis
@@ -25,6 +25,7 @@
 // term, no divergence), a harmonic term costs six fp64 operations per element instead of one against the 8 bytes stored, and the
 // row loop is unrolled by 2.
 #include "mbar_device.h"
+#include "mbar_scan_device.h"
 
 #pragma clang fp contract(off)
 

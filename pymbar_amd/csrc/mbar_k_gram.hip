@@ -1,7 +1,7 @@
 // gfx950 (CDNA4 / MI355X) kernels of the MBAR solver hot path -- fp64 MFMA Gram / Hessian sweep for up to 128 states per panel: k_gram.
 // One of the translation units of libmbar_hip.so (compiled in parallel by pymbar_amd/_build.py): the shared device helpers and
-// the data-layout notes are in mbar_device.h, the host-side interface of the launchers in mbar_internal.h.
-#include "mbar_device.h"
+// the data-layout notes are in mbar_sweep_device.h, the host-side interface of the launchers in mbar_internal.h.
+#include "mbar_sweep_device.h"
 
 namespace mbar {
 

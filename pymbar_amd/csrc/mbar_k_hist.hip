@@ -1,6 +1,6 @@
 // gfx950 (CDNA4 / MI355X) kernels of the histogram surfaces by bin LABEL (pymbar_amd.fes.histogram_fes_labels): a bin is a label
 // of the samples, not a row of a second matrix.  One of the translation units of libmbar_hip.so; the host side (chunk table,
-// C ABI) is mbar_hist.cpp, the launcher declarations are in mbar_internal.h.  DESIGN.md section 16 has the derivation.
+// C ABI) is mbar_hist.cpp, the launcher declarations are in mbar_hist.h.  DESIGN.md section 16 has the derivation.
 //
 //   pass A   lognum_bin[i] = log sum_{n in bin i} c_n exp(-v_n - logden_n)            (three N-vectors, no matrix)
 //   pass B   cross[k][i]   = sum_{n in bin i} c_n W_nk B_n,   W_nk = exp(f_k - u_kn - logden_n),  B_n = exp(f_bin[label_n] - v_n - logden_n)
@@ -22,6 +22,7 @@
 // Pass A takes the maximum per BIN first (records of maxima, merged), then sums exp(x - max_bin): every term costs one
 // exponential whose argument is <= 0, and a bin whose terms all underflow against the global maximum keeps its finite value.
 #include "mbar_device.h"
+#include "mbar_hist.h"
 
 namespace mbar {
 

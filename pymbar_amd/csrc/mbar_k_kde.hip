@@ -1,7 +1,7 @@
 // gfx950 (CDNA4 / MI355X) kernels of the weighted kernel-density sum behind pymbar_amd.kde / pymbar_amd.FES:
 //   L[m, c] = log sum_n V[n, c] k_h(|q_m - x_n|) - log sum_n V[n, c] + log-normaliser
 // One of the translation units of libmbar_hip.so: the shared device helpers (exp2 table, exp2s) are in mbar_device.h, the host
-// side of the launchers in mbar_internal.h, the C ABI in mbar_kde.cpp.  DESIGN.md ("Kernel-density surfaces") has the numbers.
+// side of the launchers in mbar_kde.h, the C ABI in mbar_kde.cpp.  DESIGN.md ("Kernel-density surfaces") has the numbers.
 //
 // Layout.  Samples X: [d][ldx] (coordinate-major, ldx = N rounded up to KDE_TILE, padding = copies of the last sample with weight
 // zero), weights of one column batch V: [ldx][CB] (the CB weights of a sample are contiguous), queries Q: [d][ldq].  For the two
@@ -30,6 +30,7 @@
 // distance in units of its largest coordinate difference -- returns the value the exact log density rounds to: finite where
 // -r / h or -r^2 / 2h^2 is inside the fp64 range, -inf below it, never NaN.
 #include "mbar_device.h"
+#include "mbar_kde.h"
 
 namespace mbar {
 

@@ -1,9 +1,9 @@
 // gfx950 (CDNA4 / MI355X) kernels of the MBAR solver hot path -- the K x K work of the solver loops: the self-consistent step on the
 // reduced sums, the Newton solve (k_newton, k_chol_*, k_newton_ldlt), the selection (k_select) and their fused forms.
 // One of the translation units of libmbar_hip.so (compiled in parallel by pymbar_amd/_build.py): the shared device helpers and
-// the data-layout notes are in mbar_device.h, the host-side interface of the launchers in mbar_internal.h.  The passes over
+// the data-layout notes are in mbar_sweep_device.h, the host-side interface of the launchers in mbar_internal.h.  The passes over
 // N-vectors, matrix rows and partial records are in mbar_k_rows.hip.
-#include "mbar_device.h"
+#include "mbar_sweep_device.h"
 
 namespace mbar {
 

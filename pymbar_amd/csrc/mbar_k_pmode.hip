@@ -1,7 +1,7 @@
 // gfx950 (CDNA4 / MI355X) kernels of the MBAR solver hot path -- resident probability matrix: build sweeps (k_build_sweep, k_build_gram) and the evaluation sweep on it (k_psweep).
 // One of the translation units of libmbar_hip.so (compiled in parallel by pymbar_amd/_build.py): the shared device helpers and
-// the data-layout notes are in mbar_device.h, the host-side interface of the launchers in mbar_internal.h.
-#include "mbar_device.h"
+// the data-layout notes are in mbar_sweep_device.h, the host-side interface of the launchers in mbar_internal.h.
+#include "mbar_sweep_device.h"
 
 namespace mbar {
 

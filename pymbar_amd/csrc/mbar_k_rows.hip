@@ -2,9 +2,10 @@
 // record reductions, log-space per-state sums, log W, the boundary check, vector fills, generators, and the row operations of
 // the expectation family.
 // One of the translation units of libmbar_hip.so (compiled in parallel by pymbar_amd/_build.py): the shared device helpers and
-// the data-layout notes are in mbar_device.h, the host-side interface of the launchers in mbar_internal.h.  The K x K work of
+// the data-layout notes are in mbar_sweep_device.h, the host-side interface of the launchers in mbar_internal.h.  The K x K work of
 // the solver loops is in mbar_k_loop.hip.
 #include "mbar_device.h"
+#include "mbar_internal.h"
 
 namespace mbar {
 

@@ -2,7 +2,7 @@
 // histogram free energy surfaces along such a scan (MBAR.compute_scan_fes): member l is the state u_l(n) = sum_b coeff[l][b]
 // basis[b][n] + offset[l], B coefficients instead of a row of N doubles.  One of the translation units of libmbar_hip.so; the host
 // side (panels, sort, chunk tables, bin groups, C ABI) is mbar_scan.cpp, the cuts and the launcher declarations are in
-// mbar_internal.h.  DESIGN.md sections 17 and 18 have the derivation, the layout and the cost model.
+// mbar_scan.h.  DESIGN.md sections 17 and 18 have the derivation, the layout and the cost model.
 //
 //   x_ln = -u_l(n) - logden_n,  u_l(n) = fma(coeff[l][B-1], basis[B-1][n], ... fma(coeff[l][0], basis[0][n], offset[l]))
 //   t_0n = 1, t_jn = A_jn - s_j (j = 1 .. Q),  J = 1 + Q
@@ -12,7 +12,7 @@
 //            cross[k][l][j]  = sum_n c_n W_nk b_ln t_jn         fp64 matrix cores: A operand = W tile, B operand = c b t, from registers
 //            within[l][i][j] = sum_n c_n b_ln^2 t_in t_jn,  refcol[l][j] = sum_n c_n b_rn b_ln t_jn,  wsum[l] = sum_n c_n b_ln
 //
-// Every kernel is written once, for a cut of the samples given as a template argument (ScanWhole, ScanBinned: mbar_internal.h).  The
+// Every kernel is written once, for a cut of the samples given as a template argument (ScanWhole, ScanBinned: mbar_scan.h).  The
 // whole cut sums over every sample in its own order, in chunks of SCAN_VCHUNK / SCAN_CHUNK samples.  The binned cut gives every
 // (member, bin) pair the sums a member gets there, over the bin's samples alone: perm lists the samples bin by bin, ascending n
 // inside a bin (a stable counting sort on the host; label -1 dropped), a chunk is a run of sorted positions of ONE bin, cut from
@@ -39,7 +39,7 @@
 // multiplicity c_n makes c_n b_ln inexact.
 //
 // The family.  The two sweeps are also written once for the kind of the members' terms, a second policy next to the cut (Fam =
-// ScanLinear, ScanHarmonic: mbar_internal.h): u_l is the chain of family_term (mbar_device.h) -- the function the fill kernels write
+// ScanLinear, ScanHarmonic: mbar_scan.h): u_l is the chain of family_term (mbar_scan_device.h) -- the function the fill kernels write
 // the resident rows with -- and a harmonic term fma(coeff, w(basis - center)^2, u) with its minimum image w replaces the linear fma
 // where the wave-uniform mask says so (mbar_ctx_set_scan_terms).  The harmonic policy keeps the centres of
 // its at most SCAN_MAX_H harmonic terms per member in registers next to the coefficients, and therefore narrower panels of pass B
@@ -47,6 +47,7 @@
 // of them is compiled out, the kernels take no family argument, and the sweeps are the operations, in the order, this file had
 // before the policy existed.  The merges know neither kind (the cross merge is told the panel width).
 #include "mbar_device.h"
+#include "mbar_scan_device.h"
 
 #pragma clang fp contract(off)
 

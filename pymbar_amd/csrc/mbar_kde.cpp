@@ -1,10 +1,11 @@
 // Host side of the weighted kernel-density sums (include/mbar_hip.h, "weighted kernel-density sums"): the mbar_kde handle (on the
-// handle layer of mbar_ctx.h), the per-column scaling of the weights and their passes, and the exact recomputation of the rare
+// handle layer of mbar_handle.h), the per-column scaling of the weights and their passes, and the exact recomputation of the rare
 // (query, column) pairs the combine kernel flags.  Kernels: mbar_k_kde.hip.
 #include <cmath>
 #include <string>
 
-#include "mbar_ctx.h"
+#include "mbar_handle.h"
+#include "mbar_kde.h"
 
 using namespace mbar;
 using namespace mbar::host;

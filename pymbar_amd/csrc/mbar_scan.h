@@ -1,0 +1,140 @@
+// ---- reweighting scans over a linear family of unsampled states, and the histogram surfaces along a scan (mbar_k_scan.hip;
+// panels, tables, bin groups and C ABI in mbar_scan.cpp) ------------------------------------------------------------------------
+#pragma once
+#include "mbar_common.h"
+
+namespace mbar {
+
+constexpr int SCAN_MAX_B = MBAR_SCAN_MAX_B;  // basis vectors
+constexpr int SCAN_MAX_Q = MBAR_SCAN_MAX_Q;  // observables
+constexpr int SCAN_VCHUNK = 2048;            // samples of one wave of pass A
+constexpr int SCAN_CHUNK = 8192;             // samples of one workgroup of pass B: the cut of N depends on N alone
+// blocks of 16 members per wave of pass B for J = 1 + Q operand columns per member, and per-member sums of its vec record
+constexpr int scan_mb(int J) { return J == 1 ? 4 : J == 2 ? 2 : 1; }
+constexpr int scan_nv(int J) { return 1 + J + J * (J + 1) / 2; }
+constexpr int SCANBIN_NV = 2;  // per (member, bin) sums of a binned pass-B record: wsum | diag
+struct ScanData {
+    int64_t N, ldv;
+    int B, Q;
+    const double* basis;   // [B][ldv]
+    const double* t;       // [Q][ldv] shifted observables (> 0)
+    const double* logden;  // [N]
+    const double* cw;      // [N] multiplicities (NULL: 1)
+};
+// The samples sorted by bin (perm: sorted position -> sample, ascending n inside a bin) and cut into chunks that never straddle a
+// bin: chunk c of a table belongs to bin chunk_bin[c] and is that bin's chunk number c - bin_chunk0[bin], positions bin_start[bin]
+// + chunk number x chunk length onward.  With one bin holding every sample the cut is the cut of the scan passes.
+struct ScanBinTable {
+    int64_t nchunks = 0;
+    const int32_t* chunk_bin = nullptr;   // [nchunks]
+    const int64_t* bin_chunk0 = nullptr;  // [nbins + 1]
+};
+struct ScanBins {
+    int64_t nbins;
+    const int32_t* perm;       // [bin_start[nbins]]
+    const int64_t* bin_start;  // [nbins + 1]
+};
+// The cut of the samples a launch sums over, the compile-time policy of the kernels: the bins [b0(), b1()) and their chunks
+// [c0(), c1()) of at most len positions (chunk c0() writes record 0), the positions [p0, p1) of chunk c and its bin, the sample at
+// position p.  The whole cut also carries what only it has, the reference member of pass B.
+struct ScanWhole {  // every sample in its own order, as one bin: chunk c is [c len, min(N, (c + 1) len))
+    static constexpr bool binned = false;
+    int64_t ref = 0;
+    MBAR_HD int64_t nbins() const { return 1; }
+    MBAR_HD int64_t b0() const { return 0; }
+    MBAR_HD int64_t b1() const { return 1; }
+    MBAR_HD int64_t c0() const { return 0; }
+    MBAR_HD int64_t c1(int64_t N, int64_t len) const { return (N + len - 1) / len; }
+    MBAR_HD void bin_chunks(int64_t, int64_t N, int64_t len, int64_t& ca, int64_t& cb) const { ca = 0, cb = c1(N, len); }
+    MBAR_HD void range(int64_t c, int64_t N, int64_t len, int64_t& bin, int64_t& p0, int64_t& p1) const {
+        bin = 0;
+        p0 = c * len;
+        p1 = p0 + len < N ? p0 + len : N;
+    }
+    MBAR_HD int64_t sample(int64_t p) const { return p; }
+};
+struct ScanBinned {  // the sorted positions of the bins [b0_, b1_), whose chunks in table t are [c0_, c1_)
+    static constexpr bool binned = true;
+    ScanBins sb;
+    ScanBinTable t;
+    int64_t b0_, b1_, c0_, c1_;
+    MBAR_HD int64_t nbins() const { return sb.nbins; }
+    MBAR_HD int64_t b0() const { return b0_; }
+    MBAR_HD int64_t b1() const { return b1_; }
+    MBAR_HD int64_t c0() const { return c0_; }
+    MBAR_HD int64_t c1(int64_t, int64_t) const { return c1_; }
+    MBAR_HD void bin_chunks(int64_t bin, int64_t, int64_t, int64_t& ca, int64_t& cb) const { ca = t.bin_chunk0[bin], cb = t.bin_chunk0[bin + 1]; }
+    MBAR_HD void range(int64_t c, int64_t, int64_t len, int64_t& bin, int64_t& p0, int64_t& p1) const {
+        bin = t.chunk_bin[c];
+        const int64_t end = sb.bin_start[bin + 1];
+        p0 = sb.bin_start[bin] + (c - t.bin_chunk0[bin]) * len;
+        p1 = p0 + len < end ? p0 + len : end;
+    }
+    MBAR_HD int64_t sample(int64_t p) const { return sb.perm[p]; }
+};
+// The kind of the terms of a member, the second compile-time policy of the scan kernels (and, as FamilyTerms, the wave-uniform
+// argument of the family fill): u_l(n) = offset[l] + sum_b term_b, b ascending, a linear term fma(coeff, basis, u), a harmonic one
+//   dl = basis - center;  P > 0: m = rint(dl rP), dl = fma(-P, m, dl);  u = fma(coeff, dl dl, u)
+// (family_term in mbar_scan_device.h: every operation rounded once).  ScanLinear is the family of mbar_ctx_set_scan alone: its
+// instantiations carry no trace of the other kind.
+constexpr int SCAN_MAX_H = MBAR_SCAN_MAX_H;  // harmonic terms
+struct FamilyTerms {
+    uint32_t mask = 0;           // bit b: term b is harmonic
+    double period[SCAN_MAX_B];   // P_b of a harmonic term (0: not periodic)
+    double rperiod[SCAN_MAX_B];  // 1.0 / P_b, rounded once on the host (0 where P_b = 0)
+};
+struct ScanLinear {
+    static constexpr bool harmonic = false;
+    static constexpr int mb(int J) { return scan_mb(J); }
+    MBAR_HD ScanLinear from(int64_t) const { return *this; }
+};
+struct ScanHarmonic {
+    static constexpr bool harmonic = true;
+    // narrower panels of pass B than the linear family's: with its members' centres next to the coefficients the widest
+    // instantiations (8 blocks of states) would not fit the register file at 4 (J = 1) or 2 (J = 2) blocks of members per wave
+    static constexpr int mb(int J) { return J == 1 ? 2 : 1; }
+    FamilyTerms terms;
+    const double* center;  // [L][SCAN_MAX_H] on the device: the centres of the harmonic terms in ascending b, zeros behind them
+    MBAR_HD ScanHarmonic from(int64_t l0) const {  // the family as the members [l0, L) see it
+        ScanHarmonic h = *this;
+        h.center += l0 * SCAN_MAX_H;
+        return h;
+    }
+};
+// Cut = ScanWhole or ScanBinned (Q = 0), Fam = ScanLinear or ScanHarmonic in the two sweeps; the merges know neither kind.
+// pass A over the members [0, L) of coeff / offset: per-chunk records of the maxima (sum = false: rec[chunk][L]) or of the J scaled
+// sums (rec[chunk][L][J]), and their merge in chunk order into M[bin][L] (bin-major, of this member panel), or into
+// lognum[l][bin] (row pitch nbins) and, on the whole cut, mean[L][J]
+template <class Cut, class Fam>
+hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, bool sum, int64_t L, const double* coeff,
+                           const double* offset, const double* M, double* rec);
+template <class Cut>
+hipError_t launch_scan_vec_merge(hipStream_t s, const ScanData& d, const Cut& cut, bool sum, int64_t L, const double* rec, double* M,
+                                 double* lognum, double* mean);
+// pass B for the panel of members [p0, p0 + 64 mb) of L, mb = Fam::mb(J): part[chunk - c0][scan_record_doubles(nb, J, nv, mb)], then
+// cross[k][l][bin][j] (K x L x nbins x J) and vec[l][bin][nv].  Whole cut: nv = scan_nv(J), vec = wsum | refcol[J] | within[i <= j],
+// fnorm = f_scan[L]; binned cut: J = 1, nv = SCANBIN_NV, vec = wsum | diag, fnorm = f_bins[L][nbins] (+inf: an empty bin of that
+// member, exact zeros).  nb = scan_nb_for(K) blocks of 16 states, or 0: no cross block.
+int scan_nb_for(int64_t K);
+int64_t scan_record_doubles(int nb, int J, int nv, int mb);
+template <class Cut, class Fam>
+hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, int nb, const double* u, int64_t ld, int64_t K,
+                             const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset, const double* fnorm,
+                             double* part);
+template <class Cut>
+hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int mb, int64_t K, int64_t L, int64_t p0,
+                                   const double* part, double* cross, double* vec);
+
+// ---- rows of the resident matrix from a family of states (mbar_k_family.hip; C ABI: mbar_ctx_fill_family_rows and ----------
+// ---- mbar_ctx_fill_linear_rows in mbar_rows.cpp) -----------------------------------------------------------------------------
+constexpr int FILL_THREADS = 256;      // a lane owns two adjacent columns: 512 columns per workgroup and pass
+constexpr int FILL_ROWS = 128;         // rows a lane writes from one read of its basis values (grid.y = row groups)
+constexpr int FILL_MAX_BLOCKS = 2048;  // grid.x; the column pairs go round it
+// rows[r][n] = offset[r] + sum_b term_b for r < nrows, n < N: the chain of family_term and scan_x, b ascending.  rows (pitch ld) and
+// basis (pitch ldb) 16-byte aligned with even pitches; coeff[nrows][B], center[nrows][B], offset[nrows] on the device.
+// terms.mask == 0, every term linear, rows[r][n] = fma(coeff[r][B-1], basis[B-1][n], ... fma(coeff[r][0], basis[0][n], offset[r])):
+// the ScanLinear instantiation, which never reads center (NULL will do); otherwise the FamilyTerms one
+hipError_t launch_fill_rows(hipStream_t s, double* rows, int64_t ld, int64_t N, int64_t nrows, int B, const double* basis, int64_t ldb,
+                            const double* coeff, const double* center, const double* offset, const FamilyTerms& terms);
+
+}  // namespace mbar

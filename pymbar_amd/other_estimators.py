@@ -6,7 +6,7 @@ Every sum over work values runs in ``csrc/libmbar_hip.so`` (``mbar_bar_*`` of in
 ``csrc/mbar_k_bar.hip``) on a copy of the values uploaded once (:class:`DeviceBAR`).  The Fermi sums of ``bar_zero`` are exact in
 log space for any finite input, in a fixed reduction order.  The reference's root find -- bracket from EXP, widening, false
 position, bisection or self-consistent iteration, with its convergence and error outcomes -- is one state machine
-(``bar_advance`` in ``csrc/mbar_internal.h``) that the device advances after every evaluation pass; the host only reads a status
+(``bar_advance`` in ``csrc/mbar_bar.h``) that the device advances after every evaluation pass; the host only reads a status
 block between groups of passes.  ``bar`` is ``bar_batch`` with P = 1, so a batch's entry p is bit-identical to the single call.
 
 Deliberate deviations from the reference: ``+inf`` work values contribute a Fermi factor and an

@@ -1,5 +1,5 @@
 """Cases, branch model, bounds and root-find drivers of the BAR and EXP sums (``mbar_bar_zero`` / ``mbar_bar_solve`` /
-``mbar_bar_moments``; mbar_k_bar.hip, mbar_bar.cpp, ``bar_advance`` of mbar_internal.h) -- TEST INFRASTRUCTURE ONLY, shared by
+``mbar_bar_moments``; mbar_k_bar.hip, mbar_bar.cpp, ``bar_advance`` of mbar_bar.h) -- TEST INFRASTRUCTURE ONLY, shared by
 tests/test_gpu_other_estimators.py (device), tests/test_other_estimators_host.py (the model's own checks, on the CPU) and
 tools/bar_branch_matrix.py.  The oracle is tests/bar_oracle.py (numpy long double).
 

@@ -1,7 +1,7 @@
 """CPU stand-in of the family builders and scan passes of ``pymbar_amd.device.DeviceMatrix`` -- TEST INFRASTRUCTURE ONLY.
 
 ``u_model_family`` is the exact statement of the chain the fill kernel and both scan passes evaluate (``family_term``,
-pymbar_amd/csrc/mbar_device.h): from the offset, ``b`` ascending, a linear term ``u = fma(cf, v, u)``, a harmonic one
+pymbar_amd/csrc/mbar_scan_device.h): from the offset, ``b`` ascending, a linear term ``u = fma(cf, v, u)``, a harmonic one
 
     d = v - c;  P > 0: m = rint(d * rP), d = fma(-P, m, d)  (rP = 1.0 / P);  q = d * d;  u = fma(cf, q, u)
 
@@ -133,7 +133,7 @@ class FamilyOracleMatrix(ScanFesOracleMatrix):
 
 # ---- the cases --------------------------------------------------------------------------------------------------------------------
 def harmonic_mb(J):
-    """Blocks of 16 members one wave of the harmonic policy's pass-B kernel owns (ScanHarmonic::mb, mbar_internal.h)"""
+    """Blocks of 16 members one wave of the harmonic policy's pass-B kernel owns (ScanHarmonic::mb, mbar_scan.h)"""
     return 2 if J == 1 else 1
 
 

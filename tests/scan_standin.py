@@ -144,7 +144,7 @@ def run_passes(dm, case, members=slice(None), ref=None):
 
 
 def scan_mb(J):
-    """Blocks of 16 members one wave of the pass-B kernel owns (mbar_internal.h)"""
+    """Blocks of 16 members one wave of the pass-B kernel owns (mbar_scan.h)"""
     return {1: 4, 2: 2}.get(J, 1)
 
 

@@ -232,7 +232,7 @@ def test_model_constants_are_the_kernels():
     import re
 
     csrc = os.path.join(os.path.dirname(amd_fes.__file__), "csrc")
-    text = open(os.path.join(csrc, "mbar_k_hist.hip")).read() + open(os.path.join(csrc, "mbar_internal.h")).read()
+    text = open(os.path.join(csrc, "mbar_k_hist.hip")).read() + open(os.path.join(csrc, "mbar_hist.h")).read()
     for name, value in (("HIST_ROUNDS", hc.HIST_ROUNDS), ("HIST_SLOTS", hc.HIST_SLOTS), ("HIST_NO_SLOT", hc.NO_SLOT),
                         ("HIST_CHUNK_SAMPLES", hc.HIST_CHUNK_SAMPLES), ("HIST_ROWS", hc.HIST_ROWS)):
         found = re.findall(r"constexpr int %s = (\d+);" % name, text)

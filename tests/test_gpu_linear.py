@@ -20,7 +20,7 @@ from tests.conftest import load_golden  # noqa: E402
 from tests.family_standin import u_model  # noqa: E402
 from tests.test_gpu_loopback import run_ranks  # noqa: E402
 
-# The geometry of k_fill_rows (mbar_internal.h): a lane owns 2 adjacent columns, 256 lanes per workgroup, at most 2048
+# The geometry of k_fill_rows (mbar_scan.h): a lane owns 2 adjacent columns, 256 lanes per workgroup, at most 2048
 # workgroups along the columns (the pairs go round them), 128 rows per row group (grid.y), the row loop unrolled by 4.  One pass of
 # the largest grid covers 2048 * 256 * 2 = 1048576 columns; N2 is one more than twice that: a full pass, a full second pass and
 # the odd last column.
