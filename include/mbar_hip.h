@@ -391,6 +391,22 @@ int mbar_scan_gram_w(mbar_ctx* ctx, const double* f, int64_t L, const double* co
  * said above of order, determinism and independence of the members holds for either kind. */
 int mbar_ctx_set_scan_terms(mbar_ctx* ctx, const int32_t* kind, const double* period);
 int mbar_ctx_set_scan_centers(mbar_ctx* ctx, int64_t L, const double* center);
+/* The member's OWN reduced potential as the observable (entropy, enthalpy and heat capacity along a scan): the two passes above with
+ *   t_0 = 1,  t_1 = u_l(n) - center_u[l],  t_2 = t_1 t_1        J = 2 or 3 (anything else: MBAR_ERR_ARG)
+ * where u_l(n) is the value the chain produced for x_ln (not a second evaluation) and every operation is rounded once.  The basis
+ * is the one of mbar_ctx_set_scan with any Q -- its observables are ignored --, the family kinds those of mbar_ctx_set_scan_terms /
+ * mbar_ctx_set_scan_centers; limits, panels, chunks, merges, determinism, independence of the members and the timer are those of
+ * mbar_scan_lognum / mbar_scan_gram_w.  center_u[L]: a centre per member (finite; NULL: zeros).  With center_u = <u_l>, mean[l][1] is
+ * ~ 0 and mean[l][2] - mean[l][1]^2 is the fluctuation of u_l without a cancellation of order <u>^2.
+ *   mbar_scan_energy_lognum   pass A: lognum[l] has the bits mbar_scan_lognum returns for the same members (the max launch and the
+ *                             chain of S_l0 are the same operations); mean[l][j] = S_lj / S_l0 with the member's own t_j (L x J).
+ *   mbar_scan_energy_gram_w   pass B: cross, within and wsum as in mbar_scan_gram_w with the member's own t_j; the reference member's
+ *                             observable is its own too, so refcol becomes refblock[l][i][j] = sum_n c_n (b_rn t_ri)(b_ln t_lj),
+ *                             i = 0, 1, j < J (L x 2 x J). */
+int mbar_scan_energy_lognum(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_u,
+                            int64_t J, double* lognum, double* mean);
+int mbar_scan_energy_gram_w(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_u,
+                            int64_t J, const double* f_scan, int64_t r, double* cross, double* within, double* refblock, double* wsum);
 
 /* ---- histogram surfaces along a scan ---------------------------------------------------------
  * The histogram free energy surface of EVERY member of a scan: the bins are labels of the resident samples as in "histogram bins

@@ -46,6 +46,12 @@
 // (ScanHarmonic::mb: at the linear family's widths the instantiations of 8 blocks of states spilled); under ScanLinear every trace
 // of them is compiled out, the kernels take no family argument, and the sweeps are the operations, in the order, this file had
 // before the policy existed.  The merges know neither kind (the cross merge is told the panel width).
+//
+// The observables.  A third policy says where t_j comes from (Obs = ScanStored, ScanEnergy: mbar_scan.h).  ScanStored reads d.t, the
+// same for every member: every instantiation this file had, with the argument blocks and instruction streams it had.  ScanEnergy is
+// the member's own reduced potential (MBAR.compute_scan_entropy_and_enthalpy): t_1 = u_l(n) - center_u[l] from
+// the u the chain produced for x_ln, t_2 = t_1 t_1, J = 2 or 3, whole cut only; pass B then keeps refblock[i < 2][J] where the
+// stored kind keeps refcol[J], because the reference member's t_1 is its own.
 #include "mbar_device.h"
 #include "mbar_scan_device.h"
 
@@ -66,14 +72,17 @@ __device__ __forceinline__ void scan_neumaier(double& s, double& e, double v) {
 
 // One wave per (chunk, 64 members).  SUM = false: rec[chunk][l] = max of x_ln over the chunk's samples with c_n > 0; SUM = true:
 // rec[(chunk L + l) J + j] = sum c_n exp(x_ln - M[bin][l]) t_jn.
-// (FamArg: nothing under ScanLinear, whose kernels keep the argument block -- and with it the instruction stream -- they had before
-// the family policy existed; the ScanHarmonic itself under ScanHarmonic)
-template <bool SUM, class Cut, class Fam, class... FamArg>
+// (Arg: nothing under ScanLinear and ScanStored, whose kernels keep the argument block -- and with it the instruction stream -- they
+// had before the family and observable policies existed; the ScanHarmonic and / or the ScanEnergy themselves otherwise.  Under
+// ScanEnergy t_1 = u_l(n) - center_u[l] from the u the chain produced for x, t_2 = t_1 t_1; acc[0] is the chain it always was.)
+template <bool SUM, class Cut, class Fam, class Obs, class... Arg>
 __global__ void __launch_bounds__(SV_THREADS)
 k_scan_vec(ScanData d, Cut cut, int64_t L, const double* __restrict__ coeff, const double* __restrict__ offset,
-           const double* __restrict__ M, double* __restrict__ rec, FamArg... fam_arg) {
-    const Fam fam{fam_arg...};
-    constexpr int MAX_Q = Cut::binned ? 0 : SCAN_MAX_Q;
+           const double* __restrict__ M, double* __restrict__ rec, Arg... arg) {
+    const Fam fam = scan_arg<Fam>(arg...);
+    const Obs obs = scan_arg<Obs>(arg...);
+    static_assert(!Obs::energy || (SUM && !Cut::binned), "the energy observable: the sums of the whole cut");
+    constexpr int MAX_Q = Cut::binned ? 0 : Obs::energy ? 2 : SCAN_MAX_Q;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (SUM) {
         exp_table_init(smem);
@@ -95,6 +104,8 @@ k_scan_vec(ScanData d, Cut cut, int64_t L, const double* __restrict__ coeff, con
     double cen[SCAN_MAX_H];
     family_load_centers(fam, live, l, cen);
     const double Ml = (SUM && live) ? M[bin * L + l] : 0.0;
+    double cu = 0.0;  // (ScanEnergy: the member's centre)
+    if constexpr (Obs::energy) cu = live ? obs.center_u[l] : 0.0;
     double acc[1 + MAX_Q];
     acc[0] = SUM ? 0.0 : -INFINITY;
 #pragma unroll
@@ -103,15 +114,22 @@ k_scan_vec(ScanData d, Cut cut, int64_t L, const double* __restrict__ coeff, con
         const int64_t n = cut.sample(p);
         const double cn = d.cw ? d.cw[n] : 1.0;
         if (!(cn > 0.0)) continue;
-        const double x = scan_x(d, fam, cf, cen, off, n);
+        const double ul = scan_u(d, fam, cf, cen, off, n);
+        const double x = scan_x_of(d, ul, n);
         if (!SUM) {
             acc[0] = fmax(acc[0], x);
         } else {
             const double e = cn * scan_exp(x - Ml);
             acc[0] += e;
+            if constexpr (Obs::energy) {
+                const double t1 = ul - cu;
+                acc[1] = fma(e, t1, acc[1]);
+                if (J > 2) acc[2] = fma(e, t1 * t1, acc[2]);
+            } else {
 #pragma unroll
-            for (int j = 1; j <= MAX_Q; ++j)
-                if (j < J) acc[j] = fma(e, d.t[(int64_t)(j - 1) * d.ldv + n], acc[j]);
+                for (int j = 1; j <= MAX_Q; ++j)
+                    if (j < J) acc[j] = fma(e, d.t[(int64_t)(j - 1) * d.ldv + n], acc[j]);
+            }
         }
     }
     if (!live) return;
@@ -174,22 +192,29 @@ k_scan_vec_merge(ScanData d, Cut cut, int64_t L, const double* __restrict__ rec,
 //   vec part    [pm < 64 MB][NV]                        whole cut: wsum | refcol[J] | within[i <= j], NV = scan_nv(J)
 //                                                       binned cut: wsum | diag, NV = SCANBIN_NV
 // Member pm of the panel sits in block pm / 16 = mb * 4 + wave (the blocks go round the waves, so a short panel keeps all four busy).
-template <int NB, int J, class Cut, class Fam, class... FamArg>
+// Obs = ScanEnergy: t_j is the member's own (t_1 = u_l(n) - center_u[l] from the chain's u, t_2 = t_1 t_1: per member block where the
+// stored kind has it per sample), no t rows in sv, and the fill stage stores t_r1 of the reference member next to b_rn, for the second
+// row of refblock (MB = Obs::mb<Fam>(J), NV = Obs::nv(J)).
+template <int NB, int J, class Cut, class Fam, class Obs, class... Arg>
 __global__ void __launch_bounds__(256)
 k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int64_t K, const double* __restrict__ f, int64_t L, int64_t p0,
              const double* __restrict__ coeff, const double* __restrict__ offset, const double* __restrict__ fnorm,
-             double* __restrict__ part, FamArg... fam_arg) {
-    const Fam fam{fam_arg...};
+             double* __restrict__ part, Arg... arg) {
+    const Fam fam = scan_arg<Fam>(arg...);
+    const Obs obs = scan_arg<Obs>(arg...);
     constexpr bool REF = !Cut::binned;  // the reference member
+    constexpr bool ENERGY = Obs::energy;
     static_assert(REF || J == 1, "the binned cut takes no observables");
-    constexpr int MB = Fam::mb(J), NCB = MB * J, NV = REF ? scan_nv(J) : SCANBIN_NV, Q = J - 1;
-    constexpr int VW = REF ? 1 + J : 1;  // where within starts in the vec record
-    constexpr int SVB = REF ? 48 : 32;   // where the basis rows start in sv
+    static_assert(!ENERGY || (REF && (J == 2 || J == 3)), "the energy observable: the whole cut, J = 2 or 3");
+    constexpr int MB = Obs::template mb<Fam>(J), NCB = MB * J, NV = REF ? Obs::nv(J) : SCANBIN_NV;
+    constexpr int Q = ENERGY ? 0 : J - 1;               // t rows in sv
+    constexpr int VW = REF ? 1 + Obs::ref_rows * J : 1;  // where within starts in the vec record
+    constexpr int SVB = REF ? (ENERGY ? 64 : 48) : 32;   // where the basis rows start in sv
     constexpr int W_DOUBLES = NB * 16 * SCAN_PITCH;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     exp_table_init(smem);
     double* Wt = reinterpret_cast<double*>(smem + EXP_TABLE_BYTES);  // [16 NB][SCAN_PITCH]
-    double* sv = Wt + W_DOUBLES;                                     // cn[16] | lden[16] | (REF: br[16]) | basis[B][16] | t[Q][16]
+    double* sv = Wt + W_DOUBLES;  // cn[16] | lden[16] | (REF: br[16]) | (ENERGY: tr1[16]) | basis[B][16] | t[Q][16]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, q4 = lane >> 4;
@@ -205,12 +230,14 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
 
     double cf[MB][SCAN_MAX_B], off[MB], fs[MB];
     double cen[Fam::harmonic ? MB : 1][SCAN_MAX_H];  // (the harmonic family alone keeps its members' centres)
+    double cu[ENERGY ? MB : 1];  // (the energy observable alone keeps its members' centres)
     bool mlive[MB];
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
         const int64_t pm = (int64_t)(mb * 4 + wave) * 16 + col;
         mlive[mb] = pm < pl;
         const int64_t l = p0 + pm;
+        if constexpr (ENERGY) cu[mb] = mlive[mb] ? obs.center_u[l] : 0.0;
 #pragma unroll
         for (int b = 0; b < SCAN_MAX_B; ++b) cf[mb][b] = (mlive[mb] && b < d.B) ? coeff[l * d.B + b] : 0.0;
         off[mb] = mlive[mb] ? offset[l] : 0.0;
@@ -283,8 +310,12 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
                         for (int b = 0; b < SCAN_MAX_B; ++b)
                             if (b < d.B) ur = family_term(fam, b, ur, cr[b], d.basis[(int64_t)b * d.ldv + n], family_center(fam, b, cenr));
                         br = scan_exp(fsr + (-ur - lden));
+                        // (ScanEnergy: t_r1 as that member's own t_1; its centre is read per tile like the family's)
+                        if constexpr (ENERGY) sv[48 + fs_s] = ur - obs.center_u[cut.ref];
                     }
                     sv[32 + fs_s] = br;
+                    if constexpr (ENERGY)
+                        if (!slive) sv[48 + fs_s] = 0.0;
                 }
             }
             if (fs_r < d.B + Q) {
@@ -310,7 +341,7 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
                 for (int b = 0; b < SCAN_MAX_B; ++b) bas[b] = b < d.B ? sv[SVB + b * 16 + s] : 0.0;
                 tj[0] = 1.0;
 #pragma unroll
-                for (int j = 1; j < J; ++j) tj[j] = sv[SVB + (d.B + j - 1) * 16 + s];
+                for (int j = 1; j < J; ++j) tj[j] = ENERGY ? 0.0 : sv[SVB + (d.B + j - 1) * 16 + s];
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb) {
                     if (mb < mine) {  // (wave-uniform)
@@ -321,6 +352,10 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
                         double bv = scan_exp(fs[mb] + (-uu - lden));
                         if (!(cn > 0.0) || !mlive[mb]) bv = 0.0;
                         const double cb = cn * bv;
+                        if constexpr (ENERGY) {  // (tj is this member block's own from here on)
+                            tj[1] = uu - cu[mb];
+                            if constexpr (J > 2) tj[2] = tj[1] * tj[1];
+                        }
                         double z[J];
 #pragma unroll
                         for (int j = 0; j < J; ++j) z[j] = cb * tj[j];
@@ -328,6 +363,11 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
                         if constexpr (REF) {
 #pragma unroll
                             for (int j = 0; j < J; ++j) vs[mb][1 + j] = fma(z[j], br, vs[mb][1 + j]);
+                        }
+                        if constexpr (ENERGY) {
+                            const double brt = br * sv[48 + s];  // (b_rn t_r1: the same product in every member block)
+#pragma unroll
+                            for (int j = 0; j < J; ++j) vs[mb][1 + J + j] = fma(z[j], brt, vs[mb][1 + J + j]);
                         }
                         int v = VW;
 #pragma unroll
@@ -370,12 +410,12 @@ k_scan_cross(ScanData d, Cut cut, const double* __restrict__ u, int64_t ld, int6
 
 // The records of the panel and of the launch's bins merged per bin in chunk order.  Threads [0, nbg pl J K):
 // cross[k][p0 + pm][bin][j]; threads behind them, [0, nbg pl NV): vec[p0 + pm][bin][v].
-template <class Cut>
+template <class Cut, class Obs>
 __global__ void __launch_bounds__(SV_THREADS)
 k_scan_cross_merge(ScanData d, Cut cut, int NB, int64_t K, int64_t L, int64_t p0, int64_t pl, const double* __restrict__ part,
                    double* __restrict__ cross, double* __restrict__ vec, int MB) {
     const int J = Cut::binned ? 1 : 1 + d.Q;
-    const int NCB = MB * J, NV = Cut::binned ? SCANBIN_NV : scan_nv(J);
+    const int NCB = MB * J, NV = Cut::binned ? SCANBIN_NV : Obs::nv(J);
     const int64_t cross_doubles = (int64_t)4 * NB * NCB * 256, stride = cross_doubles + (int64_t)64 * MB * NV;
     const int64_t nbg = cut.b1() - cut.b0(), ncross = NB > 0 ? nbg * pl * J * K : 0;
     int64_t x = (int64_t)blockIdx.x * SV_THREADS + threadIdx.x;
@@ -405,21 +445,32 @@ k_scan_cross_merge(ScanData d, Cut cut, int NB, int64_t K, int64_t L, int64_t p0
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
-template <class Cut, class Fam>
-hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, bool sum, int64_t L, const double* coeff,
-                           const double* offset, const double* M, double* rec) {
+// launch(the policies that travel as kernel arguments...): the family if it is harmonic, then the observable if it is the energy
+template <class Fam, class Obs, class F>
+static void with_policy_args(const Fam& fam, const Obs& obs, F&& launch) {
+    if constexpr (Fam::harmonic && Obs::energy) launch(fam, obs);
+    else if constexpr (Fam::harmonic) launch(fam);
+    else if constexpr (Obs::energy) launch(obs);
+    else launch();
+}
+
+template <class Cut, class Fam, class Obs>
+hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, const Obs& obs, bool sum, int64_t L,
+                           const double* coeff, const double* offset, const double* M, double* rec) {
+    if constexpr (Obs::energy) {
+        if (!sum) return launch_scan_vec(s, d, cut, fam, ScanStored{}, false, L, coeff, offset, M, rec);
+        if (d.Q < 1 || d.Q > 2) return hipErrorInvalidValue;
+    }
     const int64_t nchunks = cut.c1(d.N, SCAN_VCHUNK) - cut.c0();
     if (L < 1 || nchunks < 1) return hipSuccess;
     const int64_t gx = (nchunks + SV_THREADS / 64 - 1) / (SV_THREADS / 64);
     const dim3 grid((unsigned)gx, (unsigned)((L + 63) / 64));
     if (gx > 0x7fffffff || grid.y > 65535u) return hipErrorInvalidValue;
-    if constexpr (Fam::harmonic) {
-        if (sum) hipLaunchKernelGGL((k_scan_vec<true, Cut, Fam, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec, fam);
-        else hipLaunchKernelGGL((k_scan_vec<false, Cut, Fam, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec, fam);
-    } else {
-        if (sum) hipLaunchKernelGGL((k_scan_vec<true, Cut, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec);
-        else hipLaunchKernelGGL((k_scan_vec<false, Cut, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec);
-    }
+    with_policy_args(fam, obs, [&](auto... a) {
+        if (sum) hipLaunchKernelGGL((k_scan_vec<true, Cut, Fam, Obs, decltype(a)...>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec, a...);
+        else if constexpr (!Obs::energy)
+            hipLaunchKernelGGL((k_scan_vec<false, Cut, Fam, Obs, decltype(a)...>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, coeff, offset, M, rec, a...);
+    });
     return hipGetLastError();
 }
 
@@ -445,22 +496,21 @@ int64_t scan_record_doubles(int nb, int J, int nv, int MB) {
     return (int64_t)4 * nb * MB * J * 256 + (int64_t)64 * MB * nv;
 }
 
-// the ladder over J: the whole cut is instantiated for J = 1 .. 4, the binned cut for J = 1
-template <int NB, class Cut, class Fam>
-static hipError_t launch_scan_cross_nb(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, dim3 grid, size_t lds, const double* u, int64_t ld,
-                                       int64_t K, const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset,
-                                       const double* fnorm, double* part) {
+// the ladder over J: the whole cut is instantiated for J = 1 .. 4 (the energy observable: J = 2, 3), the binned cut for J = 1
+template <int NB, class Cut, class Fam, class Obs>
+static hipError_t launch_scan_cross_nb(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, const Obs& obs, dim3 grid, size_t lds,
+                                       const double* u, int64_t ld, int64_t K, const double* f, int64_t L, int64_t p0, const double* coeff,
+                                       const double* offset, const double* fnorm, double* part) {
     switch (Cut::binned ? 1 : 1 + d.Q) {
 #define MBAR_CASE(J_)                                                                                                                    \
     case J_:                                                                                                                             \
-        if constexpr (J_ == 1 || !Cut::binned) {                                                                                         \
-            if constexpr (Fam::harmonic)                                                                                                 \
-                hipLaunchKernelGGL((k_scan_cross<NB, J_, Cut, Fam, Fam>), grid, dim3(256), lds, s, d, cut, u, ld, K, f, L, p0, coeff,    \
-                                   offset, fnorm, part, fam);                                                                            \
-            else                                                                                                                         \
-                hipLaunchKernelGGL((k_scan_cross<NB, J_, Cut, Fam>), grid, dim3(256), lds, s, d, cut, u, ld, K, f, L, p0, coeff, offset, \
-                                   fnorm, part);                                                                                         \
-        }                                                                                                                                \
+        if constexpr ((J_ == 1 || !Cut::binned) && (!Obs::energy || J_ == 2 || J_ == 3))                                                 \
+            with_policy_args(fam, obs, [&](auto... a) {                                                                                  \
+                hipLaunchKernelGGL((k_scan_cross<NB, J_, Cut, Fam, Obs, decltype(a)...>), grid, dim3(256), lds, s, d, cut, u, ld, K, f,  \
+                                   L, p0, coeff, offset, fnorm, part, a...);                                                             \
+            });                                                                                                                          \
+        else                                                                                                                             \
+            return hipErrorInvalidValue;                                                                                                 \
         break;
         MBAR_CASE(1) MBAR_CASE(2) MBAR_CASE(3) MBAR_CASE(4)
 #undef MBAR_CASE
@@ -470,10 +520,10 @@ static hipError_t launch_scan_cross_nb(hipStream_t s, const ScanData& d, const C
 }
 
 // nb: scan_nb_for(K), or 0 (no cross block: the per-member sums only)
-template <class Cut, class Fam>
-hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, int nb, const double* u, int64_t ld, int64_t K,
-                             const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset, const double* fnorm,
-                             double* part) {
+template <class Cut, class Fam, class Obs>
+hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, const Obs& obs, int nb, const double* u,
+                             int64_t ld, int64_t K, const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset,
+                             const double* fnorm, double* part) {
     const int64_t c0 = cut.c0(), c1 = cut.c1(d.N, SCAN_CHUNK);
     if (c1 <= c0 || p0 >= L) return hipSuccess;
     if (K > 16 * (int64_t)nb && nb > 0) return hipErrorInvalidValue;
@@ -481,49 +531,54 @@ hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, c
     if constexpr (Cut::binned)
         if (c1 > cut.t.nchunks) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(c1 - c0));
-    // sv: cn | lden | (the whole cut: br) | basis rows | (the whole cut: t rows)
+    // sv: cn | lden | (the whole cut: br) | basis rows | (the whole cut: t rows; the energy observable has tr1 and no t rows)
     const size_t sv = Cut::binned ? 32 + (size_t)SCAN_MAX_B * 16 : 48 + (size_t)(SCAN_MAX_B + SCAN_MAX_Q) * 16;
     const size_t lds = EXP_TABLE_BYTES + ((size_t)nb * 16 * SCAN_PITCH + sv) * sizeof(double);
     switch (nb) {
 #define MBAR_CASE(NB_) \
-    case NB_: return launch_scan_cross_nb<NB_>(s, d, cut, fam, grid, lds, u, ld, K, f, L, p0, coeff, offset, fnorm, part);
+    case NB_: return launch_scan_cross_nb<NB_>(s, d, cut, fam, obs, grid, lds, u, ld, K, f, L, p0, coeff, offset, fnorm, part);
         MBAR_CASE(0) MBAR_CASE(1) MBAR_CASE(2) MBAR_CASE(4) MBAR_CASE(8)
 #undef MBAR_CASE
         default: return hipErrorInvalidValue;
     }
 }
 
-template <class Cut>
+template <class Cut, class Obs>
 hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int mb, int64_t K, int64_t L, int64_t p0,
                                    const double* part, double* cross, double* vec) {
     const int64_t nbg = cut.b1() - cut.b0();
     if (nbg < 1 || p0 >= L || (!Cut::binned && d.N < 1)) return hipSuccess;  // (a bin without a chunk still gets its zeros)
     const int J = Cut::binned ? 1 : 1 + d.Q;
     const int64_t pl = L - p0 < 64 * mb ? L - p0 : 64 * mb;
-    const int64_t threads = nbg * ((nb > 0 ? pl * J * K : 0) + pl * (Cut::binned ? SCANBIN_NV : scan_nv(J)));
+    const int64_t threads = nbg * ((nb > 0 ? pl * J * K : 0) + pl * (Cut::binned ? SCANBIN_NV : Obs::nv(J)));
     const int64_t blocks = (threads + SV_THREADS - 1) / SV_THREADS;
     if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_scan_cross_merge<Cut>), dim3((unsigned)blocks), dim3(SV_THREADS), 0, s, d, cut, nb, K, L, p0, pl, part, cross, vec, mb);
+    hipLaunchKernelGGL((k_scan_cross_merge<Cut, Obs>), dim3((unsigned)blocks), dim3(SV_THREADS), 0, s, d, cut, nb, K, L, p0, pl, part, cross, vec, mb);
     return hipGetLastError();
 }
 
-#define MBAR_SWEEPS(Cut, Fam)                                                                                                                \
-    template hipError_t launch_scan_vec<Cut, Fam>(hipStream_t, const ScanData&, const Cut&, const Fam&, bool, int64_t, const double*,        \
-                                                  const double*, const double*, double*);                                                    \
-    template hipError_t launch_scan_cross<Cut, Fam>(hipStream_t, const ScanData&, const Cut&, const Fam&, int, const double*, int64_t,       \
-                                                    int64_t, const double*, int64_t, int64_t, const double*, const double*, const double*,   \
-                                                    double*);
-#define MBAR_CUT(Cut)                                                                                                                        \
-    MBAR_SWEEPS(Cut, ScanLinear)                                                                                                             \
-    MBAR_SWEEPS(Cut, ScanHarmonic)                                                                                                           \
-    template hipError_t launch_scan_vec_merge<Cut>(hipStream_t, const ScanData&, const Cut&, bool, int64_t, const double*, double*, double*, \
-                                                   double*);                                                                                 \
-    template hipError_t launch_scan_cross_merge<Cut>(hipStream_t, const ScanData&, const Cut&, int, int, int64_t, int64_t, int64_t,          \
-                                                     const double*,                                                                          \
-                                                     double*, double*);
+#define MBAR_SWEEPS(Cut, Fam, Obs)                                                                                                           \
+    template hipError_t launch_scan_vec<Cut, Fam, Obs>(hipStream_t, const ScanData&, const Cut&, const Fam&, const Obs&, bool, int64_t,          \
+                                                       const double*, const double*, const double*, double*);                                    \
+    template hipError_t launch_scan_cross<Cut, Fam, Obs>(hipStream_t, const ScanData&, const Cut&, const Fam&, const Obs&, int, const double*,   \
+                                                         int64_t, int64_t, const double*, int64_t, int64_t, const double*, const double*,        \
+                                                         const double*, double*);
+#define MBAR_MERGES(Cut, Obs)                                                                                                                    \
+    template hipError_t launch_scan_cross_merge<Cut, Obs>(hipStream_t, const ScanData&, const Cut&, int, int, int64_t, int64_t, int64_t,         \
+                                                          const double*, double*, double*);
+#define MBAR_CUT(Cut)                                                                                                                            \
+    MBAR_SWEEPS(Cut, ScanLinear, ScanStored)                                                                                                     \
+    MBAR_SWEEPS(Cut, ScanHarmonic, ScanStored)                                                                                                   \
+    MBAR_MERGES(Cut, ScanStored)                                                                                                                 \
+    template hipError_t launch_scan_vec_merge<Cut>(hipStream_t, const ScanData&, const Cut&, bool, int64_t, const double*, double*, double*,     \
+                                                   double*);
 MBAR_CUT(ScanWhole)
 MBAR_CUT(ScanBinned)
+MBAR_SWEEPS(ScanWhole, ScanLinear, ScanEnergy)
+MBAR_SWEEPS(ScanWhole, ScanHarmonic, ScanEnergy)
+MBAR_MERGES(ScanWhole, ScanEnergy)
 #undef MBAR_CUT
+#undef MBAR_MERGES
 #undef MBAR_SWEEPS
 
 }  // namespace mbar

@@ -29,24 +29,26 @@ ScanData scan_data_of(const mbar_ctx* c) {
 }
 
 // The two sweeps on the context's family: the linear instantiations unless a harmonic term is set (mbar_ctx_set_scan_terms); l0:
-// the member the coeff / offset pointers of a pass-A panel start at (pass B takes the whole arrays and its own p0).
+// the member the coeff / offset pointers of a pass-A panel start at (pass B takes the whole arrays and its own p0).  obs: where the
+// observables come from, the stored ones of the context (ScanStored) or the members' own reduced potential (ScanEnergy, whole cut).
 ScanHarmonic harmonic_of(const mbar_ctx* c) { return ScanHarmonic{c->scan_terms, c->scan_center.p}; }
-template <class Cut>
-hipError_t sweep_vec(mbar_ctx* c, const ScanData& d, const Cut& cut, bool sum, int64_t l0, int64_t L, const double* coeff, const double* offset,
-                     const double* M, double* rec) {
-    if (c->scan_terms.mask) return launch_scan_vec(c->stream, d, cut, harmonic_of(c).from(l0), sum, L, coeff, offset, M, rec);
-    return launch_scan_vec(c->stream, d, cut, ScanLinear{}, sum, L, coeff, offset, M, rec);
+template <class Cut, class Obs>
+hipError_t sweep_vec(mbar_ctx* c, const ScanData& d, const Cut& cut, const Obs& obs, bool sum, int64_t l0, int64_t L, const double* coeff,
+                     const double* offset, const double* M, double* rec) {
+    if (c->scan_terms.mask) return launch_scan_vec(c->stream, d, cut, harmonic_of(c).from(l0), obs.from(l0), sum, L, coeff, offset, M, rec);
+    return launch_scan_vec(c->stream, d, cut, ScanLinear{}, obs.from(l0), sum, L, coeff, offset, M, rec);
 }
-template <class Cut>
-hipError_t sweep_cross(mbar_ctx* c, const ScanData& d, const Cut& cut, int nb, int64_t L, int64_t p0, const double* coeff, const double* offset,
-                       const double* fnorm) {
+template <class Cut, class Obs>
+hipError_t sweep_cross(mbar_ctx* c, const ScanData& d, const Cut& cut, const Obs& obs, int nb, int64_t L, int64_t p0, const double* coeff,
+                       const double* offset, const double* fnorm) {
     if (c->scan_terms.mask)
-        return launch_scan_cross(c->stream, d, cut, harmonic_of(c), nb, c->u, c->ld, c->K, d_f(c), L, p0, coeff, offset, fnorm, c->scan_part);
-    return launch_scan_cross(c->stream, d, cut, ScanLinear{}, nb, c->u, c->ld, c->K, d_f(c), L, p0, coeff, offset, fnorm, c->scan_part);
+        return launch_scan_cross(c->stream, d, cut, harmonic_of(c), obs, nb, c->u, c->ld, c->K, d_f(c), L, p0, coeff, offset, fnorm, c->scan_part);
+    return launch_scan_cross(c->stream, d, cut, ScanLinear{}, obs, nb, c->u, c->ld, c->K, d_f(c), L, p0, coeff, offset, fnorm, c->scan_part);
 }
 
 // blocks of 16 members per wave of pass B on the context's family
-int scan_mb_of(const mbar_ctx* c, int J) { return c->scan_terms.mask ? ScanHarmonic::mb(J) : ScanLinear::mb(J); }
+template <class Obs>
+int scan_mb_of(const mbar_ctx* c, int J) { return c->scan_terms.mask ? Obs::template mb<ScanHarmonic>(J) : Obs::template mb<ScanLinear>(J); }
 
 void release_terms(mbar_ctx* c) {
     c->scan_terms = FamilyTerms{};
@@ -74,7 +76,7 @@ int scan_open(mbar_ctx* c, const std::string& who, bool args_ok, bool binned, in
 }
 
 // scan_begin, once the sizes are known: the log-denominators of f; with an unusable matrix or f, or a NaN among the members'
-// normalisers fnorm[nnorm] (NULL: none), every output is filled with NaN and *done is set (the call returns MBAR_OK); otherwise
+// normalisers fnorm[nnorm] (NULL: none), or with *done set by the caller (a NaN among what only it takes), every output is filled with NaN and *done is set (the call returns MBAR_OK); otherwise
 // scan_part / scan_out are sized for the call's partial records and merged outputs (part_doubles, out_doubles: before anything of
 // the call is queued), coeff | offset (NULL: zeros) | room for L normalisers go to the device and *d is the family as the kernels
 // see it.
@@ -90,6 +92,7 @@ int scan_begin(mbar_ctx* c, const double* f, int64_t L, const double* coeff, con
             if (!std::isfinite(coeff[x])) return fail(c, MBAR_ERR_ARG, "the coefficients of a family with harmonic terms must be finite");
     int rc = pass_logden(c, f, &nan);
     if (rc) return rc;
+    nan = nan || *done;
     for (size_t x = 0; x < nnorm; ++x) nan = nan || std::isnan(fnorm[x]);
     *done = nan;
     if (nan) {
@@ -98,7 +101,7 @@ int scan_begin(mbar_ctx* c, const double* f, int64_t L, const double* coeff, con
         return MBAR_OK;
     }
     const int64_t B = c->scan_B;
-    HIPCHK(c, c->scan_in.grow((size_t)L * (size_t)(B + 2)));
+    HIPCHK(c, c->scan_in.grow((size_t)L * (size_t)(B + 3)));  // coeff | offset | normalisers | centres of the energy observable
     HIPCHK(c, c->scan_part.grow(part_doubles));
     HIPCHK(c, c->scan_out.grow(out_doubles));
     double* d_coeff = c->scan_in;
@@ -171,6 +174,131 @@ ScanBinned binned_of(const mbar_ctx* c, bool pass_b) {
     s.b1_ = s.sb.nbins;
     s.c1_ = s.t.nchunks;
     return s;
+}
+
+// ---- the two passes of the whole cut, written once for either kind of observable ----
+// The observables of a whole-cut call: the context's stored ones (J = 1 + Q), or the members' own reduced potential about
+// center_u[L] (NULL: zeros) with J = 2 or 3 (the context's Q is ignored).
+struct WholeObs {
+    bool energy = false;
+    const double* center_u = nullptr;
+    int64_t J = 0;
+};
+bool obs_ok(const WholeObs& o) { return !o.energy || o.J == 2 || o.J == 3; }
+bool obs_nan(const WholeObs& o, int64_t L) {
+    bool nan = false;
+    if (o.energy && o.center_u)
+        for (int64_t l = 0; l < L; ++l) nan = nan || std::isnan(o.center_u[l]);
+    return nan;
+}
+// the family as the kernels of the call see it, and the centres of the energy observable behind the normalisers in scan_in
+int obs_begin(mbar_ctx* c, const WholeObs& o, int64_t L, ScanData* d, ScanEnergy* e) {
+    if (!o.energy) return MBAR_OK;
+    for (int64_t l = 0; o.center_u && l < L; ++l)
+        if (std::isinf(o.center_u[l])) return fail(c, MBAR_ERR_ARG, "the centres of the energy observable must be finite");
+    d->Q = (int)o.J - 1;
+    double* d_cu = c->scan_in.p + L * (c->scan_B + 2);
+    if (o.center_u) HIPCHK(c, hipMemcpyAsync(d_cu, o.center_u, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    else HIPCHK(c, hipMemsetAsync(d_cu, 0, (size_t)L * sizeof(double), c->stream));
+    e->center_u = d_cu;
+    return MBAR_OK;
+}
+
+int whole_lognum(mbar_ctx* c, const char* who, const WholeObs& o, const double* f, int64_t L, const double* coeff, const double* offset,
+                 double* lognum, double* mean) {
+    int rc = scan_open(c, who, f && coeff && lognum && L >= 1 && obs_ok(o), false, L);
+    if (rc) return rc;
+    const int64_t B = c->scan_B, J = o.energy ? o.J : 1 + c->scan_Q;
+    bool done = obs_nan(o, L);
+    ScanData d;
+    ScanEnergy energy{nullptr};
+    const int64_t nchunks = std::max<int64_t>((c->N + SCAN_VCHUNK - 1) / SCAN_VCHUNK, 1);
+    const int64_t pw = vec_panel(c, nchunks, J, L);
+    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{lognum, (size_t)L}, {mean, (size_t)(L * J)}},
+                    (size_t)nchunks * (size_t)pw * (size_t)J, (size_t)L * (size_t)(2 + J), &done, &d);
+    if (rc || done) return rc;
+    rc = obs_begin(c, o, L, &d, &energy);
+    if (rc) return rc;
+    double* d_M = c->scan_out;
+    double* d_lognum = d_M + L;
+    double* d_mean = d_lognum + L;
+    const double* d_coeff = c->scan_in;
+    const double* d_off = d_coeff + L * B;
+    const ScanWhole cut{};
+    auto sweep = [&](bool sum, int64_t p0, int64_t pl, const double* M) {
+        if (o.energy) return sweep_vec(c, d, cut, energy, sum, p0, pl, d_coeff + p0 * B, d_off + p0, M, c->scan_part);
+        return sweep_vec(c, d, cut, ScanStored{}, sum, p0, pl, d_coeff + p0 * B, d_off + p0, M, c->scan_part);
+    };
+    {
+        ScopedTimer timer(c, MBAR_TIMER_OTHER);
+        for (int64_t p0 = 0; p0 < L; p0 += pw) {
+            const int64_t pl = std::min(pw, L - p0);
+            HIPCHK(c, sweep(false, p0, pl, nullptr));
+            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, false, pl, c->scan_part, d_M + p0, nullptr, nullptr));
+            HIPCHK(c, sweep(true, p0, pl, d_M + p0));
+            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, true, pl, c->scan_part, d_M + p0, d_lognum + p0, d_mean + p0 * J));
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(lognum, d_lognum, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (mean) HIPCHK(c, hipMemcpyAsync(mean, d_mean, (size_t)L * J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
+// refrows: refcol[L][J] of the stored observables, refblock[L][2][J] of the energy observable
+int whole_gram_w(mbar_ctx* c, const char* who, const WholeObs& o, const double* f, int64_t L, const double* coeff, const double* offset,
+                 const double* f_scan, int64_t r, double* cross, double* within, double* refrows, double* wsum) {
+    int rc = scan_open(c, who, f && coeff && f_scan && within && refrows && wsum && L >= 1 && r >= 0 && r < L && obs_ok(o), false, L);
+    if (rc) return rc;
+    const int64_t B = c->scan_B, K = c->K;
+    const int J = o.energy ? (int)o.J : 1 + (int)c->scan_Q, NW = J * (J + 1) / 2;
+    const int NR = (o.energy ? ScanEnergy::ref_rows : ScanStored::ref_rows) * J, NV = o.energy ? ScanEnergy::nv(J) : ScanStored::nv(J);
+    bool done = obs_nan(o, L);
+    ScanData d;
+    ScanEnergy energy{nullptr};
+    const int nb = cross ? scan_nb_for(K) : 0;
+    const int64_t nchunks = (c->N + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    const int mb = o.energy ? scan_mb_of<ScanEnergy>(c, J) : scan_mb_of<ScanStored>(c, J);
+    const int64_t pw = 64 * mb;
+    rc = scan_begin(c, f, L, coeff, offset, f_scan, (size_t)L,
+                    {{cross, (size_t)K * L * J}, {within, (size_t)(L * NW)}, {refrows, (size_t)(L * NR)}, {wsum, (size_t)L}},
+                    (size_t)std::max<int64_t>(nchunks, 1) * (size_t)scan_record_doubles(nb, J, NV, mb),
+                    (size_t)L * (size_t)NV + (cross ? (size_t)K * L * J : 0), &done, &d);
+    if (rc || done) return rc;
+    rc = obs_begin(c, o, L, &d, &energy);
+    if (rc) return rc;
+    double* d_vec = c->scan_out;
+    double* d_cross = d_vec + L * NV;
+    const double* d_coeff = c->scan_in;
+    const double* d_off = d_coeff + L * B;
+    double* d_fscan = c->scan_in.p + L * (B + 1);
+    HIPCHK(c, hipMemcpyAsync(d_fscan, f_scan, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_f(c), f, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ScanWhole cut;
+    cut.ref = r;
+    {
+        ScopedTimer timer(c, MBAR_TIMER_OTHER);
+        for (int64_t p0 = 0; p0 < L; p0 += pw) {  // the resident matrix is read once per panel
+            if (o.energy) {
+                HIPCHK(c, sweep_cross(c, d, cut, energy, nb, L, p0, d_coeff, d_off, d_fscan));
+                HIPCHK(c, (launch_scan_cross_merge<ScanWhole, ScanEnergy>(c->stream, d, cut, nb, mb, K, L, p0, c->scan_part, d_cross, d_vec)));
+            } else {
+                HIPCHK(c, sweep_cross(c, d, cut, ScanStored{}, nb, L, p0, d_coeff, d_off, d_fscan));
+                HIPCHK(c, (launch_scan_cross_merge<ScanWhole, ScanStored>(c->stream, d, cut, nb, mb, K, L, p0, c->scan_part, d_cross, d_vec)));
+            }
+        }
+    }
+    std::vector<double> vec((size_t)L * NV);
+    HIPCHK(c, hipMemcpyAsync(vec.data(), d_vec, vec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (cross) HIPCHK(c, hipMemcpyAsync(cross, d_cross, (size_t)K * L * J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    rc = sync_stream(c);
+    if (rc) return rc;
+    for (int64_t l = 0; l < L; ++l) {
+        const double* v = vec.data() + l * NV;
+        wsum[l] = v[0];
+        std::copy(v + 1, v + 1 + NR, refrows + l * NR);
+        std::copy(v + 1 + NR, v + NV, within + l * NW);
+    }
+    return MBAR_OK;
 }
 
 }  // namespace
@@ -253,82 +381,22 @@ int mbar_ctx_set_scan_centers(mbar_ctx* c, int64_t L, const double* center) {
 }
 
 int mbar_scan_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, double* lognum, double* mean) {
-    int rc = scan_open(c, "mbar_scan_lognum", f && coeff && lognum && L >= 1, false, L);
-    if (rc) return rc;
-    const int64_t B = c->scan_B, J = 1 + c->scan_Q;
-    bool done = false;
-    ScanData d;
-    const int64_t nchunks = std::max<int64_t>((c->N + SCAN_VCHUNK - 1) / SCAN_VCHUNK, 1);
-    const int64_t pw = vec_panel(c, nchunks, J, L);
-    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{lognum, (size_t)L}, {mean, (size_t)(L * J)}},
-                    (size_t)nchunks * (size_t)pw * (size_t)J, (size_t)L * (size_t)(2 + J), &done, &d);
-    if (rc || done) return rc;
-    double* d_M = c->scan_out;
-    double* d_lognum = d_M + L;
-    double* d_mean = d_lognum + L;
-    const double* d_coeff = c->scan_in;
-    const double* d_off = d_coeff + L * B;
-    const ScanWhole cut{};
-    {
-        ScopedTimer timer(c, MBAR_TIMER_OTHER);
-        for (int64_t p0 = 0; p0 < L; p0 += pw) {
-            const int64_t pl = std::min(pw, L - p0);
-            HIPCHK(c, sweep_vec(c, d, cut, false, p0, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
-            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, false, pl, c->scan_part, d_M + p0, nullptr, nullptr));
-            HIPCHK(c, sweep_vec(c, d, cut, true, p0, pl, d_coeff + p0 * B, d_off + p0, d_M + p0, c->scan_part));
-            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, true, pl, c->scan_part, d_M + p0, d_lognum + p0, d_mean + p0 * J));
-        }
-    }
-    HIPCHK(c, hipMemcpyAsync(lognum, d_lognum, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (mean) HIPCHK(c, hipMemcpyAsync(mean, d_mean, (size_t)L * J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    return sync_stream(c);
+    return whole_lognum(c, "mbar_scan_lognum", WholeObs{}, f, L, coeff, offset, lognum, mean);
 }
 
 int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan, int64_t r,
                      double* cross, double* within, double* refcol, double* wsum) {
-    int rc = scan_open(c, "mbar_scan_gram_w", f && coeff && f_scan && within && refcol && wsum && L >= 1 && r >= 0 && r < L, false, L);
-    if (rc) return rc;
-    const int64_t B = c->scan_B, K = c->K;
-    const int J = 1 + (int)c->scan_Q, NW = J * (J + 1) / 2, NV = scan_nv(J);
-    bool done = false;
-    ScanData d;
-    const int nb = cross ? scan_nb_for(K) : 0;
-    const int64_t nchunks = (c->N + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    const int mb = scan_mb_of(c, J);
-    const int64_t pw = 64 * mb;
-    rc = scan_begin(c, f, L, coeff, offset, f_scan, (size_t)L,
-                    {{cross, (size_t)K * L * J}, {within, (size_t)(L * NW)}, {refcol, (size_t)(L * J)}, {wsum, (size_t)L}},
-                    (size_t)std::max<int64_t>(nchunks, 1) * (size_t)scan_record_doubles(nb, J, NV, mb),
-                    (size_t)L * (size_t)NV + (cross ? (size_t)K * L * J : 0), &done, &d);
-    if (rc || done) return rc;
-    double* d_vec = c->scan_out;
-    double* d_cross = d_vec + L * NV;
-    const double* d_coeff = c->scan_in;
-    const double* d_off = d_coeff + L * B;
-    double* d_fscan = c->scan_in.p + L * (B + 1);
-    HIPCHK(c, hipMemcpyAsync(d_fscan, f_scan, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_f(c), f, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    ScanWhole cut;
-    cut.ref = r;
-    {
-        ScopedTimer timer(c, MBAR_TIMER_OTHER);
-        for (int64_t p0 = 0; p0 < L; p0 += pw) {  // the resident matrix is read once per panel
-            HIPCHK(c, sweep_cross(c, d, cut, nb, L, p0, d_coeff, d_off, d_fscan));
-            HIPCHK(c, launch_scan_cross_merge(c->stream, d, cut, nb, mb, K, L, p0, c->scan_part, d_cross, d_vec));
-        }
-    }
-    std::vector<double> vec((size_t)L * NV);
-    HIPCHK(c, hipMemcpyAsync(vec.data(), d_vec, vec.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (cross) HIPCHK(c, hipMemcpyAsync(cross, d_cross, (size_t)K * L * J * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    rc = sync_stream(c);
-    if (rc) return rc;
-    for (int64_t l = 0; l < L; ++l) {
-        const double* v = vec.data() + l * NV;
-        wsum[l] = v[0];
-        std::copy(v + 1, v + 1 + J, refcol + l * J);
-        std::copy(v + 1 + J, v + NV, within + l * NW);
-    }
-    return MBAR_OK;
+    return whole_gram_w(c, "mbar_scan_gram_w", WholeObs{}, f, L, coeff, offset, f_scan, r, cross, within, refcol, wsum);
+}
+
+int mbar_scan_energy_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_u,
+                            int64_t J, double* lognum, double* mean) {
+    return whole_lognum(c, "mbar_scan_energy_lognum", WholeObs{true, center_u, J}, f, L, coeff, offset, lognum, mean);
+}
+
+int mbar_scan_energy_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_u,
+                            int64_t J, const double* f_scan, int64_t r, double* cross, double* within, double* refblock, double* wsum) {
+    return whole_gram_w(c, "mbar_scan_energy_gram_w", WholeObs{true, center_u, J}, f, L, coeff, offset, f_scan, r, cross, within, refblock, wsum);
 }
 
 // ---- histogram surfaces along a scan ----
@@ -395,9 +463,9 @@ int mbar_scan_bin_lognum(mbar_ctx* c, const double* f, int64_t L, const double* 
         ScopedTimer timer(c, MBAR_TIMER_OTHER);
         for (int64_t p0 = 0; p0 < L; p0 += pw) {
             const int64_t pl = std::min(pw, L - p0);
-            HIPCHK(c, sweep_vec(c, d, cut, false, p0, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
+            HIPCHK(c, sweep_vec(c, d, cut, ScanStored{}, false, p0, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
             HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, false, pl, c->scan_part, d_M, nullptr, nullptr));
-            HIPCHK(c, sweep_vec(c, d, cut, true, p0, pl, d_coeff + p0 * B, d_off + p0, d_M, c->scan_part));
+            HIPCHK(c, sweep_vec(c, d, cut, ScanStored{}, true, p0, pl, d_coeff + p0 * B, d_off + p0, d_M, c->scan_part));
             HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, true, pl, c->scan_part, d_M, d_lognum + p0 * nbins, nullptr));
         }
     }
@@ -417,7 +485,7 @@ int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* 
     const int nb = cross ? scan_nb_for(K) : 0;
     // groups of whole bins whose records fit the budget ("scan_part_bytes"; a single bin is never split): one sweep per group, and
     // a (member, bin)'s sums do not depend on the cut
-    const int mb = scan_mb_of(c, 1);
+    const int mb = scan_mb_of<ScanStored>(c, 1);
     const int64_t rec = scan_record_doubles(nb, 1, SCANBIN_NV, mb);
     const int64_t max_chunks = std::max<int64_t>(c->opt_scan_part_bytes / (rec * (int64_t)sizeof(double)), 1);
     const std::vector<int64_t>& c0 = c->scanbin_c0_b_host;
@@ -444,8 +512,8 @@ int mbar_scan_bin_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* 
             cut.b0_ = group[g], cut.b1_ = group[g + 1];
             cut.c0_ = c0[(size_t)cut.b0_], cut.c1_ = c0[(size_t)cut.b1_];
             for (int64_t p0 = 0; p0 < L; p0 += pw) {  // the group's samples of the resident matrix are read once per panel
-                HIPCHK(c, sweep_cross(c, d, cut, nb, L, p0, d_coeff, d_off, c->scanbin_fbins.p));
-                HIPCHK(c, launch_scan_cross_merge(c->stream, d, cut, nb, mb, K, L, p0, c->scan_part, d_cross, d_vec));
+                HIPCHK(c, sweep_cross(c, d, cut, ScanStored{}, nb, L, p0, d_coeff, d_off, c->scanbin_fbins.p));
+                HIPCHK(c, (launch_scan_cross_merge<ScanBinned, ScanStored>(c->stream, d, cut, nb, mb, K, L, p0, c->scan_part, d_cross, d_vec)));
             }
         }
     }

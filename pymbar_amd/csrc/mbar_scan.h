@@ -101,27 +101,55 @@ struct ScanHarmonic {
         return h;
     }
 };
-// Cut = ScanWhole or ScanBinned (Q = 0), Fam = ScanLinear or ScanHarmonic in the two sweeps; the merges know neither kind.
+// Where the observables t_j of a member come from, the third compile-time policy of the two sweeps.  ScanStored: t_jn is read from
+// ScanData::t, the same for every member -- what every instantiation had before the policy existed, and they carry no trace of the
+// other kind.  ScanEnergy: the member's own reduced potential, formed from the value the chain produced for x_ln,
+//   t_0 = 1,  t_1 = u_l(n) - center_u[l],  t_2 = t_1 t_1        (J = 1 + ScanData::Q = 2 or 3; ScanData::t is not read)
+// every operation rounded once.  Pass B then keeps two rows of products with the reference member r where the stored kind keeps
+// one, because t_r1 is the reference member's own: vec = wsum | refblock[i < 2][J] | within[i <= j],
+// refblock[l][i][j] = sum_n c_n (b_rn t_ri)(b_ln t_lj).  Whole cut only.
+struct ScanStored {
+    static constexpr bool energy = false;
+    static constexpr int ref_rows = 1;
+    static constexpr int nv(int J) { return scan_nv(J); }
+    template <class Fam>
+    static constexpr int mb(int J) { return Fam::mb(J); }
+    MBAR_HD ScanStored from(int64_t) const { return *this; }
+};
+struct ScanEnergy {
+    static constexpr bool energy = true;
+    static constexpr int ref_rows = 2;
+    static constexpr int nv(int J) { return 1 + 2 * J + J * (J + 1) / 2; }
+    // the stored kind's widths at J = 2, 3: the per-member sums are wider (J more) and the centre rides along, and still no
+    // instantiation uses scratch (the compiler's report is in DESIGN.md section 21)
+    template <class Fam>
+    static constexpr int mb(int J) { return Fam::harmonic || J > 2 ? 1 : 2; }
+    const double* center_u;  // [L] on the device
+    MBAR_HD ScanEnergy from(int64_t l0) const { return ScanEnergy{center_u + l0}; }
+};
+// Cut = ScanWhole or ScanBinned (Q = 0), Fam = ScanLinear or ScanHarmonic, Obs = ScanStored or ScanEnergy (whole cut, Q = 1 or 2) in
+// the two sweeps; the merges know neither family kind (the cross merge is told the panel width and the record's Obs).
 // pass A over the members [0, L) of coeff / offset: per-chunk records of the maxima (sum = false: rec[chunk][L]) or of the J scaled
 // sums (rec[chunk][L][J]), and their merge in chunk order into M[bin][L] (bin-major, of this member panel), or into
 // lognum[l][bin] (row pitch nbins) and, on the whole cut, mean[L][J]
-template <class Cut, class Fam>
-hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, bool sum, int64_t L, const double* coeff,
-                           const double* offset, const double* M, double* rec);
+// (the maxima do not depend on the observables: sum = false is the ScanStored launch under either Obs)
+template <class Cut, class Fam, class Obs>
+hipError_t launch_scan_vec(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, const Obs& obs, bool sum, int64_t L,
+                           const double* coeff, const double* offset, const double* M, double* rec);
 template <class Cut>
 hipError_t launch_scan_vec_merge(hipStream_t s, const ScanData& d, const Cut& cut, bool sum, int64_t L, const double* rec, double* M,
                                  double* lognum, double* mean);
-// pass B for the panel of members [p0, p0 + 64 mb) of L, mb = Fam::mb(J): part[chunk - c0][scan_record_doubles(nb, J, nv, mb)], then
-// cross[k][l][bin][j] (K x L x nbins x J) and vec[l][bin][nv].  Whole cut: nv = scan_nv(J), vec = wsum | refcol[J] | within[i <= j],
-// fnorm = f_scan[L]; binned cut: J = 1, nv = SCANBIN_NV, vec = wsum | diag, fnorm = f_bins[L][nbins] (+inf: an empty bin of that
+// pass B for the panel of members [p0, p0 + 64 mb) of L, mb = Obs::mb<Fam>(J): part[chunk - c0][scan_record_doubles(nb, J, nv, mb)],
+// then cross[k][l][bin][j] (K x L x nbins x J) and vec[l][bin][nv].  Whole cut: nv = Obs::nv(J), vec = wsum | refcol[J] (ScanEnergy:
+// refblock[2][J]) | within[i <= j], fnorm = f_scan[L]; binned cut: J = 1, nv = SCANBIN_NV, vec = wsum | diag, fnorm = f_bins[L][nbins] (+inf: an empty bin of that
 // member, exact zeros).  nb = scan_nb_for(K) blocks of 16 states, or 0: no cross block.
 int scan_nb_for(int64_t K);
 int64_t scan_record_doubles(int nb, int J, int nv, int mb);
-template <class Cut, class Fam>
-hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, int nb, const double* u, int64_t ld, int64_t K,
-                             const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset, const double* fnorm,
-                             double* part);
-template <class Cut>
+template <class Cut, class Fam, class Obs>
+hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, const Fam& fam, const Obs& obs, int nb, const double* u,
+                             int64_t ld, int64_t K, const double* f, int64_t L, int64_t p0, const double* coeff, const double* offset,
+                             const double* fnorm, double* part);
+template <class Cut, class Obs>
 hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int mb, int64_t K, int64_t L, int64_t p0,
                                    const double* part, double* cross, double* vec);
 

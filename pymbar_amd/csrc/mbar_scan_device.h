@@ -3,6 +3,8 @@
 #define MBAR_SCAN_DEVICE_H
 #include "mbar_scan.h"
 
+#include <type_traits>
+
 namespace mbar {
 
 // One term of a member's chain, THE statement of it on the device: the fill kernels and both scan passes come through here, so a
@@ -49,15 +51,27 @@ __device__ __forceinline__ void family_load_centers(const ScanHarmonic& fam, boo
     for (int h = 0; h < SCAN_MAX_H; ++h) cen[h] = live ? fam.center[l * SCAN_MAX_H + h] : 0.0;
 }
 
-// -u_l(n) - logden_n with the fixed chain over ascending b
+// u_l(n) with the fixed chain over ascending b, and x_ln = -u_l(n) - logden_n from it
 template <class Fam>
-__device__ __forceinline__ double scan_x(const ScanData& d, const Fam& fam, const double (&cf)[SCAN_MAX_B], const double (&cen)[SCAN_MAX_H],
+__device__ __forceinline__ double scan_u(const ScanData& d, const Fam& fam, const double (&cf)[SCAN_MAX_B], const double (&cen)[SCAN_MAX_H],
                                          double off, int64_t n) {
     double u = off;
 #pragma unroll
     for (int b = 0; b < SCAN_MAX_B; ++b)
         if (b < d.B) u = family_term(fam, b, u, cf[b], d.basis[(int64_t)b * d.ldv + n], family_center(fam, b, cen));
-    return -u - d.logden[n];
+    return u;
+}
+__device__ __forceinline__ double scan_x_of(const ScanData& d, double u, int64_t n) { return -u - d.logden[n]; }
+
+// The trailing arguments of a sweep kernel: a policy that carries data (ScanHarmonic, ScanEnergy) travels as one, an empty one
+// (ScanLinear, ScanStored) as none, so that its kernels keep the argument block they had before the other kind existed.  The T
+// among them, or T{}.
+template <class T>
+__device__ __forceinline__ T scan_arg() { return T{}; }
+template <class T, class A0, class... A>
+__device__ __forceinline__ T scan_arg(const A0& a0, const A&... a) {
+    if constexpr (std::is_same<T, A0>::value) return a0;
+    else return scan_arg<T>(a...);
 }
 
 }  // namespace mbar

@@ -436,41 +436,79 @@ class DeviceMatrix(_ContextMatrix):
             raise ValueError("offset_l must have one entry per member")
         return coeff_lb, offset_l, L, 1 + self._scan[1]
 
-    def scan_lognum(self, f, coeff_lb, offset_l=None, center_lb=None):
-        """Pass A of a scan: ``(lognum, mean)`` with ``lognum[l] = log sum_n c_n exp(-u_l(n) - logden_n(f))`` and ``mean[l, j]``
-        the average of ``t_j`` (``t_0 = 1``) in member ``l`` (``L x (1 + Q)``)."""
+    def _scan_pass_a(self, f, coeff_lb, offset_l, center_lb, energy=None):
+        """Pass A for the stored observables (``energy=None``) or the energy observable (``energy=(center_u, J)``)."""
         f = np.ascontiguousarray(f, dtype=np.float64)
         if f.shape != (self.K,):
             raise ValueError(f"f must have shape ({self.K},)")
         coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
+        head = (self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l))
+        if energy is not None:
+            center_u, J = self._scan_energy(energy, L)
+            head += (_dptr(center_u), J)
         self._scan_centers(center_lb, L)
         lognum = np.empty(L, dtype=np.float64)
         mean = np.empty((L, J), dtype=np.float64)
-        self._check(self._lib.mbar_scan_lognum(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(lognum), _dptr(mean)))
+        call = self._lib.mbar_scan_lognum if energy is None else self._lib.mbar_scan_energy_lognum
+        self._check(call(*head, _dptr(lognum), _dptr(mean)))
         return lognum, mean
+
+    def _scan_pass_b(self, f, coeff_lb, offset_l, f_scan, reference, cross, center_lb, energy=None):
+        """Pass B for either kind of observable: ``(cross, within, the rows of products with the reference member, wsum)``."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
+        f_scan = np.ascontiguousarray(f_scan, dtype=np.float64)
+        if f.shape != (self.K,) or f_scan.shape != (L,) or not 0 <= int(reference) < L:
+            raise ValueError("f must have K entries, f_scan one per member, and the reference must be a member")
+        head = (self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l))
+        if energy is not None:
+            center_u, J = self._scan_energy(energy, L)
+            head += (_dptr(center_u), J)
+        self._scan_centers(center_lb, L)
+        X = np.empty((self.K, L, J), dtype=np.float64) if cross else None
+        tri = np.empty((L, J * (J + 1) // 2), dtype=np.float64)
+        ref = np.empty((L, J) if energy is None else (L, 2, J), dtype=np.float64)
+        w = np.empty(L, dtype=np.float64)
+        call = self._lib.mbar_scan_gram_w if energy is None else self._lib.mbar_scan_energy_gram_w
+        self._check(call(*head, _dptr(f_scan), int(reference), _dptr(X), _dptr(tri), _dptr(ref), _dptr(w)))
+        within = np.empty((L, J, J), dtype=np.float64)
+        iu = np.triu_indices(J)
+        within[:, iu[0], iu[1]] = tri
+        within[:, iu[1], iu[0]] = tri
+        return X, within, ref, w
+
+    @staticmethod
+    def _scan_energy(energy, L):
+        center_u, J = energy
+        if J not in (2, 3):
+            raise ValueError("the energy observable takes J = 2 (1, t) or 3 (1, t, t^2)")
+        center_u = np.zeros(L) if center_u is None else np.ascontiguousarray(center_u, dtype=np.float64)
+        if center_u.shape != (L,):
+            raise ValueError("center_u must have one entry per member")
+        return center_u, int(J)
+
+    def scan_lognum(self, f, coeff_lb, offset_l=None, center_lb=None):
+        """Pass A of a scan: ``(lognum, mean)`` with ``lognum[l] = log sum_n c_n exp(-u_l(n) - logden_n(f))`` and ``mean[l, j]``
+        the average of ``t_j`` (``t_0 = 1``) in member ``l`` (``L x (1 + Q)``)."""
+        return self._scan_pass_a(f, coeff_lb, offset_l, center_lb)
 
     def scan_gram_w(self, f, coeff_lb, offset_l, f_scan, reference=0, cross=True, center_lb=None):
         """Pass B of a scan: ``(cross, within, refcol, wsum)`` of the members' normalised weights ``b_ln = exp(f_scan[l] - u_l(n) -
         logden_n(f))`` -- ``cross[k, l, j] = sum_n c_n W_nk b_ln t_jn`` (``None`` with ``cross=False``), ``within[l, i, j] = sum_n
         c_n b_ln^2 t_in t_jn`` (symmetric ``J x J``), ``refcol[l, j] = sum_n c_n b_rn b_ln t_jn`` for the reference member ``r``,
         ``wsum[l] = sum_n c_n b_ln``."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
-        f_scan = np.ascontiguousarray(f_scan, dtype=np.float64)
-        if f.shape != (self.K,) or f_scan.shape != (L,) or not 0 <= int(reference) < L:
-            raise ValueError("f must have K entries, f_scan one per member, and the reference must be a member")
-        self._scan_centers(center_lb, L)
-        X = np.empty((self.K, L, J), dtype=np.float64) if cross else None
-        tri = np.empty((L, J * (J + 1) // 2), dtype=np.float64)
-        refcol = np.empty((L, J), dtype=np.float64)
-        w = np.empty(L, dtype=np.float64)
-        self._check(self._lib.mbar_scan_gram_w(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(f_scan), int(reference),
-                                               _dptr(X), _dptr(tri), _dptr(refcol), _dptr(w)))
-        within = np.empty((L, J, J), dtype=np.float64)
-        iu = np.triu_indices(J)
-        within[:, iu[0], iu[1]] = tri
-        within[:, iu[1], iu[0]] = tri
-        return X, within, refcol, w
+        return self._scan_pass_b(f, coeff_lb, offset_l, f_scan, reference, cross, center_lb)
+
+    def scan_energy_lognum(self, f, coeff_lb, offset_l=None, center_u=None, J=3, center_lb=None):
+        """Pass A with the member's own reduced potential as the observable (``mbar_scan_energy_lognum``): ``(lognum, mean)`` as
+        :meth:`scan_lognum` with ``t_1 = u_l(n) - center_u[l]``, ``t_2 = t_1^2`` (``L x J``, ``J`` 2 or 3; ``center_u`` None: zeros).
+        The stored observables of :meth:`set_scan` are ignored; ``lognum`` has the bits of :meth:`scan_lognum`."""
+        return self._scan_pass_a(f, coeff_lb, offset_l, center_lb, energy=(center_u, J))
+
+    def scan_energy_gram_w(self, f, coeff_lb, offset_l, f_scan, center_u=None, J=3, reference=0, cross=True, center_lb=None):
+        """Pass B with the energy observable (``mbar_scan_energy_gram_w``): ``(cross, within, refblock, wsum)`` as
+        :meth:`scan_gram_w` with the member's own ``t_j``; ``refblock[l, i, j] = sum_n c_n (b_rn t_ri)(b_ln t_lj)``, ``i`` 0 or 1."""
+        return self._scan_pass_b(f, coeff_lb, offset_l, f_scan, reference, cross, center_lb, energy=(center_u, J))
 
     # ---- histogram surfaces along a scan (pymbar_amd.scan.compute_scan_fes) ---------------------------------------------------
     SCAN_BIN_CROSS_BYTES = 1 << 28  # the host cross block of one slab of members of scan_bin_gram_w stays under this

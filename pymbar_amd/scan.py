@@ -232,6 +232,149 @@ def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, r
     return out
 
 
+# ---- entropy, enthalpy and heat capacity along a scan -----------------------------------------------------------------------------
+def _thermo_matrix(mbar):
+    dm = _scan_matrix(mbar)
+    if not all(hasattr(dm, name) for name in ("scan_energy_lognum", "scan_energy_gram_w")):
+        raise ParameterError(f"entropy and enthalpy along a scan need the energy passes of a single-rank device matrix and are {_NOT_HERE} for this handle")
+    return dm
+
+
+def _moments(center, mean):
+    """``(u, var_u)`` from the centred moments of pass A: ``u = c + <t_1>``, ``var_u = <t_2> - <t_1>^2`` (None at ``J = 2``)."""
+    m1 = mean[:, 1]
+    return center + m1, (mean[:, 2] - m1 * m1 if mean.shape[1] > 2 else None)
+
+
+def _theta_pairs(alpha, within, refblock, y, g, r, pairs=True):
+    """``Theta(v_l, v_l)``, ``Theta(v_l, v_r)``, ``Theta(v_r, v_r)`` of the columns ``v_l = sum_j alpha[l, j] b_l t_lj`` (DESIGN.md
+    section 21): ``v . v'`` from ``within`` (same member) and ``refblock`` (``refblock[l, i, j] = (b_r t_ri) . (b_l t_lj)``; the
+    columns that meet the reference member's have ``alpha[r, 2] = 0``), plus the border ``y(v)^T diag(g) y(v')`` with ``y`` linear in
+    the column.  ``y=None``: the ``v . v'`` terms alone ("approximate").  Sums over ``i``, ``j`` and the eigen-directions in
+    ascending order, element by element.  ``pairs=False``: ``Theta(v_l, v_l)`` only."""
+    L, J = alpha.shape
+    ll = np.zeros(L)
+    for i in range(J):
+        for j in range(J):
+            ll += alpha[:, i] * alpha[:, j] * within[:, i, j]
+    yv = None
+    if y is not None:
+        yv = np.zeros(y.shape[:2])
+        for j in range(J):
+            yv += alpha[None, :, j] * y[:, :, j]
+        ll = ll + _qform(g, yv, yv)
+    if not pairs:
+        return ll
+    lr = np.zeros(L)
+    for i in range(2):
+        for j in range(J):
+            lr += alpha[r, i] * alpha[:, j] * refblock[:, i, j]
+    rr = ll[r]
+    if yv is not None:
+        lr = lr + _qform(g, yv, yv[:, r:r + 1])
+    return ll, lr, rr
+
+
+def _thermo_analytical(mbar, dm, coeff_lb, offset_l, f, center, mean, reference, approximate, warning_cutoff, cen={}):
+    """The uncertainties of section 21 from pass B with the energy observable.  With ``a_l = b_l`` and ``d_lj = b_l t_lj - mean_lj
+    b_l`` the columns are ``a`` (``ln c``: the free energy), ``d_1`` (``u``), ``d_1 + a`` (``s = u - f``) and, for the fluctuation,
+    ``d_2 - 2 mean_1 d_1`` (the delta method); none of them divides by a mean, which is ~ 0 by construction here."""
+    L, J = mean.shape
+    r = int(reference)
+    cross, within, refblock, wsum = dm.scan_energy_gram_w(mbar.f_k, coeff_lb, offset_l, f, center_u=center, J=J, reference=r,
+                                                          cross=not approximate, **cen)
+    check_w_sums(wsum, 0.0)
+    y = g = None
+    if not approximate:
+        y, g = _border(mbar, cross)
+    m1 = mean[:, 1]
+    zero, one = np.zeros(L), np.ones(L)
+    pad = [zero] * (J - 2)
+    columns = dict(f=np.stack([one, zero] + pad, axis=1), u=np.stack([-m1, one] + pad, axis=1), s=np.stack([one - m1, one] + pad, axis=1))
+    out = {}
+    for name, alpha in columns.items():
+        ll, lr, rr = _theta_pairs(alpha, within, refblock, y, g, r)
+        d2 = ll + rr - 2.0 * lr
+        d2[r] = 0.0
+        out["dDelta_" + name] = _sqrt_small_negative_zeroed(d2, warning_cutoff)
+    if J > 2:
+        alpha = np.stack([2.0 * m1 * m1 - mean[:, 2], -2.0 * m1, one], axis=1)
+        with np.errstate(invalid="ignore"):
+            out["dvar_u"] = np.sqrt(_theta_pairs(alpha, within, refblock, y, g, r, pairs=False))
+    out["n_eff"] = 1.0 / within[:, 0, 0]  # Kish's effective sample number of the member
+    return out
+
+
+def compute_scan_entropy_and_enthalpy(mbar, basis_bn=None, coeff_lb=None, offset_l=None, reference=0, fluctuation=True, compute_uncertainty=True,
+                                      uncertainty_method=None, warning_cutoff=1.0e-10, center_lb=None, harmonic_b=None, period_b=None):
+    """Free energy, reduced enthalpy, entropy and the fluctuation of the reduced potential along a family of unsampled states.
+
+    The family (``basis_bn``, ``coeff_lb``, ``offset_l``, ``center_lb``, ``harmonic_b``, ``period_b``) and ``reference`` are those of
+    :func:`compute_scan`; the observable is each member's own reduced potential ``u_l(n)``, which the device forms from the chain it
+    evaluates anyway -- nothing of size ``L x N`` is built.  Returns a dict of ``(L,)`` arrays: ``f``, ``u = <u_l>_l``, ``s = u - f``,
+    their differences to member ``reference`` ``Delta_f``, ``Delta_u``, ``Delta_s`` with the uncertainties ``dDelta_f``,
+    ``dDelta_u``, ``dDelta_s`` -- row ``reference`` of ``compute_entropy_and_enthalpy(u_kn=u_ln)`` for the dense ``u_ln`` --, and with
+    ``fluctuation`` ``var_u = <u_l^2>_l - <u_l>_l^2`` (``C_v / k_B`` on a temperature ladder) and ``dvar_u``.  With analytical
+    uncertainties also ``n_eff``, Kish's effective sample number ``1 / sum_n b_ln^2`` of every member.
+
+    ``uncertainty_method``: None / "svd-ew" (the bordered form), "approximate", "bootstrap" (the ``std`` over replicates of the
+    differences, as ``compute_entropy_and_enthalpy`` takes it, and of ``var_u``; adds ``bootstrapped_f``, ``bootstrapped_u`` and
+    ``bootstrapped_var_u`` ``(n_bootstraps, L)``); "svd" is not offered."""
+    basis_given = basis_bn
+    if uncertainty_method == "svd":
+        raise ParameterError("uncertainty_method 'svd' needs the weight matrix itself and is not offered for scans")
+    if uncertainty_method not in (None, "svd-ew", "approximate", "bootstrap"):
+        raise ParameterError(f"Method {uncertainty_method} unrecognized.")
+    bootstrap = uncertainty_method == "bootstrap"
+    if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
+        raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
+    basis_bn, coeff_lb, offset_l, _, L = _check_inputs(mbar, _family_basis(mbar, basis_bn, coeff_lb), coeff_lb, offset_l, None, reference)
+    kinds, cen = _family_kinds(mbar, basis_given, basis_bn.shape[0], L, center_lb, harmonic_b, period_b)
+    dm = _thermo_matrix(mbar)
+    r = int(reference)
+    J = 3 if fluctuation else 2
+    dm.set_Nk(mbar.N_k)
+    dm.set_scan(basis_bn, None, **kinds)
+    try:
+        # pass A twice: about zero for <u_l>, then about that mean, so that neither u nor var_u carries a cancellation of order <u>^2
+        _, mean0 = dm.scan_energy_lognum(mbar.f_k, coeff_lb, offset_l, center_u=None, J=2, **cen)
+        center = mean0[:, 1].copy()
+        lognum, mean = dm.scan_energy_lognum(mbar.f_k, coeff_lb, offset_l, center_u=center, J=J, **cen)
+        f = -lognum
+        u, var_u = _moments(center, mean)
+        s = u - f
+        out = dict(f=f, Delta_f=f - f[r], u=u, Delta_u=u - u[r], s=s, Delta_s=s - s[r])
+        if fluctuation:
+            out["var_u"] = var_u
+        if bootstrap:
+            nb = mbar.n_bootstraps
+            fb, ub, vb = np.zeros((nb, L)), np.zeros((nb, L)), np.zeros((nb, L))
+            try:
+                for b in range(nb):
+                    mbar._set_bootstrap_weights(dm, b)
+                    ln_b, mean_b = dm.scan_energy_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l, center_u=center, J=J, **cen)
+                    fb[b] = -ln_b
+                    ub[b], v = _moments(center, mean_b)
+                    if fluctuation:
+                        vb[b] = v
+            finally:
+                dm.set_sample_weights(None)
+            out["bootstrapped_f"], out["bootstrapped_u"] = fb, ub
+            if fluctuation:
+                out["bootstrapped_var_u"] = vb
+            if compute_uncertainty:
+                for name, arr in (("dDelta_f", fb), ("dDelta_u", ub), ("dDelta_s", ub - fb)):
+                    out[name] = np.std(arr - arr[:, r:r + 1], axis=0)
+                if fluctuation:
+                    out["dvar_u"] = np.std(vb, axis=0)
+        elif compute_uncertainty:
+            out.update(_thermo_analytical(mbar, dm, coeff_lb, offset_l, f, center, mean, r, uncertainty_method == "approximate",
+                                          warning_cutoff, cen))
+    finally:
+        dm.set_scan(None)
+    return out
+
+
 # ---- histogram free energy surfaces along a scan ----------------------------------------------------------------------------------
 def _scan_fes_matrix(mbar):
     dm = _scan_matrix(mbar)

@@ -60,6 +60,17 @@ def harmonic_free_energies(K_k, beta=1.0, subtract_component=0):
     return fe
 
 
+def temperature_ladder_family(E_n, beta_l):
+    """The potential energies ``E_n`` reweighted to the inverse temperatures ``beta_l`` as a linear family for ``MBAR.compute_scan`` and
+    ``MBAR.compute_scan_entropy_and_enthalpy``: ``(basis_bn, coeff_lb, offset_l)`` with the one basis vector ``E_n`` and ``coeff =
+    beta_l``, so that ``u_ln[l, n] = beta_l E_n``.  On such a ladder ``var_u`` of the latter method is ``C_v / k_B``."""
+    E_n = np.asarray(E_n, dtype=np.float64)
+    beta_l = np.atleast_1d(np.asarray(beta_l, dtype=np.float64))
+    if E_n.ndim != 1 or beta_l.ndim != 1:
+        raise ValueError("E_n must have one entry per sample and beta_l one per member")
+    return E_n[None, :].copy(), beta_l[:, None].copy(), np.zeros(len(beta_l))
+
+
 def harmonic_scan_family(x_n, O_l, K_l, beta=1.0):
     """The harmonic oscillators ``(O_l, K_l)`` as a linear family over the samples ``x_n`` for ``MBAR.compute_scan``:
     ``(basis_bn, coeff_lb, offset_l)`` with basis ``{x^2, x}``, so that ``coeff_lb @ basis_bn + offset_l[:, None]`` is
