@@ -1,4 +1,6 @@
-"""ctypes binding of libmbar_hip.so (include/mbar_hip.h).  Thin: no numpy logic lives here.
+"""ctypes binding of libmbar_hip.so (include/mbar_hip.h), and the argument layer every Python face of it goes through: ``f64`` and
+``labels_i32`` give an array its dtype, layout and checked shape before it crosses the ABI, ``ptr`` casts it, ``check`` reads the
+return code.
 
 The product path has exactly one compute backend -- the gfx950 library.  If it cannot be loaded,
 or no MI355X is visible, every entry point raises :class:`BackendUnavailable`; there is no CPU
@@ -7,10 +9,13 @@ fallback (the numpy oracle under ``oracle/`` is test infrastructure and is never
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MBAR_HIP_LIBRARY") or os.path.join(HERE, "csrc", "libmbar_hip.so")  # (override: A/B builds)
 
 MBAR_OK = 0
+MBAR_ERR_ARG = -1  # the caller's input was bad
 EVAL_GRAM = 1
 EVAL_USE_OFFSET = 2
 TIMER_LSE, TIMER_GRAM, TIMER_REDUCE, TIMER_OTHER, TIMER_FUSED, TIMER_NEWTON, TIMER_COMM = 0, 1, 2, 3, 4, 5, 6
@@ -73,6 +78,8 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_int, C
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
+_i32p = C.POINTER(C.c_int32)
+_u64p = C.POINTER(C.c_uint64)
 _ctx = C.c_void_p
 
 # name -> (restype, argtypes); this table is also what tests/test_capi_symbols.py checks against
@@ -220,8 +227,12 @@ def last_error(ctx=None):
     return msg.decode("utf-8", "replace") if msg else ""
 
 
-def check(code, ctx=None):
+def check(code, ctx=None, arg_error=None):
+    """Raise unless ``code`` is MBAR_OK: ``arg_error(message)`` for MBAR_ERR_ARG where the caller names one (the inputs were
+    bad), :class:`MbarHipError` for everything else."""
     if code != MBAR_OK:
+        if code == MBAR_ERR_ARG and arg_error is not None:
+            raise arg_error(last_error(ctx))
         raise MbarHipError(code, last_error(ctx))
 
 
@@ -235,33 +246,22 @@ def host_digest(a, threads=0):
 def bootstrap_draws(seed, replicate, cumN, order=None):
     """The draws of replicate ``replicate`` of the counter-based bootstrap stream ``seed`` as the reference's ``bootstrap_rints`` row
     (``mbar_bootstrap_draws``; host only, no GPU needed): ``rints[sample of slot j] = sample drawn``, state by state."""
-    import numpy as np
-
     cumN = np.ascontiguousarray(cumN, dtype=np.int64)
-    total = int(cumN[-1])
-    out = np.zeros(total, dtype=np.int64)
-    ip = C.POINTER(C.c_int64)
-    optr = None
-    if order is not None:
-        order = np.ascontiguousarray(order, dtype=np.int64)
-        optr = order.ctypes.data_as(ip)
-    check(load_library().mbar_bootstrap_draws(C.c_uint64(int(seed)), int(replicate), cumN.ctypes.data_as(ip), len(cumN) - 1, optr,
-                                              out.ctypes.data_as(ip)))
+    out = np.zeros(int(cumN[-1]), dtype=np.int64)
+    order = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
+    check(load_library().mbar_bootstrap_draws(C.c_uint64(int(seed)), int(replicate), ptr(cumN, _ip), len(cumN) - 1, ptr(order, _ip),
+                                              ptr(out, _ip)))
     return out
 
 
 def host_newton_direction(H, g, threads=0):
     """``x = H^+ g - (H^+ g)[0]`` as the host-driven adaptive loop computes it (``mbar_host_newton_direction``; host only).
     ``threads > 0`` forces the blocked, threaded Cholesky factorisation with that team size (tests)."""
-    import numpy as np
-
-    H = np.ascontiguousarray(H, dtype=np.float64)
-    g = np.ascontiguousarray(g, dtype=np.float64)
+    g = f64(g, (None,), "g")
     m = g.shape[0]
-    if H.shape != (m, m):
-        raise ValueError("H must be (m, m) for g of length m")
+    H = f64(H, (m, m), "H")
     x = np.empty(m, dtype=np.float64)
-    check(load_library().mbar_host_newton_direction(H.ctypes.data_as(_dp), g.ctypes.data_as(_dp), m, int(threads), x.ctypes.data_as(_dp)))
+    check(load_library().mbar_host_newton_direction(ptr(H), ptr(g), m, int(threads), ptr(x)))
     return x
 
 
@@ -296,6 +296,36 @@ def default_device(device=None):
 def ptr(a, t=_dp):
     """ctypes pointer to the data of a numpy array (None for None)."""
     return a.ctypes.data_as(t) if a is not None else None
+
+
+def _shape_text(shape):
+    return "(" + ", ".join("*" if s is None else str(s) for s in shape) + ("," if len(shape) == 1 else "") + ")"
+
+
+def f64(a, shape, name, error=ValueError, optional=False):
+    """``a`` as a C-contiguous float64 array of shape ``shape`` (a tuple; ``None`` matches any extent), or ``error``.  An array that
+    conforms already comes back as it is, without a copy.  ``None`` stays ``None`` with ``optional`` and is refused otherwise."""
+    if a is None:
+        if optional:
+            return None
+        raise error(f"{name} is required")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != shape and (a.ndim != len(shape) or any(s is not None and s != n for s, n in zip(shape, a.shape))):
+        raise error(f"{name} must have shape {_shape_text(shape)}")
+    return a
+
+
+def labels_i32(label_n, nbins, n, name):
+    """The ``n`` bin labels of the resident samples as a contiguous int32 array: every label in ``[-1, nbins)`` (-1: in no bin).
+    Another dtype is range-checked before it is narrowed: a value that does not fit an int32 would wrap into the valid range."""
+    label_n = np.asarray(label_n)
+    if label_n.shape != (n,):
+        raise ValueError(f"{name} must have shape ({n},)")
+    if label_n.dtype != np.int32:
+        if label_n.size and (label_n.min() < -1 or label_n.max() >= int(nbins)):
+            raise ValueError("labels must lie in [-1, nbins)")
+        label_n = label_n.astype(np.int32)
+    return np.ascontiguousarray(label_n)
 
 
 class Handle:

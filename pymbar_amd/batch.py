@@ -32,8 +32,7 @@ logger = logging.getLogger(__name__)
 MAX_K = _lib.MBAR_BATCH_MAX_K
 MAX_AUG = _lib.MBAR_BATCH_MAX_AUG
 RUNNING, DONE, FALLBACK = 0, 1, 2
-_dp = C.POINTER(C.c_double)
-_ip = C.POINTER(C.c_int64)
+_dp, _ip, _i32p, _u64p = _lib._dp, _lib._ip, _lib._i32p, _lib._u64p
 # Device memory one group of replica slots may take for its multiplicities (8 N bytes per slot), chunk records and states
 BOOTSTRAP_GROUP_BYTES = 2 << 30
 # Device memory the partial records of one group of problems may take in the augmented Gram pass of MBARBatch
@@ -42,9 +41,16 @@ EXT_GRAM_GROUP_BYTES = 1 << 30
 
 def _check_inputs(rc):
     """MBAR_ERR_ARG is about the inputs (NaN / -inf entries, a batch larger than the device, bad weights): a ParameterError."""
-    if rc == -1:
-        raise ParameterError(_lib.last_error(None))
-    _lib.check(rc)
+    _lib.check(rc, arg_error=ParameterError)
+
+
+def _at(F, mask, n):
+    """Where a pass over ``n`` problems or slots evaluates: ``F`` (n, MAX_K), entry e's free energies in the first K columns of row
+    e, and ``mask`` (n,) as int32."""
+    mask = np.ascontiguousarray(mask, dtype=np.int32)
+    if mask.shape != (n,):
+        raise ValueError(f"mask must have shape ({n},)")
+    return _lib.f64(F, (n, MAX_K), "F"), mask
 
 
 class DeviceBatch(_lib.Handle):
@@ -56,31 +62,34 @@ class DeviceBatch(_lib.Handle):
         self._lib = _lib.load_library()
         _lib.require_device()
         self.device = _lib.default_device(device)
+        blocks = [_lib.f64(b, (None, None), f"block {p}") for p, b in enumerate(blocks)]
         self.P = len(blocks)
         self.K = np.array([b.shape[0] for b in blocks], dtype=np.int64)
         self.N = np.array([b.shape[1] for b in blocks], dtype=np.int64)
         self.R = np.zeros(self.P, dtype=np.int64)  # extension rows per problem (set_ext)
-        ptrs = (_dp * self.P)(*[b.ctypes.data_as(_dp) for b in blocks])
+        self.base = np.zeros(0, dtype=np.int64)  # the problem of every replica slot (set_replicas)
+        ptrs = (_dp * self.P)(*[_lib.ptr(b) for b in blocks])
         h = C.c_void_p()
         _check_inputs(self._lib.mbar_batch_create(C.byref(h), self.device, self.P, _lib.ptr(self.K, _ip), _lib.ptr(self.N, _ip), ptrs))
         self._h = h
 
     # The problems and the replica slots are two sets of solves over the same blocks: `fn` is the set's entry point, Ks its widths
-    def _solve(self, fn, states):
+    def _solve(self, fn, states, n):
+        if len(states) != n:
+            raise ValueError(f"{n} states are needed, one per entry of the set")
         passes = C.c_int64(0)
         _lib.check(fn(self._h, states, C.byref(passes)))
         return passes.value
 
     def _gram_w(self, fn, Ks, F, mask):
-        F = np.ascontiguousarray(F, dtype=np.float64)
-        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        F, mask = _at(F, mask, len(Ks))
         gram = np.zeros(int(np.sum(Ks * Ks)), dtype=np.float64)
         wsum = np.zeros(int(np.sum(Ks)), dtype=np.float64)
-        _lib.check(fn(self._h, _lib.ptr(F), mask.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(gram), _lib.ptr(wsum)))
+        _lib.check(fn(self._h, _lib.ptr(F), _lib.ptr(mask, _i32p), _lib.ptr(gram), _lib.ptr(wsum)))
         return gram, wsum
 
     def solve(self, states):
-        return self._solve(self._lib.mbar_batch_solve, states)
+        return self._solve(self._lib.mbar_batch_solve, states, self.P)
 
     def gram_w(self, F, mask):
         """Packed ``W^T W`` and ``sum_n W_nk`` at ``F[p, :K[p]]`` for the problems with ``mask[p]``."""
@@ -91,28 +100,31 @@ class DeviceBatch(_lib.Handle):
         """Declares ``len(base)`` replica slots: slot s shares problem ``base[s]``'s block; ``N_k_list[p]`` (every problem's samples
         per state) fixes the layout of the draws.  An empty ``base`` releases the slots."""
         base = np.ascontiguousarray(base, dtype=np.int64)
+        if base.ndim != 1 or len(N_k_list) != self.P:
+            raise ValueError(f"base must be a vector of problems and N_k_list hold {self.P} vectors")
         Nk = np.zeros((self.P, MAX_K), dtype=np.int64)
         for p in range(self.P):
+            if np.shape(N_k_list[p]) != (self.K[p],):
+                raise ValueError(f"problem {p}: N_k must have shape ({int(self.K[p])},)")
             Nk[p, :self.K[p]] = N_k_list[p]
         _check_inputs(self._lib.mbar_batch_set_replicas(self._h, len(base), _lib.ptr(base, _ip), _lib.ptr(Nk, _ip)))
         self.base = base
 
     def replica_set_weights(self, slot, c_n):
         """Slot ``slot``'s per-sample multiplicities from a host vector (finite, >= 0)."""
-        c_n = np.ascontiguousarray(c_n, dtype=np.float64)
-        if c_n.shape != (int(self.N[self.base[slot]]),):
-            raise ValueError(f"sample weights must have shape ({int(self.N[self.base[slot]])},)")
+        c_n = _lib.f64(c_n, (int(self.N[self.base[slot]]),), "sample weights")
         _check_inputs(self._lib.mbar_batch_replica_set_weights(self._h, int(slot), _lib.ptr(c_n)))
 
     def replicas_draw(self, first, seeds, replicates):
         """Draw counts of the slots ``first .. first + len(seeds)`` on the device: replicate ``replicates[i]`` of stream ``seeds[i]``."""
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
         replicates = np.ascontiguousarray(replicates, dtype=np.int64)
-        _lib.check(self._lib.mbar_batch_replicas_draw(self._h, int(first), len(seeds), seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                      _lib.ptr(replicates, _ip)))
+        if seeds.ndim != 1 or replicates.shape != seeds.shape:
+            raise ValueError("seeds and replicates must be vectors of one length")
+        _lib.check(self._lib.mbar_batch_replicas_draw(self._h, int(first), len(seeds), _lib.ptr(seeds, _u64p), _lib.ptr(replicates, _ip)))
 
     def replicas_solve(self, states):
-        return self._solve(self._lib.mbar_batch_replicas_solve, states)
+        return self._solve(self._lib.mbar_batch_replicas_solve, states, len(self.base))
 
     def replicas_gram_w(self, F, mask):
         """``gram_w`` of the slots: packed ``sum_n c_n W_ni W_nj`` and ``sum_n c_n W_nk`` at ``F[s, :K]``."""
@@ -125,10 +137,10 @@ class DeviceBatch(_lib.Handle):
             self.R = np.zeros(self.P, dtype=np.int64)
             _check_inputs(self._lib.mbar_batch_set_ext(self._h, None, None))
             return
-        rows = [None if r is None or len(r) == 0 else np.ascontiguousarray(r, dtype=np.float64) for r in rows]
-        for p, r in enumerate(rows):
-            if r is not None and (r.ndim != 2 or r.shape[1] != self.N[p]):
-                raise ValueError(f"problem {p}: extension rows must have shape (R, {int(self.N[p])})")
+        if len(rows) != self.P:
+            raise ValueError(f"rows must hold {self.P} entries, one per problem")
+        rows = [None if r is None or len(r) == 0 else _lib.f64(r, (None, int(self.N[p])), f"problem {p}: extension rows")
+                for p, r in enumerate(rows)]
         R = np.array([0 if r is None else r.shape[0] for r in rows], dtype=np.int64)
         ptrs = (_dp * self.P)(*[_lib.ptr(r) for r in rows])
         _check_inputs(self._lib.mbar_batch_set_ext(self._h, _lib.ptr(R, _ip), ptrs))  # (rejected: the earlier rows stay)
@@ -136,26 +148,22 @@ class DeviceBatch(_lib.Handle):
 
     def ext_lognum(self, F, mask):
         """Packed ``log sum_n exp(-logden_n(F[p]) - e_rn)`` of the extension rows of the problems with ``mask[p]``."""
-        F = np.ascontiguousarray(F, dtype=np.float64)
-        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        F, mask = _at(F, mask, self.P)
         out = np.zeros(int(self.R.sum()), dtype=np.float64)
         if out.size:
-            _check_inputs(self._lib.mbar_batch_ext_lognum(self._h, _lib.ptr(F), mask.ctypes.data_as(C.POINTER(C.c_int32)), _lib.ptr(out)))
+            _check_inputs(self._lib.mbar_batch_ext_lognum(self._h, _lib.ptr(F), _lib.ptr(mask, _i32p), _lib.ptr(out)))
         return out
 
     def ext_gram(self, F, f_ext, mask, group_bytes=0):
         """Packed ``Q^T Q`` ((K + R)^2 per problem) and column sums of ``Q = [W | exp(f_ext_r - e_rn - logden_n)]`` at ``F`` for the
         problems with ``mask[p]``; the records of one group of problems take at most ``group_bytes`` of device memory."""
-        F = np.ascontiguousarray(F, dtype=np.float64)
-        f_ext = np.ascontiguousarray(f_ext, dtype=np.float64)
-        mask = np.ascontiguousarray(mask, dtype=np.int32)
-        if f_ext.shape != (int(self.R.sum()),):
-            raise ValueError(f"f_ext must have shape ({int(self.R.sum())},)")
+        F, mask = _at(F, mask, self.P)
+        f_ext = _lib.f64(f_ext, (int(self.R.sum()),), "f_ext")
         A = self.K + self.R
         gram = np.zeros(int(np.sum(A * A)), dtype=np.float64)
         wsum = np.zeros(int(np.sum(A)), dtype=np.float64)
-        _check_inputs(self._lib.mbar_batch_ext_gram(self._h, _lib.ptr(F), _lib.ptr(f_ext), mask.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                    int(group_bytes), _lib.ptr(gram), _lib.ptr(wsum)))
+        _check_inputs(self._lib.mbar_batch_ext_gram(self._h, _lib.ptr(F), _lib.ptr(f_ext), _lib.ptr(mask, _i32p), int(group_bytes),
+                                                    _lib.ptr(gram), _lib.ptr(wsum)))
         return gram, wsum
 
 

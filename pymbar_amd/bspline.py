@@ -65,16 +65,14 @@ class DeviceBSplineMoments(_lib.Handle):
             raise ParameterError(f"the number of groups must be 1 .. {MAX_GROUPS} on this backend, got {G}")
         if np.any(g < 0) or np.any(g >= G):
             raise ParameterError("group labels must lie in [0, n_groups)")
-        _lib.check(self._lib.mbar_bspline_set_groups(self._h, G, g.ctypes.data_as(C.POINTER(C.c_int32))))
+        _lib.check(self._lib.mbar_bspline_set_groups(self._h, G, _lib.ptr(g, _lib._i32p)))
         self.n_groups = G
 
     def set_weights(self, V):
         """V: (N,) or (N, C), finite."""
         V = np.asarray(V, dtype=np.float64)
-        if V.ndim == 1:
-            V = V[:, None]
-        V = np.ascontiguousarray(V)
-        if V.ndim != 2 or V.shape[0] != self.n_samples or V.shape[1] < 1:
+        V = _lib.f64(V[:, None] if V.ndim == 1 else V, (self.n_samples, None), "weights", error=ParameterError)
+        if V.shape[1] < 1:
             raise ParameterError("weights must be (n_samples, C)")
         if not np.all(np.isfinite(V)):
             raise DataError("weights must be finite")

@@ -89,17 +89,30 @@ def family_centers(center_rb, R, B, harmonic_b, error=ValueError, name="center_k
     return center_rb
 
 
+def _solve_result(res):
+    """A ``SolveResult`` as the dict the solver functions return."""
+    out = {k: getattr(res, k) for k, _ in _lib.SolveResult._fields_}
+    out["success"] = bool(res.success)
+    return out
+
+
 class _ContextMatrix:
     """What :class:`DeviceMatrix` and :class:`ExtendedMatrix` share: they own one ``mbar_ctx`` (``_ctx``) and write whole rows of
     it (the row-level assembly of the expectation family).  The two differ in three hooks: where a destination row lives
     (``_dst_row``), where a source run lives (``_src``) and what a write invalidates (``_touched``)."""
 
-    def _check(self, rc):
+    _ctx = None  # (until the constructor has made one: close() of a half-built object has nothing to release)
+
+    def _check(self, rc, arg_error=None):
         if rc != _lib.MBAR_OK:
-            raise _lib.MbarHipError(rc, _lib.last_error(self._ctx))
+            _lib.check(rc, self._ctx, arg_error)
+
+    def _f(self, f):
+        """The free energies of a call: one per row, as the library reads them."""
+        return _lib.f64(f, (self.K,), "f")
 
     def close(self):
-        if getattr(self, "_ctx", None) is not None and self._ctx:
+        if self._ctx:
             self._lib.mbar_ctx_destroy(self._ctx)
             self._ctx = C.c_void_p()
 
@@ -130,19 +143,12 @@ class _ContextMatrix:
     # ---- row-level assembly of an augmented matrix on the device (expectation family) ----------------------
     def _vec(self, v_n, name):
         """A host vector of N_local entries for the staging vector, contiguous; None stays None (the vector staged before)."""
-        if v_n is None:
-            return None
-        v_n = np.ascontiguousarray(v_n, dtype=np.float64)
-        if v_n.shape != (self.N_local,):
-            raise ValueError(f"{name} must have N_local entries")
-        return v_n
+        return _lib.f64(v_n, (self.N_local,), name, optional=True)
 
     def upload_rows(self, row0, rows):
         """Whole rows ``[row0, row0 + len(rows))`` from a host array ``rows`` (R, N_local)."""
+        rows = _lib.f64(np.atleast_2d(rows), (None, self.N_local), "rows")
         self._touched()
-        rows = np.ascontiguousarray(np.atleast_2d(rows), dtype=np.float64)
-        if rows.shape[1] != self.N_local:
-            raise ValueError("rows must have N_local columns")
         self._check(self._lib.mbar_ctx_upload_rows(self._ctx, self._dst_row(row0, rows.shape[0]), rows.shape[0], _dptr(rows),
                                                    rows.shape[1]))
 
@@ -194,15 +200,20 @@ class DeviceMatrix(_ContextMatrix):
         self.N_local = int(N_local)
         self.device = _lib.default_device(device)
         self._ctx = C.c_void_p()
-        rc = self._lib.mbar_ctx_create(C.byref(self._ctx), self.device, self.K, self.N_local)
-        if rc != _lib.MBAR_OK:
-            raise _lib.MbarHipError(rc, _lib.last_error(None))
+        _lib.check(self._lib.mbar_ctx_create(C.byref(self._ctx), self.device, self.K, self.N_local))
         self._Nk = None
         self._version = 0  # bumped by everything that changes the matrix, N_k or the transport
         self._wtag = None  # None = unit sample multiplicities; otherwise a token of the weights last installed
         self._lognum_cache = None
         self._gram_w_cache = None
+        self._rowmin_cache = None  # (key, minima) of a run of rows, kept for the ExtendedMatrix objects on this matrix
+        self._nbins = 0  # set_bins
+        self._scan = None  # (B, Q) of set_scan
+        self._scan_harmonic = None  # the bool mask of the scan family's harmonic terms
+        self._scan_nbins = 0  # set_scan_bins
+        self._boot_layout_key = None  # the caller's key of the bootstrap layout on the device
         self._cb = None  # keeps the host all-reduce callback alive
+        self._loop = None  # keeps the loopback group alive
         self.nranks = 1
         self.rank = 0
         self.allreduce_kind = "none"
@@ -216,11 +227,7 @@ class DeviceMatrix(_ContextMatrix):
     @classmethod
     def from_host(cls, u_kn, device=None, columns=None):
         """Upload a host ``u_kn`` (K, N) -- or only its ``columns=(n0, n1)`` slice (this rank's shard)."""
-        u_kn = np.asarray(u_kn)
-        if u_kn.ndim != 2:
-            raise ValueError("u_kn must be 2-D (K, N)")
-        if u_kn.dtype != np.float64 or not u_kn.flags.c_contiguous:
-            u_kn = np.ascontiguousarray(u_kn, dtype=np.float64)
+        u_kn = _lib.f64(u_kn, (None, None), "u_kn")
         K, N = u_kn.shape
         n0, n1 = (0, N) if columns is None else columns
         dm = cls(K, n1 - n0, device=device)
@@ -277,30 +284,39 @@ class DeviceMatrix(_ContextMatrix):
             basis_bn, coeff_rb, offset_r = linear_family_inputs(basis_bn, coeff_rb, offset_r)
             harmonic_b, period_b = family_terms(basis_bn.shape[0], harmonic_b, period_b)
             center_rb = family_centers(center_rb, coeff_rb.shape[0], basis_bn.shape[0], harmonic_b, name="center_rb")
+        # (what crosses the ABI is checked whether or not the caller validated: conforming arrays pass through as they are)
+        basis_bn = _lib.f64(basis_bn, (None, None), "basis_bn")
+        B = basis_bn.shape[0]
+        coeff_rb = _lib.f64(coeff_rb, (None, B), "coeff_rb")
+        R = coeff_rb.shape[0]
+        offset_r = _lib.f64(offset_r, (R,), "offset_r", optional=True)
+        center_rb = _lib.f64(center_rb, (R, B), "center_rb", optional=True)
+        period_b = _lib.f64(period_b, (B,), "period_b", optional=True)
         col0 = int(col0)
         if col0 < 0 or col0 + self.N_local > basis_bn.shape[1]:
             raise ValueError("basis_bn must cover the columns [col0, col0 + N_local)")
         self._touched()
-        B, R = basis_bn.shape[0], coeff_rb.shape[0]
         kind = None if harmonic_b is None else np.ascontiguousarray(harmonic_b, dtype=np.int32)
-        rc = self._lib.mbar_ctx_fill_family_rows(self._ctx, int(row0), R, B, _dptr(basis_bn), basis_bn.shape[1], col0, _dptr(coeff_rb),
-                                                 _dptr(center_rb), _dptr(offset_r),
-                                                 None if kind is None else kind.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(period_b))
-        self._check(rc)
+        if kind is not None and kind.shape != (B,):
+            raise ValueError(f"harmonic_b must have shape ({B},)")
+        self._check(self._lib.mbar_ctx_fill_family_rows(self._ctx, int(row0), R, B, _dptr(basis_bn), basis_bn.shape[1], col0,
+                                                        _dptr(coeff_rb), _dptr(center_rb), _dptr(offset_r), _dptr(kind, _lib._i32p),
+                                                        _dptr(period_b)))
 
     @classmethod
     def harmonic(cls, O_k, K_k, N_k_global, seed=0, n_global0=0, N_local=None, device=None):
         """Generate the synthetic harmonic ladder of SURVEY.md 8(d) directly in HBM."""
-        O_k = np.ascontiguousarray(O_k, dtype=np.float64)
-        K_k = np.ascontiguousarray(K_k, dtype=np.float64)
-        N_k_global = np.ascontiguousarray(N_k_global, dtype=np.int64)
+        O_k = _lib.f64(O_k, (None,), "O_k")
         K = len(O_k)
+        K_k = _lib.f64(K_k, (K,), "K_k")
+        N_k_global = np.ascontiguousarray(N_k_global, dtype=np.int64)
+        if N_k_global.shape != (K,):
+            raise ValueError(f"N_k_global must have shape ({K},)")
         if N_local is None:
             N_local = int(N_k_global.sum()) - n_global0
         dm = cls(K, N_local, device=device)
-        dm._check(dm._lib.mbar_ctx_generate_harmonic(
-            dm._ctx, C.c_uint64(seed), _dptr(O_k), _dptr(K_k),
-            N_k_global.ctypes.data_as(C.POINTER(C.c_int64)), n_global0))
+        dm._check(dm._lib.mbar_ctx_generate_harmonic(dm._ctx, C.c_uint64(seed), _dptr(O_k), _dptr(K_k), _dptr(N_k_global, _lib._ip),
+                                                     n_global0))
         return dm
 
     def _touched(self):
@@ -320,13 +336,12 @@ class DeviceMatrix(_ContextMatrix):
     def fill_masked_rows(self, row0, nrows, v_n, label_n):
         """Rows ``row0 + i`` (``i < nrows``) become ``v_n`` on the samples with ``label_n == i`` and ``+inf`` (weight zero)
         elsewhere: one extra "state" per histogram bin of a free energy surface, built on the device."""
-        self._version += 1
-        v_n = np.ascontiguousarray(v_n, dtype=np.float64)
-        label_n = np.ascontiguousarray(label_n, dtype=np.int32)
-        if v_n.shape != (self.N_local,) or label_n.shape != (self.N_local,):
-            raise ValueError("v_n and label_n must have N_local entries")
-        self._check(self._lib.mbar_ctx_fill_masked_rows(self._ctx, int(row0), int(nrows), _dptr(v_n),
-                                                        label_n.ctypes.data_as(C.POINTER(C.c_int32))))
+        v_n = _lib.f64(v_n, (self.N_local,), "v_n")
+        label_n = np.ascontiguousarray(label_n, dtype=np.int32)  # (any label is allowed here: one of no row marks no row)
+        if label_n.shape != (self.N_local,):
+            raise ValueError(f"label_n must have shape ({self.N_local},)")
+        self._touched()
+        self._check(self._lib.mbar_ctx_fill_masked_rows(self._ctx, int(row0), int(nrows), _dptr(v_n), _dptr(label_n, _lib._i32p)))
 
     # ---- histogram bins by label (the label path of pymbar_amd.fes) ----------------------------------------------------------
     def set_bins(self, nbins, label_n=None, v_n=None):
@@ -336,19 +351,10 @@ class DeviceMatrix(_ContextMatrix):
             self._check(self._lib.mbar_ctx_set_bins(self._ctx, 0, None, None))
             self._nbins = 0
             return
-        label_n = np.asarray(label_n)
-        v_n = np.ascontiguousarray(v_n, dtype=np.float64)
-        if v_n.shape != (self.N_local,) or label_n.shape != (self.N_local,):
-            raise ValueError("v_n and label_n must have N_local entries")
-        if label_n.dtype != np.int32:  # (values that do not fit an int32 would wrap into the valid range)
-            if label_n.size and (label_n.min() < -1 or label_n.max() >= int(nbins)):
-                raise ValueError("labels must lie in [-1, nbins)")
-            label_n = label_n.astype(np.int32)
-        label_n = np.ascontiguousarray(label_n)
-        rc = self._lib.mbar_ctx_set_bins(self._ctx, int(nbins), label_n.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(v_n))
-        if rc == -1:  # MBAR_ERR_ARG: a label outside [-1, nbins), or NaN / -inf in v_n
-            raise ValueError(_lib.last_error(self._ctx))
-        self._check(rc)
+        v_n = _lib.f64(v_n, (self.N_local,), "v_n")
+        label_n = _lib.labels_i32(label_n, nbins, self.N_local, "label_n")
+        # (MBAR_ERR_ARG: a label outside [-1, nbins), or NaN / -inf in v_n)
+        self._check(self._lib.mbar_ctx_set_bins(self._ctx, int(nbins), _dptr(label_n, _lib._i32p), _dptr(v_n)), ValueError)
         self._nbins = int(nbins)
 
     def bins_info(self):
@@ -359,10 +365,8 @@ class DeviceMatrix(_ContextMatrix):
 
     def bin_lognum(self, f):
         """``log sum_{n in bin i} c_n exp(-v_n - logden_n(f))`` for every bin (``-inf``: no sample with ``c_n > 0``)."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        if f.shape != (self.K,):
-            raise ValueError(f"f must have shape ({self.K},)")
-        out = np.empty(getattr(self, "_nbins", 0), dtype=np.float64)
+        f = self._f(f)
+        out = np.empty(self._nbins, dtype=np.float64)
         self._check(self._lib.mbar_bin_lognum(self._ctx, _dptr(f), _dptr(out)))
         return out
 
@@ -370,11 +374,8 @@ class DeviceMatrix(_ContextMatrix):
         """``(cross, diag, wsum)`` of the bins' normalised weights ``B_n = exp(f_bins[label_n] - v_n - logden_n(f))`` against the
         resident states' ``W``: ``cross[k, i] = sum_{n in i} c_n W_nk B_n`` (``None`` with ``cross=False``), ``diag[i] = sum c_n
         B_n^2``, ``wsum[i] = sum c_n B_n``."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        f_bins = np.ascontiguousarray(f_bins, dtype=np.float64)
-        nbins = getattr(self, "_nbins", 0)
-        if f.shape != (self.K,) or f_bins.shape != (nbins,):
-            raise ValueError("f must have K entries and f_bins one per bin")
+        f, nbins = self._f(f), self._nbins
+        f_bins = _lib.f64(f_bins, (nbins,), "f_bins")
         X = np.empty((self.K, nbins), dtype=np.float64) if cross else None
         d = np.empty(nbins, dtype=np.float64)
         w = np.empty(nbins, dtype=np.float64)
@@ -387,60 +388,47 @@ class DeviceMatrix(_ContextMatrix):
         None) of a scan, uploaded once (``mbar_ctx_set_scan``).  ``basis_bn=None`` releases them.  ``harmonic_b`` / ``period_b``
         (:func:`family_terms`): the kind of the family's terms (``mbar_ctx_set_scan_terms``); the four ``scan_*`` methods then
         need the members' centres ``center_lb``."""
+        if basis_bn is not None:  # (what Python can refuse is refused before anything changes)
+            basis_bn = _lib.f64(basis_bn, (None, self.N_local), "basis_bn")
+            t_qn = np.zeros((0, self.N_local)) if t_qn is None else _lib.f64(t_qn, (None, self.N_local), "t_qn")
+            B, Q = basis_bn.shape[0], t_qn.shape[0]
+            harmonic_b, period_b = family_terms(B, harmonic_b, period_b)
         self._scan = None
         self._scan_harmonic = None
         if basis_bn is None:
             self._check(self._lib.mbar_ctx_set_scan(self._ctx, 0, None, 0, None))
             return
-        basis_bn = np.ascontiguousarray(basis_bn, dtype=np.float64)
-        t_qn = np.zeros((0, self.N_local)) if t_qn is None else np.ascontiguousarray(t_qn, dtype=np.float64)
-        if basis_bn.ndim != 2 or t_qn.ndim != 2 or basis_bn.shape[1] != self.N_local or t_qn.shape[1] != self.N_local:
-            raise ValueError("basis_bn and t_qn must have N_local columns")
-        B, Q = basis_bn.shape[0], t_qn.shape[0]
-        rc = self._lib.mbar_ctx_set_scan(self._ctx, B, _dptr(basis_bn), Q, _dptr(t_qn) if Q else None)
-        if rc == -1:  # MBAR_ERR_ARG: B or Q outside the limits
-            raise ValueError(_lib.last_error(self._ctx))
-        self._check(rc)
-        harmonic_b, period_b = family_terms(B, harmonic_b, period_b)
+        # (MBAR_ERR_ARG: B or Q outside the limits)
+        self._check(self._lib.mbar_ctx_set_scan(self._ctx, B, _dptr(basis_bn), Q, _dptr(t_qn) if Q else None), ValueError)
         if harmonic_b is not None:
             kind = np.ascontiguousarray(harmonic_b, dtype=np.int32)
-            rc = self._lib.mbar_ctx_set_scan_terms(self._ctx, kind.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(period_b))
-            if rc == -1:
-                raise ValueError(_lib.last_error(self._ctx))
-            self._check(rc)
+            self._check(self._lib.mbar_ctx_set_scan_terms(self._ctx, _dptr(kind, _lib._i32p), _dptr(period_b)), ValueError)
             self._scan_harmonic = harmonic_b
         self._scan = (B, Q)
 
     def _scan_centers(self, center_lb, L):
         """The centres of the members of the next scan call go to the context (a family with harmonic terms needs them)."""
-        harmonic_b = getattr(self, "_scan_harmonic", None)
+        harmonic_b = self._scan_harmonic
         if harmonic_b is None:
             if center_lb is not None and np.shape(center_lb) != (L, self._scan[0]):
                 raise ValueError("center_lb must have one row per member and one column per basis vector")
             return
         center_lb = family_centers(center_lb, L, self._scan[0], harmonic_b, name="center_lb")
-        rc = self._lib.mbar_ctx_set_scan_centers(self._ctx, L, _dptr(center_lb))
-        if rc == -1:
-            raise ValueError(_lib.last_error(self._ctx))
-        self._check(rc)
+        self._check(self._lib.mbar_ctx_set_scan_centers(self._ctx, L, _dptr(center_lb)), ValueError)
 
     def _scan_members(self, coeff_lb, offset_l):
-        if getattr(self, "_scan", None) is None:
+        if self._scan is None:
             raise ValueError("no basis on this matrix (set_scan first)")
-        coeff_lb = np.ascontiguousarray(coeff_lb, dtype=np.float64)
-        if coeff_lb.ndim != 2 or coeff_lb.shape[1] != self._scan[0] or coeff_lb.shape[0] < 1:
-            raise ValueError("coeff_lb must have one row per member and one column per basis vector")
+        coeff_lb = _lib.f64(coeff_lb, (None, self._scan[0]), "coeff_lb")
         L = coeff_lb.shape[0]
-        offset_l = np.zeros(L) if offset_l is None else np.ascontiguousarray(offset_l, dtype=np.float64)
-        if offset_l.shape != (L,):
-            raise ValueError("offset_l must have one entry per member")
+        if L < 1:
+            raise ValueError("coeff_lb must have one row per member and one column per basis vector")
+        offset_l = np.zeros(L) if offset_l is None else _lib.f64(offset_l, (L,), "offset_l")
         return coeff_lb, offset_l, L, 1 + self._scan[1]
 
     def _scan_pass_a(self, f, coeff_lb, offset_l, center_lb, energy=None):
         """Pass A for the stored observables (``energy=None``) or the energy observable (``energy=(center_u, J)``)."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        if f.shape != (self.K,):
-            raise ValueError(f"f must have shape ({self.K},)")
+        f = self._f(f)
         coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
         head = (self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l))
         if energy is not None:
@@ -455,11 +443,11 @@ class DeviceMatrix(_ContextMatrix):
 
     def _scan_pass_b(self, f, coeff_lb, offset_l, f_scan, reference, cross, center_lb, energy=None):
         """Pass B for either kind of observable: ``(cross, within, the rows of products with the reference member, wsum)``."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
-        f_scan = np.ascontiguousarray(f_scan, dtype=np.float64)
-        if f.shape != (self.K,) or f_scan.shape != (L,) or not 0 <= int(reference) < L:
-            raise ValueError("f must have K entries, f_scan one per member, and the reference must be a member")
+        f_scan = _lib.f64(f_scan, (L,), "f_scan")
+        if not 0 <= int(reference) < L:
+            raise ValueError("the reference must be a member")
         head = (self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l))
         if energy is not None:
             center_u, J = self._scan_energy(energy, L)
@@ -482,10 +470,7 @@ class DeviceMatrix(_ContextMatrix):
         center_u, J = energy
         if J not in (2, 3):
             raise ValueError("the energy observable takes J = 2 (1, t) or 3 (1, t, t^2)")
-        center_u = np.zeros(L) if center_u is None else np.ascontiguousarray(center_u, dtype=np.float64)
-        if center_u.shape != (L,):
-            raise ValueError("center_u must have one entry per member")
-        return center_u, int(J)
+        return (np.zeros(L) if center_u is None else _lib.f64(center_u, (L,), "center_u")), int(J)
 
     def scan_lognum(self, f, coeff_lb, offset_l=None, center_lb=None):
         """Pass A of a scan: ``(lognum, mean)`` with ``lognum[l] = log sum_n c_n exp(-u_l(n) - logden_n(f))`` and ``mean[l, j]``
@@ -516,33 +501,23 @@ class DeviceMatrix(_ContextMatrix):
     def set_scan_bins(self, nbins, label_n=None):
         """Histogram bins as labels of the resident samples for the binned scan passes: ``label_n`` in ``[-1, nbins)`` (-1: in no
         bin), sorted by bin on the host and uploaded once (``mbar_ctx_set_scan_bins``).  ``nbins=0`` releases them."""
-        self._scan_nbins = 0
         if int(nbins) == 0:
             self._check(self._lib.mbar_ctx_set_scan_bins(self._ctx, 0, None))
+            self._scan_nbins = 0
             return
-        label_n = np.asarray(label_n)
-        if label_n.shape != (self.N_local,):
-            raise ValueError("label_n must have N_local entries")
-        if label_n.dtype != np.int32:  # (values that do not fit an int32 would wrap into the valid range)
-            if label_n.size and (label_n.min() < -1 or label_n.max() >= int(nbins)):
-                raise ValueError("labels must lie in [-1, nbins)")
-            label_n = label_n.astype(np.int32)
-        label_n = np.ascontiguousarray(label_n)
-        rc = self._lib.mbar_ctx_set_scan_bins(self._ctx, int(nbins), label_n.ctypes.data_as(C.POINTER(C.c_int32)))
-        if rc == -1:  # MBAR_ERR_ARG: a label outside [-1, nbins)
-            raise ValueError(_lib.last_error(self._ctx))
-        self._check(rc)
+        label_n = _lib.labels_i32(label_n, nbins, self.N_local, "label_n")
+        # (MBAR_ERR_ARG: a label outside [-1, nbins).  A refused call leaves the library's bins as they were, so the count that
+        # sizes the output of the binned passes changes only with them.)
+        self._check(self._lib.mbar_ctx_set_scan_bins(self._ctx, int(nbins), _dptr(label_n, _lib._i32p)), ValueError)
         self._scan_nbins = int(nbins)
 
     def scan_bin_lognum(self, f, coeff_lb, offset_l=None, center_lb=None):
         """Pass A of a binned scan: ``lognum[l, i] = log sum_{n in bin i} c_n exp(-u_l(n) - logden_n(f))`` (``L x nbins``; ``-inf``
         where no sample of the bin has ``c_n > 0``)."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        if f.shape != (self.K,):
-            raise ValueError(f"f must have shape ({self.K},)")
+        f = self._f(f)
         coeff_lb, offset_l, L, _ = self._scan_members(coeff_lb, offset_l)
         self._scan_centers(center_lb, L)
-        lognum = np.empty((L, getattr(self, "_scan_nbins", 0)), dtype=np.float64)
+        lognum = np.empty((L, self._scan_nbins), dtype=np.float64)
         self._check(self._lib.mbar_scan_bin_lognum(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(lognum)))
         return lognum
 
@@ -552,12 +527,10 @@ class DeviceMatrix(_ContextMatrix):
         ``cross=False``), ``diag[l, i] = sum c_n Bv^2``, ``wsum[l, i] = sum c_n Bv``.  The members go to the device in slabs (of
         ``slab`` members; by default as many as keep a slab's ``cross`` block under 256 MiB): a (member, bin)'s bits do not depend
         on the cut."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         coeff_lb, offset_l, L, _ = self._scan_members(coeff_lb, offset_l)
-        nbins = getattr(self, "_scan_nbins", 0)
-        f_bins = np.ascontiguousarray(f_bins, dtype=np.float64)
-        if f.shape != (self.K,) or f_bins.shape != (L, nbins):
-            raise ValueError("f must have K entries and f_bins one row per member and one column per bin")
+        nbins = self._scan_nbins
+        f_bins = _lib.f64(f_bins, (L, nbins), "f_bins")
         if slab is None:
             slab = self.SCAN_BIN_CROSS_BYTES // (8 * self.K * max(nbins, 1)) if cross else L
         slab = max(1, min(int(slab), L))
@@ -589,24 +562,17 @@ class DeviceMatrix(_ContextMatrix):
 
     def set_Nk(self, N_k):
         """GLOBAL sample counts (any numeric dtype; zeros allowed)."""
-        Nk = np.ascontiguousarray(N_k, dtype=np.float64)
-        if Nk.shape != (self.K,):
-            raise ValueError(f"N_k must have shape ({self.K},)")
+        Nk = _lib.f64(N_k, (self.K,), "N_k")
         if self._Nk is None or not np.array_equal(Nk, self._Nk):
-            self._version += 1
+            self._touched()
             self._check(self._lib.mbar_ctx_set_Nk(self._ctx, _dptr(Nk)))
             self._Nk = Nk.copy()
 
     def set_sample_weights(self, c_n):
         """Per-sample multiplicities (``None`` restores 1): every sum over samples becomes ``sum_n c_n (...)``.
         A bootstrap replicate is ``np.bincount(resampled_indices, minlength=N)``."""
+        c_n = _lib.f64(c_n, (self.N_local,), "sample weights", optional=True)
         self._wtag = None if c_n is None else object()
-        if c_n is None:
-            self._check(self._lib.mbar_ctx_set_sample_weights(self._ctx, None))
-            return
-        c_n = np.ascontiguousarray(c_n, dtype=np.float64)
-        if c_n.shape != (self.N_local,):
-            raise ValueError(f"sample weights must have shape ({self.N_local},)")
         self._check(self._lib.mbar_ctx_set_sample_weights(self._ctx, _dptr(c_n)))
 
     def draw_bootstrap_weights(self, seed, replicate, cumN, order=None, n_global0=0, layout_key=None):
@@ -616,24 +582,22 @@ class DeviceMatrix(_ContextMatrix):
         ``layout_key``: any object that identifies (cumN, order) for the caller -- the layout is uploaded when the key changes
         (``mbar_ctx_set_bootstrap_layout``) and replicates with the same key touch no host array of N integers; without a key the
         arrays travel with every call and the library digests them to see whether its device copy still matches."""
-        self._wtag = object()
-        ip = C.POINTER(C.c_int64)
-        if layout_key is not None and layout_key is getattr(self, "_boot_layout_key", None):
-            self._check(self._lib.mbar_ctx_draw_bootstrap_weights(self._ctx, C.c_uint64(int(seed)), int(replicate), None, 0, None, int(n_global0)))
-            return
-        cumN = np.ascontiguousarray(cumN, dtype=np.int64)
-        optr = None
-        if order is not None:
-            order = np.ascontiguousarray(order, dtype=np.int64)
-            optr = order.ctypes.data_as(ip)
-        if layout_key is not None:
-            self._check(self._lib.mbar_ctx_set_bootstrap_layout(self._ctx, cumN.ctypes.data_as(ip), len(cumN) - 1, optr))
+        layout = (None, 0, None)  # a known key: the layout on the device
+        if layout_key is None or layout_key is not self._boot_layout_key:
+            cumN = np.ascontiguousarray(cumN, dtype=np.int64)
+            if cumN.ndim != 1 or len(cumN) < 2:
+                raise ValueError("cumN must hold the K + 1 run boundaries of K >= 1 states")
+            order = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
+            if order is not None and order.shape != (max(int(cumN[-1]), 0),):
+                raise ValueError("order must have one entry per position: cumN[-1] of them")
+            arrays = (_dptr(cumN, _lib._ip), len(cumN) - 1, _dptr(order, _lib._ip))
+            if layout_key is None:  # the arrays travel with the draw
+                layout = arrays
+            else:  # a new key: uploaded now, the draw finds it there
+                self._check(self._lib.mbar_ctx_set_bootstrap_layout(self._ctx, *arrays))
             self._boot_layout_key = layout_key
-            self._check(self._lib.mbar_ctx_draw_bootstrap_weights(self._ctx, C.c_uint64(int(seed)), int(replicate), None, 0, None, int(n_global0)))
-            return
-        self._boot_layout_key = None
-        self._check(self._lib.mbar_ctx_draw_bootstrap_weights(self._ctx, C.c_uint64(int(seed)), int(replicate), cumN.ctypes.data_as(ip),
-                                                              len(cumN) - 1, optr, int(n_global0)))
+        self._wtag = object()
+        self._check(self._lib.mbar_ctx_draw_bootstrap_weights(self._ctx, C.c_uint64(int(seed)), int(replicate), *layout, int(n_global0)))
 
     def weights_from_vec(self, power):
         """Per-sample weights ``(A_n - shift)**power`` from the observable ``vec_logshift`` left on the device (no upload, no host
@@ -643,14 +607,14 @@ class DeviceMatrix(_ContextMatrix):
 
     # ---- multi-GPU --------------------------------------------------------------------------------
     def comm_init_rccl(self, unique_id, rank, nranks):
-        self._version += 1
+        self._touched()
         buf = C.create_string_buffer(bytes(unique_id), 128)
         self._check(self._lib.mbar_ctx_comm_init(self._ctx, buf, rank, nranks))
         self.rank, self.nranks, self.allreduce_kind = rank, nranks, "rccl"
 
     def set_host_allreduce(self, fn, rank, nranks):
         """``fn(array, op)`` must all-reduce the float64 numpy ``array`` in place (op 'sum'|'max')."""
-        self._version += 1
+        self._touched()
 
         def _cb(ptr, count, op, _user):
             try:
@@ -667,23 +631,21 @@ class DeviceMatrix(_ContextMatrix):
     def set_loopback(self, group, rank):
         """Join the in-process transport ``group`` (:class:`LoopbackGroup`) as ``rank``: collectives run on the compute stream
         like RCCL's, between contexts of this process on one device (one caller thread per context)."""
-        self._version += 1
+        self._touched()
         self._check(self._lib.mbar_ctx_set_loopback(self._ctx, group._h, int(rank)))
         self._loop = group  # (keeps the group alive)
         self.rank, self.nranks, self.allreduce_kind = int(rank), group.nranks, "loopback"
 
     def comm_destroy(self):
         """Detach the cross-rank transport (destroys an RCCL communicator); the matrix is single-rank again."""
-        self._version += 1
+        self._touched()
         self._check(self._lib.mbar_ctx_comm_destroy(self._ctx))
         self._cb = None
         self.rank, self.nranks, self.allreduce_kind = 0, 1, "none"
 
     def device_synchronize(self):
         """``hipDeviceSynchronize`` on this matrix's GPU (all streams)."""
-        rc = self._lib.mbar_device_synchronize(self.device)
-        if rc != _lib.MBAR_OK:
-            raise _lib.MbarHipError(rc, _lib.last_error(None))
+        _lib.check(self._lib.mbar_device_synchronize(self.device))
 
     # ---- L1 ---------------------------------------------------------------------------------------
     def eval(self, f, gram=False, use_offset=False):
@@ -692,7 +654,7 @@ class DeviceMatrix(_ContextMatrix):
         ``gram = sum_n p p^T`` at ``f[0]`` (all summed over ranks)."""
         f = np.ascontiguousarray(np.atleast_2d(np.asarray(f, dtype=np.float64)))
         nf = f.shape[0]
-        if f.shape[1] != self.K or nf not in (1, 2):
+        if f.ndim != 2 or f.shape[1] != self.K or nf not in (1, 2):
             raise ValueError("f must be (K,) or (1|2, K)")
         psum = np.empty((nf, self.K), dtype=np.float64)
         sld = np.empty(nf, dtype=np.float64)
@@ -703,14 +665,11 @@ class DeviceMatrix(_ContextMatrix):
         return psum, sld, G
 
     def set_objective_offset(self, f0):
-        if f0 is None:
-            self._check(self._lib.mbar_ctx_set_objective_offset(self._ctx, None))
-        else:
-            f0 = np.ascontiguousarray(f0, dtype=np.float64)
-            self._check(self._lib.mbar_ctx_set_objective_offset(self._ctx, _dptr(f0)))
+        f0 = _lib.f64(f0, (self.K,), "f0", optional=True)
+        self._check(self._lib.mbar_ctx_set_objective_offset(self._ctx, _dptr(f0)))
 
     def lognum(self, f):
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         out = np.empty(self.K, dtype=np.float64)
         self._check(self._lib.mbar_lognum(self._ctx, _dptr(f), _dptr(out)))
         return out
@@ -718,7 +677,7 @@ class DeviceMatrix(_ContextMatrix):
     def lognum_cached(self, f):
         """``lognum(f)``, kept while neither the matrix, N_k, the multiplicities nor ``f`` change (consecutive methods of the
         class at the same ``f_k``: one sweep of the resident rows instead of one per call)."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         if self._wtag is not None:
             return self.lognum(f)
         key = (self._version, f.tobytes())
@@ -729,7 +688,7 @@ class DeviceMatrix(_ContextMatrix):
     def gram_w_cached(self, f):
         """``gram_w(f)`` with unit multiplicities, kept like ``lognum_cached`` (the covariance of the free energies, overlap and
         every expectation at the same ``f_k`` start from the same ``W^T W`` of the resident states)."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         if self._wtag is not None:
             return self.gram_w(f)
         key = (self._version, f.tobytes())
@@ -751,7 +710,7 @@ class DeviceMatrix(_ContextMatrix):
         return ExtendedMatrix(self, ctx, int(nrows))
 
     def logden(self, f):
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         out = np.empty(self.N_local, dtype=np.float64)
         self._check(self._lib.mbar_logden(self._ctx, _dptr(f), _dptr(out)))
         return out
@@ -759,7 +718,7 @@ class DeviceMatrix(_ContextMatrix):
     def logw_kn(self, f):
         """``log W`` of this shard as a C-ordered (K, N_local) array; its ``.T`` is the reference's
         F-ordered (N, K) ``Log_W_nk``."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         from .utils import prefault
 
         out = prefault(np.empty((self.K, self.N_local), dtype=np.float64))  # (pages touched by several threads first)
@@ -771,14 +730,14 @@ class DeviceMatrix(_ContextMatrix):
         reference's (N, K) ``W_nk``."""
         from .utils import prefault
 
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         out = prefault(np.empty((self.K, self.N_local), dtype=np.float64))
         self._check(self._lib.mbar_w(self._ctx, _dptr(f), _dptr(out), self.N_local))
         return out
 
     def gram_w(self, f):
         """``(W^T W, sum_n W_nk)`` over all states (MFMA), summed over ranks."""
-        f = np.ascontiguousarray(f, dtype=np.float64)
+        f = self._f(f)
         G = np.empty((self.K, self.K), dtype=np.float64)
         ws = np.empty(self.K, dtype=np.float64)
         self._check(self._lib.mbar_gram_w(self._ctx, _dptr(f), _dptr(G), _dptr(ws)))
@@ -787,14 +746,13 @@ class DeviceMatrix(_ContextMatrix):
     # ---- solver loops -----------------------------------------------------------------------------
     def solve_adaptive(self, f, tol=1e-12, maxiter=10000, min_sc_iter=2, gamma=1.0, check_convergence=True,
                        history_rows=0):
-        f = np.array(f, dtype=np.float64)
+        f = self._f(f).copy()  # (the library writes the solution over the start)
         res = _lib.SolveResult()
         hist = np.zeros((max(1, history_rows), 4), dtype=np.float64)
         self._check(self._lib.mbar_solve_adaptive(self._ctx, _dptr(f), tol, int(maxiter), int(min_sc_iter),
                                                   float(gamma), 1 if check_convergence else 0, _dptr(hist),
                                                   int(history_rows), C.byref(res)))
-        out = {k: getattr(res, k) for k, _ in _lib.SolveResult._fields_ if not k.endswith("_")}
-        out["success"] = bool(res.success)
+        out = _solve_result(res)
         out["history"] = hist[: min(history_rows, res.iterations)]
         # per-state sums at the returned f (the solver has them anyway): gradient norm and all-state update without another sweep
         psum = np.empty(self.K, dtype=np.float64)
@@ -802,13 +760,11 @@ class DeviceMatrix(_ContextMatrix):
         return f, out
 
     def solve_sci(self, f, tol=1e-12, maxiter=10000, check_convergence=True):
-        f = np.array(f, dtype=np.float64)
+        f = self._f(f).copy()  # (the library writes the solution over the start)
         res = _lib.SolveResult()
         self._check(self._lib.mbar_solve_sci(self._ctx, _dptr(f), tol, int(maxiter),
                                              1 if check_convergence else 0, C.byref(res)))
-        out = {k: getattr(res, k) for k, _ in _lib.SolveResult._fields_ if not k.endswith("_")}
-        out["success"] = bool(res.success)
-        return f, out
+        return f, _solve_result(res)
 
     # ---- measurement ------------------------------------------------------------------------------
     def timing(self):
@@ -874,7 +830,7 @@ class ExtendedMatrix(_ContextMatrix):
         shift = np.empty(int(nrows), dtype=np.float64)
         # (the minima of resident rows are a property of the resident matrix: kept on it, keyed by its version and the row run)
         key = (self.base._version, int(obs_row0), int(nrows))
-        cache = getattr(self.base, "_rowmin_cache", None)
+        cache = self.base._rowmin_cache
         mins = cache[1] if cache is not None and cache[0] == key else None
         out = np.empty(int(nrows), dtype=np.float64) if mins is None else None
         self._check(self._lib.mbar_ctx_rows_obs_from(self._ctx, self._ext_row(dst_row0, nrows), self.base._ctx, int(state_row0),
@@ -891,24 +847,21 @@ class ExtendedMatrix(_ContextMatrix):
             raise ValueError("the appended rows are unsampled states of the resident matrix's mixture")
 
     def lognum(self, f):
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        fb = np.ascontiguousarray(f[:self.Kb])
+        f = self._f(f)
+        fb = f[:self.Kb]  # (a run of a contiguous vector is contiguous)
         out = np.empty(self.K, dtype=np.float64)
         out[:self.Kb] = self.base.lognum_cached(fb)
-        ext = np.empty(self.K - self.Kb, dtype=np.float64)
-        self._check(self._lib.mbar_lognum_ext(self._ctx, self.base._ctx, _dptr(fb), _dptr(ext)))
-        out[self.Kb:] = ext
+        self._check(self._lib.mbar_lognum_ext(self._ctx, self.base._ctx, _dptr(fb), _dptr(out[self.Kb:])))
         return out
 
     def gram_w(self, f):
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        fb, fe = np.ascontiguousarray(f[:self.Kb]), np.ascontiguousarray(f[self.Kb:])
+        f = self._f(f)
+        fb, fe = f[:self.Kb], f[self.Kb:]
         G = np.empty((self.K, self.K), dtype=np.float64)
         ws = np.empty(self.K, dtype=np.float64)
         # (a few appended rows: only their entries are swept for, the resident states' own W^T W is the one the class keeps)
-        Gb = np.ascontiguousarray(self.base.gram_w_cached(fb)[0]) if self.K - self.Kb <= 16 else None
-        self._check(self._lib.mbar_gram_w_ext(self._ctx, self.base._ctx, _dptr(fb), _dptr(fe), None if Gb is None else _dptr(Gb),
-                                              _dptr(G), _dptr(ws)))
+        Gb = self.base.gram_w_cached(fb)[0] if self.K - self.Kb <= 16 else None  # (a copy: C-contiguous)
+        self._check(self._lib.mbar_gram_w_ext(self._ctx, self.base._ctx, _dptr(fb), _dptr(fe), _dptr(Gb), _dptr(G), _dptr(ws)))
         return G, ws
 
 

@@ -277,6 +277,8 @@ class FES:
     The histogram from-normalization / all-differences modes raise ``ParameterError``, as they do in the reference.  The deliberate
     differences from the reference are listed in INTEGRATION.md ("FES")."""
 
+    _w_kn = None  # exp(mbar.Log_W_nk), built on first access and dropped by every new surface
+
     def __init__(self, u_kn, N_k, verbose=False, mbar_options=None, timings=True, **kwargs):
         from .mbar import MBAR
         from .utils import kln_to_kn
@@ -403,7 +405,7 @@ class FES:
     @property
     def w_kn(self):
         """``exp(mbar.Log_W_nk)`` (fes.py:413): built on first access only."""
-        if getattr(self, "_w_kn", None) is None:
+        if self._w_kn is None:
             self._w_kn = np.exp(self.mbar.Log_W_nk)
         return self._w_kn
 

@@ -41,7 +41,7 @@ class DeviceKDE(_lib.Handle):
     def __init__(self, X, kernel, bandwidth, device=None):
         _lib.require_device()
         self._lib = _lib.load_library()
-        X = np.ascontiguousarray(X, dtype=np.float64)
+        X = _lib.f64(X, (None, None), "X")
         self.n_samples, self.dim = X.shape
         self.device = _lib.default_device(device)
         self._h = C.c_void_p()
@@ -52,11 +52,7 @@ class DeviceKDE(_lib.Handle):
     def set_weights(self, V):
         """V: (N,) or (N, C), finite and non-negative."""
         V = np.asarray(V, dtype=np.float64)
-        if V.ndim == 1:
-            V = V[:, None]
-        V = np.ascontiguousarray(V)
-        if V.shape[0] != self.n_samples:
-            raise ValueError("one weight row per sample is needed")
+        V = _lib.f64(V[:, None] if V.ndim == 1 else V, (self.n_samples, None), "V")
         _lib.check(self._lib.mbar_kde_set_weights(self._h, V.shape[1], _lib.ptr(V)))
         self.n_columns = V.shape[1]
 
@@ -65,7 +61,7 @@ class DeviceKDE(_lib.Handle):
         _lib.check(self._lib.mbar_kde_set_option(self._h, key.encode(), int(value)))
 
     def log_density(self, Q):
-        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        Q = _lib.f64(Q, (None, self.dim), "Q")
         out = np.empty((Q.shape[0], self.n_columns), dtype=np.float64)
         if Q.shape[0]:
             _lib.check(self._lib.mbar_kde_eval(self._h, Q.shape[0], _lib.ptr(Q), _lib.ptr(out)))

@@ -124,6 +124,8 @@ class MBAR:
     numbers; a replicate then costs its solve -- no pass over N integers on the host -- and ``bootstrap_rints`` is materialised on
     first access)."""
 
+    _dm = None  # the device matrix (until the constructor has made one, and after close())
+
     def __init__(self, u_kn, N_k, maximum_iterations=10000, relative_tolerance=1.0e-7, verbose=False,
                  initial_f_k=None, solver_protocol=None, initialize="zeros", x_kindices=None, n_bootstraps=0,
                  bootstrap_solver_protocol=None, rseed=None, device=None, copy=True, bootstrap_rng="reference"):
@@ -197,7 +199,7 @@ class MBAR:
         """(K, N) reduced potentials on the host: the constructor's private copy (or reference); on an object made by
         :meth:`from_linear` downloaded from the device on first access, then kept (the same array on every access)."""
         if self._u_kn is None and self.basis_bn is not None:
-            if getattr(self, "_dm", None) is None:
+            if self._dm is None:
                 raise ParameterError("the device matrix of this object has been released: u_kn can no longer be downloaded")
             u = self._dm.to_host()
             u.setflags(write=False)
@@ -264,7 +266,7 @@ class MBAR:
         from .device import DeviceMatrix
         import time as _time
 
-        if getattr(self, "_dm", None) is None:
+        if self._dm is None:
             t0 = _time.perf_counter()
             self._dm = DeviceMatrix.from_family(self.basis_bn, self.coeff_kb, self.offset_k, self.center_kb, self.harmonic_b,
                                                 self.period_b, device=device, validate=False)  # (checked by _from_family)
@@ -509,7 +511,7 @@ class MBAR:
 
     def close(self):
         """Release the device copy of ``u_kn``."""
-        if getattr(self, "_dm", None) is not None:
+        if self._dm is not None:
             self._dm.close()
             self._dm = None
 

@@ -31,7 +31,7 @@ CHUNK = 4096  # MBAR_BAR_CHUNK
 RUNNING, DONE, NAN_BRACKET, BOUNDS, NOT_CONVERGED = 0, 1, 2, 3, 4
 METHODS = {"false-position": 0, "bisection": 1, "self-consistent-iteration": 2}
 
-_ip = C.POINTER(C.c_int64)
+_ip = _lib._ip
 _POOR_OVERLAP = ("BAR is likely to be inaccurate because of poor overlap. Improve the sampling, or decrease the spacing between "
                  "states.  For now, guessing that the free energy difference is 0 with no uncertainty.")
 
@@ -86,7 +86,8 @@ class DeviceBAR(_lib.Handle):
 
     def zero(self, DeltaF):
         """[P][5]: (F, log_numer, log_denom, log_numer2, log_denom2) at DeltaF[p], one pass."""
-        d = np.ascontiguousarray(np.broadcast_to(np.asarray(DeltaF, dtype=np.float64), (self.P,)))
+        d = np.asarray(DeltaF, dtype=np.float64)  # (one value for every problem, or one per problem)
+        d = _lib.f64(np.full(self.P, d) if d.ndim == 0 else d, (self.P,), "DeltaF")
         out = np.empty((self.P, 5))
         _lib.check(self._lib.mbar_bar_zero(self._h, _lib.ptr(d), _lib.ptr(out)))
         return out

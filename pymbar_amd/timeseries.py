@@ -42,7 +42,7 @@ logger.warning(LongWarning)
 STOPPED, ZERO_VARIANCE, END = 1, 2, 3
 _ZERO_COV = "Sample covariance sigma_AB^2 = 0 -- cannot compute statistical inefficiency"
 
-_ip = C.POINTER(C.c_int64)
+_ip = _lib._ip
 
 
 def lag_schedule(fast, tmax):
@@ -67,10 +67,10 @@ class DeviceACF(_lib.Handle):
     def __init__(self, a, b=None, seg=None, shift_a=0.0, shift_b=0.0, device=None):
         _lib.require_device()
         self._lib = _lib.load_library()
-        self.a = np.ascontiguousarray(a, dtype=np.float64)
-        self.b = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+        self.a = _lib.f64(a, (None,), "a")
         self.T = self.a.size
-        self.seg = np.ascontiguousarray([self.T] if seg is None else seg, dtype=np.int64)
+        self.b = _lib.f64(b, (self.T,), "b", optional=True)
+        self.seg = np.ascontiguousarray([self.T] if seg is None else seg, dtype=np.int64)  # (the library checks their sum against T)
         self.device = _lib.default_device(device)
         self._h = C.c_void_p()
         _lib.check(self._lib.mbar_acf_create(C.byref(self._h), self.device, self.T, _lib.ptr(self.a), _lib.ptr(self.b), self.seg.size,
@@ -81,7 +81,7 @@ class DeviceACF(_lib.Handle):
         n = (self.T - 2) // nskip + 1
         g, stop, st = np.empty(n), np.empty(n, np.int64), np.empty(n, np.int32)
         _lib.check(self._lib.mbar_acf_suffix_g(self._h, int(nskip), int(bool(fast)), int(mintime), int(bool(fft)), _lib.ptr(g),
-                                               _lib.ptr(stop, _ip), st.ctypes.data_as(C.POINTER(C.c_int32))))
+                                               _lib.ptr(stop, _ip), _lib.ptr(st, _lib._i32p)))
         return g, stop, st
 
     def multiple_g(self, fast, mintime, want_ct=False):
@@ -93,7 +93,7 @@ class DeviceACF(_lib.Handle):
             _lib.check(self._lib.mbar_acf_schedule_length(int(bool(fast)), int(self.seg.max()), C.byref(n)))
             ct = np.zeros(n.value)
         _lib.check(self._lib.mbar_acf_multiple_g(self._h, int(bool(fast)), int(mintime), _lib.ptr(g), _lib.ptr(stop, _ip),
-                                                 st.ctypes.data_as(C.POINTER(C.c_int32)), 0 if ct is None else ct.size, _lib.ptr(ct)))
+                                                 _lib.ptr(st, _lib._i32p), 0 if ct is None else ct.size, _lib.ptr(ct)))
         return float(g[0]), int(stop[0]), int(st[0]), ct
 
     def lag_sums(self, lags, origins, segments=False):
