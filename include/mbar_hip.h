@@ -408,6 +408,26 @@ int mbar_scan_energy_lognum(mbar_ctx* ctx, const double* f, int64_t L, const dou
 int mbar_scan_energy_gram_w(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_u,
                             int64_t J, const double* f_scan, int64_t r, double* cross, double* within, double* refblock, double* wsum);
 
+/* The FEATURES the chain is made of next to the stored observables (derivatives of f and of the averages along a scan): pass A once
+ * more, on the family of mbar_ctx_set_scan / mbar_ctx_set_scan_terms / mbar_ctx_set_scan_centers with its Q observables.  Walking the
+ * terms in ascending b, a linear term contributes the feature phi = basis[b][n], a harmonic one two, dl_b then dl_b^2 with dl_b the
+ * wrapped displacement exactly as the chain forms it (dl = v - c; P > 0: dl = fma(-P, rint(dl rP), dl)): F = B + H <= 12 features.
+ * With e = c_n exp(x_ln - M_l), d_i = phi_i - center_phi[l][i] and the sums S0 = sum e, S_q = sum e t_qn, A_i = sum e d_i,
+ * B_ij = sum e d_i d_j, C_qi = sum e t_qn d_i (every difference and product rounded once, every accumulation one fma, chunks
+ * merged in chunk order, compensated):
+ *   lognum[l], mean[l][1 + Q]   the bits mbar_scan_lognum returns for the same call
+ *   m1[l][i]  = A_i / S0        <phi_i - c_i>_l                                   (L x F)
+ *   m2[l][ij] = B_ij / S0       <(phi_i - c_i)(phi_j - c_j)>_l, i <= j            (L x F (F + 1) / 2, row-major upper triangle)
+ *   ma[l][q][i] = C_qi / S0     <t_q (phi_i - c_i)>_l                             (L x Q x F; may be NULL when Q = 0)
+ * center_phi[L][F] (finite, else MBAR_ERR_ARG; NULL: zeros): with center_phi = <phi>_l of a first call the covariances m2 - m1 m1^T
+ * and ma - mean m1 carry no cancellation of order <phi>^2.  e, x_ln, u_l and dl come from ONE evaluation of the chain: the pass
+ * costs about L N exponentials plus F (F + 3) / 2 + Q (F + 1) fused multiply-adds per (member, sample) and reads the B + Q + 2
+ * N-vectors twice, never the matrix.  Limits, determinism, independence of the members, the timer and "scan_part_bytes" (now
+ * with the record of 1 + Q + F' + F' (F' + 1) / 2 + Q F' doubles per member and chunk, F' the feature slots of the kernel's
+ * bucket) are those of mbar_scan_lognum. */
+int mbar_scan_moments(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_phi,
+                      double* lognum, double* mean, double* m1, double* m2, double* ma);
+
 /* ---- histogram surfaces along a scan ---------------------------------------------------------
  * The histogram free energy surface of EVERY member of a scan: the bins are labels of the resident samples as in "histogram bins
  * by label", the target states are the members of the family uploaded by mbar_ctx_set_scan (with Q = 0).  Nothing of size L x N is

@@ -52,6 +52,9 @@
 // the member's own reduced potential (MBAR.compute_scan_entropy_and_enthalpy): t_1 = u_l(n) - center_u[l] from
 // the u the chain produced for x_ln, t_2 = t_1 t_1, J = 2 or 3, whole cut only; pass B then keeps refblock[i < 2][J] where the
 // stored kind keeps refcol[J], because the reference member's t_1 is its own.
+// ScanMoments (mbar_scan.h) adds to the stored observables the features the chain itself is made of and accumulates their first and
+// second moments (mbar_scan_moments): pass A on the whole cut, in a sweep and a merge of its own below
+// (k_scan_moments, k_scan_moments_merge), between the maxima launch and the outputs of the ScanStored pass A, whose bits it keeps.
 #include "mbar_device.h"
 #include "mbar_scan_device.h"
 
@@ -182,6 +185,151 @@ k_scan_vec_merge(ScanData d, Cut cut, int64_t L, const double* __restrict__ rec,
             mean[l * J + j] = s / s0;
         }
     }
+}
+
+// ---- the moments of the features (mbar_scan_moments) -------------------------------------------------------
+// One wave per (chunk, 64 members), lane = member, as k_scan_vec<true>; e, x_ln and u_l come from the one evaluation of the chain,
+// which also hands out what every term was made of.  HB, BB: the bucket of ScanMoments (mbar_scan.h), FB = HB + BB slots, B <= BB terms
+// of which at most HB are harmonic.  S0 and S_q are the operations of k_scan_vec<true, ScanWhole, Fam, ScanStored>.  The record is
+// rec[chunk][r][L]: lane-contiguous stores.
+template <int HB, int BB, class Fam, class... Arg>
+__global__ void __launch_bounds__(SV_THREADS)
+k_scan_moments(ScanData d, int64_t L, const double* __restrict__ coeff, const double* __restrict__ offset, const double* __restrict__ M,
+               const double* __restrict__ cphi, double* __restrict__ rec, Arg... arg) {
+    static_assert(Fam::harmonic == (HB > 0) && HB <= SCAN_MAX_H && BB <= SCAN_MAX_B, "the bucket and the family");
+    constexpr int FB = HB + BB, NT = FB * (FB + 1) / 2;
+    const Fam fam = scan_arg<Fam>(arg...);
+    const ScanWhole cut{};
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    exp_table_init(smem);
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = (int64_t)blockIdx.x * (SV_THREADS / 64) + wave;
+    if (c >= cut.c1(d.N, SCAN_VCHUNK)) return;
+    int64_t bin, p0, p1;
+    cut.range(c, d.N, SCAN_VCHUNK, bin, p0, p1);
+    const int64_t l = (int64_t)blockIdx.y * 64 + lane;
+    const bool live = l < L;
+    const int Q = d.Q;
+    double cf[BB];
+#pragma unroll
+    for (int b = 0; b < BB; ++b) cf[b] = (live && b < d.B) ? coeff[l * d.B + b] : 0.0;
+    const double off = live ? offset[l] : 0.0;
+    double cen[SCAN_MAX_H];
+    family_load_centers(fam, live, l, cen);
+    const double Ml = live ? M[l] : 0.0;
+    double cp[FB];
+#pragma unroll
+    for (int i = 0; i < FB; ++i) cp[i] = live ? cphi[l * FB + i] : 0.0;
+    double s0 = 0.0, sq[SCAN_MAX_Q], sa[FB], sb[NT], sc[SCAN_MAX_Q][FB];
+#pragma unroll
+    for (int q = 0; q < SCAN_MAX_Q; ++q) {
+        sq[q] = 0.0;
+#pragma unroll
+        for (int i = 0; i < FB; ++i) sc[q][i] = 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < FB; ++i) sa[i] = 0.0;
+#pragma unroll
+    for (int k = 0; k < NT; ++k) sb[k] = 0.0;
+    for (int64_t n = p0; n < p1; ++n) {  // (n is wave-uniform: the per-sample values are scalar loads)
+        const double cn = d.cw ? d.cw[n] : 1.0;
+        if (!(cn > 0.0)) continue;
+        double dl[BB];
+        const double ul = scan_u(d, fam, cf, cen, off, n, dl);
+        const double x = scan_x_of(d, ul, n);
+        const double e = cn * scan_exp(x - Ml);
+        s0 += e;
+        // the features by slot, about the member's centres
+        double dv[FB];
+        if constexpr (HB > 0) {
+            double sqr[HB];
+#pragma unroll
+            for (int h = 0; h < HB; ++h) sqr[h] = 0.0;
+#pragma unroll
+            for (int b = 0; b < BB; ++b)
+                if ((fam.terms.mask >> b) & 1u) {  // (wave-uniform, and so is the slot)
+                    const int slot = __popc(fam.terms.mask & ((1u << b) - 1u));
+                    const double q2 = dl[b] * dl[b];
+#pragma unroll
+                    for (int h = 0; h < HB; ++h) sqr[h] = slot == h ? q2 : sqr[h];
+                }
+#pragma unroll
+            for (int h = 0; h < HB; ++h) dv[h] = sqr[h] - cp[h];
+        }
+#pragma unroll
+        for (int b = 0; b < BB; ++b) dv[HB + b] = dl[b] - cp[HB + b];
+#pragma unroll
+        for (int q = 0; q < SCAN_MAX_Q; ++q)
+            if (q < Q) {
+                const double t = d.t[(int64_t)q * d.ldv + n];
+                sq[q] = fma(e, t, sq[q]);
+                const double et = e * t;
+#pragma unroll
+                for (int i = 0; i < FB; ++i) sc[q][i] = fma(et, dv[i], sc[q][i]);
+            }
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < FB; ++i) {
+            sa[i] = fma(e, dv[i], sa[i]);
+            const double w = e * dv[i];
+#pragma unroll
+            for (int j = i; j < FB; ++j) {
+                sb[k] = fma(w, dv[j], sb[k]);
+                ++k;
+            }
+        }
+    }
+    if (!live) return;
+    const int R = 1 + Q + FB + NT + Q * FB;
+    double* r = rec + (c * R) * L + l;
+    *r = s0;
+    r += L;
+#pragma unroll
+    for (int q = 0; q < SCAN_MAX_Q; ++q)
+        if (q < Q) {
+            *r = sq[q];
+            r += L;
+        }
+#pragma unroll
+    for (int i = 0; i < FB; ++i, r += L) *r = sa[i];
+#pragma unroll
+    for (int k = 0; k < NT; ++k, r += L) *r = sb[k];
+#pragma unroll
+    for (int q = 0; q < SCAN_MAX_Q; ++q)
+        if (q < Q) {
+#pragma unroll
+            for (int i = 0; i < FB; ++i, r += L) *r = sc[q][i];
+        }
+}
+
+// One thread per (sum r, member l): its chunk records merged in chunk order, then divided by the member's S0 (every thread merges
+// that too).  lognum and out[l][0 .. Q] are the operations of k_scan_vec_merge<true, ScanWhole>.
+__global__ void __launch_bounds__(SV_THREADS)
+k_scan_moments_merge(ScanData d, int64_t L, int R, const double* __restrict__ rec, const double* __restrict__ M, double* __restrict__ lognum,
+                     double* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    exp_table_init(smem);
+    __syncthreads();
+    const int64_t x = (int64_t)blockIdx.x * SV_THREADS + threadIdx.x;
+    if (x >= L * R) return;
+    const int64_t r = x / L, l = x - r * L;
+    const int64_t nchunks = (d.N + SCAN_VCHUNK - 1) / SCAN_VCHUNK, stride = (int64_t)R * L;
+    double s0 = 0.0, e0 = 0.0;
+    const double* p = rec + l;
+    for (int64_t c = 0; c < nchunks; ++c, p += stride) scan_neumaier(s0, e0, *p);
+    s0 += e0;
+    if (r == 0) {
+        lognum[l] = s0 > 0.0 ? M[l] + log_pos(s0) : -INFINITY;
+        out[l * R] = 1.0;
+        return;
+    }
+    double s = 0.0, e = 0.0;
+    p = rec + r * L + l;
+    for (int64_t c = 0; c < nchunks; ++c, p += stride) scan_neumaier(s, e, *p);
+    s += e;
+    out[l * R + r] = s / s0;
 }
 
 // ---- pass B --------------------------------------------------------------------------------------------------------------------
@@ -484,6 +632,50 @@ hipError_t launch_scan_vec_merge(hipStream_t s, const ScanData& d, const Cut& cu
     const dim3 grid((unsigned)blocks);
     if (sum) hipLaunchKernelGGL((k_scan_vec_merge<true, Cut>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, rec, M, lognum, mean);
     else hipLaunchKernelGGL((k_scan_vec_merge<false, Cut>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, cut, L, rec, M, lognum, mean);
+    return hipGetLastError();
+}
+
+template <class Fam>
+hipError_t launch_scan_moments(hipStream_t s, const ScanData& d, const Fam& fam, const ScanMoments& mom, int64_t L, const double* coeff,
+                               const double* offset, const double* M, double* rec) {
+    const int64_t nchunks = (d.N + SCAN_VCHUNK - 1) / SCAN_VCHUNK;
+    if (L < 1 || nchunks < 1) return hipSuccess;
+    if (d.B < 1 || d.B > mom.bb || d.Q < 0 || d.Q > SCAN_MAX_Q) return hipErrorInvalidValue;
+    const int64_t gx = (nchunks + SV_THREADS / 64 - 1) / (SV_THREADS / 64);
+    const dim3 grid((unsigned)gx, (unsigned)((L + 63) / 64));
+    if (gx > 0x7fffffff || grid.y > 65535u) return hipErrorInvalidValue;
+#define MBAR_CASE(HB_, BB_)                                                                                                              \
+    if (mom.hb == HB_ && mom.bb == BB_) {                                                                                                \
+        if constexpr (Fam::harmonic) {                                                                                                   \
+            if (__builtin_popcount(fam.terms.mask) > HB_ || (fam.terms.mask >> BB_) != 0) return hipErrorInvalidValue;                   \
+            hipLaunchKernelGGL((k_scan_moments<HB_, BB_, Fam, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, L, coeff, offset, M, \
+                               mom.center_phi, rec, fam);                                                                                \
+        } else {                                                                                                                         \
+            hipLaunchKernelGGL((k_scan_moments<HB_, BB_, Fam>), grid, dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, L, coeff, offset, M,      \
+                               mom.center_phi, rec);                                                                                     \
+        }                                                                                                                                \
+        return hipGetLastError();                                                                                                        \
+    }
+    if constexpr (Fam::harmonic) {
+        MBAR_CASE(1, 3) MBAR_CASE(4, 8)
+    } else {
+        MBAR_CASE(0, 2) MBAR_CASE(0, 8)
+    }
+#undef MBAR_CASE
+    return hipErrorInvalidValue;
+}
+template hipError_t launch_scan_moments<ScanLinear>(hipStream_t, const ScanData&, const ScanLinear&, const ScanMoments&, int64_t, const double*,
+                                                    const double*, const double*, double*);
+template hipError_t launch_scan_moments<ScanHarmonic>(hipStream_t, const ScanData&, const ScanHarmonic&, const ScanMoments&, int64_t,
+                                                      const double*, const double*, const double*, double*);
+
+hipError_t launch_scan_moments_merge(hipStream_t s, const ScanData& d, const ScanMoments& mom, int64_t L, const double* rec, const double* M,
+                                     double* lognum, double* out) {
+    if (L < 1 || d.N < 1) return hipSuccess;
+    const int R = mom.record(d.Q);
+    const int64_t blocks = (L * R + SV_THREADS - 1) / SV_THREADS;
+    if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scan_moments_merge, dim3((unsigned)blocks), dim3(SV_THREADS), EXP_TABLE_BYTES, s, d, L, R, rec, M, lognum, out);
     return hipGetLastError();
 }
 

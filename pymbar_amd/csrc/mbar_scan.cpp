@@ -3,6 +3,7 @@
 // vectors, the stable counting sort of the samples by bin and the chunk tables of the two passes, the member panels and the bin
 // groups under the record budget, and the C ABI.  Kernels: mbar_k_scan.hip, one source for both cuts of the samples.
 #include "mbar_ctx.h"
+#include "mbar_scan_moments.h"
 
 #include <initializer_list>
 
@@ -85,7 +86,7 @@ struct ScanOut {
     size_t n;
 };
 int scan_begin(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* fnorm, size_t nnorm,
-               std::initializer_list<ScanOut> outs, size_t part_doubles, size_t out_doubles, bool* done, ScanData* d) {
+               std::initializer_list<ScanOut> outs, size_t part_doubles, size_t out_doubles, bool* done, ScanData* d, size_t in_extra = 0) {
     bool nan = false;
     if (c->scan_terms.mask)  // (the linear family keeps what it always did with such a member)
         for (int64_t x = 0; x < L * c->scan_B; ++x)
@@ -101,7 +102,8 @@ int scan_begin(mbar_ctx* c, const double* f, int64_t L, const double* coeff, con
         return MBAR_OK;
     }
     const int64_t B = c->scan_B;
-    HIPCHK(c, c->scan_in.grow((size_t)L * (size_t)(B + 3)));  // coeff | offset | normalisers | centres of the energy observable
+    // coeff | offset | normalisers | centres of the energy observable | in_extra: the centres of the features (mbar_scan_moments)
+    HIPCHK(c, c->scan_in.grow((size_t)L * (size_t)(B + 3) + in_extra));
     HIPCHK(c, c->scan_part.grow(part_doubles));
     HIPCHK(c, c->scan_out.grow(out_doubles));
     double* d_coeff = c->scan_in;
@@ -397,6 +399,63 @@ int mbar_scan_energy_lognum(mbar_ctx* c, const double* f, int64_t L, const doubl
 int mbar_scan_energy_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_u,
                             int64_t J, const double* f_scan, int64_t r, double* cross, double* within, double* refblock, double* wsum) {
     return whole_gram_w(c, "mbar_scan_energy_gram_w", WholeObs{true, center_u, J}, f, L, coeff, offset, f_scan, r, cross, within, refblock, wsum);
+}
+
+int mbar_scan_moments(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_phi,
+                      double* lognum, double* mean, double* m1, double* m2, double* ma) {
+    const char* who = "mbar_scan_moments";
+    int rc = scan_open(c, who, f && coeff && lognum && mean && m1 && m2 && (ma || (c && c->scan_Q == 0)) && L >= 1, false, L);
+    if (rc) return rc;
+    const int B = (int)c->scan_B, Q = (int)c->scan_Q, J = 1 + Q;
+    const int H = __builtin_popcount(c->scan_terms.mask), F = B + H, NT = F * (F + 1) / 2;
+    if (center_phi)
+        for (int64_t x = 0; x < L * F; ++x)
+            if (!std::isfinite(center_phi[x])) return fail(c, MBAR_ERR_ARG, std::string(who) + ": the centres of the features must be finite");
+    ScanMoments mom = scan_moments_bucket(B, H);
+    const std::vector<int> slot = moment_slots(c->scan_terms, B, mom);
+    const int FB = mom.slots(), R = mom.record(Q);
+    const int64_t nchunks = std::max<int64_t>((c->N + SCAN_VCHUNK - 1) / SCAN_VCHUNK, 1);
+    const MomentSizes z = moment_sizes(c->opt_scan_part_bytes, nchunks, R, L);
+    bool done = false;
+    ScanData d;
+    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0,
+                    {{lognum, (size_t)L}, {mean, (size_t)(L * J)}, {m1, (size_t)(L * F)}, {m2, (size_t)(L * NT)}, {ma, (size_t)(L * Q * F)}},
+                    std::max(z.part, (size_t)nchunks * (size_t)z.panel), z.out, &done, &d, (size_t)L * (size_t)FB);
+    if (rc || done) return rc;
+    double* d_M = c->scan_out;
+    double* d_lognum = d_M + L;
+    double* d_out = d_lognum + L;
+    const double* d_coeff = c->scan_in;
+    const double* d_off = d_coeff + L * B;
+    double* d_cphi = c->scan_in.p + L * (B + 3);
+    std::vector<double> packed((size_t)L * (size_t)FB, 0.0);
+    if (center_phi)
+        for (int64_t l = 0; l < L; ++l)
+            for (int i = 0; i < F; ++i) packed[(size_t)(l * FB + slot[(size_t)i])] = center_phi[l * F + i];
+    HIPCHK(c, hipMemcpyAsync(d_cphi, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    mom.center_phi = d_cphi;
+    const ScanWhole cut{};
+    {
+        ScopedTimer timer(c, MBAR_TIMER_OTHER);
+        for (int64_t p0 = 0; p0 < L; p0 += z.panel) {
+            const int64_t pl = std::min(z.panel, L - p0);
+            HIPCHK(c, sweep_vec(c, d, cut, ScanStored{}, false, p0, pl, d_coeff + p0 * B, d_off + p0, nullptr, c->scan_part));
+            HIPCHK(c, launch_scan_vec_merge(c->stream, d, cut, false, pl, c->scan_part, d_M + p0, nullptr, nullptr));
+            if (c->scan_terms.mask)
+                HIPCHK(c, launch_scan_moments(c->stream, d, harmonic_of(c).from(p0), mom.from(p0), pl, d_coeff + p0 * B, d_off + p0, d_M + p0, c->scan_part));
+            else
+                HIPCHK(c, launch_scan_moments(c->stream, d, ScanLinear{}, mom.from(p0), pl, d_coeff + p0 * B, d_off + p0, d_M + p0, c->scan_part));
+            HIPCHK(c, launch_scan_moments_merge(c->stream, d, mom, pl, c->scan_part, d_M + p0, d_lognum + p0, d_out + p0 * R));
+        }
+    }
+    std::vector<double> out((size_t)L * (size_t)R);
+    HIPCHK(c, hipMemcpyAsync(lognum, d_lognum, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    rc = sync_stream(c);
+    if (rc) return rc;
+    for (int64_t l = 0; l < L; ++l)
+        moment_outputs(out.data() + l * R, Q, mom, slot, mean + l * J, m1 + l * F, m2 + l * NT, ma ? ma + l * Q * F : nullptr);
+    return MBAR_OK;
 }
 
 // ---- histogram surfaces along a scan ----

@@ -127,6 +127,31 @@ struct ScanEnergy {
     const double* center_u;  // [L] on the device
     MBAR_HD ScanEnergy from(int64_t l0) const { return ScanEnergy{center_u + l0}; }
 };
+// ScanMoments: the stored observables AND the features the chain is made of, for the derivatives of f and of the averages along
+// a scan (mbar_scan_moments).  Pass A on the whole cut only, in a sweep of its own (k_scan_moments): term b
+// hands out phi = basis[b][n] when linear and dl_b, dl_b^2 (the wrapped displacement family_term formed) when harmonic, and member l
+// accumulates, with d_i = phi_i - center_phi[l][i] and e = c_n exp(x_ln - M_l),
+//   S0 = sum e | S_q = sum e t_qn | A_i = sum e d_i | B_ij = sum e d_i d_j (i <= j) | C_qi = sum e t_qn d_i
+// every difference and product rounded once, every accumulation one fma.  The kernel keeps the features in SLOTS that are static in
+// the term: the squares of the harmonic terms, in ascending b, in slots [0, hb), the term's own value (basis or dl) in slot hb + b;
+// a bucket (hb, bb) serves the families with at most hb harmonic terms among at most bb, slots nobody fills carry exact zeros.  The
+// host maps slots to the features of the C ABI (ascending b: a linear term's basis, a harmonic term's dl then dl^2).
+struct ScanMoments {
+    int hb = 0, bb = 0;                  // the bucket: one of (0, 2), (0, 8) under ScanLinear, (1, 3), (4, 8) under ScanHarmonic
+    const double* center_phi = nullptr;  // [L][hb + bb] on the device, by slot
+    MBAR_HD int slots() const { return hb + bb; }
+    // doubles of a (chunk, member) record, of a member's merged sums: S0 | S[Q] | A[slots] | B[slots (slots + 1) / 2] | C[Q][slots]
+    MBAR_HD int record(int Q) const { return 1 + Q + slots() + slots() * (slots() + 1) / 2 + Q * slots(); }
+    MBAR_HD ScanMoments from(int64_t l0) const { return ScanMoments{hb, bb, center_phi + l0 * slots()}; }
+};
+// (scan_moments_bucket in mbar_scan_moments.h: the smallest bucket that serves a family)
+// the sums of the members [0, L) of coeff / offset / mom.center_phi about the maxima M[L] (of launch_scan_vec, sum = false, ScanStored):
+// rec[chunk][record][L], and their merge in chunk order: lognum[L] and out[L][record] = the sums over S0 (out[l][0] = 1)
+template <class Fam>
+hipError_t launch_scan_moments(hipStream_t s, const ScanData& d, const Fam& fam, const ScanMoments& mom, int64_t L, const double* coeff,
+                               const double* offset, const double* M, double* rec);
+hipError_t launch_scan_moments_merge(hipStream_t s, const ScanData& d, const ScanMoments& mom, int64_t L, const double* rec, const double* M,
+                                     double* lognum, double* out);
 // Cut = ScanWhole or ScanBinned (Q = 0), Fam = ScanLinear or ScanHarmonic, Obs = ScanStored or ScanEnergy (whole cut, Q = 1 or 2) in
 // the two sweeps; the merges know neither family kind (the cross merge is told the panel width and the record's Obs).
 // pass A over the members [0, L) of coeff / offset: per-chunk records of the maxima (sum = false: rec[chunk][L]) or of the J scaled

@@ -12,11 +12,17 @@ namespace mbar {
 // member's centre of term b (read at a harmonic term only).  The kind of term b is wave-uniform (terms.mask); the linear family
 // is the one fma it always was.  Every operation is rounded once: rint is v_rndne_f64 (ties to even), a tie dl = +-P / 2 gives the
 // same dl dl either way.
-__device__ __forceinline__ double family_term(const ScanLinear&, int, double u, double cf, double v, double) { return fma(cf, v, u); }
-__device__ __forceinline__ double family_term(const FamilyTerms& terms, int b, double u, double cf, double v, double c) {
+// (the forms with a last argument also hand out what the term was made of, for the moments of mbar_scan_moments: v itself at a
+// linear term, the wrapped displacement dl at a harmonic one; the forms without it are the same operations)
+__device__ __forceinline__ double family_term(const ScanLinear&, int, double u, double cf, double v, double, double& dl) {
+    dl = v;
+    return fma(cf, v, u);
+}
+__device__ __forceinline__ double family_term(const FamilyTerms& terms, int b, double u, double cf, double v, double c, double& dl) {
 #pragma clang fp contract(off)
+    dl = v;
     if (!((terms.mask >> b) & 1u)) return fma(cf, v, u);
-    double dl = v - c;
+    dl = v - c;
     const double P = terms.period[b];
     if (P > 0.0) {
         const double m = rint(dl * terms.rperiod[b]);
@@ -25,8 +31,13 @@ __device__ __forceinline__ double family_term(const FamilyTerms& terms, int b, d
     const double q = dl * dl;
     return fma(cf, q, u);
 }
-__device__ __forceinline__ double family_term(const ScanHarmonic& fam, int b, double u, double cf, double v, double c) {
-    return family_term(fam.terms, b, u, cf, v, c);
+__device__ __forceinline__ double family_term(const ScanHarmonic& fam, int b, double u, double cf, double v, double c, double& dl) {
+    return family_term(fam.terms, b, u, cf, v, c, dl);
+}
+template <class Terms>
+__device__ __forceinline__ double family_term(const Terms& terms, int b, double u, double cf, double v, double c) {
+    double dl;
+    return family_term(terms, b, u, cf, v, c, dl);
 }
 // the centre of term b among a member's centres in registers (cen: the harmonic terms' in ascending b); the slot is wave-uniform
 __device__ __forceinline__ double family_center(const ScanLinear&, int, const double (&)[SCAN_MAX_H]) { return 0.0; }
@@ -52,14 +63,24 @@ __device__ __forceinline__ void family_load_centers(const ScanHarmonic& fam, boo
 }
 
 // u_l(n) with the fixed chain over ascending b, and x_ln = -u_l(n) - logden_n from it
+// (dl[b]: basis[b][n] of a linear term, the wrapped displacement of a harmonic one, 0 for b >= B; NB: the terms the caller's
+// instantiation serves, B <= NB)
+template <int NB, class Fam>
+__device__ __forceinline__ double scan_u(const ScanData& d, const Fam& fam, const double (&cf)[NB], const double (&cen)[SCAN_MAX_H],
+                                         double off, int64_t n, double (&dl)[NB]) {
+    double u = off;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        dl[b] = 0.0;
+        if (b < d.B) u = family_term(fam, b, u, cf[b], d.basis[(int64_t)b * d.ldv + n], family_center(fam, b, cen), dl[b]);
+    }
+    return u;
+}
 template <class Fam>
 __device__ __forceinline__ double scan_u(const ScanData& d, const Fam& fam, const double (&cf)[SCAN_MAX_B], const double (&cen)[SCAN_MAX_H],
                                          double off, int64_t n) {
-    double u = off;
-#pragma unroll
-    for (int b = 0; b < SCAN_MAX_B; ++b)
-        if (b < d.B) u = family_term(fam, b, u, cf[b], d.basis[(int64_t)b * d.ldv + n], family_center(fam, b, cen));
-    return u;
+    double dl[SCAN_MAX_B];
+    return scan_u(d, fam, cf, cen, off, n, dl);
 }
 __device__ __forceinline__ double scan_x_of(const ScanData& d, double u, int64_t n) { return -u - d.logden[n]; }
 

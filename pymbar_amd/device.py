@@ -495,6 +495,41 @@ class DeviceMatrix(_ContextMatrix):
         :meth:`scan_gram_w` with the member's own ``t_j``; ``refblock[l, i, j] = sum_n c_n (b_rn t_ri)(b_ln t_lj)``, ``i`` 0 or 1."""
         return self._scan_pass_b(f, coeff_lb, offset_l, f_scan, reference, cross, center_lb, energy=(center_u, J))
 
+    def scan_features(self):
+        """``(B, H, F)`` of the family :meth:`set_scan` put on the matrix: terms, harmonic terms among them and the features
+        :meth:`scan_moments` takes moments of (a linear term's basis vector; a harmonic term's wrapped displacement ``dl`` and
+        ``dl^2``), ``F = B + H``."""
+        if self._scan is None:
+            raise ValueError("no basis on this matrix (set_scan first)")
+        B = self._scan[0]
+        H = 0 if self._scan_harmonic is None else int(np.count_nonzero(self._scan_harmonic))
+        return B, H, B + H
+
+    def scan_moments(self, f, coeff_lb, offset_l=None, center_phi=None, center_lb=None):
+        """Pass A of a scan with the moments of the features the chain is made of (``mbar_scan_moments``): ``(lognum, mean, m1, m2,
+        ma)``.  ``lognum`` and ``mean`` are :meth:`scan_lognum`'s, to the bit.  Walking the terms in ascending ``b``, a linear term
+        contributes the feature ``basis_bn[b]``, a harmonic one ``dl_b`` then ``dl_b^2`` (the wrapped displacement from the member's
+        centre, as the chain forms it): ``F = B + H`` features ``phi_i``.  About ``center_phi`` ``(L, F)`` (None: zeros), in member
+        ``l``: ``m1[l, i] = <phi_i - c_i>``, ``m2[l, i, j] = <(phi_i - c_i)(phi_j - c_j)>`` (``L x F x F``, symmetric) and ``ma[l, q, i]
+        = <t_q (phi_i - c_i)>`` (``L x Q x F``) for the ``Q`` observables of :meth:`set_scan`."""
+        f = self._f(f)
+        coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
+        _, _, F = self.scan_features()
+        center_phi = _lib.f64(center_phi, (L, F), "center_phi", optional=True)
+        self._scan_centers(center_lb, L)
+        lognum = np.empty(L, dtype=np.float64)
+        mean = np.empty((L, J), dtype=np.float64)
+        m1 = np.empty((L, F), dtype=np.float64)
+        tri = np.empty((L, F * (F + 1) // 2), dtype=np.float64)
+        ma = np.empty((L, J - 1, F), dtype=np.float64)
+        self._check(self._lib.mbar_scan_moments(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(center_phi), _dptr(lognum),
+                                                _dptr(mean), _dptr(m1), _dptr(tri), _dptr(ma) if J > 1 else None), ValueError)
+        m2 = np.empty((L, F, F), dtype=np.float64)
+        iu = np.triu_indices(F)
+        m2[:, iu[0], iu[1]] = tri
+        m2[:, iu[1], iu[0]] = tri
+        return lognum, mean, m1, m2, ma
+
     # ---- histogram surfaces along a scan (pymbar_amd.scan.compute_scan_fes) ---------------------------------------------------
     SCAN_BIN_CROSS_BYTES = 1 << 28  # the host cross block of one slab of members of scan_bin_gram_w stays under this
 

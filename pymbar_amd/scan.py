@@ -375,6 +375,158 @@ def compute_scan_entropy_and_enthalpy(mbar, basis_bn=None, coeff_lb=None, offset
     return out
 
 
+# ---- derivatives of f and of the averages along a scan ----------------------------------------------------------------------------
+def _gradient_matrix(mbar):
+    dm = _scan_matrix(mbar)
+    if not hasattr(dm, "scan_moments"):
+        raise ParameterError(f"derivatives along a scan need the moments pass of a single-rank device matrix and are {_NOT_HERE} for this handle")
+    return dm
+
+
+def gradient_layout(B, harmonic_b=None):
+    """``(features, params)`` of a family of ``B`` terms.  ``features``: ``(b, kind)`` of every feature the moments pass returns, in
+    its order -- ``(b, "basis")`` of a linear term, ``(b, "dl")`` then ``(b, "dl2")`` of a harmonic one.  ``params``: ``("coeff", b)``
+    for every ``b``, then ``("center", b)`` for the harmonic ``b`` ascending."""
+    harmonic = np.zeros(B, dtype=bool) if harmonic_b is None else np.asarray(harmonic_b, dtype=bool)
+    features = []
+    for b in range(B):
+        features += [(b, "dl"), (b, "dl2")] if harmonic[b] else [(b, "basis")]
+    params = [("coeff", b) for b in range(B)] + [("center", b) for b in range(B) if harmonic[b]]
+    return features, params
+
+
+def gradient_from_moments(coeff_lb, harmonic_b, center_phi, m1, m2, ma=None, mean=None, hessian=True):
+    """The chain rule on the centred moments of one moments pass (``center_phi``, ``m1``, ``m2``, ``ma``, ``mean`` as
+    ``DeviceMatrix.scan_moments`` takes and returns them): a dict with ``feature_mean = center_phi + m1``, ``feature_cov = m2 - m1
+    m1^T``, ``grad_f`` ``(L, P)``, ``hess_f`` ``(L, P, P)`` and, with observables, ``grad_mu`` ``(Q, L, P)``.  Every parameter's
+    ``g = du/dp`` is one feature times a factor -- a linear ``coeff_b``: ``basis_b``; a harmonic ``coeff_b``: ``dl_b^2``; ``center_b``:
+    ``-2 coeff_lb dl_b`` -- so ``grad_f = <g>``, ``hess_f = <h> - Cov(g, g')`` with ``h(center_b, center_b) = 2 coeff_lb``, ``h(coeff_b,
+    center_b) = -2 dl_b`` and 0 otherwise, ``grad_mu = -Cov(A, g)``.  Explicit ascending loops, element by element over the members: a
+    member's numbers do not depend on the others."""
+    coeff_lb = np.asarray(coeff_lb, dtype=np.float64)
+    L, B = coeff_lb.shape
+    features, params = gradient_layout(B, harmonic_b)
+    F, P = len(features), len(params)
+    slot = {fk: i for i, fk in enumerate(features)}
+    fmean = center_phi + m1
+    fcov = np.empty((L, F, F))
+    for i in range(F):
+        for j in range(F):
+            fcov[:, i, j] = m2[:, i, j] - m1[:, i] * m1[:, j]
+    # g_p = scale[:, p] * feature idx[p]
+    idx, scale = [], np.ones((L, P))
+    for p, (kind, b) in enumerate(params):
+        if kind == "coeff":
+            idx.append(slot[(b, "dl2")] if (b, "dl2") in slot else slot[(b, "basis")])
+        else:
+            idx.append(slot[(b, "dl")])
+            scale[:, p] = -2.0 * coeff_lb[:, b]
+    out = dict(feature_mean=fmean, feature_cov=fcov)
+    grad = np.empty((L, P))
+    for p in range(P):
+        grad[:, p] = scale[:, p] * fmean[:, idx[p]]
+    out["grad_f"] = grad
+    if hessian:
+        hess = np.empty((L, P, P))
+        for p in range(P):
+            for r in range(p, P):
+                h = -(scale[:, p] * scale[:, r]) * fcov[:, idx[p], idx[r]]
+                (kp, bp), (kr, br) = params[p], params[r]
+                if bp == br and kp == "center" and kr == "center":
+                    h = 2.0 * coeff_lb[:, bp] + h
+                elif bp == br and kp == "coeff" and kr == "center":
+                    h = -2.0 * fmean[:, slot[(bp, "dl")]] + h
+                hess[:, p, r] = h
+                hess[:, r, p] = h
+        out["hess_f"] = hess
+    if ma is not None and ma.shape[1] > 0:
+        Q = ma.shape[1]
+        gmu = np.empty((Q, L, P))
+        for q in range(Q):
+            for p in range(P):
+                gmu[q, :, p] = -scale[:, p] * (ma[:, q, idx[p]] - mean[:, 1 + q] * m1[:, idx[p]])
+        out["grad_mu"] = gmu
+    return out
+
+
+def compute_scan_gradient(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, hessian=True, uncertainty_method=None,
+                          center_lb=None, harmonic_b=None, period_b=None):
+    """The derivatives of the free energy and of the averages along a family of unsampled states with respect to the family's own
+    parameters: which way ``f`` and ``<A>`` move.
+
+    The family (``basis_bn``, ``coeff_lb``, ``offset_l``, ``center_lb``, ``harmonic_b``, ``period_b``) and ``A_qn`` are those of
+    :func:`compute_scan`.  The parameters are listed in the returned ``params``: ``("coeff", b)`` for every ``b``, then ``("center",
+    b)`` for the harmonic ``b`` ascending, ``P = B + H``.  With ``g = du_l/dp`` and ``h = d2u_l/dp dp'``, all averages in member ``l``:
+
+    * ``f`` ``(L,)``: the bits of :func:`compute_scan`;
+    * ``grad_f`` ``(L, P)``: ``df/dp = <g>``;
+    * ``hess_f`` ``(L, P, P)`` (with ``hessian``): ``d2f/dp dp' = <h> - Cov(g, g')``, symmetric;
+    * with observables ``mu`` ``(Q, L)``, the bits of :func:`compute_scan`, and ``grad_mu`` ``(Q, L, P)``: ``d<A>/dp = -Cov(A, g)``;
+    * ``feature_mean`` ``(L, F)`` and ``feature_cov`` ``(L, F, F)``: the raw moments of the features ``features`` lists (``(b,
+      "basis")`` of a linear term, ``(b, "dl")`` and ``(b, "dl2")`` -- the wrapped displacement from the member's centre and its square --
+      of a harmonic one) from which the chain rule forms the rest.
+
+    The offset is not a parameter: ``df/doffset = 1`` and every covariance with it vanishes.  The device evaluates ``u_l`` once per
+    (member, sample) and accumulates the moments of what the chain is made of next to the sums of :func:`compute_scan`; nothing of
+    size ``L x N`` is built.  The pass runs twice, about zero and then about the feature means, so that no covariance carries a
+    cancellation of order ``<phi>^2``.
+
+    The derivative with respect to the centre of a PERIODIC harmonic term is the almost-everywhere one: ``u`` is continuous where a
+    sample crosses the seam ``dl = +-P / 2`` but its slope has a kink there, which the second derivative does not see.
+
+    ``uncertainty_method``: None (no uncertainties) or "bootstrap" -- one pass per replicate under that replicate's multiplicities and
+    free energies, about the centres of the full sample; adds ``bootstrapped_f``, ``bootstrapped_grad_f``, ``bootstrapped_hess_f``,
+    ``bootstrapped_mu``, ``bootstrapped_grad_mu``, ``bootstrapped_feature_mean``, ``bootstrapped_feature_cov`` (replicate first) and
+    ``df``, ``dgrad_f``, ``dhess_f``, ``dmu``, ``dgrad_mu``, the ``std`` over the replicates.  Analytical uncertainties are not offered."""
+    basis_given = basis_bn
+    if uncertainty_method not in (None, "bootstrap"):
+        raise ParameterError(f"uncertainty_method {uncertainty_method} is not offered for the derivatives along a scan: None or 'bootstrap'")
+    bootstrap = uncertainty_method == "bootstrap"
+    if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
+        raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
+    basis_bn, coeff_lb, offset_l, A_qn, L = _check_inputs(mbar, _family_basis(mbar, basis_bn, coeff_lb), coeff_lb, offset_l, A_qn, 0)
+    B = basis_bn.shape[0]
+    kinds, cen = _family_kinds(mbar, basis_given, B, L, center_lb, harmonic_b, period_b)
+    dm = _gradient_matrix(mbar)
+    hb = kinds.get("harmonic_b")
+    features, params = gradient_layout(B, hb)
+    Q = len(A_qn)
+    t_qn, shift = _shifted(A_qn)
+
+    def derived(lognum, mean, m1, m2, ma, center):
+        res = gradient_from_moments(coeff_lb, hb, center, m1, m2, ma, mean, hessian)
+        res["f"] = -lognum
+        if Q:
+            res["mu"] = mean[:, 1:].T + shift[:, None]
+        return res
+
+    dm.set_Nk(mbar.N_k)
+    dm.set_scan(basis_bn, t_qn, **kinds)
+    try:
+        _, _, m1_0, _, _ = dm.scan_moments(mbar.f_k, coeff_lb, offset_l, None, **cen)
+        center = np.ascontiguousarray(m1_0)
+        out = derived(*dm.scan_moments(mbar.f_k, coeff_lb, offset_l, center, **cen), center)
+        out.update(params=params, features=features)
+        if bootstrap:
+            names = [k for k in ("f", "grad_f", "hess_f", "mu", "grad_mu", "feature_mean", "feature_cov") if k in out]
+            boots = {k: np.zeros((mbar.n_bootstraps,) + out[k].shape) for k in names}
+            try:
+                for b in range(mbar.n_bootstraps):
+                    mbar._set_bootstrap_weights(dm, b)
+                    res_b = derived(*dm.scan_moments(mbar.f_k_boots[b, :], coeff_lb, offset_l, center, **cen), center)
+                    for k in names:
+                        boots[k][b] = res_b[k]
+            finally:
+                dm.set_sample_weights(None)
+            for k in names:
+                out["bootstrapped_" + k] = boots[k]
+                if not k.startswith("feature"):
+                    out["d" + k] = np.std(boots[k], axis=0)
+    finally:
+        dm.set_scan(None)
+    return out
+
+
 # ---- histogram free energy surfaces along a scan ----------------------------------------------------------------------------------
 def _scan_fes_matrix(mbar):
     dm = _scan_matrix(mbar)
