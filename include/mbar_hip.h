@@ -408,6 +408,25 @@ int mbar_scan_energy_lognum(mbar_ctx* ctx, const double* f, int64_t L, const dou
 int mbar_scan_energy_gram_w(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_u,
                             int64_t J, const double* f_scan, int64_t r, double* cross, double* within, double* refblock, double* wsum);
 
+/* The members' own Gram block, for differences between ANY two members of a scan (MBAR.compute_scan_pairs): on the family of
+ * mbar_ctx_set_scan / mbar_ctx_set_scan_terms / mbar_ctx_set_scan_centers with its Q observables, for the R reference members
+ * rows[R] (indices into the call's L members; they may repeat),
+ *   pair[r][l][i][j] = sum_n c_n (b_{rows[r]} n t_in)(b_ln t_jn)        R x L x J x J, row-major
+ * with b_ln = exp(f_scan[l] + x_ln) as in mbar_scan_gram_w: pair[r][l][0][j] is the refcol[l][j] that call returns for r = rows[r],
+ * pair[r][rows[r]][i][j] the reference member's own within.  Both operands are generated on the device from the B numbers per
+ * sample -- the (reference member, i) rows once per tile of 16 samples in LDS, the members' columns in registers -- and multiplied
+ * on the fp64 matrix cores; nothing of size L x N is stored and the resident matrix is read only through logden_n(f).  The
+ * reference members are taken in panels of 32 / J or 128 / J, the members in the panels of mbar_scan_gram_w; one launch per pair of
+ * panels costs (reference members + members of the panels) x N exponentials and 2 x (rows of the panel) x (members) x J x N flop.
+ * A member's b is formed by the same operations as a row and as a column.  No floating-point atomics; chunks of 8192 samples cut
+ * by N alone and merged in chunk order: two identical calls return identical bits, element (r, l, i, j) does not depend on the
+ * other members or reference members of the call nor on where they sit, and without sample weights pair[r][l][i][j] and the
+ * pair[l'][r'][j][i] of the same two members are the same bits.  Limits and state errors are those of mbar_scan_gram_w;
+ * MBAR_ERR_ARG: R < 1, a row outside [0, L), a NULL pointer, a non-finite f_scan.  A NaN in f fills pair with NaN (MBAR_OK).
+ * Kernel time: MBAR_TIMER_OTHER. */
+int mbar_scan_pair_gram(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan,
+                        int64_t R, const int64_t* rows, double* pair);
+
 /* The FEATURES the chain is made of next to the stored observables (derivatives of f and of the averages along a scan): pass A once
  * more, on the family of mbar_ctx_set_scan / mbar_ctx_set_scan_terms / mbar_ctx_set_scan_centers with its Q observables.  Walking the
  * terms in ascending b, a linear term contributes the feature phi = basis[b][n], a harmonic one two, dl_b then dl_b^2 with dl_b the

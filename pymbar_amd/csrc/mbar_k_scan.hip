@@ -55,6 +55,10 @@
 // ScanMoments (mbar_scan.h) adds to the stored observables the features the chain itself is made of and accumulates their first and
 // second moments (mbar_scan_moments): pass A on the whole cut, in a sweep and a merge of its own below
 // (k_scan_moments, k_scan_moments_merge), between the maxima launch and the outputs of the ScanStored pass A, whose bits it keeps.
+//
+// The members' own Gram block (MBAR.compute_scan_pairs, mbar_scan_pair_gram): pass B once more with the rows
+// of the LDS tile being (reference member, i) instead of sampled states, pair[r][l][i][j] = sum_n c_n (b_rn t_in)(b_ln t_jn), in a
+// sweep and a merge of its own (k_scan_pair, k_scan_pair_merge) behind the merge of pass B; whole cut, stored observables.
 #include "mbar_device.h"
 #include "mbar_scan_device.h"
 
@@ -592,6 +596,196 @@ k_scan_cross_merge(ScanData d, Cut cut, int NB, int64_t K, int64_t L, int64_t p0
     *out = s + e;
 }
 
+// ---- the member-member Gram block (mbar_scan_pair_gram) -----------------------------------------------------
+//   pair[r][l][i][j] = sum_n c_n (b_{rows[r]} n t_in)(b_ln t_jn)
+// k_scan_cross with the rows of the LDS tile being (reference member, i) instead of sampled states: row m J + i of the tile is b t_i
+// of the panel's m-th reference member, RMAX = 16 NB / J of them (at J = 3 the last 16 NB - 3 RMAX rows stay zero).  The parameters
+// of the panel's reference members (coeff | offset | f_scan | centres, PAIR_RP doubles each) are staged in LDS once; in the fill
+// stage thread tid forms b of the members (tid >> 4) + 16 mm at tile position tid & 15 by exactly the operations of the product
+// stage -- the chain of family_term over the same basis values, then scan_exp(fs + (-u - lden)) -- so that, without sample weights,
+// element (r, l, i, j) and element (l, r, j, i) are the same products in the other order of their factors, accumulated over the
+// same positions in the same order: the same bits.  An element's operations do not depend on the row it has in the tile, on NB or
+// on its column.  The record is the cross part of k_scan_cross's: [wave][I < NB][cb < NCB][r < 4][lane].
+constexpr int PAIR_RP = SCAN_MAX_B + 2 + SCAN_MAX_H;
+
+template <int NB, int J, class Fam, class... Arg>
+__global__ void __launch_bounds__(256)
+k_scan_pair(ScanData d, int64_t L, int64_t p0, const int64_t* __restrict__ rows, int rm, const double* __restrict__ coeff,
+            const double* __restrict__ offset, const double* __restrict__ fnorm, double* __restrict__ part, Arg... arg) {
+    const Fam fam = scan_arg<Fam>(arg...);
+    const ScanWhole cut{};
+    constexpr int MB = Fam::mb(J), NCB = MB * J, Q = J - 1;
+    constexpr int RMAX = scan_pair_rows(NB, J), RPT = (RMAX + 15) / 16;  // reference members of a panel, and of one fill thread
+    constexpr int SVB = 32;                                              // where the basis rows start in sv
+    constexpr int W_DOUBLES = NB * 16 * SCAN_PITCH;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    exp_table_init(smem);
+    double* Wt = reinterpret_cast<double*>(smem + EXP_TABLE_BYTES);  // [16 NB][SCAN_PITCH]
+    double* sv = Wt + W_DOUBLES;                                     // cn[16] | lden[16] | basis[B][16] | t[Q][16]
+    double* rp = sv + SVB + (SCAN_MAX_B + SCAN_MAX_Q) * 16;          // [RMAX][PAIR_RP]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, q4 = lane >> 4;
+    int64_t bin, q0c, q1c;
+    cut.range(blockIdx.x, d.N, SCAN_CHUNK, bin, q0c, q1c);
+    const int64_t pl = L - p0 < 64 * MB ? L - p0 : 64 * MB;  // members of the panel
+    const int nblk = (int)((pl + 15) / 16);
+    int mine = 0;
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) mine += (mb * 4 + wave) < nblk;
+    mine = __builtin_amdgcn_readfirstlane(mine);
+
+    double cf[MB][SCAN_MAX_B], off[MB], fs[MB];
+    double cen[Fam::harmonic ? MB : 1][SCAN_MAX_H];
+    bool mlive[MB];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+        const int64_t pm = (int64_t)(mb * 4 + wave) * 16 + col;
+        mlive[mb] = pm < pl;
+        const int64_t l = p0 + pm;
+#pragma unroll
+        for (int b = 0; b < SCAN_MAX_B; ++b) cf[mb][b] = (mlive[mb] && b < d.B) ? coeff[l * d.B + b] : 0.0;
+        off[mb] = mlive[mb] ? offset[l] : 0.0;
+        if constexpr (Fam::harmonic) family_load_centers(fam, mlive[mb], l, cen[mb]);
+        fs[mb] = mlive[mb] ? fnorm[l] : 0.0;
+    }
+    // the parameters of the panel's reference members, and a tile of zeros (rows nobody owns stay zero)
+    for (int x = tid; x < RMAX * PAIR_RP; x += 256) {
+        const int m = x / PAIR_RP, k = x - m * PAIR_RP;
+        double v = 0.0;
+        if (m < rm) {
+            const int64_t l = rows[m];
+            if (k < SCAN_MAX_B) v = k < d.B ? coeff[l * d.B + k] : 0.0;
+            else if (k == SCAN_MAX_B) v = offset[l];
+            else if (k == SCAN_MAX_B + 1) v = fnorm[l];
+            else if constexpr (Fam::harmonic) v = fam.center[l * SCAN_MAX_H + (k - SCAN_MAX_B - 2)];
+        }
+        rp[x] = v;
+    }
+    for (int x = tid; x < W_DOUBLES; x += 256) Wt[x] = 0.0;
+    const int fs_s = tid & 15, fs_r = tid >> 4;
+
+    v4d acc[NB * NCB];
+#pragma unroll
+    for (int i = 0; i < NB * NCB; ++i) acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
+
+    __syncthreads();  // the exp table, the parameters
+    for (int64_t q0 = q0c; q0 < q1c; q0 += 16) {
+        // ---- fill: the row tile and the per-sample values of the tile
+        {
+            const int64_t q = q0 + fs_s;
+            int64_t n = 0;
+            double cn = 0.0, lden = 0.0;
+            if (q < q1c) {
+                n = q;
+                cn = d.cw ? d.cw[n] : 1.0;
+                if (cn > 0.0) lden = d.logden[n];
+                else cn = 0.0;
+            }
+            const bool slive = cn > 0.0;
+            double bas[SCAN_MAX_B], tq[J];
+#pragma unroll
+            for (int b = 0; b < SCAN_MAX_B; ++b) bas[b] = (slive && b < d.B) ? d.basis[(int64_t)b * d.ldv + n] : 0.0;
+            tq[0] = 1.0;
+#pragma unroll
+            for (int j = 1; j < J; ++j) tq[j] = slive ? d.t[(int64_t)(j - 1) * d.ldv + n] : 0.0;
+#pragma unroll
+            for (int mm = 0; mm < RPT; ++mm) {
+                const int m = fs_r + 16 * mm;
+                if (m < RMAX) {
+                    double br = 0.0;
+                    if (slive && m < rm) {
+                        const double* pr = rp + m * PAIR_RP;
+                        double ur = pr[SCAN_MAX_B], cenr[SCAN_MAX_H];
+#pragma unroll
+                        for (int h = 0; h < SCAN_MAX_H; ++h) cenr[h] = Fam::harmonic ? pr[SCAN_MAX_B + 2 + h] : 0.0;
+#pragma unroll
+                        for (int b = 0; b < SCAN_MAX_B; ++b)
+                            if (b < d.B) ur = family_term(fam, b, ur, pr[b], bas[b], family_center(fam, b, cenr));
+                        br = scan_exp(pr[SCAN_MAX_B + 1] + (-ur - lden));
+                    }
+#pragma unroll
+                    for (int i = 0; i < J; ++i) Wt[(m * J + i) * SCAN_PITCH + fs_s] = br * tq[i];
+                }
+            }
+            if (tid < 16) {
+                sv[fs_s] = cn;
+                sv[16 + fs_s] = lden;
+            }
+            if (fs_r < d.B + Q) {
+                double v = 0.0;
+                if (slive) v = (Q == 0 || fs_r < d.B) ? d.basis[(int64_t)fs_r * d.ldv + n] : d.t[(int64_t)(fs_r - d.B) * d.ldv + n];
+                sv[SVB + fs_r * 16 + fs_s] = v;
+            }
+        }
+        __syncthreads();
+        // ---- products: four groups of four positions
+        if (mine > 0) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int s = 4 * g + q4;
+                double a[NB];
+#pragma unroll
+                for (int I = 0; I < NB; ++I) a[I] = Wt[(16 * I + col) * SCAN_PITCH + s];
+                const double cn = sv[s], lden = sv[16 + s];
+                double bas[SCAN_MAX_B], tj[J];
+#pragma unroll
+                for (int b = 0; b < SCAN_MAX_B; ++b) bas[b] = b < d.B ? sv[SVB + b * 16 + s] : 0.0;
+                tj[0] = 1.0;
+#pragma unroll
+                for (int j = 1; j < J; ++j) tj[j] = sv[SVB + (d.B + j - 1) * 16 + s];
+#pragma unroll
+                for (int mb = 0; mb < MB; ++mb) {
+                    if (mb < mine) {  // (wave-uniform)
+                        double uu = off[mb];
+#pragma unroll
+                        for (int b = 0; b < SCAN_MAX_B; ++b)
+                            if (b < d.B) uu = family_term(fam, b, uu, cf[mb][b], bas[b], family_center(fam, b, cen[Fam::harmonic ? mb : 0]));
+                        double bv = scan_exp(fs[mb] + (-uu - lden));
+                        if (!(cn > 0.0) || !mlive[mb]) bv = 0.0;
+                        const double cb = cn * bv;
+                        double z[J];
+#pragma unroll
+                        for (int j = 0; j < J; ++j) z[j] = cb * tj[j];
+#pragma unroll
+                        for (int I = 0; I < NB; ++I)
+#pragma unroll
+                            for (int j = 0; j < J; ++j)
+                                acc[I * NCB + mb * J + j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[I], z[j], acc[I * NCB + mb * J + j], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // ---- the record
+    double* rec = part + (int64_t)blockIdx.x * ((int64_t)4 * NB * NCB * 256);
+#pragma unroll
+    for (int i = 0; i < NB * NCB; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rec[(((int64_t)wave * NB * NCB + i) * 4 + r) * 64 + lane] = acc[i][r];
+}
+
+// One thread per (row rho = m J + i of the row panel, member pm of the member panel, j): its chunk records added in chunk order,
+// compensated, into pair[m][p0 + pm][i][j] (pair: at the row panel's first reference member, rows of L J J doubles).
+__global__ void __launch_bounds__(SV_THREADS)
+k_scan_pair_merge(int64_t nchunks, int NB, int J, int MB, int rm, int64_t L, int64_t p0, int64_t pl, const double* __restrict__ part,
+                  double* __restrict__ pair) {
+    const int NCB = MB * J;
+    const int64_t stride = (int64_t)4 * NB * NCB * 256;
+    const int64_t x = (int64_t)blockIdx.x * SV_THREADS + threadIdx.x;
+    if (x >= (int64_t)rm * J * pl * J) return;
+    const int64_t pm = x % pl, j = (x / pl) % J, rho = x / (pl * J);
+    const int64_t m = rho / J, i = rho - m * J;
+    const int64_t blk = pm / 16, colm = pm % 16, wave = blk % 4, mb = blk / 4;
+    const int64_t I = rho / 16, row = rho % 16, r = row >> 2, lane = (row & 3) * 16 + colm;
+    const int64_t at = (((wave * NB + I) * NCB + mb * J + j) * 4 + r) * 64 + lane;
+    double s = 0.0, e = 0.0;
+    const double* p = part + at;
+    for (int64_t c = 0; c < nchunks; ++c, p += stride) scan_neumaier(s, e, *p);
+    pair[((m * L + p0 + pm) * J + i) * J + j] = s + e;
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
 // launch(the policies that travel as kernel arguments...): the family if it is harmonic, then the observable if it is the energy
 template <class Fam, class Obs, class F>
@@ -749,7 +943,52 @@ hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& 
     return hipGetLastError();
 }
 
-#define MBAR_SWEEPS(Cut, Fam, Obs)                                                                                                           \
+// ---- the member-member Gram block: nb = scan_pair_nb_for(rows left, J), rm <= scan_pair_rows(nb, J) reference members rows[0 .. rm)
+int scan_pair_nb_for(int64_t R, int J) { return R <= scan_pair_rows(2, J) ? 2 : 8; }
+
+int64_t scan_pair_record_doubles(int nb, int J, int MB) { return (int64_t)4 * nb * MB * J * 256; }
+
+template <class Fam>
+hipError_t launch_scan_pair(hipStream_t s, const ScanData& d, const Fam& fam, int nb, int64_t L, int64_t p0, const int64_t* rows, int rm,
+                            const double* coeff, const double* offset, const double* fnorm, double* part) {
+    const int64_t nchunks = (d.N + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    const int J = 1 + d.Q;
+    if (nchunks < 1 || p0 >= L) return hipSuccess;
+    if (nchunks > 0x7fffffff || J < 1 || J > 1 + SCAN_MAX_Q || (nb != 2 && nb != 8) || rm < 1 || rm > scan_pair_rows(nb, J))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nchunks);
+    const size_t lds = EXP_TABLE_BYTES + ((size_t)nb * 16 * SCAN_PITCH + 32 + (size_t)(SCAN_MAX_B + SCAN_MAX_Q) * 16 +
+                                          (size_t)scan_pair_rows(nb, J) * PAIR_RP) * sizeof(double);
+#define MBAR_CASE(NB_, J_)                                                                                                                   \
+    if (nb == NB_ && J == J_) {                                                                                                              \
+        if constexpr (Fam::harmonic)                                                                                                         \
+            hipLaunchKernelGGL((k_scan_pair<NB_, J_, Fam, Fam>), grid, dim3(256), lds, s, d, L, p0, rows, rm, coeff, offset, fnorm, part, fam); \
+        else                                                                                                                                 \
+            hipLaunchKernelGGL((k_scan_pair<NB_, J_, Fam>), grid, dim3(256), lds, s, d, L, p0, rows, rm, coeff, offset, fnorm, part);        \
+        return hipGetLastError();                                                                                                            \
+    }
+    MBAR_CASE(2, 1) MBAR_CASE(2, 2) MBAR_CASE(2, 3) MBAR_CASE(2, 4) MBAR_CASE(8, 1) MBAR_CASE(8, 2) MBAR_CASE(8, 3) MBAR_CASE(8, 4)
+#undef MBAR_CASE
+    return hipErrorInvalidValue;
+}
+template hipError_t launch_scan_pair<ScanLinear>(hipStream_t, const ScanData&, const ScanLinear&, int, int64_t, int64_t, const int64_t*, int,
+                                                 const double*, const double*, const double*, double*);
+template hipError_t launch_scan_pair<ScanHarmonic>(hipStream_t, const ScanData&, const ScanHarmonic&, int, int64_t, int64_t, const int64_t*, int,
+                                                   const double*, const double*, const double*, double*);
+
+hipError_t launch_scan_pair_merge(hipStream_t s, const ScanData& d, int nb, int mb, int64_t L, int64_t p0, int rm, const double* part,
+                                  double* pair) {
+    if (p0 >= L || d.N < 1) return hipSuccess;
+    const int J = 1 + d.Q;
+    const int64_t pl = L - p0 < 64 * mb ? L - p0 : 64 * mb;
+    const int64_t blocks = ((int64_t)rm * J * pl * J + SV_THREADS - 1) / SV_THREADS;
+    if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scan_pair_merge, dim3((unsigned)blocks), dim3(SV_THREADS), 0, s, (d.N + SCAN_CHUNK - 1) / SCAN_CHUNK, nb, J, mb, rm, L, p0, pl,
+                       part, pair);
+    return hipGetLastError();
+}
+
+#define MBAR_SWEEPS(Cut, Fam, Obs)                                                                                                         \
     template hipError_t launch_scan_vec<Cut, Fam, Obs>(hipStream_t, const ScanData&, const Cut&, const Fam&, const Obs&, bool, int64_t,          \
                                                        const double*, const double*, const double*, double*);                                    \
     template hipError_t launch_scan_cross<Cut, Fam, Obs>(hipStream_t, const ScanData&, const Cut&, const Fam&, const Obs&, int, const double*,   \

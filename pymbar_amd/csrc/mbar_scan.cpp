@@ -391,6 +391,53 @@ int mbar_scan_gram_w(mbar_ctx* c, const double* f, int64_t L, const double* coef
     return whole_gram_w(c, "mbar_scan_gram_w", WholeObs{}, f, L, coeff, offset, f_scan, r, cross, within, refcol, wsum);
 }
 
+// The members' own Gram block for the reference members rows[R]: one launch and one merge per (row panel, member panel), the row
+// panels cut as scan_pair_nb_for says (a function of the reference members left and J alone), the member panels those of pass B.
+int mbar_scan_pair_gram(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan, int64_t R,
+                        const int64_t* rows, double* pair) {
+    bool ok = f && coeff && f_scan && rows && pair && L >= 1 && R >= 1;
+    for (int64_t r = 0; ok && r < R; ++r) ok = rows[r] >= 0 && rows[r] < L;
+    for (int64_t l = 0; ok && l < L; ++l) ok = std::isfinite(f_scan[l]);
+    int rc = scan_open(c, "mbar_scan_pair_gram", ok, false, L);
+    if (rc) return rc;
+    const int64_t B = c->scan_B;
+    const int J = 1 + (int)c->scan_Q;
+    const int mb = scan_mb_of<ScanStored>(c, J);
+    const int64_t pw = 64 * mb, nchunks = std::max<int64_t>((c->N + SCAN_CHUNK - 1) / SCAN_CHUNK, 1);
+    const size_t out_doubles = (size_t)R * (size_t)L * (size_t)(J * J);
+    bool done = false;
+    ScanData d;
+    // (the record of the widest row panel the call can meet; the reference members ride behind the other inputs in scan_in)
+    rc = scan_begin(c, f, L, coeff, offset, nullptr, 0, {{pair, out_doubles}},
+                    (size_t)nchunks * (size_t)scan_pair_record_doubles(scan_pair_nb_for(R, J), J, mb), out_doubles, &done, &d, (size_t)R);
+    if (rc || done) return rc;
+    const double* d_coeff = c->scan_in;
+    const double* d_off = d_coeff + L * B;
+    double* d_fscan = c->scan_in.p + L * (B + 1);
+    static_assert(sizeof(int64_t) == sizeof(double), "the reference members ride in scan_in");
+    int64_t* d_rows = reinterpret_cast<int64_t*>(c->scan_in.p + L * (B + 3));
+    double* d_pair = c->scan_out;
+    HIPCHK(c, hipMemcpyAsync(d_fscan, f_scan, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_rows, rows, (size_t)R * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedTimer timer(c, MBAR_TIMER_OTHER);
+        for (int64_t r0 = 0; r0 < R;) {  // row panels: the widest while more than a narrow one's reference members are left
+            const int nb = scan_pair_nb_for(R - r0, J);
+            const int rm = (int)std::min<int64_t>(R - r0, scan_pair_rows(nb, J));
+            for (int64_t p0 = 0; p0 < L; p0 += pw) {
+                if (c->scan_terms.mask)
+                    HIPCHK(c, launch_scan_pair(c->stream, d, harmonic_of(c), nb, L, p0, d_rows + r0, rm, d_coeff, d_off, d_fscan, c->scan_part));
+                else
+                    HIPCHK(c, launch_scan_pair(c->stream, d, ScanLinear{}, nb, L, p0, d_rows + r0, rm, d_coeff, d_off, d_fscan, c->scan_part));
+                HIPCHK(c, launch_scan_pair_merge(c->stream, d, nb, mb, L, p0, rm, c->scan_part, d_pair + r0 * L * J * J));
+            }
+            r0 += rm;
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(pair, d_pair, out_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return sync_stream(c);
+}
+
 int mbar_scan_energy_lognum(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_u,
                             int64_t J, double* lognum, double* mean) {
     return whole_lognum(c, "mbar_scan_energy_lognum", WholeObs{true, center_u, J}, f, L, coeff, offset, lognum, mean);

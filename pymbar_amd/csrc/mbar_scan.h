@@ -177,6 +177,20 @@ hipError_t launch_scan_cross(hipStream_t s, const ScanData& d, const Cut& cut, c
 template <class Cut, class Obs>
 hipError_t launch_scan_cross_merge(hipStream_t s, const ScanData& d, const Cut& cut, int nb, int mb, int64_t K, int64_t L, int64_t p0,
                                    const double* part, double* cross, double* vec);
+// The member-member Gram block (mbar_scan_pair_gram), whole cut, stored observables, either family:
+//   pair[r][l][i][j] = sum_n c_n (b_{rows[r]} n t_in)(b_ln t_jn)
+// One launch per (row panel, member panel): the row panel is the rm <= scan_pair_rows(nb, J) reference members rows[0 .. rm) (on the
+// device, indices into the call's L members) as 16 nb rows (member, i) of the LDS tile, nb = 2 or 8 (scan_pair_nb_for(reference
+// members left, J)); the member panel is [p0, p0 + 64 mb), mb = Fam::mb(J).  part[chunk][scan_pair_record_doubles(nb, J, mb)], then
+// the merge in chunk order into pair (at the row panel's first reference member: rows of L J J doubles).
+constexpr int scan_pair_rows(int nb, int J) { return 16 * nb / J; }
+int scan_pair_nb_for(int64_t R, int J);
+int64_t scan_pair_record_doubles(int nb, int J, int mb);
+template <class Fam>
+hipError_t launch_scan_pair(hipStream_t s, const ScanData& d, const Fam& fam, int nb, int64_t L, int64_t p0, const int64_t* rows, int rm,
+                            const double* coeff, const double* offset, const double* fnorm, double* part);
+hipError_t launch_scan_pair_merge(hipStream_t s, const ScanData& d, int nb, int mb, int64_t L, int64_t p0, int rm, const double* part,
+                                  double* pair);
 
 // ---- rows of the resident matrix from a family of states (mbar_k_family.hip; C ABI: mbar_ctx_fill_family_rows and ----------
 // ---- mbar_ctx_fill_linear_rows in mbar_rows.cpp) -----------------------------------------------------------------------------

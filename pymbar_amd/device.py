@@ -484,6 +484,32 @@ class DeviceMatrix(_ContextMatrix):
         ``wsum[l] = sum_n c_n b_ln``."""
         return self._scan_pass_b(f, coeff_lb, offset_l, f_scan, reference, cross, center_lb)
 
+    SCAN_PAIR_BYTES = 1 << 28  # the pair block of one slab of reference members of scan_pair_gram stays under this
+
+    def scan_pair_gram(self, f, coeff_lb, offset_l, f_scan, rows, center_lb=None, slab=None):
+        """The members' own Gram block (``mbar_scan_pair_gram``): ``pair[r, l, i, j] = sum_n c_n (b_rows[r] n t_in)(b_ln t_jn)``, ``R x L
+        x J x J``, for the reference members ``rows`` (``R`` indices into the ``L`` members) with ``b`` as in :meth:`scan_gram_w`:
+        ``pair[r, :, 0, :]`` is the ``refcol`` of ``scan_gram_w(reference=rows[r])``.  The reference members go to the device in slabs
+        (of ``slab`` of them; by default as many as keep a slab's block under 256 MiB): an entry's bits do not depend on the cut."""
+        f = self._f(f)
+        coeff_lb, offset_l, L, J = self._scan_members(coeff_lb, offset_l)
+        f_scan = _lib.f64(f_scan, (L,), "f_scan")
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or rows.size < 1 or rows.dtype.kind not in "iu" or rows.min() < 0 or rows.max() >= L:
+            raise ValueError("rows must be a 1-D integer array of at least one member index in [0, L)")
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        R = rows.shape[0]
+        if slab is None:
+            slab = self.SCAN_PAIR_BYTES // (8 * L * J * J)
+        slab = max(1, min(int(slab), R))
+        self._scan_centers(center_lb, L)
+        pair = np.empty((R, L, J, J), dtype=np.float64)
+        for r0 in range(0, R, slab):
+            r1 = min(R, r0 + slab)
+            self._check(self._lib.mbar_scan_pair_gram(self._ctx, _dptr(f), L, _dptr(coeff_lb), _dptr(offset_l), _dptr(f_scan), r1 - r0,
+                                                      _dptr(rows[r0:r1], _lib._ip), _dptr(pair[r0:r1])))
+        return pair
+
     def scan_energy_lognum(self, f, coeff_lb, offset_l=None, center_u=None, J=3, center_lb=None):
         """Pass A with the member's own reduced potential as the observable (``mbar_scan_energy_lognum``): ``(lognum, mean)`` as
         :meth:`scan_lognum` with ``t_1 = u_l(n) - center_u[l]``, ``t_2 = t_1^2`` (``L x J``, ``J`` 2 or 3; ``center_u`` None: zeros).

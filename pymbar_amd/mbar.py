@@ -662,6 +662,7 @@ class MBAR:
     compute_scan_fes = _scan.compute_scan_fes
     compute_scan_entropy_and_enthalpy = _scan.compute_scan_entropy_and_enthalpy
     compute_scan_gradient = _scan.compute_scan_gradient
+    compute_scan_pairs = _scan.compute_scan_pairs
 
     def _computeUnnormalizedLogWeights(self, u_n):
         """``-ln sum_k N_k exp(f_k - (u_k(x_n) - u(x_n)))`` for one target potential ``u_n`` (mbar.py:1919-1934):

@@ -232,6 +232,149 @@ def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, r
     return out
 
 
+# ---- differences between any two members of a scan --------------------------------------------------------------------------------
+def _pairs_matrix(mbar):
+    dm = _scan_matrix(mbar)
+    if not hasattr(dm, "scan_pair_gram"):
+        raise ParameterError(f"differences between the members of a scan need the pair pass of a single-rank device matrix and are {_NOT_HERE} for this handle")
+    return dm
+
+
+def _reference_members(reference_members, L):
+    if reference_members is None:
+        return np.arange(L, dtype=np.int64)
+    members = np.asarray(reference_members)
+    if members.ndim != 1 or members.size < 1 or members.dtype.kind not in "iu":
+        raise ParameterError("reference_members must be None or a 1-D integer array of at least one member index")
+    members = members.astype(np.int64)
+    if members.min() < 0 or members.max() >= L or len(np.unique(members)) != len(members):
+        raise ParameterError("reference_members must be distinct indices of members of the family")
+    return members
+
+
+def _pairs_analytical(mbar, dm, coeff_lb, offset_l, f, mean, members, approximate, warning_cutoff, cen={}):
+    """``(cov_f, dDelta_f, cov_mu, dDelta_mu)`` of DESIGN.md section 23: ``Theta(z_ri, z_lj) = z_ri . z_lj + y(z_ri)^T diag(g) y(z_lj)``
+    with ``z_l0 = b_l``, ``z_lq = b_l t_q / mean_lq``; the ``z . z'`` of two different members come from the pair block, a member's own
+    from ``within`` as in :func:`_analytical`, the border from the one cross block.  Every entry is formed element by element, the
+    eigen-directions summed in ascending order."""
+    L, J = mean.shape
+    R = len(members)
+    cross, within, _, wsum = dm.scan_gram_w(mbar.f_k, coeff_lb, offset_l, f, reference=int(members[0]), cross=not approximate, **cen)
+    check_w_sums(wsum, 0.0)
+    pair = dm.scan_pair_gram(mbar.f_k, coeff_lb, offset_l, f, members, **cen)
+    y = g = None
+    if not approximate:
+        y, g = _border(mbar, cross)
+    scale = np.ones((J, L))  # z_lj = b_l t_j / scale[j, l]
+    scale[1:] = mean[:, 1:].T
+
+    def theta(i, j):
+        """``Theta(z_ri, z_lj)``, ``(R, L)``"""
+        si, sj = scale[i][members], scale[j]
+        out = pair[:, :, i, j] / (si[:, None] * sj[None, :])
+        if y is not None:
+            out = out + _qform(g, (y[:, members, i] / si[None, :])[:, :, None], (y[:, :, j] / sj[None, :])[:, None, :])
+        return out
+
+    def own(i, j):
+        """``Theta(z_li, z_lj)`` of every member with itself, ``(L,)``"""
+        out = within[:, i, j] / (scale[i] * scale[j])
+        if y is not None:
+            out = out + _qform(g, y[:, :, i] / scale[i][None, :], y[:, :, j] / scale[j][None, :])
+        return out
+
+    at_self = (np.arange(R), members)
+    t00, d00 = theta(0, 0), own(0, 0)
+    d2 = (d00[None, :] + d00[members][:, None]) - 2.0 * t00
+    d2[at_self] = 0.0
+    cov_mu = np.zeros((J - 1, R, L))
+    dmu = np.zeros((J - 1, R, L))
+    for q in range(1, J):
+        m = mean[:, q]
+        var = (m * m) * (own(q, q) + d00 - 2.0 * own(0, q))
+        cov_mu[q - 1] = (m[members][:, None] * m[None, :]) * (theta(q, q) - theta(q, 0) - theta(0, q) + t00)
+        dq2 = (var[None, :] + var[members][:, None]) - 2.0 * cov_mu[q - 1]
+        dq2[at_self] = 0.0
+        dmu[q - 1] = _sqrt_small_negative_zeroed(dq2, warning_cutoff)
+    return t00, _sqrt_small_negative_zeroed(d2, warning_cutoff), cov_mu, dmu
+
+
+def _std_of_differences(x_bl, members):
+    """``std`` over the replicates of ``x[b, l] - x[b, members[r]]``: ``(R, L)`` (the rule of the reference's
+    ``compute_free_energy_differences`` and ``compute_expectations(output="differences")``)."""
+    return np.std(x_bl[:, None, :] - x_bl[:, members][:, :, None], axis=0)
+
+
+def compute_scan_pairs(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, reference_members=None, compute_uncertainty=True,
+                       uncertainty_method=None, warning_cutoff=1.0e-10, center_lb=None, harmonic_b=None, period_b=None):
+    """Differences between ANY two members of a scan, and their uncertainties: the rows ``reference_members`` of the full ``L x L``
+    matrices ``compute_perturbed_free_energies(u_ln)`` and ``compute_expectations(A, u_kn=u_ln, state_dependent=False,
+    output="differences")`` return for the dense ``u_ln`` -- the uncertainty of ``f(T_1) - f(T_2)`` between two arbitrary grid points, of
+    a finite difference along the grid, of ``Delta f`` between adjacent members.
+
+    The family (``basis_bn``, ``coeff_lb``, ``offset_l``, ``center_lb``, ``harmonic_b``, ``period_b``), ``A_qn``, the limits and the errors
+    are those of :func:`compute_scan`.  ``reference_members``: None (all ``L`` members) or a 1-D integer array of ``R`` distinct member
+    indices.  Returns a dict, ``r`` running over ``reference_members``: ``f`` ``(L,)`` and with observables ``mu`` ``(Q, L)`` (the bits
+    of :func:`compute_scan`); ``members`` ``(R,)``; ``Delta_f[r, l] = f[l] - f[members[r]]`` (the reference's sign); ``cov_f[r, l]``,
+    the covariance of ``-f`` of the two members, and ``dDelta_f[r, l] = sqrt(cov_f[r, r'] + cov_f[l, l] - 2 cov_f[r, l])`` with both
+    diagonal entries the members' own (exactly 0 for a member with itself); with observables ``Delta_mu``, ``cov_mu``, ``dDelta_mu``
+    ``(Q, R, L)`` likewise for ``<A_q>``.  The members' products come from one pass of the device that generates both operands of the
+    Gram block from the ``B`` numbers per sample (``DeviceMatrix.scan_pair_gram``) instead of one pass B per reference member.
+
+    ``uncertainty_method``: None / "svd-ew" (the bordered form), "approximate" (``Theta = z . z'``), "bootstrap" (the ``std`` over the
+    replicates of the differences; adds ``bootstrapped_f`` and ``bootstrapped_observables`` as :func:`compute_scan` does; no ``cov_f`` /
+    ``cov_mu``); "svd" is not offered."""
+    basis_given = basis_bn
+    if uncertainty_method == "svd":
+        raise ParameterError("uncertainty_method 'svd' needs the weight matrix itself and is not offered for scans")
+    if uncertainty_method not in (None, "svd-ew", "approximate", "bootstrap"):
+        raise ParameterError(f"Method {uncertainty_method} unrecognized.")
+    bootstrap = uncertainty_method == "bootstrap"
+    if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
+        raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
+    basis_bn, coeff_lb, offset_l, A_qn, L = _check_inputs(mbar, _family_basis(mbar, basis_bn, coeff_lb), coeff_lb, offset_l, A_qn, 0)
+    members = _reference_members(reference_members, L)
+    kinds, cen = _family_kinds(mbar, basis_given, basis_bn.shape[0], L, center_lb, harmonic_b, period_b)
+    dm = _pairs_matrix(mbar)
+    Q = len(A_qn)
+    t_qn, shift = _shifted(A_qn)
+    dm.set_Nk(mbar.N_k)
+    dm.set_scan(basis_bn, t_qn, **kinds)
+    try:
+        lognum, mean = dm.scan_lognum(mbar.f_k, coeff_lb, offset_l, **cen)
+        f = -lognum
+        out = dict(f=f, members=members, Delta_f=f[None, :] - f[members][:, None])
+        if Q:
+            mu = mean[:, 1:].T + shift[:, None]
+            out["mu"] = mu
+            out["Delta_mu"] = mu[:, None, :] - mu[:, members][:, :, None]
+        if bootstrap:
+            fb = np.zeros((mbar.n_bootstraps, L))
+            Ab = np.zeros((mbar.n_bootstraps, Q, L))
+            try:
+                for b in range(mbar.n_bootstraps):
+                    mbar._set_bootstrap_weights(dm, b)
+                    ln_b, mean_b = dm.scan_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l, **cen)
+                    fb[b] = -ln_b
+                    Ab[b] = mean_b[:, 1:].T + shift[:, None]
+            finally:
+                dm.set_sample_weights(None)
+            out["bootstrapped_f"], out["bootstrapped_observables"] = fb, Ab
+            if compute_uncertainty:
+                out["dDelta_f"] = _std_of_differences(fb, members)
+                if Q:
+                    out["dDelta_mu"] = np.stack([_std_of_differences(Ab[:, q, :], members) for q in range(Q)])
+        elif compute_uncertainty:
+            cov_f, ddf, cov_mu, dmu = _pairs_analytical(mbar, dm, coeff_lb, offset_l, f, mean, members, uncertainty_method == "approximate",
+                                                        warning_cutoff, cen)
+            out["cov_f"], out["dDelta_f"] = cov_f, ddf
+            if Q:
+                out["cov_mu"], out["dDelta_mu"] = cov_mu, dmu
+    finally:
+        dm.set_scan(None)
+    return out
+
+
 # ---- entropy, enthalpy and heat capacity along a scan -----------------------------------------------------------------------------
 def _thermo_matrix(mbar):
     dm = _scan_matrix(mbar)
