@@ -447,6 +447,34 @@ int mbar_scan_pair_gram(mbar_ctx* ctx, const double* f, int64_t L, const double*
 int mbar_scan_moments(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* center_phi,
                       double* lognum, double* mean, double* m1, double* m2, double* ma);
 
+/* MANY observables along a scan (MBAR.compute_scan_expectations): a fit against hundreds of experimental numbers, a distribution
+ * function with one observable per bin.  The observables are kept on the context, apart from the Q <= MBAR_SCAN_MAX_Q ones of
+ * mbar_ctx_set_scan, and the sums are an (L x N)(N x Q) product on the fp64 matrix cores: the member operand is generated in
+ * registers as in mbar_scan_gram_w, against tiles of 16 samples x up to 128 observables in LDS, so one member exponential serves
+ * up to 128 observables.
+ *   mbar_ctx_set_scan_obs   uploads Q >= 1 rows of N doubles (host rows of pitch ld_host >= N) into a block the context owns, at the
+ *                           device pitch of the basis; the limit on Q is memory.  Q = 0 releases the block.  The block does not
+ *                           depend on mbar_ctx_set_scan: it survives a change of basis, term kinds, centres and sample weights, and
+ *                           is dropped at destroy or when replaced.  MBAR_ERR_ARG: a NULL pointer with Q > 0, Q < 0, ld_host < N, a
+ *                           non-finite entry (the block on the context is left as it was).
+ *   mbar_scan_obs_sums      on the family currently set (mbar_ctx_set_scan / mbar_ctx_set_scan_terms / mbar_ctx_set_scan_centers), with
+ *                           b_ln = exp(f_scan[l] + x_ln) formed by the operations mbar_scan_gram_w uses for a member column, c_n the
+ *                           multiplicities and a_qn the stored rows:
+ *                             s1[l][q] = sum_n c_n b_ln a_qn          t1[l][q] = sum_n c_n b_ln^2 a_qn       (L x Q, row-major)
+ *                             t2[l][q] = sum_n c_n b_ln^2 a_qn^2      wsum[l] = sum_n c_n b_ln               w2sum[l] = sum_n c_n b_ln^2
+ *                           t1, t2 and w2sum are all NULL (only the first-moment launches run) or all non-NULL (else MBAR_ERR_ARG).
+ * The members are taken in the panels of mbar_scan_gram_w, the observables in panels of 128 (the last one of 16, 32, 64 or 128
+ * rows); one launch per pair of panels costs (members of the panel) x N exponentials and 2 x members x observables x N flop per
+ * sum.  The resident matrix is read only through logden_n(f), and nothing of size L x N exists.  No floating-point atomics; chunks
+ * of 8192 samples cut by N alone and merged in chunk order, compensated: two identical calls return identical bits, and element
+ * (l, q) does not depend on L, Q, the other members or observables, where member l sits in the call or where row q sits among the
+ * stored rows; s1 and wsum are the same bits with and without the second moments.  A NaN in f or f_scan fills the outputs with
+ * NaN (MBAR_OK).  Limits, state and argument errors are those of mbar_scan_gram_w; MBAR_ERR_STATE also when no observables are set.
+ * Kernel time: MBAR_TIMER_OTHER. */
+int mbar_ctx_set_scan_obs(mbar_ctx* ctx, int64_t Q, const double* a_host, int64_t ld_host);
+int mbar_scan_obs_sums(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan,
+                       double* s1, double* t1, double* t2, double* wsum, double* w2sum);
+
 /* ---- histogram surfaces along a scan ---------------------------------------------------------
  * The histogram free energy surface of EVERY member of a scan: the bins are labels of the resident samples as in "histogram bins
  * by label", the target states are the members of the family uploaded by mbar_ctx_set_scan (with Q = 0).  Nothing of size L x N is

@@ -142,6 +142,8 @@ SIGNATURES = {
     "mbar_scan_energy_gram_w": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, C.c_int64, _dp, _dp, _dp, _dp]),
     "mbar_scan_pair_gram": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _ip, _dp]),
     "mbar_scan_moments": (C.c_int,[_ctx, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbar_ctx_set_scan_obs": (C.c_int, [_ctx, C.c_int64, _dp, C.c_int64]),
+    "mbar_scan_obs_sums": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbar_ctx_set_scan_terms": (C.c_int, [_ctx, C.POINTER(C.c_int32), _dp]),
     "mbar_ctx_set_scan_centers": (C.c_int, [_ctx, C.c_int64, _dp]),
     "mbar_ctx_set_scan_bins": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int32)]),

@@ -59,6 +59,10 @@
 // The members' own Gram block (MBAR.compute_scan_pairs, mbar_scan_pair_gram): pass B once more with the rows
 // of the LDS tile being (reference member, i) instead of sampled states, pair[r][l][i][j] = sum_n c_n (b_rn t_in)(b_ln t_jn), in a
 // sweep and a merge of its own (k_scan_pair, k_scan_pair_merge) behind the merge of pass B; whole cut, stored observables.
+//
+// Many observables (MBAR.compute_scan_expectations, mbar_scan_obs_sums): pass B a third time, the rows of the LDS
+// tile being observables the context keeps resident (any number of them, in panels of 128), s1[l][q] = sum_n c_n b_ln a_qn and its
+// two second-moment companions, in a sweep and a merge of its own (k_scan_obs, k_scan_obs_merge); whole cut.
 #include "mbar_device.h"
 #include "mbar_scan_device.h"
 
@@ -786,6 +790,191 @@ k_scan_pair_merge(int64_t nchunks, int NB, int J, int MB, int rm, int64_t L, int
     pair[((m * L + p0 + pm) * J + i) * J + j] = s + e;
 }
 
+// ---- many observables along a scan (mbar_scan_obs_sums) ------------------------------------------------------
+//   MODE 0   s1[l][q] = sum_n c_n b_ln a_qn                                              tile a,   z = (c b)
+//   MODE 1   s1 and t1[l][q] = sum_n c_n b_ln^2 a_qn                                     tile a,   z = (c b, c b b)
+//   MODE 2   t2[l][q] = sum_n c_n b_ln^2 a_qn^2                                          tile a a, z = (c b b)
+// k_scan_cross with the rows of the LDS tile being stored observables instead of sampled states: one workgroup owns one chunk, one
+// panel of 64 MB members (MB = Fam::mb(J), J = 2 in mode 1 and 1 otherwise) and one panel of nq <= 16 NB observables, the rows of a
+// (pitch d.ldv).  The fill stage loads the tile as it lies in memory (thread tid: row 16 I + (tid >> 4), position tid & 15) with exact
+// zeros where c_n <= 0, past nq and past the chunk; the product stage is k_scan_cross's, b formed by the same operations.  wsum =
+// sum c b and w2sum = sum c b b are lane-local as there (one addition, one fma per position) and written by every workgroup; the host
+// merges those of the first observable panel.  An element's operations depend neither on the row it has in the tile nor on NB, the
+// member's column or MB; s1 is the same instruction sequence in modes 0 and 1.  The record is the cross part of k_scan_cross's,
+// [wave][I < NB][cb < NCB][r < 4][lane], then [pm < 64 MB][wsum | w2sum].
+constexpr int SCANOBS_NV = 2;
+
+template <int NB, int MODE, class Fam, class... Arg>
+__global__ void __launch_bounds__(256)
+k_scan_obs(ScanData d, const double* __restrict__ a, int nq, int64_t L, int64_t p0, const double* __restrict__ coeff,
+           const double* __restrict__ offset, const double* __restrict__ fnorm, double* __restrict__ part, Arg... arg) {
+    const Fam fam = scan_arg<Fam>(arg...);
+    const ScanWhole cut{};
+    constexpr int J = MODE == 1 ? 2 : 1, MB = Fam::mb(J), NCB = MB * J, NV = SCANOBS_NV;
+    static_assert(NB * NCB <= 32, "at most 32 accumulator blocks per wave");
+    constexpr int SVB = 32;  // where the basis rows start in sv
+    constexpr int W_DOUBLES = NB * 16 * SCAN_PITCH;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    exp_table_init(smem);
+    double* Wt = reinterpret_cast<double*>(smem + EXP_TABLE_BYTES);  // [16 NB][SCAN_PITCH]
+    double* sv = Wt + W_DOUBLES;                                     // cn[16] | lden[16] | basis[B][16]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, q4 = lane >> 4;
+    int64_t bin, q0c, q1c;
+    cut.range(blockIdx.x, d.N, SCAN_CHUNK, bin, q0c, q1c);
+    const int64_t pl = L - p0 < 64 * MB ? L - p0 : 64 * MB;  // members of the panel
+    const int nblk = (int)((pl + 15) / 16);
+    int mine = 0;
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) mine += (mb * 4 + wave) < nblk;
+    mine = __builtin_amdgcn_readfirstlane(mine);
+
+    double cf[MB][SCAN_MAX_B], off[MB], fs[MB];
+    double cen[Fam::harmonic ? MB : 1][SCAN_MAX_H];
+    bool mlive[MB];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+        const int64_t pm = (int64_t)(mb * 4 + wave) * 16 + col;
+        mlive[mb] = pm < pl;
+        const int64_t l = p0 + pm;
+#pragma unroll
+        for (int b = 0; b < SCAN_MAX_B; ++b) cf[mb][b] = (mlive[mb] && b < d.B) ? coeff[l * d.B + b] : 0.0;
+        off[mb] = mlive[mb] ? offset[l] : 0.0;
+        if constexpr (Fam::harmonic) family_load_centers(fam, mlive[mb], l, cen[mb]);
+        fs[mb] = mlive[mb] ? fnorm[l] : 0.0;
+    }
+    const int fs_s = tid & 15, fs_r = tid >> 4;
+
+    v4d acc[NB * NCB];
+#pragma unroll
+    for (int i = 0; i < NB * NCB; ++i) acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
+    double vs[MB][NV];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) vs[mb][v] = 0.0;
+
+    __syncthreads();  // the exp table
+    for (int64_t q0 = q0c; q0 < q1c; q0 += 16) {
+        // ---- fill: the observable tile and the per-sample values of the tile
+        {
+            const int64_t q = q0 + fs_s;
+            int64_t n = 0;
+            double cn = 0.0, lden = 0.0;
+            if (q < q1c) {
+                n = q;
+                cn = d.cw ? d.cw[n] : 1.0;
+                if (cn > 0.0) lden = d.logden[n];
+                else cn = 0.0;
+            }
+            const bool slive = cn > 0.0;
+#pragma unroll
+            for (int I = 0; I < NB; ++I) {
+                const int row = 16 * I + fs_r;
+                double v = 0.0;
+                if (slive && row < nq) {
+                    v = a[(int64_t)row * d.ldv + n];
+                    if constexpr (MODE == 2) v = v * v;
+                }
+                Wt[row * SCAN_PITCH + fs_s] = v;
+            }
+            if (tid < 16) {
+                sv[fs_s] = cn;
+                sv[16 + fs_s] = lden;
+            }
+            if (fs_r < d.B) sv[SVB + fs_r * 16 + fs_s] = slive ? d.basis[(int64_t)fs_r * d.ldv + n] : 0.0;
+        }
+        __syncthreads();
+        // ---- products: four groups of four positions
+        if (mine > 0) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int s = 4 * g + q4;
+                double at[NB];
+#pragma unroll
+                for (int I = 0; I < NB; ++I) at[I] = Wt[(16 * I + col) * SCAN_PITCH + s];
+                const double cn = sv[s], lden = sv[16 + s];
+                double bas[SCAN_MAX_B];
+#pragma unroll
+                for (int b = 0; b < SCAN_MAX_B; ++b) bas[b] = b < d.B ? sv[SVB + b * 16 + s] : 0.0;
+#pragma unroll
+                for (int mb = 0; mb < MB; ++mb) {
+                    if (mb < mine) {  // (wave-uniform)
+                        double uu = off[mb];
+#pragma unroll
+                        for (int b = 0; b < SCAN_MAX_B; ++b)
+                            if (b < d.B) uu = family_term(fam, b, uu, cf[mb][b], bas[b], family_center(fam, b, cen[Fam::harmonic ? mb : 0]));
+                        double bv = scan_exp(fs[mb] + (-uu - lden));
+                        if (!(cn > 0.0) || !mlive[mb]) bv = 0.0;
+                        const double cb = cn * bv;
+                        double z[J];
+                        z[0] = MODE == 2 ? cb * bv : cb;
+                        if constexpr (MODE == 1) z[1] = cb * bv;
+                        vs[mb][0] += cb;
+                        vs[mb][1] = fma(bv, cb, vs[mb][1]);
+#pragma unroll
+                        for (int I = 0; I < NB; ++I)
+#pragma unroll
+                            for (int j = 0; j < J; ++j)
+                                acc[I * NCB + mb * J + j] = __builtin_amdgcn_mfma_f64_16x16x4f64(at[I], z[j], acc[I * NCB + mb * J + j], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // ---- the record
+    constexpr int64_t CROSS_DOUBLES = (int64_t)4 * NB * NCB * 256;
+    double* rec = part + (int64_t)blockIdx.x * (CROSS_DOUBLES + (int64_t)64 * MB * NV);
+#pragma unroll
+    for (int i = 0; i < NB * NCB; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rec[(((int64_t)wave * NB * NCB + i) * 4 + r) * 64 + lane] = acc[i][r];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            double x = vs[mb][v];
+            x += __shfl_xor(x, 16);
+            x += __shfl_xor(x, 32);
+            if (lane < 16) rec[CROSS_DOUBLES + ((int64_t)(mb * 4 + wave) * 16 + lane) * NV + v] = x;
+        }
+}
+
+// The chunk records of one (member panel, observable panel) added in chunk order, compensated.  Threads [0, pl J nq): column j of
+// member p0 + pm and observable qb + qi into out0 (j = 0) or out1 (j = 1), L x Q row-major; threads behind them, [0, pl NV): wsum
+// into vec0[p0 + pm], w2sum into vec1 (a NULL destination: nobody wants it).
+__global__ void __launch_bounds__(SV_THREADS)
+k_scan_obs_merge(int64_t nchunks, int NB, int J, int MB, int64_t Q, int64_t p0, int64_t pl, int64_t qb, int64_t nq,
+                 const double* __restrict__ part, double* __restrict__ out0, double* __restrict__ out1, double* __restrict__ vec0,
+                 double* __restrict__ vec1) {
+    const int NCB = MB * J;
+    const int64_t cross_doubles = (int64_t)4 * NB * NCB * 256, stride = cross_doubles + (int64_t)64 * MB * SCANOBS_NV;
+    int64_t x = (int64_t)blockIdx.x * SV_THREADS + threadIdx.x;
+    int64_t at;
+    double* out;
+    if (x < pl * J * nq) {
+        const int64_t pm = x % pl, j = (x / pl) % J, qi = x / (pl * J);
+        const int64_t blk = pm / 16, colm = pm % 16, wave = blk % 4, mb = blk / 4;
+        const int64_t I = qi / 16, row = qi % 16, r = row >> 2, lane = (row & 3) * 16 + colm;
+        at = (((wave * NB + I) * NCB + mb * J + j) * 4 + r) * 64 + lane;
+        out = (j == 0 ? out0 : out1) + (p0 + pm) * Q + qb + qi;
+    } else {
+        x -= pl * J * nq;
+        if (x >= pl * SCANOBS_NV) return;
+        const int64_t pm = x % pl, v = x / pl;
+        double* dst = v == 0 ? vec0 : vec1;
+        if (!dst) return;
+        at = cross_doubles + pm * SCANOBS_NV + v;
+        out = dst + p0 + pm;
+    }
+    double s = 0.0, e = 0.0;
+    const double* r = part + at;
+    for (int64_t c = 0; c < nchunks; ++c, r += stride) scan_neumaier(s, e, *r);
+    *out = s + e;
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
 // launch(the policies that travel as kernel arguments...): the family if it is harmonic, then the observable if it is the energy
 template <class Fam, class Obs, class F>
@@ -988,7 +1177,51 @@ hipError_t launch_scan_pair_merge(hipStream_t s, const ScanData& d, int nb, int 
     return hipGetLastError();
 }
 
-#define MBAR_SWEEPS(Cut, Fam, Obs)                                                                                                         \
+// ---- many observables along a scan: nb = scan_nb_for(nq) blocks of 16 observables, mode 0, 1 or 2 (k_scan_obs)
+int scan_obs_columns(int mode) { return mode == 1 ? 2 : 1; }
+
+int64_t scan_obs_record_doubles(int nb, int J, int MB) { return (int64_t)4 * nb * MB * J * 256 + (int64_t)64 * MB * SCANOBS_NV; }
+
+template <class Fam>
+hipError_t launch_scan_obs(hipStream_t s, const ScanData& d, const Fam& fam, int nb, int mode, const double* a, int64_t nq, int64_t L,
+                           int64_t p0, const double* coeff, const double* offset, const double* fnorm, double* part) {
+    const int64_t nchunks = (d.N + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    if (nchunks < 1 || p0 >= L) return hipSuccess;
+    if (nchunks > 0x7fffffff || nq < 1 || nq > 16 * (int64_t)nb || d.B < 1 || d.B > SCAN_MAX_B) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nchunks);
+    const size_t lds = EXP_TABLE_BYTES + ((size_t)nb * 16 * SCAN_PITCH + 32 + (size_t)SCAN_MAX_B * 16) * sizeof(double);
+#define MBAR_CASE(NB_, MODE_)                                                                                                              \
+    if (nb == NB_ && mode == MODE_) {                                                                                                      \
+        if constexpr (Fam::harmonic)                                                                                                       \
+            hipLaunchKernelGGL((k_scan_obs<NB_, MODE_, Fam, Fam>), grid, dim3(256), lds, s, d, a, (int)nq, L, p0, coeff, offset, fnorm, part, fam); \
+        else                                                                                                                               \
+            hipLaunchKernelGGL((k_scan_obs<NB_, MODE_, Fam>), grid, dim3(256), lds, s, d, a, (int)nq, L, p0, coeff, offset, fnorm, part);  \
+        return hipGetLastError();                                                                                                          \
+    }
+#define MBAR_MODES(NB_) MBAR_CASE(NB_, 0) MBAR_CASE(NB_, 1) MBAR_CASE(NB_, 2)
+    MBAR_MODES(1) MBAR_MODES(2) MBAR_MODES(4) MBAR_MODES(8)
+#undef MBAR_MODES
+#undef MBAR_CASE
+    return hipErrorInvalidValue;
+}
+template hipError_t launch_scan_obs<ScanLinear>(hipStream_t, const ScanData&, const ScanLinear&, int, int, const double*, int64_t, int64_t,
+                                                int64_t, const double*, const double*, const double*, double*);
+template hipError_t launch_scan_obs<ScanHarmonic>(hipStream_t, const ScanData&, const ScanHarmonic&, int, int, const double*, int64_t, int64_t,
+                                                  int64_t, const double*, const double*, const double*, double*);
+
+hipError_t launch_scan_obs_merge(hipStream_t s, const ScanData& d, int nb, int mode, int mb, int64_t L, int64_t Q, int64_t p0, int64_t qb,
+                                 int64_t nq, const double* part, double* out0, double* out1, double* vec0, double* vec1) {
+    if (p0 >= L || d.N < 1) return hipSuccess;
+    const int J = scan_obs_columns(mode);
+    const int64_t pl = L - p0 < 64 * mb ? L - p0 : 64 * mb;
+    const int64_t blocks = (pl * J * nq + pl * SCANOBS_NV + SV_THREADS - 1) / SV_THREADS;
+    if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scan_obs_merge, dim3((unsigned)blocks), dim3(SV_THREADS), 0, s, (d.N + SCAN_CHUNK - 1) / SCAN_CHUNK, nb, J, mb, Q, p0, pl,
+                       qb, nq, part, out0, out1, vec0, vec1);
+    return hipGetLastError();
+}
+
+#define MBAR_SWEEPS(Cut, Fam, Obs)                                                                                                      \
     template hipError_t launch_scan_vec<Cut, Fam, Obs>(hipStream_t, const ScanData&, const Cut&, const Fam&, const Obs&, bool, int64_t,          \
                                                        const double*, const double*, const double*, double*);                                    \
     template hipError_t launch_scan_cross<Cut, Fam, Obs>(hipStream_t, const ScanData&, const Cut&, const Fam&, const Obs&, int, const double*,   \

@@ -505,6 +505,97 @@ int mbar_scan_moments(mbar_ctx* c, const double* f, int64_t L, const double* coe
     return MBAR_OK;
 }
 
+// ---- many observables along a scan ----
+
+int mbar_ctx_set_scan_obs(mbar_ctx* c, int64_t Q, const double* a_host, int64_t ld_host) {
+    const char* who = "mbar_ctx_set_scan_obs";
+    int rc = scan_ready(c, who);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (Q == 0) {
+        c->scan_obs_Q = 0;
+        c->scan_obs.reset();
+        return MBAR_OK;
+    }
+    const int64_t N = c->N, ld = c->ld;
+    if (Q < 0 || !a_host || ld_host < N) return fail(c, MBAR_ERR_ARG, std::string(who) + ": Q >= 0 rows of N doubles at a pitch of at least N");
+    for (int64_t q = 0; q < Q; ++q)
+        for (int64_t n = 0; n < N; ++n)
+            if (!std::isfinite(a_host[q * ld_host + n])) return fail(c, MBAR_ERR_ARG, std::string(who) + ": the observables must be finite");
+    c->scan_obs_Q = 0;
+    HIPCHK(c, c->scan_obs.grow((size_t)Q * (size_t)ld));
+    HIPCHK(c, hipMemset(c->scan_obs, 0, (size_t)Q * (size_t)ld * sizeof(double)));
+    HIPCHK(c, hipMemcpy2D(c->scan_obs, (size_t)ld * sizeof(double), a_host, (size_t)ld_host * sizeof(double), (size_t)N * sizeof(double), (size_t)Q,
+                          hipMemcpyHostToDevice));
+    c->scan_obs_Q = Q;
+    return MBAR_OK;
+}
+
+// One launch and one merge per (mode, member panel, observable panel): the member panels are those of pass B at the mode's operand
+// columns, the observable panels 128 rows (the last one the narrowest instantiation that holds it).
+int mbar_scan_obs_sums(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan, double* s1,
+                       double* t1, double* t2, double* wsum, double* w2sum) {
+    const char* who = "mbar_scan_obs_sums";
+    const bool second = t1 || t2 || w2sum;
+    int rc = scan_open(c, who, f && coeff && f_scan && s1 && wsum && L >= 1 && (!second || (t1 && t2 && w2sum)), false, L);
+    if (rc) return rc;
+    if (c->scan_obs_Q < 1) return fail(c, MBAR_ERR_STATE, std::string(who) + ": no observables on this context (mbar_ctx_set_scan_obs first)");
+    const int64_t B = c->scan_B, Q = c->scan_obs_Q, ld = c->ld;
+    const size_t LQ = (size_t)L * (size_t)Q;
+    constexpr int64_t QP = 128;  // observables of a panel: one tile of the widest instantiation
+    const int64_t nchunks = std::max<int64_t>((c->N + SCAN_CHUNK - 1) / SCAN_CHUNK, 1);
+    const int nb_max = scan_nb_for(std::min(Q, QP));
+    int64_t record = 0;
+    for (int mode = second ? 1 : 0; mode <= (second ? 2 : 0); ++mode) {
+        const int J = scan_obs_columns(mode);
+        record = std::max(record, scan_obs_record_doubles(nb_max, J, scan_mb_of<ScanStored>(c, J)));
+    }
+    bool done = false;
+    ScanData d;
+    rc = scan_begin(c, f, L, coeff, offset, f_scan, (size_t)L, {{s1, LQ}, {t1, LQ}, {t2, LQ}, {wsum, (size_t)L}, {w2sum, (size_t)L}},
+                    (size_t)nchunks * (size_t)record, 3 * LQ + 2 * (size_t)L, &done, &d);
+    if (rc || done) return rc;
+    double* d_s1 = c->scan_out;
+    double* d_t1 = d_s1 + LQ;
+    double* d_t2 = d_t1 + LQ;
+    double* d_wsum = d_t2 + LQ;
+    double* d_w2sum = d_wsum + L;
+    const double* d_coeff = c->scan_in;
+    const double* d_off = d_coeff + L * B;
+    double* d_fscan = c->scan_in.p + L * (B + 1);
+    HIPCHK(c, hipMemcpyAsync(d_fscan, f_scan, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    {
+        ScopedTimer timer(c, MBAR_TIMER_OTHER);
+        for (int mode = second ? 1 : 0; mode <= (second ? 2 : 0); ++mode) {
+            const int mb = scan_mb_of<ScanStored>(c, scan_obs_columns(mode));
+            double* out0 = mode == 2 ? d_t2 : d_s1;
+            double* out1 = mode == 1 ? d_t1 : nullptr;
+            for (int64_t p0 = 0; p0 < L; p0 += 64 * mb)
+                for (int64_t qb = 0; qb < Q; qb += QP) {
+                    const int64_t nq = std::min(QP, Q - qb);
+                    const int nb = scan_nb_for(nq);
+                    const double* a = c->scan_obs.p + qb * ld;
+                    if (c->scan_terms.mask)
+                        HIPCHK(c, launch_scan_obs(c->stream, d, harmonic_of(c), nb, mode, a, nq, L, p0, d_coeff, d_off, d_fscan, c->scan_part));
+                    else
+                        HIPCHK(c, launch_scan_obs(c->stream, d, ScanLinear{}, nb, mode, a, nq, L, p0, d_coeff, d_off, d_fscan, c->scan_part));
+                    const bool vec = qb == 0 && mode != 2;  // wsum and w2sum: the first observable panel's
+                    HIPCHK(c, launch_scan_obs_merge(c->stream, d, nb, mode, mb, L, Q, p0, qb, nq, c->scan_part, out0, out1, vec ? d_wsum : nullptr,
+                                                    vec && second ? d_w2sum : nullptr));
+                }
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(s1, d_s1, LQ * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(wsum, d_wsum, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (second) {
+        HIPCHK(c, hipMemcpyAsync(t1, d_t1, LQ * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(t2, d_t2, LQ * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(w2sum, d_w2sum, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    return sync_stream(c);
+}
+
 // ---- histogram surfaces along a scan ----
 
 int mbar_scan_bins_table(int64_t N, int64_t nbins, const int32_t* label, int32_t* perm_out, int64_t* bin_start_out) {

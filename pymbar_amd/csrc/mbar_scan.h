@@ -191,6 +191,19 @@ hipError_t launch_scan_pair(hipStream_t s, const ScanData& d, const Fam& fam, in
                             const double* coeff, const double* offset, const double* fnorm, double* part);
 hipError_t launch_scan_pair_merge(hipStream_t s, const ScanData& d, int nb, int mb, int64_t L, int64_t p0, int rm, const double* part,
                                   double* pair);
+// Many observables along a scan (mbar_scan_obs_sums), whole cut, either family: pass B with the rows of the LDS
+// tile being nq <= 16 nb stored observables a[nq][d.ldv] (nb = scan_nb_for(nq)) instead of sampled states.  mode 0: s1 = sum c b a;
+// mode 1: s1 and t1 = sum c b b a (two operand columns per member); mode 2: t2 = sum c b b a a (the fill stage squares the tile).
+// One launch per (member panel [p0, p0 + 64 mb), observable panel, mode), mb = Fam::mb(scan_obs_columns(mode));
+// part[chunk][scan_obs_record_doubles(nb, J, mb)], then the merge in chunk order into out0 / out1 (column 0 / 1; L x Q row-major, at
+// observable qb) and, where asked for (the first observable panel), wsum into vec0[L] and w2sum into vec1[L].
+int scan_obs_columns(int mode);
+int64_t scan_obs_record_doubles(int nb, int J, int mb);
+template <class Fam>
+hipError_t launch_scan_obs(hipStream_t s, const ScanData& d, const Fam& fam, int nb, int mode, const double* a, int64_t nq, int64_t L,
+                           int64_t p0, const double* coeff, const double* offset, const double* fnorm, double* part);
+hipError_t launch_scan_obs_merge(hipStream_t s, const ScanData& d, int nb, int mode, int mb, int64_t L, int64_t Q, int64_t p0, int64_t qb,
+                                 int64_t nq, const double* part, double* out0, double* out1, double* vec0, double* vec1);
 
 // ---- rows of the resident matrix from a family of states (mbar_k_family.hip; C ABI: mbar_ctx_fill_family_rows and ----------
 // ---- mbar_ctx_fill_linear_rows in mbar_rows.cpp) -----------------------------------------------------------------------------

@@ -211,6 +211,7 @@ class DeviceMatrix(_ContextMatrix):
         self._scan = None  # (B, Q) of set_scan
         self._scan_harmonic = None  # the bool mask of the scan family's harmonic terms
         self._scan_nbins = 0  # set_scan_bins
+        self._scan_obs = 0  # rows of set_scan_observables
         self._boot_layout_key = None  # the caller's key of the bootstrap layout on the device
         self._cb = None  # keeps the host all-reduce callback alive
         self._loop = None  # keeps the loopback group alive
@@ -555,6 +556,52 @@ class DeviceMatrix(_ContextMatrix):
         m2[:, iu[0], iu[1]] = tri
         m2[:, iu[1], iu[0]] = tri
         return lognum, mean, m1, m2, ma
+
+    # ---- many observables along a scan (pymbar_amd.scan.compute_scan_expectations) ---------------------------------------------
+    SCAN_OBS_BYTES = 1 << 28  # the three L x Q blocks of one slab of members of scan_obs_sums stay under this
+
+    def set_scan_observables(self, a_qn=None):
+        """``Q >= 1`` observables (``Q x N``) kept resident for :meth:`scan_obs_sums` (``mbar_ctx_set_scan_obs``), in a block of their
+        own: it survives :meth:`set_scan`, a change of term kinds, centres and sample weights.  ``None`` releases it."""
+        if a_qn is None:
+            self._check(self._lib.mbar_ctx_set_scan_obs(self._ctx, 0, None, 0))
+            self._scan_obs = 0
+            return
+        a_qn = _lib.f64(a_qn, (None, self.N_local), "a_qn")
+        if a_qn.shape[0] < 1:
+            raise ValueError("a_qn must have at least one row")
+        # (MBAR_ERR_ARG: a non-finite entry.  A refused call leaves the library's block, and the count that sizes the outputs, as
+        # they were.)
+        self._check(self._lib.mbar_ctx_set_scan_obs(self._ctx, a_qn.shape[0], _dptr(a_qn), self.N_local), ValueError)
+        self._scan_obs = a_qn.shape[0]
+
+    def scan_obs_sums(self, f, coeff_lb, offset_l, f_scan, second=True, center_lb=None, slab=None):
+        """The sums of the resident observables along a scan (``mbar_scan_obs_sums``): ``(s1, t1, t2, wsum, w2sum)`` with ``b_ln`` as in
+        :meth:`scan_gram_w` -- ``s1[l, q] = sum_n c_n b_ln a_qn``, ``t1[l, q] = sum_n c_n b_ln^2 a_qn``, ``t2[l, q] = sum_n c_n b_ln^2
+        a_qn^2`` (``L x Q``), ``wsum[l] = sum_n c_n b_ln``, ``w2sum[l] = sum_n c_n b_ln^2``; with ``second=False`` only the first-moment
+        launches run and ``t1``, ``t2``, ``w2sum`` are None.  The members go to the device in slabs (of ``slab`` members; by default
+        as many as keep a slab's blocks under 256 MiB): an entry's bits do not depend on the cut."""
+        f = self._f(f)
+        coeff_lb, offset_l, L, _ = self._scan_members(coeff_lb, offset_l)
+        f_scan = _lib.f64(f_scan, (L,), "f_scan")
+        Q = self._scan_obs
+        if Q < 1:
+            raise ValueError("no observables on this matrix (set_scan_observables first)")
+        if center_lb is not None and np.shape(center_lb) != (L, self._scan[0]):
+            raise ValueError("center_lb must have one row per member and one column per basis vector")
+        if slab is None:
+            slab = self.SCAN_OBS_BYTES // (24 * Q)
+        slab = max(1, min(int(slab), L))
+        s1 = np.empty((L, Q), dtype=np.float64)
+        wsum = np.empty(L, dtype=np.float64)
+        t1, t2, w2sum = (np.empty((L, Q)), np.empty((L, Q)), np.empty(L)) if second else (None, None, None)
+        for l0 in range(0, L, slab):
+            l1 = min(L, l0 + slab)
+            self._scan_centers(None if center_lb is None else center_lb[l0:l1], l1 - l0)
+            part = lambda a: None if a is None else _dptr(a[l0:l1])
+            self._check(self._lib.mbar_scan_obs_sums(self._ctx, _dptr(f), l1 - l0, _dptr(coeff_lb[l0:l1]), _dptr(offset_l[l0:l1]),
+                                                     _dptr(f_scan[l0:l1]), part(s1), part(t1), part(t2), part(wsum), part(w2sum)))
+        return s1, t1, t2, wsum, w2sum
 
     # ---- histogram surfaces along a scan (pymbar_amd.scan.compute_scan_fes) ---------------------------------------------------
     SCAN_BIN_CROSS_BYTES = 1 << 28  # the host cross block of one slab of members of scan_bin_gram_w stays under this

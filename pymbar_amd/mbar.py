@@ -663,6 +663,9 @@ class MBAR:
     compute_scan_entropy_and_enthalpy = _scan.compute_scan_entropy_and_enthalpy
     compute_scan_gradient = _scan.compute_scan_gradient
     compute_scan_pairs = _scan.compute_scan_pairs
+    _scan_obs_shift = None  # s_q of the observables set_scan_observables keeps resident (None: none are set)
+    set_scan_observables = _scan.set_scan_observables
+    compute_scan_expectations = _scan.compute_scan_expectations
 
     def _computeUnnormalizedLogWeights(self, u_n):
         """``-ln sum_k N_k exp(f_k - (u_k(x_n) - u(x_n)))`` for one target potential ``u_n`` (mbar.py:1919-1934):

@@ -232,6 +232,137 @@ def compute_scan(mbar, basis_bn=None, coeff_lb=None, offset_l=None, A_qn=None, r
     return out
 
 
+# ---- many observables along a scan --------------------------------------------------------------------------------------------------
+def _obs_matrix(mbar):
+    dm = _scan_matrix(mbar)
+    if not all(hasattr(dm, name) for name in ("set_scan_observables", "scan_obs_sums")):
+        raise ParameterError(f"many observables along a scan need the observable pass of a single-rank device matrix and are {_NOT_HERE} for this handle")
+    return dm
+
+
+def _centred_observables(mbar, A_qn):
+    """``(A_qn - s_q, s_q)`` with ``s_q`` the row's plain mean, or a ``ParameterError`` / ``DataError``."""
+    A_qn = np.asarray(A_qn, dtype=np.float64)
+    if A_qn.ndim == 1:
+        A_qn = A_qn.reshape(1, -1)
+    if A_qn.ndim != 2 or A_qn.shape[1] != mbar.N or A_qn.shape[0] < 1:
+        raise ParameterError("A_qn must have shape (Q, N) with Q >= 1, or (N,)")
+    if not np.all(np.isfinite(A_qn)):
+        raise DataError("A_qn must be finite")
+    shift = np.zeros(A_qn.shape[0])
+    for q in range(A_qn.shape[0]):  # (row by row: an observable's centre does not depend on the others)
+        shift[q] = np.sum(A_qn[q]) / A_qn.shape[1]
+    return A_qn - shift[:, None], shift
+
+
+def set_scan_observables(mbar, A_qn=None):
+    """Keep ``A_qn`` -- ``(Q, N)`` with any ``Q >= 1``, or ``(N,)`` -- resident on the device for :func:`compute_scan_expectations`: a fit
+    iterates over trial parameters hundreds of times against the same observables.  Stored is ``A_qn - s_q`` with ``s_q`` the row's
+    plain mean (kept on the object), so that the variance expansion does not cancel against a large offset.  ``None`` releases them.
+    The block survives the other scan methods."""
+    dm = _obs_matrix(mbar)
+    if A_qn is None:
+        dm.set_scan_observables(None)
+        mbar._scan_obs_shift = None
+        return
+    a_qn, shift = _centred_observables(mbar, A_qn)
+    mbar._scan_obs_shift = None
+    dm.set_scan_observables(a_qn)
+    mbar._scan_obs_shift = shift
+
+
+def _expectation_numbers(s1, t1, t2, w2sum, shift):
+    """``(mu, sigma)`` ``(Q, L)`` from the sums: ``mu = s1 + s`` and, with ``m = s1``, ``sigma^2 = t2 - 2 m t1 + m^2 w2sum = sum c b^2 (a -
+    m)^2``, the Kong estimate; element by element, so that an entry depends on its own member and observable alone."""
+    mu = s1.T + shift[:, None]
+    if t1 is None:
+        return mu, None
+    m = s1.T
+    var = (t2.T - 2.0 * m * t1.T) + (m * m) * w2sum[None, :]
+    with np.errstate(invalid="ignore"):
+        sigma = np.sqrt(np.maximum(var, 0.0))
+    return mu, sigma
+
+
+def compute_scan_expectations(mbar, A_qn=None, basis_bn=None, coeff_lb=None, offset_l=None, compute_uncertainty=True,
+                              uncertainty_method="approximate", center_lb=None, harmonic_b=None, period_b=None):
+    """Averages of MANY observables along a family of unsampled states: a force-field fit against hundreds of experimental numbers, a
+    distribution function with one observable per bin, per-residue quantities along a temperature ladder.
+
+    ``A_qn``: ``(Q, N)`` with any ``Q >= 1`` or ``(N,)``, uploaded for this call and released afterwards; None: the observables
+    :meth:`set_scan_observables` keeps resident (none set: a ``ParameterError``).  The family (``basis_bn``, ``coeff_lb``, ``offset_l``,
+    ``center_lb``, ``harmonic_b``, ``period_b``) is that of :func:`compute_scan`.  Returns a dict: ``f`` ``(L,)``, the bits
+    :func:`compute_scan` returns; ``mu`` ``(Q, L)``, entry ``l`` of ``compute_expectations(A_qn[q], u_kn=u_ln, state_dependent=False)``;
+    ``n_eff`` ``(L,)``, Kish's effective sample number ``1 / sum_n w_ln^2`` of every member; with ``compute_uncertainty`` ``sigma``
+    ``(Q, L)``.
+
+    The sums are one ``(L x N)(N x Q)`` product on the fp64 matrix cores (``DeviceMatrix.scan_obs_sums``): every member weight is
+    evaluated once per 128 observables, where ``ceil(Q / 3)`` calls of :func:`compute_scan` evaluate it once per 3.
+
+    ``uncertainty_method``: "approximate" (the default: ``sigma^2 = sum_n w_ln^2 (A_qn - mu)^2``, what the reference's "approximate"
+    returns) or "bootstrap" (the ``std`` over the replicates; adds ``bootstrapped_f`` ``(n_bootstraps, L)`` and
+    ``bootstrapped_observables`` ``(n_bootstraps, Q, L)``).  The bordered forms need a ``K x L x Q`` cross block and stay with
+    :func:`compute_scan` (``Q <= 3``)."""
+    basis_given = basis_bn
+    if uncertainty_method in (None, "svd-ew", "svd"):
+        raise ParameterError(f"uncertainty_method {uncertainty_method!r}: the bordered uncertainty needs a K x L x Q cross block and stays "
+                             f"with compute_scan (Q <= {MAX_OBSERVABLES}); compute_scan_expectations offers 'approximate' and 'bootstrap'")
+    if uncertainty_method not in ("approximate", "bootstrap"):
+        raise ParameterError(f"Method {uncertainty_method} unrecognized.")
+    bootstrap = uncertainty_method == "bootstrap"
+    if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
+        raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
+    basis_bn, coeff_lb, offset_l, _, L = _check_inputs(mbar, _family_basis(mbar, basis_bn, coeff_lb), coeff_lb, offset_l, None, 0)
+    kinds, cen = _family_kinds(mbar, basis_given, basis_bn.shape[0], L, center_lb, harmonic_b, period_b)
+    dm = _obs_matrix(mbar)
+    resident = A_qn is None
+    if resident:
+        shift = getattr(mbar, "_scan_obs_shift", None)
+        if shift is None:
+            raise ParameterError("A_qn=None stands for the resident observables and none are set (set_scan_observables first)")
+    else:
+        a_qn, shift = _centred_observables(mbar, A_qn)
+        if getattr(mbar, "_scan_obs_shift", None) is not None:
+            raise ParameterError("observables are resident on this object (set_scan_observables): pass A_qn=None, or release them first")
+    Q = len(shift)
+    dm.set_Nk(mbar.N_k)
+    dm.set_scan(basis_bn, None, **kinds)
+    try:
+        if not resident:
+            dm.set_scan_observables(a_qn)
+        lognum, _ = dm.scan_lognum(mbar.f_k, coeff_lb, offset_l, **cen)
+        f = -lognum
+        second = compute_uncertainty and not bootstrap
+        s1, t1, t2, wsum, w2sum = dm.scan_obs_sums(mbar.f_k, coeff_lb, offset_l, f, second=second, **cen)
+        check_w_sums(wsum, 0.0)
+        if not second:  # (n_eff alone: the members' own products of pass B, without its cross block)
+            w2sum = dm.scan_gram_w(mbar.f_k, coeff_lb, offset_l, f, reference=0, cross=False, **cen)[1][:, 0, 0]
+        mu, sigma = _expectation_numbers(s1, t1, t2, w2sum, shift)
+        out = dict(f=f, mu=mu, n_eff=1.0 / w2sum)
+        if second:
+            out["sigma"] = sigma
+        if bootstrap:
+            fb = np.zeros((mbar.n_bootstraps, L))
+            Ab = np.zeros((mbar.n_bootstraps, Q, L))
+            try:
+                for b in range(mbar.n_bootstraps):
+                    mbar._set_bootstrap_weights(dm, b)
+                    ln_b, _ = dm.scan_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l, **cen)
+                    fb[b] = -ln_b
+                    s1_b = dm.scan_obs_sums(mbar.f_k_boots[b, :], coeff_lb, offset_l, fb[b], second=False, **cen)[0]
+                    Ab[b] = s1_b.T + shift[:, None]
+            finally:
+                dm.set_sample_weights(None)
+            out["bootstrapped_f"], out["bootstrapped_observables"] = fb, Ab
+            if compute_uncertainty:
+                out["sigma"] = np.std(Ab, axis=0)
+    finally:
+        if not resident:
+            dm.set_scan_observables(None)
+        dm.set_scan(None)
+    return out
+
+
 # ---- differences between any two members of a scan --------------------------------------------------------------------------------
 def _pairs_matrix(mbar):
     dm = _scan_matrix(mbar)
