@@ -475,6 +475,39 @@ int mbar_ctx_set_scan_obs(mbar_ctx* ctx, int64_t Q, const double* a_host, int64_
 int mbar_scan_obs_sums(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan,
                        double* s1, double* t1, double* t2, double* wsum, double* w2sum);
 
+/* KERNEL-DENSITY surfaces along a scan (MBAR.compute_scan_kde): the gaussian density of every member of the family at M query points,
+ * F(x; T) on a ladder or F(phi, psi; restraint centre), without a dense u_l, an upload or a weight evaluation per member.  The sums
+ * are an (M x N)(N x L) product on the fp64 matrix cores with BOTH operands generated on the device: the member weight from the B
+ * numbers per sample as in mbar_scan_obs_sums, the kernel value from the d coordinates per sample kept here.
+ *   mbar_ctx_set_scan_points  uploads the d = 1 or 2 coordinates of the N samples (host rows of pitch ld_host >= N, coordinate-major)
+ *                             into a block the context owns, at the device pitch of the basis.  d = 0 releases the block.  Like the
+ *                             block of mbar_ctx_set_scan_obs it does not depend on mbar_ctx_set_scan and survives the other scan
+ *                             calls.  MBAR_ERR_ARG: d outside [0, 2], a NULL pointer with d > 0, ld_host < N, a non-finite entry --
+ *                             refused before the block on the context is touched.
+ *   mbar_scan_kde_sums        on the family currently set, with b_ln = exp(f_scan[l] + x_ln) formed by the operations
+ *                             mbar_scan_gram_w uses for a member column, c_n the multiplicities, q the M queries (coordinate-major,
+ *                             d rows of M doubles), h = bandwidth and r the distance from x_n to q_m:
+ *                               logsum[l][m] = log sum_n c_n b_ln exp(-r^2 / 2h^2)     (L x M, row-major)      wsum[l] = sum_n c_n b_ln
+ *                             period: NULL or d entries, 0 = not periodic; where P > 0 the displacement of that coordinate is the
+ *                             minimum image dl = q - x; dl = fma(-P, rint(dl / P), dl), the operations of a periodic harmonic term
+ *                             (1 / P rounded once).  NULL and zeros are the same call.  The log density of member l is logsum[l][m] -
+ *                             log wsum[l] + mbar_kde_log_norm(gaussian, d, h): the normaliser is the unwrapped kernel's.
+ * The members are taken in the panels of mbar_scan_obs_sums, the queries in panels of 128 (the last one of 16, 32, 64 or 128); one
+ * launch per pair of panels costs (members of the panel) x N member exponentials, (queries of the panel) x N kernel exponentials and
+ * 2 x members x queries x N flop.  k <= 1 and c_n b_ln <= 1 for a normalised member, so the sums carry no running shift; a pair whose
+ * sum is not >= 2^-900 (every term underflowed, or a NaN) of a member with wsum > 0 is recomputed in plain log space with its own
+ * maximum, one workgroup per pair, fixed-order tree reductions: finite wherever a term is inside the fp64 range, -inf below it, never
+ * NaN for finite input (a distance whose square overflows is measured in units of its largest coordinate); *n_exact: how many pairs
+ * took this path.  A member with wsum = 0 keeps NaN.  No floating-point atomics; chunks of 8192 samples cut by N alone and merged in
+ * chunk order, compensated: two identical calls return identical bits, and element (l, m) does not depend on L, M, the other members
+ * or queries, or where member l and query m sit in the call.  A NaN in f or f_scan fills the outputs with NaN (MBAR_OK, *n_exact = 0).
+ * Limits, state and argument errors are those of mbar_scan_gram_w; MBAR_ERR_STATE also when no points are set; MBAR_ERR_ARG: M < 1, a
+ * non-finite query, a bandwidth that is not positive and finite (or whose 1 / 2h^2 is not), a negative or non-finite period.
+ * Kernel time: MBAR_TIMER_OTHER. */
+int mbar_ctx_set_scan_points(mbar_ctx* ctx, int64_t d, const double* x_host, int64_t ld_host);
+int mbar_scan_kde_sums(mbar_ctx* ctx, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan, int64_t M,
+                       const double* q, double bandwidth, const double* period, double* logsum, double* wsum, int64_t* n_exact);
+
 /* ---- histogram surfaces along a scan ---------------------------------------------------------
  * The histogram free energy surface of EVERY member of a scan: the bins are labels of the resident samples as in "histogram bins
  * by label", the target states are the members of the family uploaded by mbar_ctx_set_scan (with Q = 0).  Nothing of size L x N is

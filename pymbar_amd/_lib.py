@@ -144,6 +144,8 @@ SIGNATURES = {
     "mbar_scan_moments": (C.c_int,[_ctx, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbar_ctx_set_scan_obs": (C.c_int, [_ctx, C.c_int64, _dp, C.c_int64]),
     "mbar_scan_obs_sums": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbar_ctx_set_scan_points": (C.c_int, [_ctx, C.c_int64, _dp, C.c_int64]),
+    "mbar_scan_kde_sums": (C.c_int, [_ctx, _dp, C.c_int64, _dp, _dp, _dp, C.c_int64, _dp, C.c_double, _dp, _dp, _dp, _ip]),
     "mbar_ctx_set_scan_terms": (C.c_int, [_ctx, C.POINTER(C.c_int32), _dp]),
     "mbar_ctx_set_scan_centers": (C.c_int, [_ctx, C.c_int64, _dp]),
     "mbar_ctx_set_scan_bins": (C.c_int, [_ctx, C.c_int64, C.POINTER(C.c_int32)]),

@@ -185,6 +185,9 @@ struct mbar_ctx {
     // many observables along a scan (mbar_ctx_set_scan_obs): a[scan_obs_Q][ld], a block of its own next to the family's
     int64_t scan_obs_Q = 0;
     DevBuf<double> scan_obs;
+    // kernel-density surfaces along a scan (mbar_ctx_set_scan_points): x[scan_pts_d][ld], the coordinates of the samples
+    int64_t scan_pts_d = 0;
+    DevBuf<double> scan_pts;
     // histogram surfaces along a scan (mbar_ctx_set_scan_bins): the samples sorted by bin and the chunk tables of the two passes
     // (chunks of SCAN_VCHUNK / SCAN_CHUNK sorted positions, cut from the start of every bin); the host keeps pass B's chunk
     // offsets to group the bins under the record budget

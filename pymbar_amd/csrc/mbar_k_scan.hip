@@ -63,6 +63,10 @@
 // Many observables (MBAR.compute_scan_expectations, mbar_scan_obs_sums): pass B a third time, the rows of the LDS
 // tile being observables the context keeps resident (any number of them, in panels of 128), s1[l][q] = sum_n c_n b_ln a_qn and its
 // two second-moment companions, in a sweep and a merge of its own (k_scan_obs, k_scan_obs_merge); whole cut.
+//
+// Kernel-density surfaces (MBAR.compute_scan_kde, mbar_scan_kde_sums): k_scan_obs's first moments with the tile
+// COMPUTED, the gaussian kernel values of up to 128 queries against the 16 positions (k_scan_kde, k_scan_kde_merge), and the pairs
+// whose terms all underflow once more in log space (k_scan_kde_exact); whole cut.  At the end of the file.
 #include "mbar_device.h"
 #include "mbar_scan_device.h"
 
@@ -1244,5 +1248,370 @@ MBAR_MERGES(ScanWhole, ScanEnergy)
 #undef MBAR_CUT
 #undef MBAR_MERGES
 #undef MBAR_SWEEPS
+
+// ---- kernel-density surfaces along a scan (mbar_scan_kde_sums) -----------------------------------------------
+// The gaussian density of EVERY member of the family at M query points,
+//   S[l][m] = sum_n c_n b_ln k(q_m, x_n),   b_ln = exp(f_scan[l] - u_l(n) - logden_n),   k = exp(-r^2 / 2h^2),
+// an (M x N)(N x L) product with BOTH operands generated on the device: the member weight from the B numbers per sample as in pass B,
+// the kernel value from the d coordinates per sample the context keeps (mbar_ctx_set_scan_points).  k_scan_kde is k_scan_obs (mode 0)
+// with another fill stage: where that one loads a tile of stored observables, this one computes the tile k(q_i, x_n) of 16 NB queries x
+// 16 positions, NB exponentials per thread.  Everything behind the fill -- the product stage, the record, the chunks cut by N alone,
+// the member panels -- is that kernel's, so one member exponential serves up to 128 queries and one kernel exponential every member of
+// the panel.  k <= 1 and c_n b_ln <= 1 for a normalised member: the sums cannot overflow and carry no running shift.
+// k_scan_kde_merge adds the chunk records in chunk order, compensated, and writes log S; a pair whose sum is not >= 2^-900 (underflow,
+// or a NaN) gets a NaN there, and the host hands the pairs of members with wsum > 0 among them to k_scan_kde_exact, which works in
+// plain log space with the pair's own maximum.  The displacement of a coordinate with period P > 0 is the minimum image, formed by
+// the operations of the harmonic chain (family_term): dl = q - x; dl = fma(-P, rint(dl rP), dl).
+namespace {
+constexpr double SCANKDE_FLAG_BELOW = 0x1p-900;  // merged sums not at or above this are recomputed by k_scan_kde_exact
+
+// the displacement of coordinate k from a sample to a query
+__device__ __forceinline__ double scan_kde_dl(const ScanKde& kd, int k, double q, double x) {
+    double dl = q - x;
+    const double P = kd.period[k];
+    if (P > 0.0) {
+        const double m = rint(dl * kd.rperiod[k]);
+        dl = fma(-P, m, dl);
+    }
+    return dl;
+}
+}  // namespace
+
+// One workgroup owns one chunk, one panel of 64 MB members (MB = Fam::mb(1)) and one panel of nq <= 16 NB queries, those from qb on.
+// Fill: thread tid computes the NB values of rows 16 I + (tid >> 4) at position tid & 15 -- D subtractions, the wrap where a period is
+// set, r^2 by fma in coordinate order, exp2s_fast(r^2 coef) -- with exact zeros where c_n <= 0, past nq and past the chunk.  The
+// queries of the panel wait in LDS ([D][16 NB]).  The record is k_scan_obs's with one per-member sum: [wave][I < NB][mb < MB][r < 4]
+// [lane], then [pm < 64 MB] wsum.  An element's operations depend neither on the row it has in the tile nor on NB, the member's
+// column or MB.
+template <int NB, int D, class Fam, class... Arg>
+__global__ void __launch_bounds__(256)
+k_scan_kde(ScanData d, ScanKde kd, int64_t qb, int nq, int64_t L, int64_t p0, const double* __restrict__ coeff,
+           const double* __restrict__ offset, const double* __restrict__ fnorm, double* __restrict__ part, Arg... arg) {
+    const Fam fam = scan_arg<Fam>(arg...);
+    const ScanWhole cut{};
+    constexpr int MB = Fam::mb(1);
+    static_assert(NB * MB <= 32, "at most 32 accumulator blocks per wave");
+    constexpr int SVB = 32;  // where the basis rows start in sv
+    constexpr int W_DOUBLES = NB * 16 * SCAN_PITCH;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    exp_table_init(smem);
+    double* Wt = reinterpret_cast<double*>(smem + EXP_TABLE_BYTES);  // [16 NB][SCAN_PITCH]
+    double* sv = Wt + W_DOUBLES;                                     // cn[16] | lden[16] | basis[SCAN_MAX_B][16]
+    double* qs = sv + SVB + SCAN_MAX_B * 16;                         // [D][16 NB]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15, q4 = lane >> 4;
+    int64_t bin, q0c, q1c;
+    cut.range(blockIdx.x, d.N, SCAN_CHUNK, bin, q0c, q1c);
+    const int64_t pl = L - p0 < 64 * MB ? L - p0 : 64 * MB;  // members of the panel
+    const int nblk = (int)((pl + 15) / 16);
+    int mine = 0;
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) mine += (mb * 4 + wave) < nblk;
+    mine = __builtin_amdgcn_readfirstlane(mine);
+
+    double cf[MB][SCAN_MAX_B], off[MB], fs[MB];
+    double cen[Fam::harmonic ? MB : 1][SCAN_MAX_H];
+    bool mlive[MB];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+        const int64_t pm = (int64_t)(mb * 4 + wave) * 16 + col;
+        mlive[mb] = pm < pl;
+        const int64_t l = p0 + pm;
+#pragma unroll
+        for (int b = 0; b < SCAN_MAX_B; ++b) cf[mb][b] = (mlive[mb] && b < d.B) ? coeff[l * d.B + b] : 0.0;
+        off[mb] = mlive[mb] ? offset[l] : 0.0;
+        if constexpr (Fam::harmonic) family_load_centers(fam, mlive[mb], l, cen[mb]);
+        fs[mb] = mlive[mb] ? fnorm[l] : 0.0;
+    }
+    const int fs_s = tid & 15, fs_r = tid >> 4;
+    for (int i = tid; i < D * 16 * NB; i += 256) {
+        const int k = i / (16 * NB), row = i % (16 * NB);
+        qs[i] = row < nq ? kd.q[(int64_t)k * kd.ldq + qb + row] : 0.0;
+    }
+
+    v4d acc[NB * MB];
+#pragma unroll
+    for (int i = 0; i < NB * MB; ++i) acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
+    double vs[MB];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) vs[mb] = 0.0;
+
+    __syncthreads();  // the exp table, the queries
+    for (int64_t q0 = q0c; q0 < q1c; q0 += 16) {
+        // ---- fill: the kernel tile and the per-sample values of the tile
+        {
+            const int64_t q = q0 + fs_s;
+            int64_t n = 0;
+            double cn = 0.0, lden = 0.0;
+            if (q < q1c) {
+                n = q;
+                cn = d.cw ? d.cw[n] : 1.0;
+                if (cn > 0.0) lden = d.logden[n];
+                else cn = 0.0;
+            }
+            const bool slive = cn > 0.0;
+            double xc[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) xc[k] = slive ? kd.x[(int64_t)k * d.ldv + n] : 0.0;
+#pragma unroll
+            for (int I = 0; I < NB; ++I) {
+                const int row = 16 * I + fs_r;
+                double v = 0.0;
+                if (slive && row < nq) {
+                    double r2 = 0.0;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        const double dl = scan_kde_dl(kd, k, qs[k * 16 * NB + row], xc[k]);
+                        r2 = fma(dl, dl, r2);
+                    }
+                    v = exp2s_fast(r2 * kd.coef);
+                }
+                Wt[row * SCAN_PITCH + fs_s] = v;
+            }
+            if (tid < 16) {
+                sv[fs_s] = cn;
+                sv[16 + fs_s] = lden;
+            }
+            if (fs_r < d.B) sv[SVB + fs_r * 16 + fs_s] = slive ? d.basis[(int64_t)fs_r * d.ldv + n] : 0.0;
+        }
+        __syncthreads();
+        // ---- products: four groups of four positions (k_scan_obs's, one operand column per member)
+        if (mine > 0) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int s = 4 * g + q4;
+                double at[NB];
+#pragma unroll
+                for (int I = 0; I < NB; ++I) at[I] = Wt[(16 * I + col) * SCAN_PITCH + s];
+                const double cn = sv[s], lden = sv[16 + s];
+                double bas[SCAN_MAX_B];
+#pragma unroll
+                for (int b = 0; b < SCAN_MAX_B; ++b) bas[b] = b < d.B ? sv[SVB + b * 16 + s] : 0.0;
+#pragma unroll
+                for (int mb = 0; mb < MB; ++mb) {
+                    if (mb < mine) {  // (wave-uniform)
+                        double uu = off[mb];
+#pragma unroll
+                        for (int b = 0; b < SCAN_MAX_B; ++b)
+                            if (b < d.B) uu = family_term(fam, b, uu, cf[mb][b], bas[b], family_center(fam, b, cen[Fam::harmonic ? mb : 0]));
+                        double bv = scan_exp(fs[mb] + (-uu - lden));
+                        if (!(cn > 0.0) || !mlive[mb]) bv = 0.0;
+                        const double cb = cn * bv;
+                        vs[mb] += cb;
+#pragma unroll
+                        for (int I = 0; I < NB; ++I) acc[I * MB + mb] = __builtin_amdgcn_mfma_f64_16x16x4f64(at[I], cb, acc[I * MB + mb], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // ---- the record
+    constexpr int64_t CROSS_DOUBLES = (int64_t)4 * NB * MB * 256;
+    double* rec = part + (int64_t)blockIdx.x * (CROSS_DOUBLES + (int64_t)64 * MB);
+#pragma unroll
+    for (int i = 0; i < NB * MB; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rec[(((int64_t)wave * NB * MB + i) * 4 + r) * 64 + lane] = acc[i][r];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+        double x = vs[mb];
+        x += __shfl_xor(x, 16);
+        x += __shfl_xor(x, 32);
+        if (lane < 16) rec[CROSS_DOUBLES + (int64_t)(mb * 4 + wave) * 16 + lane] = x;
+    }
+}
+
+// The chunk records of one (member panel, query panel) added in chunk order, compensated.  Threads [0, pl nq): member p0 + pm and
+// query qb + qi, logsum[(p0 + pm) M + qb + qi] = log S, or NaN where !(S >= 2^-900): the exact kernel's, if the member has weight.
+// Threads behind them, [0, pl): wsum[p0 + pm] (a NULL destination: another query panel wrote it).
+__global__ void __launch_bounds__(SV_THREADS)
+k_scan_kde_merge(int64_t nchunks, int NB, int MB, int64_t M, int64_t p0, int64_t pl, int64_t qb, int64_t nq, const double* __restrict__ part,
+                 double* __restrict__ logsum, double* __restrict__ wsum) {
+    const int64_t cross_doubles = (int64_t)4 * NB * MB * 256, stride = cross_doubles + (int64_t)64 * MB;
+    int64_t x = (int64_t)blockIdx.x * SV_THREADS + threadIdx.x;
+    int64_t at;
+    double* out;
+    const bool cross = x < pl * nq;
+    if (cross) {
+        const int64_t pm = x % pl, qi = x / pl;
+        const int64_t blk = pm / 16, colm = pm % 16, wave = blk % 4, mb = blk / 4;
+        const int64_t I = qi / 16, row = qi % 16, r = row >> 2, lane = (row & 3) * 16 + colm;
+        at = (((wave * NB + I) * MB + mb) * 4 + r) * 64 + lane;
+        out = logsum + (p0 + pm) * M + qb + qi;
+    } else {
+        x -= pl * nq;
+        if (x >= pl || !wsum) return;
+        at = cross_doubles + x;
+        out = wsum + p0 + x;
+    }
+    double s = 0.0, e = 0.0;
+    const double* r = part + at;
+    for (int64_t c = 0; c < nchunks; ++c, r += stride) scan_neumaier(s, e, *r);
+    s += e;
+    if (cross) s = s >= SCANKDE_FLAG_BELOW ? log(s) : NAN;
+    *out = s;
+}
+
+// One workgroup per pair (member pairs[2 i], query pairs[2 i + 1]): two passes over the samples in plain log space -- the maximum
+// over the samples with c_n > 0 of (f_scan[l] - u_l(n) - logden_n) - r^2 / 2h^2, then the sum of c_n exp(. - max) -- with fixed-order
+// tree reductions; out[i] = max + log(sum), -inf when no sample has c_n > 0 or every term is below the fp64 range.  A displacement
+// whose square overflows is measured in units of its largest coordinate as k_kde_exact does: never NaN for finite input.
+template <class Fam, class... Arg>
+__global__ void __launch_bounds__(256)
+k_scan_kde_exact(ScanData d, ScanKde kd, const int64_t* __restrict__ pairs, const double* __restrict__ coeff,
+                 const double* __restrict__ offset, const double* __restrict__ fnorm, double* __restrict__ out, Arg... arg) {
+    const Fam fam = scan_arg<Fam>(arg...);
+    __shared__ double red[256];
+    const int64_t l = pairs[2 * blockIdx.x], m = pairs[2 * blockIdx.x + 1];
+    const int tid = threadIdx.x;
+    double cf[SCAN_MAX_B], cen[SCAN_MAX_H];
+#pragma unroll
+    for (int b = 0; b < SCAN_MAX_B; ++b) cf[b] = b < d.B ? coeff[l * d.B + b] : 0.0;
+    family_load_centers(fam, true, l, cen);
+    const double off = offset[l], fs = fnorm[l];
+    double qc[SCANKDE_MAX_D];
+#pragma unroll
+    for (int k = 0; k < SCANKDE_MAX_D; ++k) qc[k] = k < kd.d ? kd.q[(int64_t)k * kd.ldq + m] : 0.0;
+    const double inv_h2 = kd.inv_h * kd.inv_h;
+    auto logterm = [&](int64_t n) -> double {
+        const double cn = d.cw ? d.cw[n] : 1.0;
+        if (!(cn > 0.0)) return -INFINITY;
+        const double uu = scan_u(d, fam, cf, cen, off, n);
+        const double x = fs + (-uu - d.logden[n]);
+        double r2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < SCANKDE_MAX_D; ++k)
+            if (k < kd.d) {
+                const double dl = scan_kde_dl(kd, k, qc[k], kd.x[(int64_t)k * d.ldv + n]);
+                r2 = fma(dl, dl, r2);
+            }
+        double lk;
+        if (r2 < INFINITY) {
+            lk = -0.5 * r2 * inv_h2;
+        } else {
+            // r^2 is beyond the fp64 range, r / h need not be: halved displacements (q - x itself may overflow where no period
+            // folds it) in units of the largest one
+            double hd[SCANKDE_MAX_D], amax = 0.0;
+#pragma unroll
+            for (int k = 0; k < SCANKDE_MAX_D; ++k) {
+                hd[k] = 0.0;
+                if (k < kd.d) {
+                    const double xk = kd.x[(int64_t)k * d.ldv + n];
+                    hd[k] = kd.period[k] > 0.0 ? 0.5 * scan_kde_dl(kd, k, qc[k], xk) : 0.5 * qc[k] - 0.5 * xk;
+                }
+                amax = fmax(amax, fabs(hd[k]));
+            }
+            double u2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < SCANKDE_MAX_D; ++k) {
+                const double u = hd[k] / amax;
+                u2 = fma(u, u, u2);
+            }
+            const double rh = 2.0 * (amax * kd.inv_h * sqrt(u2));  // r / h (inf when that is out of range too)
+            lk = -0.5 * rh * rh;
+        }
+        return x + lk;
+    };
+    double mx = -INFINITY;
+    for (int64_t n = tid; n < d.N; n += 256) mx = fmax(mx, logterm(n));
+    red[tid] = mx;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] = fmax(red[tid], red[tid + w]);
+        __syncthreads();
+    }
+    mx = red[0];
+    __syncthreads();
+    double s = 0.0;
+    if (mx > -INFINITY)
+        for (int64_t n = tid; n < d.N; n += 256) {
+            const double t = logterm(n);
+            if (t > -INFINITY) s = fma(d.cw ? d.cw[n] : 1.0, exp(t - mx), s);
+        }
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[blockIdx.x] = mx > -INFINITY ? mx + log(red[0]) : -INFINITY;
+}
+
+// ---- launchers -----------------------------------------------------------------------------------------------------------------
+ScanKde scan_kde_make(int d, const double* x, const double* q, int64_t ldq, int64_t M, double h, const double* period) {
+    ScanKde kd{};
+    kd.d = d;
+    kd.x = x;
+    kd.q = q;
+    kd.ldq = ldq;
+    kd.M = M;
+    kd.inv_h = 1.0 / h;
+    kd.coef = -(LOG2E_S * (0.5 / (h * h)));
+    for (int k = 0; k < SCANKDE_MAX_D; ++k) {
+        const double P = (period && k < d) ? period[k] : 0.0;
+        kd.period[k] = P;
+        kd.rperiod[k] = P > 0.0 ? 1.0 / P : 0.0;
+    }
+    return kd;
+}
+
+int64_t scan_kde_record_doubles(int nb, int mb) { return (int64_t)4 * nb * mb * 256 + (int64_t)64 * mb; }
+
+template <class Fam>
+hipError_t launch_scan_kde(hipStream_t s, const ScanData& d, const Fam& fam, const ScanKde& kd, int nb, int64_t qb, int64_t nq, int64_t L,
+                           int64_t p0, const double* coeff, const double* offset, const double* fnorm, double* part) {
+    const int64_t nchunks = (d.N + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    if (nchunks < 1 || p0 >= L) return hipSuccess;
+    if (nchunks > 0x7fffffff || nq < 1 || nq > 16 * (int64_t)nb || qb < 0 || qb + nq > kd.M || d.B < 1 || d.B > SCAN_MAX_B)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)nchunks);
+    const size_t lds = EXP_TABLE_BYTES + ((size_t)nb * 16 * SCAN_PITCH + 32 + (size_t)SCAN_MAX_B * 16 + (size_t)SCANKDE_MAX_D * 16 * nb) * sizeof(double);
+#define MBAR_CASE(NB_, D_)                                                                                                                  \
+    if (nb == NB_ && kd.d == D_) {                                                                                                          \
+        if constexpr (Fam::harmonic)                                                                                                        \
+            hipLaunchKernelGGL((k_scan_kde<NB_, D_, Fam, Fam>), grid, dim3(256), lds, s, d, kd, qb, (int)nq, L, p0, coeff, offset, fnorm, part, fam); \
+        else                                                                                                                                \
+            hipLaunchKernelGGL((k_scan_kde<NB_, D_, Fam>), grid, dim3(256), lds, s, d, kd, qb, (int)nq, L, p0, coeff, offset, fnorm, part);  \
+        return hipGetLastError();                                                                                                           \
+    }
+#define MBAR_DIMS(NB_) MBAR_CASE(NB_, 1) MBAR_CASE(NB_, 2)
+    MBAR_DIMS(1) MBAR_DIMS(2) MBAR_DIMS(4) MBAR_DIMS(8)
+#undef MBAR_DIMS
+#undef MBAR_CASE
+    return hipErrorInvalidValue;
+}
+template hipError_t launch_scan_kde<ScanLinear>(hipStream_t, const ScanData&, const ScanLinear&, const ScanKde&, int, int64_t, int64_t, int64_t,
+                                                int64_t, const double*, const double*, const double*, double*);
+template hipError_t launch_scan_kde<ScanHarmonic>(hipStream_t, const ScanData&, const ScanHarmonic&, const ScanKde&, int, int64_t, int64_t,
+                                                  int64_t, int64_t, const double*, const double*, const double*, double*);
+
+hipError_t launch_scan_kde_merge(hipStream_t s, const ScanData& d, const ScanKde& kd, int nb, int mb, int64_t L, int64_t p0, int64_t qb,
+                                 int64_t nq, const double* part, double* logsum, double* wsum) {
+    if (p0 >= L || d.N < 1) return hipSuccess;
+    const int64_t pl = L - p0 < 64 * mb ? L - p0 : 64 * mb;
+    const int64_t blocks = (pl * nq + pl + SV_THREADS - 1) / SV_THREADS;
+    if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scan_kde_merge, dim3((unsigned)blocks), dim3(SV_THREADS), 0, s, (d.N + SCAN_CHUNK - 1) / SCAN_CHUNK, nb, mb, kd.M, p0, pl,
+                       qb, nq, part, logsum, wsum);
+    return hipGetLastError();
+}
+
+template <class Fam>
+hipError_t launch_scan_kde_exact(hipStream_t s, const ScanData& d, const Fam& fam, const ScanKde& kd, int64_t npairs, const int64_t* pairs,
+                                 const double* coeff, const double* offset, const double* fnorm, double* out) {
+    if (npairs <= 0) return hipSuccess;
+    if (npairs > 0x7fffffff || d.N < 1 || kd.d < 1 || kd.d > SCANKDE_MAX_D) return hipErrorInvalidValue;
+    if constexpr (Fam::harmonic)
+        hipLaunchKernelGGL((k_scan_kde_exact<Fam, Fam>), dim3((unsigned)npairs), dim3(256), 0, s, d, kd, pairs, coeff, offset, fnorm, out, fam);
+    else
+        hipLaunchKernelGGL((k_scan_kde_exact<Fam>), dim3((unsigned)npairs), dim3(256), 0, s, d, kd, pairs, coeff, offset, fnorm, out);
+    return hipGetLastError();
+}
+template hipError_t launch_scan_kde_exact<ScanLinear>(hipStream_t, const ScanData&, const ScanLinear&, const ScanKde&, int64_t, const int64_t*,
+                                                      const double*, const double*, const double*, double*);
+template hipError_t launch_scan_kde_exact<ScanHarmonic>(hipStream_t, const ScanData&, const ScanHarmonic&, const ScanKde&, int64_t,
+                                                        const int64_t*, const double*, const double*, const double*, double*);
 
 }  // namespace mbar

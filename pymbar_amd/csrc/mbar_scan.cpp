@@ -596,6 +596,125 @@ int mbar_scan_obs_sums(mbar_ctx* c, const double* f, int64_t L, const double* co
     return sync_stream(c);
 }
 
+// ---- kernel-density surfaces along a scan ----
+
+int mbar_ctx_set_scan_points(mbar_ctx* c, int64_t d, const double* x_host, int64_t ld_host) {
+    const char* who = "mbar_ctx_set_scan_points";
+    int rc = scan_ready(c, who);
+    if (rc) return rc;
+    const int64_t N = c->N, ld = c->ld;
+    // (refused before the block is touched)
+    if (d < 0 || d > SCANKDE_MAX_D || (d > 0 && (!x_host || ld_host < N)))
+        return fail(c, MBAR_ERR_ARG, std::string(who) + ": d = 0, 1 or 2 rows of N doubles at a pitch of at least N");
+    for (int64_t k = 0; k < d; ++k)
+        for (int64_t n = 0; n < N; ++n)
+            if (!std::isfinite(x_host[k * ld_host + n])) return fail(c, MBAR_ERR_ARG, std::string(who) + ": the points must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->scan_pts_d = 0;
+    if (d == 0) {
+        c->scan_pts.reset();
+        return MBAR_OK;
+    }
+    HIPCHK(c, c->scan_pts.grow((size_t)d * (size_t)ld));
+    HIPCHK(c, hipMemset(c->scan_pts, 0, (size_t)d * (size_t)ld * sizeof(double)));
+    HIPCHK(c, hipMemcpy2D(c->scan_pts, (size_t)ld * sizeof(double), x_host, (size_t)ld_host * sizeof(double), (size_t)N * sizeof(double), (size_t)d,
+                          hipMemcpyHostToDevice));
+    c->scan_pts_d = d;
+    return MBAR_OK;
+}
+
+// One launch and one merge per (member panel, query panel): the member panels are those of mbar_scan_obs_sums' first moments, the
+// query panels 128 queries (the last one the narrowest instantiation that holds it).  Then the pairs the merge left as NaN, of
+// members with weight, in batches of KDE_EXACT_BATCH through the exact kernel.
+int mbar_scan_kde_sums(mbar_ctx* c, const double* f, int64_t L, const double* coeff, const double* offset, const double* f_scan, int64_t M,
+                       const double* q, double bandwidth, const double* period, double* logsum, double* wsum, int64_t* n_exact) {
+    const char* who = "mbar_scan_kde_sums";
+    int rc = scan_open(c, who, f && coeff && f_scan && q && logsum && wsum && n_exact && L >= 1 && M >= 1, false, L);
+    if (rc) return rc;
+    if (c->scan_pts_d < 1) return fail(c, MBAR_ERR_STATE, std::string(who) + ": no points on this context (mbar_ctx_set_scan_points first)");
+    const int dim = (int)c->scan_pts_d;
+    const double inv2h2 = 0.5 / (bandwidth * bandwidth);
+    if (!(bandwidth > 0.0) || !std::isfinite(bandwidth) || !std::isfinite(inv2h2) || !(inv2h2 > 0.0))
+        return fail(c, MBAR_ERR_ARG, std::string(who) + ": the bandwidth must be positive and finite, and so must 1 / 2h^2");
+    for (int64_t x = 0; x < (int64_t)dim * M; ++x)
+        if (!std::isfinite(q[x])) return fail(c, MBAR_ERR_ARG, std::string(who) + ": the queries must be finite");
+    for (int k = 0; period && k < dim; ++k)
+        if (!(period[k] >= 0.0) || !std::isfinite(period[k])) return fail(c, MBAR_ERR_ARG, std::string(who) + ": a period is 0 (none) or positive and finite");
+    *n_exact = 0;
+    const int64_t B = c->scan_B;
+    const size_t LM = (size_t)L * (size_t)M;
+    constexpr int64_t QP = 128;                  // queries of a panel: one tile of the widest instantiation
+    constexpr int64_t KDE_EXACT_BATCH = 1 << 16;  // pairs of one launch of the exact kernel
+    const int64_t nchunks = std::max<int64_t>((c->N + SCAN_CHUNK - 1) / SCAN_CHUNK, 1);
+    const int mb = scan_mb_of<ScanStored>(c, 1);
+    const int64_t record = scan_kde_record_doubles(scan_nb_for(std::min(M, QP)), mb);
+    const size_t batch = (size_t)std::min<int64_t>(KDE_EXACT_BATCH, (int64_t)LM);
+    bool done = false;
+    ScanData d;
+    // out: logsum | wsum | the exact kernel's results | its pairs (two int64 each); in, behind the members': the queries
+    rc = scan_begin(c, f, L, coeff, offset, f_scan, (size_t)L, {{logsum, LM}, {wsum, (size_t)L}}, (size_t)nchunks * (size_t)record,
+                    LM + (size_t)L + 3 * batch, &done, &d, (size_t)dim * (size_t)M);
+    if (rc || done) return rc;
+    double* d_logsum = c->scan_out;
+    double* d_wsum = d_logsum + LM;
+    double* d_exact = d_wsum + L;
+    int64_t* d_pairs = reinterpret_cast<int64_t*>(d_exact + batch);
+    const double* d_coeff = c->scan_in;
+    const double* d_off = d_coeff + L * B;
+    double* d_fscan = c->scan_in.p + L * (B + 1);
+    double* d_q = c->scan_in.p + L * (B + 3);
+    HIPCHK(c, hipMemcpyAsync(d_fscan, f_scan, (size_t)L * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_q, q, (size_t)dim * (size_t)M * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const ScanKde kd = scan_kde_make(dim, c->scan_pts, d_q, M, M, bandwidth, period);
+    {
+        ScopedTimer timer(c, MBAR_TIMER_OTHER);
+        for (int64_t p0 = 0; p0 < L; p0 += 64 * mb)
+            for (int64_t qb = 0; qb < M; qb += QP) {
+                const int64_t nq = std::min(QP, M - qb);
+                const int nb = scan_nb_for(nq);
+                if (c->scan_terms.mask)
+                    HIPCHK(c, launch_scan_kde(c->stream, d, harmonic_of(c), kd, nb, qb, nq, L, p0, d_coeff, d_off, d_fscan, c->scan_part));
+                else
+                    HIPCHK(c, launch_scan_kde(c->stream, d, ScanLinear{}, kd, nb, qb, nq, L, p0, d_coeff, d_off, d_fscan, c->scan_part));
+                HIPCHK(c, launch_scan_kde_merge(c->stream, d, kd, nb, mb, L, p0, qb, nq, c->scan_part, d_logsum, qb == 0 ? d_wsum : nullptr));
+            }
+    }
+    HIPCHK(c, hipMemcpyAsync(logsum, d_logsum, LM * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(wsum, d_wsum, (size_t)L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    rc = sync_stream(c);
+    if (rc) return rc;
+    // ---- the exact path: a NaN of a member with weight
+    std::vector<int64_t> pairs;
+    for (int64_t l = 0; l < L; ++l) {
+        if (!(wsum[l] > 0.0)) continue;
+        for (int64_t m = 0; m < M; ++m)
+            if (std::isnan(logsum[l * M + m])) {
+                pairs.push_back(l);
+                pairs.push_back(m);
+            }
+    }
+    const int64_t npairs = (int64_t)pairs.size() / 2;
+    std::vector<double> exact(npairs > 0 ? batch : 0);
+    for (int64_t i0 = 0; i0 < npairs; i0 += (int64_t)batch) {
+        const int64_t nb = std::min<int64_t>((int64_t)batch, npairs - i0);
+        HIPCHK(c, hipMemcpyAsync(d_pairs, pairs.data() + 2 * i0, (size_t)nb * 2 * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        {
+            ScopedTimer timer(c, MBAR_TIMER_OTHER);
+            if (c->scan_terms.mask)
+                HIPCHK(c, launch_scan_kde_exact(c->stream, d, harmonic_of(c), kd, nb, d_pairs, d_coeff, d_off, d_fscan, d_exact));
+            else
+                HIPCHK(c, launch_scan_kde_exact(c->stream, d, ScanLinear{}, kd, nb, d_pairs, d_coeff, d_off, d_fscan, d_exact));
+        }
+        HIPCHK(c, hipMemcpyAsync(exact.data(), d_exact, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        rc = sync_stream(c);
+        if (rc) return rc;
+        for (int64_t i = 0; i < nb; ++i) logsum[pairs[2 * (i0 + i)] * M + pairs[2 * (i0 + i) + 1]] = exact[i];
+    }
+    *n_exact = npairs;
+    return MBAR_OK;
+}
+
 // ---- histogram surfaces along a scan ----
 
 int mbar_scan_bins_table(int64_t N, int64_t nbins, const int32_t* label, int32_t* perm_out, int64_t* bin_start_out) {

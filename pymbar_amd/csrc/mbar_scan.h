@@ -204,6 +204,32 @@ hipError_t launch_scan_obs(hipStream_t s, const ScanData& d, const Fam& fam, int
                            int64_t p0, const double* coeff, const double* offset, const double* fnorm, double* part);
 hipError_t launch_scan_obs_merge(hipStream_t s, const ScanData& d, int nb, int mode, int mb, int64_t L, int64_t Q, int64_t p0, int64_t qb,
                                  int64_t nq, const double* part, double* out0, double* out1, double* vec0, double* vec1);
+// Kernel-density surfaces along a scan (mbar_scan_kde_sums), whole cut, either family:
+// launch_scan_obs at mode 0 with the tile COMPUTED, k(q_i, x_n) = exp(-r^2 / 2h^2) of the queries [qb, qb + nq) of q[d][ldq] against
+// the points x[d][d.ldv] (nq <= 16 nb, nb = scan_nb_for(nq), d = 1 or 2).  One launch per (member panel [p0, p0 + 64 mb), query
+// panel), mb = Fam::mb(1); part[chunk][scan_kde_record_doubles(nb, mb)], then the merge in chunk order into logsum[L][M] (log of the
+// sum; NaN where the sum is not >= 2^-900) and, where asked for, wsum[L].  launch_scan_kde_exact: out[i] = the log of the sum of pair
+// (member pairs[2 i], query pairs[2 i + 1]) in plain log space, one workgroup each.
+constexpr int SCANKDE_MAX_D = 2;
+struct ScanKde {
+    int d;
+    const double* x;  // [d][ScanData::ldv] the points of the samples
+    const double* q;  // [d][ldq] the queries
+    int64_t ldq, M;
+    double coef;   // -S log2(e) / 2h^2: the exp2s argument of a pair is r^2 coef
+    double inv_h;  // 1 / h
+    double period[SCANKDE_MAX_D], rperiod[SCANKDE_MAX_D];  // P_k (0: not periodic) and 1.0 / P_k, rounded once on the host
+};
+ScanKde scan_kde_make(int d, const double* x, const double* q, int64_t ldq, int64_t M, double h, const double* period);
+int64_t scan_kde_record_doubles(int nb, int mb);
+template <class Fam>
+hipError_t launch_scan_kde(hipStream_t s, const ScanData& d, const Fam& fam, const ScanKde& kd, int nb, int64_t qb, int64_t nq, int64_t L,
+                           int64_t p0, const double* coeff, const double* offset, const double* fnorm, double* part);
+hipError_t launch_scan_kde_merge(hipStream_t s, const ScanData& d, const ScanKde& kd, int nb, int mb, int64_t L, int64_t p0, int64_t qb,
+                                 int64_t nq, const double* part, double* logsum, double* wsum);
+template <class Fam>
+hipError_t launch_scan_kde_exact(hipStream_t s, const ScanData& d, const Fam& fam, const ScanKde& kd, int64_t npairs, const int64_t* pairs,
+                                 const double* coeff, const double* offset, const double* fnorm, double* out);
 
 // ---- rows of the resident matrix from a family of states (mbar_k_family.hip; C ABI: mbar_ctx_fill_family_rows and ----------
 // ---- mbar_ctx_fill_linear_rows in mbar_rows.cpp) -----------------------------------------------------------------------------

@@ -212,6 +212,7 @@ class DeviceMatrix(_ContextMatrix):
         self._scan_harmonic = None  # the bool mask of the scan family's harmonic terms
         self._scan_nbins = 0  # set_scan_bins
         self._scan_obs = 0  # rows of set_scan_observables
+        self._scan_pts = 0  # coordinates of set_scan_points
         self._boot_layout_key = None  # the caller's key of the bootstrap layout on the device
         self._cb = None  # keeps the host all-reduce callback alive
         self._loop = None  # keeps the loopback group alive
@@ -602,6 +603,62 @@ class DeviceMatrix(_ContextMatrix):
             self._check(self._lib.mbar_scan_obs_sums(self._ctx, _dptr(f), l1 - l0, _dptr(coeff_lb[l0:l1]), _dptr(offset_l[l0:l1]),
                                                      _dptr(f_scan[l0:l1]), part(s1), part(t1), part(t2), part(wsum), part(w2sum)))
         return s1, t1, t2, wsum, w2sum
+
+    # ---- kernel-density surfaces along a scan (pymbar_amd.scan.compute_scan_kde) -------------------------------------------------
+    SCAN_KDE_BYTES = 1 << 28  # the L x M block of one slab of members of scan_kde_sums stays under this
+
+    def set_scan_points(self, x_dn=None):
+        """The ``d = 1`` or ``2`` coordinates of the samples (``d x N``, coordinate-major) kept resident for :meth:`scan_kde_sums`
+        (``mbar_ctx_set_scan_points``), in a block of their own: it survives :meth:`set_scan` and the other scan methods.  ``None``
+        releases it."""
+        if x_dn is None:
+            self._check(self._lib.mbar_ctx_set_scan_points(self._ctx, 0, None, 0))
+            self._scan_pts = 0
+            return
+        x_dn = _lib.f64(x_dn, (None, self.N_local), "x_dn")
+        if not 1 <= x_dn.shape[0] <= 2:
+            raise ValueError("x_dn must have one or two rows of coordinates")
+        # (MBAR_ERR_ARG: a non-finite entry.  A refused call leaves the library's block, and the dimension the queries are checked
+        # against, as they were.)
+        self._check(self._lib.mbar_ctx_set_scan_points(self._ctx, x_dn.shape[0], _dptr(x_dn), self.N_local), ValueError)
+        self._scan_pts = x_dn.shape[0]
+
+    def scan_kde_sums(self, f, coeff_lb, offset_l, f_scan, queries_dm, bandwidth, period=None, center_lb=None, slab=None):
+        """The gaussian kernel sums of the resident points along a scan (``mbar_scan_kde_sums``): ``(logsum, wsum, n_exact)`` with
+        ``b_ln`` as in :meth:`scan_gram_w` -- ``logsum[l, m] = log sum_n c_n b_ln exp(-r^2 / 2h^2)`` (``L x M``), ``r`` the distance from
+        sample ``n`` to query ``m`` of ``queries_dm`` (``d x M``, coordinate-major), ``wsum[l] = sum_n c_n b_ln``, ``n_exact`` the number of
+        pairs whose terms all underflowed and that were recomputed in log space.  ``period`` (``d`` entries, 0: not periodic): the
+        minimum image of that coordinate; None is zeros.  The members go to the device in slabs (of ``slab`` members; by default as
+        many as keep a slab's block under 256 MiB): an entry's bits do not depend on the cut."""
+        f = self._f(f)
+        coeff_lb, offset_l, L, _ = self._scan_members(coeff_lb, offset_l)
+        f_scan = _lib.f64(f_scan, (L,), "f_scan")
+        d = self._scan_pts
+        if d < 1:
+            raise ValueError("no points on this matrix (set_scan_points first)")
+        queries_dm = _lib.f64(queries_dm, (d, None), "queries_dm")
+        M = queries_dm.shape[1]
+        if M < 1:
+            raise ValueError("queries_dm must have at least one query")
+        period = _lib.f64(period, (d,), "period", optional=True)
+        if center_lb is not None and np.shape(center_lb) != (L, self._scan[0]):
+            raise ValueError("center_lb must have one row per member and one column per basis vector")
+        if slab is None:
+            slab = self.SCAN_KDE_BYTES // (8 * M)
+        slab = max(1, min(int(slab), L))
+        logsum = np.empty((L, M), dtype=np.float64)
+        wsum = np.empty(L, dtype=np.float64)
+        n_exact = 0
+        for l0 in range(0, L, slab):
+            l1 = min(L, l0 + slab)
+            self._scan_centers(None if center_lb is None else center_lb[l0:l1], l1 - l0)
+            ne = C.c_int64(0)
+            # (MBAR_ERR_ARG: a non-finite query, a bandwidth or a period out of range)
+            self._check(self._lib.mbar_scan_kde_sums(self._ctx, _dptr(f), l1 - l0, _dptr(coeff_lb[l0:l1]), _dptr(offset_l[l0:l1]),
+                                                     _dptr(f_scan[l0:l1]), M, _dptr(queries_dm), float(bandwidth), _dptr(period),
+                                                     _dptr(logsum[l0:l1]), _dptr(wsum[l0:l1]), C.byref(ne)), ValueError)
+            n_exact += ne.value
+        return logsum, wsum, n_exact
 
     # ---- histogram surfaces along a scan (pymbar_amd.scan.compute_scan_fes) ---------------------------------------------------
     SCAN_BIN_CROSS_BYTES = 1 << 28  # the host cross block of one slab of members of scan_bin_gram_w stays under this

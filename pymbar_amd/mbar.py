@@ -666,6 +666,7 @@ class MBAR:
     _scan_obs_shift = None  # s_q of the observables set_scan_observables keeps resident (None: none are set)
     set_scan_observables = _scan.set_scan_observables
     compute_scan_expectations = _scan.compute_scan_expectations
+    compute_scan_kde = _scan.compute_scan_kde
 
     def _computeUnnormalizedLogWeights(self, u_n):
         """``-ln sum_k N_k exp(f_k - (u_k(x_n) - u(x_n)))`` for one target potential ``u_n`` (mbar.py:1919-1934):

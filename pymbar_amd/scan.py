@@ -363,6 +363,170 @@ def compute_scan_expectations(mbar, A_qn=None, basis_bn=None, coeff_lb=None, off
     return out
 
 
+# ---- kernel-density surfaces along a scan -------------------------------------------------------------------------------------------
+def _kde_matrix(mbar):
+    dm = _scan_matrix(mbar)
+    if not all(hasattr(dm, name) for name in ("set_scan_points", "scan_kde_sums")):
+        raise ParameterError(f"kernel-density surfaces along a scan need the density pass of a single-rank device matrix and are {_NOT_HERE} for this handle")
+    return dm
+
+
+def _kde_points(mbar, x_n, queries, fes_reference, reference_point):
+    """``(x_dn, q_dm, d, M)``: the samples and the queries coordinate-major, the point of "from-specified" appended as one more query."""
+    x_n = np.asarray(x_n, dtype=np.float64)
+    if x_n.ndim == 1:
+        x_n = x_n.reshape(-1, 1)
+    if x_n.ndim != 2 or x_n.shape[0] != mbar.N or x_n.shape[1] not in (1, 2):
+        raise ParameterError("x_n must have shape (N,) or (N, d) with d = 1 or 2: kernel-density surfaces along a scan serve one or two dimensions")
+    d = x_n.shape[1]
+    queries = np.asarray(queries, dtype=np.float64)
+    if queries.ndim == 1 and (d == 1 or queries.size == 0):
+        queries = queries.reshape(-1, 1)
+    if queries.ndim != 2 or queries.shape[1] != d or queries.shape[0] < 1:
+        raise ParameterError(f"queries must have shape (M, {d}) with M >= 1" + (" or (M,)" if d == 1 else ""))
+    M = queries.shape[0]
+    if reference_point == "from-specified":
+        if fes_reference is None:
+            raise ParameterError("Specified reference point for FES not given")
+        ref = np.array(fes_reference, dtype=np.float64).reshape(1, -1)
+        if ref.shape[1] != d:
+            raise DataError("fes_reference has inconsistent dimension with the data the FES is fit to.")
+        queries = np.vstack([queries, ref])
+    if not (np.all(np.isfinite(x_n)) and np.all(np.isfinite(queries))):
+        raise DataError("x_n, queries and fes_reference must be finite")
+    return np.ascontiguousarray(x_n.T), np.ascontiguousarray(queries.T), d, M
+
+
+def _kde_surface(log_density, M, reference_point):
+    """``(f_i, reference)`` of every member from its log densities at the queries (and, behind them, at the point of
+    "from-specified"): ``FES._get_fes_kde``'s rule, row by row."""
+    f_all = -log_density
+    f_i = f_all[:, :M]
+    L = len(f_i)
+    reference = np.full(L, -1, dtype=np.int64)
+    if reference_point == "from-lowest":
+        reference = np.argmin(f_i, axis=1).astype(np.int64)
+        f_i = f_i - f_i[np.arange(L), reference][:, None]
+    elif reference_point == "from-specified":
+        f_i = f_i - f_all[:, M][:, None]
+    return np.ascontiguousarray(f_i), reference
+
+
+def _kde_bootstrap_spread(fb, reference, reference_point, M):
+    """``df_i`` ``(L, M)``: the ``std`` over the replicates of ``f^b_lm - f^b_l,ref`` with the reference query of the main estimate
+    (column ``M`` for "from-specified", none for "from-normalization").  A replicate in which either is not finite is left out of
+    that entry; fewer than two usable replicates give NaN."""
+    nb, L, _ = fb.shape
+    rows = np.arange(L)
+    with np.errstate(invalid="ignore"):
+        if reference_point == "from-lowest":
+            fall = fb[:, :, :M] - fb[:, rows, reference][:, :, None]
+        elif reference_point == "from-specified":
+            fall = fb[:, :, :M] - fb[:, :, M][:, :, None]
+        else:
+            fall = fb[:, :, :M].copy()
+    fall[~np.isfinite(fall)] = np.nan
+    usable = np.sum(~np.isnan(fall), axis=0)
+    df = np.full((L, M), np.nan)
+    ok = usable >= 2
+    if np.any(ok):
+        df[ok] = np.nanstd(fall[:, ok], axis=0)
+    return df
+
+
+def compute_scan_kde(mbar, x_n, queries, bandwidth, basis_bn=None, coeff_lb=None, offset_l=None, kernel="gaussian", period=None,
+                     reference_point="from-lowest", fes_reference=None, uncertainty_method=None, center_lb=None, harmonic_b=None,
+                     period_b=None):
+    """Kernel-density free energy surfaces of EVERY member of a family of unsampled states: F(x; T) on a temperature ladder, F(phi,
+    psi; restraint centre) -- row ``l`` of every returned array is what ``FES(...).generate_fes(u_n=u_l, x_n, fes_type="kde",
+    kde_parameters={"bandwidth": bandwidth})`` and ``get_fes(queries, reference_point, fes_reference)`` return for the dense member
+    ``u_l``, without a dense ``u_l``, an upload or a weight evaluation per member, and, unlike :func:`compute_scan_fes`, without bins
+    that must all hold samples.
+
+    ``x_n``: ``(N,)`` or ``(N, d)`` with ``d`` 1 or 2; ``queries``: ``(M,)`` or ``(M, d)``, any ``M >= 1``; ``bandwidth`` positive and
+    finite.  The family (``basis_bn``, ``coeff_lb``, ``offset_l``, ``center_lb``, ``harmonic_b``, ``period_b``) is that of
+    :func:`compute_scan`.  ``kernel``: "gaussian" only (the other sklearn kernels are offered by ``FES(fes_type="kde")``).  ``period``:
+    ``(d,)``, 0 = not periodic; where positive, the displacement of that coordinate is the minimum image ``dl - P rint(dl / P)``, formed
+    by the operations of a periodic harmonic term, so a torsion surface is continuous over the +-180 degree seam.  The normaliser stays
+    the unwrapped kernel's: exact to ``erfc(P / (2 sqrt(2) h))`` per periodic coordinate, i.e. for ``h << P``.  ``period=None`` is
+    ``zeros(d)``, to the bit.
+
+    Returns a dict: ``f`` ``(L,)``, the bits of :func:`compute_scan`; ``log_density`` ``(L, M)``, what
+    ``KernelDensity(bandwidth=h).fit(x_n, sample_weight=w_l).score_samples(queries)`` gives for the dense member's weights ``w_l``;
+    ``f_i`` ``(L, M)`` and ``reference`` ``(L,)`` by ``reference_point`` as ``FES.get_fes`` applies it per member -- "from-lowest" (the
+    member's lowest query, its index in ``reference``), "from-specified" (the density at ``fes_reference``, evaluated as one more query;
+    ``reference`` -1), "from-normalization" (``f_i = -log_density``; -1); ``n_exact``: the (member, query) pairs whose kernel terms
+    all underflowed and that the device recomputed in log space.
+
+    ``uncertainty_method``: None or "bootstrap" -- adds ``bootstrapped_log_density`` ``(n_bootstraps, L, M)`` and ``df_i``, the ``std``
+    over the replicates of ``f^b_lm - f^b_l,ref`` with the reference query taken from the main estimate.  A replicate is what it is in
+    :func:`compute_scan_fes`: that replicate's multiplicities and ``f_k_boots[b]``.  (Deliberately not the reference's KDE replicate,
+    which refits resampled positions with the weights of the full sample.)
+
+    The sums are one ``(M x N)(N x L)`` product on the fp64 matrix cores with both operands generated on the device
+    (``DeviceMatrix.scan_kde_sums``): one member exponential serves up to 128 queries, one kernel exponential every member of a panel."""
+    from .kde import KERNELS, log_normaliser
+
+    basis_given = basis_bn
+    if kernel != "gaussian":
+        if kernel in KERNELS:
+            raise ParameterError(f"kernel {kernel!r} is offered by FES(fes_type=\"kde\") only: kernel-density surfaces along a scan are gaussian")
+        raise ParameterError(f"kernel must be one of {KERNELS}, got {kernel!r}")
+    if reference_point not in ("from-lowest", "from-specified", "from-normalization"):
+        raise ParameterError(f"reference point choice {reference_point} for kde is unavailable")
+    if uncertainty_method not in (None, "bootstrap"):
+        raise ParameterError(f"Uncertainty method {uncertainty_method} for kde is not implemented")
+    bootstrap = uncertainty_method == "bootstrap"
+    if bootstrap and (mbar.n_bootstraps is None or mbar.n_bootstraps <= 0):
+        raise ParameterError("Cannot request bootstrap sampling of expectations without any bootstraps.")
+    try:
+        h = float(bandwidth)
+    except (TypeError, ValueError):
+        raise ParameterError(f"bandwidth must be a positive float, got {bandwidth!r}") from None
+    if not (h > 0.0 and np.isfinite(h)):
+        raise ParameterError(f"bandwidth must be a positive float, got {bandwidth!r}")
+    x_dn, q_dm, d, M = _kde_points(mbar, x_n, queries, fes_reference, reference_point)
+    if period is not None:
+        period = np.ascontiguousarray(period, dtype=np.float64)
+        if period.shape != (d,) or not np.all(np.isfinite(period)) or np.any(period < 0.0):
+            raise ParameterError(f"period must have shape ({d},): 0 for a coordinate that is not periodic, its period otherwise")
+    basis_bn, coeff_lb, offset_l, _, L = _check_inputs(mbar, _family_basis(mbar, basis_bn, coeff_lb), coeff_lb, offset_l, None, 0)
+    kinds, cen = _family_kinds(mbar, basis_given, basis_bn.shape[0], L, center_lb, harmonic_b, period_b)
+    dm = _kde_matrix(mbar)
+    lognorm = log_normaliser("gaussian", d, h)
+
+    def densities(f_k, f):
+        logsum, wsum, n_exact = dm.scan_kde_sums(f_k, coeff_lb, offset_l, f, q_dm, h, period=period, **cen)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (logsum - np.log(wsum)[:, None]) + lognorm, wsum, n_exact
+
+    dm.set_Nk(mbar.N_k)
+    dm.set_scan(basis_bn, None, **kinds)
+    try:
+        dm.set_scan_points(x_dn)
+        lognum, _ = dm.scan_lognum(mbar.f_k, coeff_lb, offset_l, **cen)
+        f = -lognum
+        log_density, wsum, n_exact = densities(mbar.f_k, f)
+        check_w_sums(wsum, 0.0)
+        f_i, reference = _kde_surface(log_density, M, reference_point)
+        out = dict(f=f, log_density=np.ascontiguousarray(log_density[:, :M]), f_i=f_i, reference=reference, n_exact=int(n_exact))
+        if bootstrap:
+            Lb = np.zeros((mbar.n_bootstraps,) + log_density.shape)
+            try:
+                for b in range(mbar.n_bootstraps):
+                    mbar._set_bootstrap_weights(dm, b)
+                    ln_b, _ = dm.scan_lognum(mbar.f_k_boots[b, :], coeff_lb, offset_l, **cen)
+                    Lb[b] = densities(mbar.f_k_boots[b, :], -ln_b)[0]
+            finally:
+                dm.set_sample_weights(None)
+            out["bootstrapped_log_density"] = np.ascontiguousarray(Lb[:, :, :M])
+            out["df_i"] = _kde_bootstrap_spread(-Lb, reference, reference_point, M)
+    finally:
+        dm.set_scan_points(None)
+        dm.set_scan(None)
+    return out
+
+
 # ---- differences between any two members of a scan --------------------------------------------------------------------------------
 def _pairs_matrix(mbar):
     dm = _scan_matrix(mbar)

@@ -215,6 +215,26 @@ def periodic_umbrella_family(K=6, n_per_state=300, kappa=0.002, barrier=1.5, bet
             np.full(K, n_per_state, dtype=np.int64))
 
 
+def umbrella_2d_family(x_n, u_n, centers, Ku, beta=1.0):
+    """A 2-D umbrella system as a LINEAR family over the basis ``[u_n, x^2 + y^2, x, y]``: state ``k`` is ``beta [u_n + Ku / 2 |x_n -
+    centers[k]|^2]``, the system of the reference's ``fes_2d`` test (fixture (b) of tests/golden/fes_kde.npz).  ``x_n`` is ``(N, 2)``,
+    ``u_n`` the unbiased reduced potential, ``centers`` ``(K, 2)``.  Returns ``(basis_bn, coeff_kb, offset_k)`` as ``MBAR.from_linear``
+    and the scan methods take them; a temperature member ``beta' u_n`` of a scan is the row ``[beta', 0, 0, 0]``."""
+    x_n = np.asarray(x_n, dtype=np.float64)
+    centers = np.atleast_2d(np.asarray(centers, dtype=np.float64))
+    if x_n.ndim != 2 or x_n.shape[1] != 2 or centers.shape[1] != 2:
+        raise ValueError("x_n must be (N, 2) and centers (K, 2)")
+    K = len(centers)
+    basis_bn = np.stack([np.asarray(u_n, dtype=np.float64), x_n[:, 0] ** 2 + x_n[:, 1] ** 2, x_n[:, 0], x_n[:, 1]])
+    coeff_kb = np.empty((K, 4))
+    coeff_kb[:, 0] = beta
+    coeff_kb[:, 1] = 0.5 * beta * Ku
+    coeff_kb[:, 2] = -beta * Ku * centers[:, 0]
+    coeff_kb[:, 3] = -beta * Ku * centers[:, 1]
+    offset_k = 0.5 * beta * Ku * np.sum(centers * centers, axis=1)
+    return basis_bn, coeff_kb, offset_k
+
+
 def correlated_timeseries_example(N=10000, tau=5.0, seed=None):
     """A Gaussian AR(1) series of length N with correlation time tau (Janke, Eq. 41), as float32.
 
