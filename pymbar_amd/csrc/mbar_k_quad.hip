@@ -27,6 +27,14 @@ namespace mbar {
 #else
 #define QUAD_OWN_AT(n) ((n) - 4)
 #endif
+// The matrix instruction of the pinned accumulators, with the two wait states between a VALU write of its accumulator and its read
+// as C inside the string.  hipcc keeps some accumulators of the 192-row kernels in VGPRs across the back edge of the tile loop and
+// writes them back (v_accvgpr_write) right in front of the instruction; the asm is opaque to its hazard recogniser, so nothing is
+// padded there, and on a workgroup's first tile the instruction read what the launch had left in the low word of the register: a
+// few 1e-313 on top of block (2, 6) of a trimmed panel, seen where W^T W is exactly 0 (profiles/expectation_primitives_matrix.txt).
+// The rectangle kernel k_gram_rect<4, 4> and the fused sweep k_fused_quad<12, 10> had the same write-back in their code, so all
+// three bodies of this file use the string.  Cost: profiles/expectation_primitives_matrix.txt, section 2.
+#define QUAD_MFMA "s_nop 1\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, %0"
 constexpr int quad_blocks_of(int nbt, int w) { return (nbt * (nbt + 1) / 2 - w + 3) / 4; }
 // A wave's blocks into the workgroup's record (the NBT panel's layout: block (I, J), I <= J, row-major): live blocks -- every
 // fourth of the NBM triangle -- from the accumulators, the blocks of the padding rows (every fourth of those) as zeros.
@@ -123,9 +131,9 @@ __device__ __forceinline__ void gram_quad_body(const double* __restrict__ u, int
     auto mfma = [&](int b, double x, double y) {
         if constexpr (PINNED) {
             if (b < GRAM_AGPR_BLOCKS)
-                asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+a"(acc[b]) : "v"(x), "v"(y));
+                asm volatile(QUAD_MFMA : "+a"(acc[b]) : "v"(x), "v"(y));
             else
-                asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[b]) : "v"(x), "v"(y));
+                asm volatile(QUAD_MFMA : "+v"(acc[b]) : "v"(x), "v"(y));
         } else {
             acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, acc[b], 0, 0, 0);
         }
@@ -348,9 +356,9 @@ __device__ __forceinline__ void gram_rect_body(const double* __restrict__ P, int
     };
     auto mfma = [&](int b, double x, double y) {
         if (b < GRAM_AGPR_BLOCKS)
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+a"(acc[b]) : "v"(x), "v"(y));
+            asm volatile(QUAD_MFMA : "+a"(acc[b]) : "v"(x), "v"(y));
         else
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[b]) : "v"(x), "v"(y));
+            asm volatile(QUAD_MFMA : "+v"(acc[b]) : "v"(x), "v"(y));
     };
     double x[GROUPS * NQ], ldc[GROUPS];
     auto read_own = [&](const char* tb) {
@@ -530,9 +538,9 @@ __device__ __forceinline__ void fused_quad_body(const double* __restrict__ P, in
     };
     auto mfma = [&](int b, double x, double y) {
         if (b < GRAM_AGPR_BLOCKS)
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+a"(acc[b]) : "v"(x), "v"(y));
+            asm volatile(QUAD_MFMA : "+a"(acc[b]) : "v"(x), "v"(y));
         else
-            asm volatile("v_mfma_f64_16x16x4_f64 %0, %1, %2, %0" : "+v"(acc[b]) : "v"(x), "v"(y));
+            asm volatile(QUAD_MFMA : "+v"(acc[b]) : "v"(x), "v"(y));
     };
     double x[GROUPS * NQ], w[GROUPS], sw[GROUPS];
     auto read_own = [&](const char* tb) {
